@@ -14,7 +14,13 @@ encoder backward -> flat-gradient all-reduce (N > 1) -> AdamW, dropout 0.1 ON. `
 (3 x B x 200 int64) starting in page-locked HOST memory (SURVEY section 8d counts that copy into the metric: one
 hipMemcpyAsync per batch on a copy stream one batch ahead, xfmr_rec_amd.data.PinnedBatchRing); `resident` repeats the
 timed region on batches that already lie in HBM. Rank 0 prints ONE JSON line; see the task contract for the fields.
-Extra objects:
+
+A plain run does only what `value` needs: set-up, the spin-up and --warmup steps, the --steps timed steps, the line.
+`--full` adds the other figures (`resident`, `h2d_on_compute_stream`, `ragged`, `cold_start`, `roofline`, `cpu_baseline`),
+each measured in steps of its own. `--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy
+(float32): the train loss, every value the step logged and the flat parameter buffer after AdamW; the inputs are seeded,
+so two builds run with the same arguments can be compared file by file.
+Extra objects (--full):
 
   roofline     the DOMINANT kernel of the step = the one with the most GPU time per step (launch duration x launches per
                step; the top row of profiles/*_kernel_stats.md), chosen among the kernels this run times LIVE with HIP events
@@ -90,7 +96,12 @@ def parse(argv=None):
     ap.add_argument("--spinup-steps", type=int, default=300,
                     help="untimed steps of the same workload BEFORE the --warmup steps (same count on every rank): a "
                          "fresh box can take > 100 ms of sustained load to reach its steady clocks; the cold rate "
-                         "(--warmup steps only) is measured first and reported as `cold_start`")
+                         "(--warmup steps only) is measured first and reported as `cold_start` (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside `value` (resident / compute-stream H2D / ragged / cold-start rates, "
+                         "the per-kernel roofline, the CPU baseline), each in steps of its own beside the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, logged values, parameters after AdamW) as DIR/<name>.npy")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-seconds", type=float, default=5.0,
                     help="time budget of EACH cpu_baseline variant beyond its 3 warm-up + 10 timed steps (up to 50 steps)")
@@ -186,6 +197,31 @@ def unit_table(V, H, seed=1234):
     t = t / t.norm(dim=-1, keepdim=True)
     t[0] = 0
     return t
+
+
+DUMP_MAX_ELEMENTS = 8 << 20  # 32 MB of float32: the parameter buffer is the only array that can reach it
+
+
+def dump_outputs(path, loss, logged, flat):
+    """--dump-outputs: what the last timed step handed its caller -- the train loss, every value it logged (0-dim device
+    tensors) and the flat parameter buffer after AdamW -- as float32 DIR/<name>.npy. An array above DUMP_MAX_ELEMENTS is
+    written as the same sample in every run: its elements at the sorted first DUMP_MAX_ELEMENTS indices of
+    torch.randperm(numel, generator seeded 0)."""
+    import re
+
+    import numpy as np
+    import torch
+
+    out = pathlib.Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {"loss": loss, "params": flat}
+    arrays |= {"logged_" + re.sub(r"\W", "_", k): v for k, v in logged.items()}
+    for name, v in arrays.items():
+        a = torch.as_tensor(v).detach().float().cpu()
+        if a.numel() > DUMP_MAX_ELEMENTS:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMENTS].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(out / f"{name}.npy", a.numpy())
 
 
 class HipEvents:
@@ -532,17 +568,18 @@ def main():
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         return float(t.item()), loss, out
 
-    # cold rate: what a run WITHOUT the spin-up would report (--warmup steps, then --steps steps timed)
-    for i in range(args.warmup):
-        step(i)
-    cold_s, _, _ = timed(args.steps)
+    if args.full:  # cold rate: what a run WITHOUT the spin-up would report (--warmup steps, then --steps steps timed)
+        for i in range(args.warmup):
+            step(i)
+        cold_s, _, _ = timed(args.steps)
     for i in range(args.spinup_steps):  # device spin-up (clocks, caches, allocator pools): untimed, not the warmup
         step(i)
     torch.cuda.synchronize()
     for i in range(args.warmup):
         step(i)
-    ev = HipEvents(args.steps) if gstep is None else None  # (a captured step has no per-launch events: see `alone_ms`)
-    enc_events = HipEvents(args.steps) if (gstep is None and enc_parts_ok) else None
+    # per-kernel durations of the timed steps (--full; a captured step has no per-launch events: see `alone_ms`)
+    ev = HipEvents(args.steps) if (args.full and gstep is None) else None
+    enc_events = HipEvents(args.steps) if (args.full and gstep is None and enc_parts_ok) else None
     # THE timed region: batch in page-locked host memory -> H2D of the three index tensors -> gather ->
     # encoder -> loss -> backward -> [all-reduce] -> AdamW
     for i in range(2):
@@ -550,211 +587,227 @@ def main():
     elapsed, loss, out = timed(args.steps, ev, from_host=True)
     per_rank_ms = [round(s / args.steps * 1e3, 4) for s in getattr(timed, "per_rank_s", [elapsed])]
     ar_ms = ar_events.elapsed_ms() if ar_events is not None else []
-    resident_s, _, _ = timed(args.steps)  # the same steps on batches that already lie in HBM
-    inline_s, _, _ = timed(args.steps, None, from_host="inline")
-    # SURVEY section 8(d) names two length regimes: dense rows (the roofline stress: `value`) and MovieLens-like ragged rows,
-    # len ~ clip(round(exp(N(4.35, 1))), 16, L), right-padded with 0 as the reference's collate does (data.py:799-805). The
-    # same timed region on ragged batches of the same (B, L) shape, beside the dense figure.
-    ragged = None
-    if args.lengths == "dense" and not args.no_ragged:
-        while ring.pending:
-            ring.take()
-        ring.release()
-        dense_sets = (host_batches, batches, host_lens)
-        r_host, r_dev, r_lens, r_hl = [], [], [], []
-        for i in range(n_batches):
-            b, lens = synth_batch(B, L, V, 5000 + rank * 97 + i, "ml")
-            r_host.append(torch.stack([b[k] for k in KEYS]).pin_memory())
-            r_dev.append({k: v.to(dev) for k, v in b.items()})
-            r_hl.append(torch.tensor(lens, dtype=torch.int64))
-            r_lens += lens
-        host_batches, batches, host_lens = r_host, r_dev, r_hl
-        # (the packed layout's tensors have other sizes than the dense steps before them, and four different ones: the caching
-        #  allocator settles over the first dozens of steps -- until then a step may pay a hipMalloc, which synchronises)
-        for i in range(max(args.warmup, 80)):
-            step(i, True)
-        ragged_s, _, _ = timed(args.steps, None, from_host=True)
-        # ... and the same batches in the reference's padded layout (XFMR_PACKED=0: the lengths are ignored)
-        os.environ["XFMR_PACKED"] = "0"
-        for i in range(max(args.warmup, 10)):
-            step(i, True)
-        ragged_padded_s, _, _ = timed(args.steps, None, from_host=True)
-        os.environ.pop("XFMR_PACKED", None)
-        while ring.pending:
-            ring.take()
-        ring.release()
-        host_batches, batches, host_lens = dense_sets
-        ragged = {"value": round(B * world * args.steps / ragged_s, 2), "unit": "sequences/s",
-                  "ms_per_step": round(ragged_s / args.steps * 1e3, 4), "lengths": "ml",
-                  "mean_tokens_per_sequence": round(sum(r_lens) / len(r_lens), 1),
-                  "tokens_per_s": round(sum(r_lens) / len(r_lens) * B * world * args.steps / ragged_s, 1),
-                  "layout": "packed rows (xfmr_encoder_cfg.seq_offsets): the encoder and the loss run each sequence's own rows; "
-                            "the batch still arrives as the reference's right-padded (B, L) tensors, with the lengths its "
-                            "collate knows",
-                  "padded_layout": {"value": round(B * world * args.steps / ragged_padded_s, 2),
-                                    "ms_per_step": round(ragged_padded_s / args.steps * 1e3, 4),
-                                    "note": "the same batches with the padding rows computed, as the reference does (XFMR_PACKED=0)"},
-                  "note": "the timed region of `value` (H2D included) on MovieLens-like ragged rows of the same (B, L) shape: "
-                          "len = clip(round(exp(N(4.35, 1))), 16, L), right-padded with 0 (SURVEY section 8d, data.py:799-805)"}
-    # The dominant kernel once more with nothing beside it (outside the timed region): in the timed region the logging pass
-    # sits on a lowest-priority stream underneath the encoder backward, so its duration there includes the time it is held
-    # back -- what a one-stream rocprofv3 trace (profiles/*_kernel_stats.md) sees is this figure.
-    alone_ms, alone_grad_ms = [], []
-    # in line the layer's four weight-gradient GEMMs are ONE launch (dw_ring_kernel) and can be bracketed too, and so can
-    # the backward's final reduction launch
-    ALONE_PARTS = ENC_PARTS + ((N.PROF_DW, "dw_ring_kernel"), (N.PROF_REDUCE, "multi_rowsum_kernel"))
-    alone_enc = {k: [] for k, _ in ALONE_PARTS}
-    if (overlap or gstep is not None) and not args.lean:
-        n_alone = 18
-        ev2 = HipEvents(n_alone)
-        ev3 = HipEvents(n_alone) if enc_parts_ok else None
-        for i in range(n_alone):  # even: the gradient pass, odd: the logging pass -- both on the main stream, one after the other
-            encp = (ALONE_PARTS[i % 6][0], ENC_LAYER) + ev3.pairs[i] if ev3 is not None else None
-            step(i, in_line=True, profile=(None, ev2.pairs[i]) if (i & 1) else (ev2.pairs[i], None), enc_profile=encp)
-        torch.cuda.synchronize()
-        alone_ms = ev2.elapsed_ms({i for i in range(n_alone) if i & 1})
-        alone_grad_ms = ev2.elapsed_ms({i for i in range(n_alone) if not (i & 1)})
-        if ev3 is not None:
-            for j, (k, _) in enumerate(ALONE_PARTS):
-                alone_enc[k] = ev3.elapsed_ms({i for i in range(n_alone) if i % 6 == j})
-    mod.model.enc_profile = None
-
-    stats = out["stats/device"].tolist()
-    n_valid, n_query = stats[N.STAT["n_valid"]], stats[N.STAT["n_query"]]
-    n_cols = stats[N.STAT["neg_distinct"]]
-    if ev is not None:
-        grad_ms = ev.elapsed_ms({i for i in range(args.steps) if not (i & 1)})
-        log_ms = ev.elapsed_ms({i for i in range(args.steps) if (i & 1)}) if not args.lean else []
-    else:  # graph replay: the kernels are timed in the eager in-line steps after the timed region only
-        grad_ms, log_ms = list(alone_grad_ms), list(alone_ms)
-    grad_avg = sum(grad_ms) / max(len(grad_ms), 1)
-    log_avg = sum(log_ms) / max(len(log_ms), 1)
-    peak = PEAK_BF16_MFMA_TFLOPS if args.precision == "bf16" else PEAK_F32_MFMA_TFLOPS
-    # Executed = algorithmic flops of THESE kernels: their columns are the distinct negative items (<= min(N, V): in-batch
-    # negatives repeat items and every per-column term is a function of the item; the north star's "batch x seq x
-    # item-catalogue" GEMM). The reference's materialised form scores all N sampled columns: its count is reported
-    # beside it, it is not a hardware rate.
-    grad_flops = 4.0 * n_query * n_cols * H
-    log_flops = 2.0 * n_query * n_cols * H
-    ref_form_flops = 4.0 * n_query * n_valid * H
-
-    def kernel_entry(name, flops, avg_ms, n):
-        tf = flops / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-        return {"kernel": name, "bound": "mfma", "achieved": round(tf, 2), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(tf / peak, 5), "avg_launch_ms": round(avg_ms, 4), "algorithmic_flops_per_launch": flops,
-                "launches_timed": n}
-
-    k_grad = kernel_entry("loss_main_dma_kernel, gradient pass (logit GEMM + fused epilogue + dQ GEMM)", grad_flops,
-                          grad_avg, len(grad_ms))
-    k_log = kernel_entry("loss_main_dma_kernel, logging pass (six logging heads + LogitsStatistics, values only; "
-                         "VALU-issue-bound: profiles/)", log_flops, log_avg, len(log_ms))
-    note = ("avg_launch_ms / achieved / frac: the kernel with nothing beside it -- 6 further steps after the timed region "
-            "with both loss passes on the main stream, one after the other: the figure a one-stream rocprofv3 trace "
-            "(profiles/*_kernel_stats.md) shows; *_overlapped: in the timed region, where the logging pass runs on a "
-            "lowest-priority stream beside the gradient pass and underneath the encoder backward (each pass's duration "
-            "then includes what the others take from it)")
-    for k, ms, fl in ((k_log, alone_ms, log_flops), (k_grad, alone_grad_ms, grad_flops)):
-        if ms:
-            a = sum(ms) / len(ms)
-            tf = fl / (a * 1e-3) / 1e12
-            k |= {"avg_launch_ms_overlapped": k["avg_launch_ms"], "achieved_overlapped": k["achieved"],
-                  "frac_overlapped": k["frac"]}
-            k |= {"avg_launch_ms": round(a, 4), "achieved": round(tf, 2), "frac": round(tf / peak, 5), "note": note}
-    k_log["launches_per_step"] = k_grad["launches_per_step"] = 1
-    if args.loss in ("AlignmentContrastiveLoss", "ContrastiveLoss", "PairwiseHingeLoss"):
-        # hinge-type gradient weights are exactly 0 inside the margin: the gradient pass skips the dQ MFMAs of every 32 x 32
-        # block without an active pair (csrc/loss_dma.inc). The algorithmic flops above still count the dQ product, so on
-        # batches with few active pairs (random-init weights, a random table: none) `achieved` is up to 2 x the executed rate.
-        k_grad["dq_product"] = ("skipped per 32x32 block when every gradient weight of the block is 0 (hinge-type head); "
-                                "algorithmic_flops_per_launch counts it in full")
-    # The encoder's four big kernels (one launch per layer each), against HBM: ALGORITHMIC bytes per launch = what the kernel
-    # must read and write once (scripts/kernel_roofline.py holds the same table) / the launch duration.
-    Tt = B * L
-    TH, TI = Tt * H, Tt * args.inter
-    A_heads = args.heads or H // 32
-    enc_model = {
-        N.PROF_FFN_FWD: ("ffn_fwd_fused_kernel (FFN1 + GELU + FFN2 + dropout + residual + LayerNorm; writes u, g)",
-                         TH * 2 + TH * 4 + 2 * TI * 2 + 2 * TH * 4 + TH * 2, 4.0 * Tt * args.inter * H),
-        N.PROF_FFN_BWD: ("ffn_bwd_dx_fused_kernel (FFN2 dX x gelu'(u) -> dI -> FFN1 dX + LayerNorm backward)",
-                         TH * 2 + 2 * TI * 2 + TH * 4 * 3 + TH * 2, 4.0 * Tt * args.inter * H),
-        N.PROF_ATTN_FWD: ("attn_fwd_seq_bf16_kernel (one workgroup per (batch, head))",
-                          3 * TH * 2 + TH * 2 + B * A_heads * L * 4, 4.0 * B * A_heads * L * (L + 1) / 2 * 32),
-        N.PROF_ATTN_BWD: ("attn_bwd_fused_bf16_kernel (one workgroup per (batch, head): dQ, dK, dV)",
-                          2 * 3 * TH * 2 + 2 * TH * 2, 10.0 * B * A_heads * L * (L + 1) / 2 * 32),
-        # operands only: dy + g, dI + x1, d_lin + ctx, dQKV + x (all bf16); the split-K slabs it also writes are overhead
-        N.PROF_DW: ("dw_ring_kernel (the layer's four weight-gradient GEMMs, token slabs through an LDS-DMA ring, in one launch: the in-line form)",
-                    (TH + TI) * 2 * 2 + 2 * TH * 2 + (3 * TH + TH) * 2, 2.0 * Tt * (2 * H * args.inter + H * H + 3 * H * H)),
-    }
-    enc_entries = []
-    if enc_parts_ok:
-        over = {k: (enc_events.elapsed_ms({i for i in range(args.steps) if i % 4 == j}) if enc_events is not None else [])
-                for j, (k, _) in enumerate(ENC_PARTS)}
-        for k, _short in ALONE_PARTS:
-            ms_alone, ms_over = alone_enc.get(k) or [], over.get(k) or []
-            ms = ms_alone or ms_over
-            if not ms or k not in enc_model:
-                continue
-            name, nbytes, flops = enc_model[k]
-            avg = sum(ms) / len(ms)
-            e = {"kernel": name, "bound": "hbm", "achieved": round(nbytes / (avg * 1e-3) / 1e12, 3), "peak": PEAK_HBM_TBPS,
-                 "unit": "TB/s", "frac": round(nbytes / (avg * 1e-3) / 1e12 / PEAK_HBM_TBPS, 5),
-                 "avg_launch_ms": round(avg, 4), "algorithmic_bytes_per_launch": float(nbytes),
-                 "launches_per_step": args.layers, "launches_timed": len(ms), "layer_timed": ENC_LAYER,
-                 "mfma_tflops": round(flops / (avg * 1e-3) / 1e12, 1)}
-            if ms_alone and ms_over:
-                e["avg_launch_ms_overlapped"] = round(sum(ms_over) / len(ms_over), 4)
-            enc_entries.append(e)
-    # dominant = the kernel with the most GPU time per step (launch duration with nothing beside it x launches per step):
-    # the top row of a one-stream rocprofv3 trace (profiles/*_kernel_stats.md). (The 4 x layers weight-gradient GEMMs run on
-    # a side stream in many launches and are not bracketed; their sum per step is in profiles/.)
-    cands = ([k_log] if log_ms else []) + [k_grad] + enc_entries
-    dominant = max(cands, key=lambda e: e["avg_launch_ms"] * e["launches_per_step"])
-    for e in cands:
-        e["ms_per_step"] = round(e["avg_launch_ms"] * e["launches_per_step"], 4)
-    # whole step: executed flops of the encoder (fwd + bwd, valid tokens) and of the two loss passes / step time
+    if args.dump_outputs and rank == 0:  # before any further step changes the parameters
+        dump_outputs(args.dump_outputs, loss, gstep.logged if gstep is not None else mod.logged, mod.model.flat)
     step_ms = elapsed / args.steps * 1e3
-    enc_flops = n_valid * encoder_flops_per_token(tokens_per_seq, H, args.inter, args.layers)
-    step_flops = enc_flops + grad_flops + (log_flops if log_ms else 0.0)
-    step_tf = step_flops / (step_ms * 1e-3) / 1e12
-    static = static_profile(f"{PROFILE_ROUND}_bench_static.json") or {}
-    step_bytes = step_algorithmic_bytes(B, tokens_per_seq, H, args.inter, args.heads or H // 32, args.layers,
-                                        int(mod.model.flat.numel()))
+    seqs = B * world * args.steps
+    extra = {}  # the --full figures of the line
+    if args.full:
+        resident_s, _, _ = timed(args.steps)  # the same steps on batches that already lie in HBM
+        inline_s, _, _ = timed(args.steps, None, from_host="inline")
+        # SURVEY section 8(d) names two length regimes: dense rows (the roofline stress: `value`) and MovieLens-like ragged rows,
+        # len ~ clip(round(exp(N(4.35, 1))), 16, L), right-padded with 0 as the reference's collate does (data.py:799-805). The
+        # same timed region on ragged batches of the same (B, L) shape, beside the dense figure.
+        ragged = None
+        if args.lengths == "dense" and not args.no_ragged:
+            while ring.pending:
+                ring.take()
+            ring.release()
+            dense_sets = (host_batches, batches, host_lens)
+            r_host, r_dev, r_lens, r_hl = [], [], [], []
+            for i in range(n_batches):
+                b, lens = synth_batch(B, L, V, 5000 + rank * 97 + i, "ml")
+                r_host.append(torch.stack([b[k] for k in KEYS]).pin_memory())
+                r_dev.append({k: v.to(dev) for k, v in b.items()})
+                r_hl.append(torch.tensor(lens, dtype=torch.int64))
+                r_lens += lens
+            host_batches, batches, host_lens = r_host, r_dev, r_hl
+            # (the packed layout's tensors have other sizes than the dense steps before them, and four different ones: the caching
+            #  allocator settles over the first dozens of steps -- until then a step may pay a hipMalloc, which synchronises)
+            for i in range(max(args.warmup, 80)):
+                step(i, True)
+            ragged_s, _, _ = timed(args.steps, None, from_host=True)
+            # ... and the same batches in the reference's padded layout (XFMR_PACKED=0: the lengths are ignored)
+            os.environ["XFMR_PACKED"] = "0"
+            for i in range(max(args.warmup, 10)):
+                step(i, True)
+            ragged_padded_s, _, _ = timed(args.steps, None, from_host=True)
+            os.environ.pop("XFMR_PACKED", None)
+            while ring.pending:
+                ring.take()
+            ring.release()
+            host_batches, batches, host_lens = dense_sets
+            ragged = {"value": round(B * world * args.steps / ragged_s, 2), "unit": "sequences/s",
+                      "ms_per_step": round(ragged_s / args.steps * 1e3, 4), "lengths": "ml",
+                      "mean_tokens_per_sequence": round(sum(r_lens) / len(r_lens), 1),
+                      "tokens_per_s": round(sum(r_lens) / len(r_lens) * B * world * args.steps / ragged_s, 1),
+                      "layout": "packed rows (xfmr_encoder_cfg.seq_offsets): the encoder and the loss run each sequence's own rows; "
+                                "the batch still arrives as the reference's right-padded (B, L) tensors, with the lengths its "
+                                "collate knows",
+                      "padded_layout": {"value": round(B * world * args.steps / ragged_padded_s, 2),
+                                        "ms_per_step": round(ragged_padded_s / args.steps * 1e3, 4),
+                                        "note": "the same batches with the padding rows computed, as the reference does (XFMR_PACKED=0)"},
+                      "note": "the timed region of `value` (H2D included) on MovieLens-like ragged rows of the same (B, L) shape: "
+                              "len = clip(round(exp(N(4.35, 1))), 16, L), right-padded with 0 (SURVEY section 8d, data.py:799-805)"}
+        # The dominant kernel once more with nothing beside it (outside the timed region): in the timed region the logging pass
+        # sits on a lowest-priority stream underneath the encoder backward, so its duration there includes the time it is held
+        # back -- what a one-stream rocprofv3 trace (profiles/*_kernel_stats.md) sees is this figure.
+        alone_ms, alone_grad_ms = [], []
+        # in line the layer's four weight-gradient GEMMs are ONE launch (dw_ring_kernel) and can be bracketed too, and so can
+        # the backward's final reduction launch
+        ALONE_PARTS = ENC_PARTS + ((N.PROF_DW, "dw_ring_kernel"), (N.PROF_REDUCE, "multi_rowsum_kernel"))
+        alone_enc = {k: [] for k, _ in ALONE_PARTS}
+        if (overlap or gstep is not None) and not args.lean:
+            n_alone = 18
+            ev2 = HipEvents(n_alone)
+            ev3 = HipEvents(n_alone) if enc_parts_ok else None
+            for i in range(n_alone):  # even: the gradient pass, odd: the logging pass -- both on the main stream, one after the other
+                encp = (ALONE_PARTS[i % 6][0], ENC_LAYER) + ev3.pairs[i] if ev3 is not None else None
+                step(i, in_line=True, profile=(None, ev2.pairs[i]) if (i & 1) else (ev2.pairs[i], None), enc_profile=encp)
+            torch.cuda.synchronize()
+            alone_ms = ev2.elapsed_ms({i for i in range(n_alone) if i & 1})
+            alone_grad_ms = ev2.elapsed_ms({i for i in range(n_alone) if not (i & 1)})
+            if ev3 is not None:
+                for j, (k, _) in enumerate(ALONE_PARTS):
+                    alone_enc[k] = ev3.elapsed_ms({i for i in range(n_alone) if i % 6 == j})
+        mod.model.enc_profile = None
+
+        stats = out["stats/device"].tolist()
+        n_valid, n_query = stats[N.STAT["n_valid"]], stats[N.STAT["n_query"]]
+        n_cols = stats[N.STAT["neg_distinct"]]
+        if ev is not None:
+            grad_ms = ev.elapsed_ms({i for i in range(args.steps) if not (i & 1)})
+            log_ms = ev.elapsed_ms({i for i in range(args.steps) if (i & 1)}) if not args.lean else []
+        else:  # graph replay: the kernels are timed in the eager in-line steps after the timed region only
+            grad_ms, log_ms = list(alone_grad_ms), list(alone_ms)
+        grad_avg = sum(grad_ms) / max(len(grad_ms), 1)
+        log_avg = sum(log_ms) / max(len(log_ms), 1)
+        peak = PEAK_BF16_MFMA_TFLOPS if args.precision == "bf16" else PEAK_F32_MFMA_TFLOPS
+        # Executed = algorithmic flops of THESE kernels: their columns are the distinct negative items (<= min(N, V): in-batch
+        # negatives repeat items and every per-column term is a function of the item; the north star's "batch x seq x
+        # item-catalogue" GEMM). The reference's materialised form scores all N sampled columns: its count is reported
+        # beside it, it is not a hardware rate.
+        grad_flops = 4.0 * n_query * n_cols * H
+        log_flops = 2.0 * n_query * n_cols * H
+        ref_form_flops = 4.0 * n_query * n_valid * H
+
+        def kernel_entry(name, flops, avg_ms, n):
+            tf = flops / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+            return {"kernel": name, "bound": "mfma", "achieved": round(tf, 2), "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(tf / peak, 5), "avg_launch_ms": round(avg_ms, 4), "algorithmic_flops_per_launch": flops,
+                    "launches_timed": n}
+
+        k_grad = kernel_entry("loss_main_dma_kernel, gradient pass (logit GEMM + fused epilogue + dQ GEMM)", grad_flops,
+                              grad_avg, len(grad_ms))
+        k_log = kernel_entry("loss_main_dma_kernel, logging pass (six logging heads + LogitsStatistics, values only; "
+                             "VALU-issue-bound: profiles/)", log_flops, log_avg, len(log_ms))
+        note = ("avg_launch_ms / achieved / frac: the kernel with nothing beside it -- 6 further steps after the timed region "
+                "with both loss passes on the main stream, one after the other: the figure a one-stream rocprofv3 trace "
+                "(profiles/*_kernel_stats.md) shows; *_overlapped: in the timed region, where the logging pass runs on a "
+                "lowest-priority stream beside the gradient pass and underneath the encoder backward (each pass's duration "
+                "then includes what the others take from it)")
+        for k, ms, fl in ((k_log, alone_ms, log_flops), (k_grad, alone_grad_ms, grad_flops)):
+            if ms:
+                a = sum(ms) / len(ms)
+                tf = fl / (a * 1e-3) / 1e12
+                k |= {"avg_launch_ms_overlapped": k["avg_launch_ms"], "achieved_overlapped": k["achieved"],
+                      "frac_overlapped": k["frac"]}
+                k |= {"avg_launch_ms": round(a, 4), "achieved": round(tf, 2), "frac": round(tf / peak, 5), "note": note}
+        k_log["launches_per_step"] = k_grad["launches_per_step"] = 1
+        if args.loss in ("AlignmentContrastiveLoss", "ContrastiveLoss", "PairwiseHingeLoss"):
+            # hinge-type gradient weights are exactly 0 inside the margin: the gradient pass skips the dQ MFMAs of every 32 x 32
+            # block without an active pair (csrc/loss_dma.inc). The algorithmic flops above still count the dQ product, so on
+            # batches with few active pairs (random-init weights, a random table: none) `achieved` is up to 2 x the executed rate.
+            k_grad["dq_product"] = ("skipped per 32x32 block when every gradient weight of the block is 0 (hinge-type head); "
+                                    "algorithmic_flops_per_launch counts it in full")
+        # The encoder's four big kernels (one launch per layer each), against HBM: ALGORITHMIC bytes per launch = what the kernel
+        # must read and write once (scripts/kernel_roofline.py holds the same table) / the launch duration.
+        Tt = B * L
+        TH, TI = Tt * H, Tt * args.inter
+        A_heads = args.heads or H // 32
+        enc_model = {
+            N.PROF_FFN_FWD: ("ffn_fwd_fused_kernel (FFN1 + GELU + FFN2 + dropout + residual + LayerNorm; writes u, g)",
+                             TH * 2 + TH * 4 + 2 * TI * 2 + 2 * TH * 4 + TH * 2, 4.0 * Tt * args.inter * H),
+            N.PROF_FFN_BWD: ("ffn_bwd_dx_fused_kernel (FFN2 dX x gelu'(u) -> dI -> FFN1 dX + LayerNorm backward)",
+                             TH * 2 + 2 * TI * 2 + TH * 4 * 3 + TH * 2, 4.0 * Tt * args.inter * H),
+            N.PROF_ATTN_FWD: ("attn_fwd_seq_bf16_kernel (one workgroup per (batch, head))",
+                              3 * TH * 2 + TH * 2 + B * A_heads * L * 4, 4.0 * B * A_heads * L * (L + 1) / 2 * 32),
+            N.PROF_ATTN_BWD: ("attn_bwd_fused_bf16_kernel (one workgroup per (batch, head): dQ, dK, dV)",
+                              2 * 3 * TH * 2 + 2 * TH * 2, 10.0 * B * A_heads * L * (L + 1) / 2 * 32),
+            # operands only: dy + g, dI + x1, d_lin + ctx, dQKV + x (all bf16); the split-K slabs it also writes are overhead
+            N.PROF_DW: ("dw_ring_kernel (the layer's four weight-gradient GEMMs, token slabs through an LDS-DMA ring, in one launch: the in-line form)",
+                        (TH + TI) * 2 * 2 + 2 * TH * 2 + (3 * TH + TH) * 2, 2.0 * Tt * (2 * H * args.inter + H * H + 3 * H * H)),
+        }
+        enc_entries = []
+        if enc_parts_ok:
+            over = {k: (enc_events.elapsed_ms({i for i in range(args.steps) if i % 4 == j}) if enc_events is not None else [])
+                    for j, (k, _) in enumerate(ENC_PARTS)}
+            for k, _short in ALONE_PARTS:
+                ms_alone, ms_over = alone_enc.get(k) or [], over.get(k) or []
+                ms = ms_alone or ms_over
+                if not ms or k not in enc_model:
+                    continue
+                name, nbytes, flops = enc_model[k]
+                avg = sum(ms) / len(ms)
+                e = {"kernel": name, "bound": "hbm", "achieved": round(nbytes / (avg * 1e-3) / 1e12, 3), "peak": PEAK_HBM_TBPS,
+                     "unit": "TB/s", "frac": round(nbytes / (avg * 1e-3) / 1e12 / PEAK_HBM_TBPS, 5),
+                     "avg_launch_ms": round(avg, 4), "algorithmic_bytes_per_launch": float(nbytes),
+                     "launches_per_step": args.layers, "launches_timed": len(ms), "layer_timed": ENC_LAYER,
+                     "mfma_tflops": round(flops / (avg * 1e-3) / 1e12, 1)}
+                if ms_alone and ms_over:
+                    e["avg_launch_ms_overlapped"] = round(sum(ms_over) / len(ms_over), 4)
+                enc_entries.append(e)
+        # dominant = the kernel with the most GPU time per step (launch duration with nothing beside it x launches per step):
+        # the top row of a one-stream rocprofv3 trace (profiles/*_kernel_stats.md). (The 4 x layers weight-gradient GEMMs run on
+        # a side stream in many launches and are not bracketed; their sum per step is in profiles/.)
+        cands = ([k_log] if log_ms else []) + [k_grad] + enc_entries
+        dominant = max(cands, key=lambda e: e["avg_launch_ms"] * e["launches_per_step"])
+        for e in cands:
+            e["ms_per_step"] = round(e["avg_launch_ms"] * e["launches_per_step"], 4)
+        # whole step: executed flops of the encoder (fwd + bwd, valid tokens) and of the two loss passes / step time
+        enc_flops = n_valid * encoder_flops_per_token(tokens_per_seq, H, args.inter, args.layers)
+        step_flops = enc_flops + grad_flops + (log_flops if log_ms else 0.0)
+        step_tf = step_flops / (step_ms * 1e-3) / 1e12
+        static = static_profile(f"{PROFILE_ROUND}_bench_static.json") or {}
+        step_bytes = step_algorithmic_bytes(B, tokens_per_seq, H, args.inter, args.heads or H // 32, args.layers,
+                                            int(mod.model.flat.numel()))
+        if rank == 0:
+            roofline = dict(dominant)
+            ktraffic = static.get("kernel_hbm_bytes_per_launch") or {}
+            dom_key = next((short for k, short in ALONE_PARTS if dominant["kernel"].startswith(short)), None)
+            if dom_key is None:
+                dom_key = "loss_logging_pass" if dominant is k_log else "loss_gradient_pass"
+            dom_traffic = ktraffic.get(dom_key)
+            if dom_traffic is None and dominant is k_log:
+                dom_traffic = static.get("dominant_kernel_hbm_bytes_per_launch")
+            roofline |= {
+                "traffic": dom_traffic,
+                "traffic_source": static.get("source") if dom_traffic else
+                                  f"null: profiles/{PROFILE_ROUND}_bench_static.json (scripts/collect_profiles.sh {PROFILE_ROUND}) "
+                                  "is missing or holds no counter run of this kernel; files of other rounds are refused",
+                # step level: what the whole step moves if every tensor crosses HBM once / ms_per_step / the HBM peak
+                "step_hbm": {"algorithmic_bytes": step_bytes, "achieved": round(step_bytes / (step_ms * 1e-3) / 1e12, 3),
+                             "peak": PEAK_HBM_TBPS, "unit": "TB/s",
+                             "frac": round(step_bytes / (step_ms * 1e-3) / 1e12 / PEAK_HBM_TBPS, 4),
+                             "note": "step_algorithmic_bytes() of bench.py (per-kernel compulsory bytes, mean row length) / "
+                                     "ms_per_step; the two loss passes and the attention kernels are not bound by bytes"},
+                "columns": int(n_cols), "sampled_negative_columns": int(n_valid),
+                "reference_form_flops_per_launch": ref_form_flops,
+                "kernels": [k_grad] + ([k_log] if log_ms else []) + enc_entries,
+                "step": {"executed_flops": step_flops, "achieved": round(step_tf, 1), "unit": "TFLOP/s", "peak": peak,
+                         "frac": round(step_tf / peak, 4),
+                         "note": "encoder fwd+bwd on valid tokens + both loss passes, / ms_per_step"},
+                "reduction_launch_ms": (round(sum(alone_enc[N.PROF_REDUCE]) / len(alone_enc[N.PROF_REDUCE]), 4)
+                                        if alone_enc.get(N.PROF_REDUCE) else None),
+                "valu": valu_roofline(static.get("dominant_kernel_valu"), k_log["avg_launch_ms"]) if log_ms else None,
+                "valu_kernel": k_log["kernel"] if log_ms else None,
+                "gemm_family_tbps": static.get("gemm_family_tbps"),
+                "gemm_family_tbps_source": static.get("source") if static.get("gemm_family_tbps") else None,
+                "hbm_peak_tbps": PEAK_HBM_TBPS,
+            }
+            extra = {
+                "resident": {"value": round(seqs / resident_s, 2), "ms_per_step": round(resident_s / args.steps * 1e3, 4),
+                             "note": "the same timed region on batches that already lie in HBM (no copy in the step)"},
+                "h2d_on_compute_stream": {"value": round(seqs / inline_s, 2), "ms_per_step": round(inline_s / args.steps * 1e3, 4),
+                                          "note": "Lightning's plain batch transfer: three .to(device, non_blocking=True) copies on "
+                                                  "the compute stream itself, nothing prefetched"},
+                **({"ragged": ragged} if ragged else {}),
+                "cold_start": {"value": round(seqs / cold_s, 2), "ms_per_step": round(cold_s / args.steps * 1e3, 4),
+                               "note": f"the first {args.steps} steps after {args.warmup} warm-up steps only, before the spin-up"},
+                "roofline": roofline,
+            }
 
     if rank == 0:
-        seqs = B * world * args.steps
-        roofline = dict(dominant)
-        ktraffic = static.get("kernel_hbm_bytes_per_launch") or {}
-        dom_key = next((short for k, short in ALONE_PARTS if dominant["kernel"].startswith(short)), None)
-        if dom_key is None:
-            dom_key = "loss_logging_pass" if dominant is k_log else "loss_gradient_pass"
-        dom_traffic = ktraffic.get(dom_key)
-        if dom_traffic is None and dominant is k_log:
-            dom_traffic = static.get("dominant_kernel_hbm_bytes_per_launch")
-        roofline |= {
-            "traffic": dom_traffic,
-            "traffic_source": static.get("source") if dom_traffic else
-                              f"null: profiles/{PROFILE_ROUND}_bench_static.json (scripts/collect_profiles.sh {PROFILE_ROUND}) "
-                              "is missing or holds no counter run of this kernel; files of other rounds are refused",
-            # step level: what the whole step moves if every tensor crosses HBM once / ms_per_step / the HBM peak
-            "step_hbm": {"algorithmic_bytes": step_bytes, "achieved": round(step_bytes / (step_ms * 1e-3) / 1e12, 3),
-                         "peak": PEAK_HBM_TBPS, "unit": "TB/s",
-                         "frac": round(step_bytes / (step_ms * 1e-3) / 1e12 / PEAK_HBM_TBPS, 4),
-                         "note": "step_algorithmic_bytes() of bench.py (per-kernel compulsory bytes, mean row length) / "
-                                 "ms_per_step; the two loss passes and the attention kernels are not bound by bytes"},
-            "columns": int(n_cols), "sampled_negative_columns": int(n_valid),
-            "reference_form_flops_per_launch": ref_form_flops,
-            "kernels": [k_grad] + ([k_log] if log_ms else []) + enc_entries,
-            "step": {"executed_flops": step_flops, "achieved": round(step_tf, 1), "unit": "TFLOP/s", "peak": peak,
-                     "frac": round(step_tf / peak, 4),
-                     "note": "encoder fwd+bwd on valid tokens + both loss passes, / ms_per_step"},
-            "reduction_launch_ms": (round(sum(alone_enc[N.PROF_REDUCE]) / len(alone_enc[N.PROF_REDUCE]), 4)
-                                    if alone_enc.get(N.PROF_REDUCE) else None),
-            "valu": valu_roofline(static.get("dominant_kernel_valu"), k_log["avg_launch_ms"]) if log_ms else None,
-            "valu_kernel": k_log["kernel"] if log_ms else None,
-            "gemm_family_tbps": static.get("gemm_family_tbps"),
-            "gemm_family_tbps_source": static.get("source") if static.get("gemm_family_tbps") else None,
-            "hbm_peak_tbps": PEAK_HBM_TBPS,
-        }
         result = {
             "metric": METRIC,
             "value": round(seqs / elapsed, 2),
@@ -785,15 +838,7 @@ def main():
             "h2d": {"included_in_value": True, "bytes_per_step": 3 * B * L * 8,
                     "how": "page-locked (3, B, L) int64 host block -> persistent device slot, ONE hipMemcpyAsync per batch on a "
                            "copy stream one batch ahead of the compute stream, pre-created events (PinnedBatchRing)"},
-            "resident": {"value": round(seqs / resident_s, 2), "ms_per_step": round(resident_s / args.steps * 1e3, 4),
-                         "note": "the same timed region on batches that already lie in HBM (no copy in the step)"},
-            "h2d_on_compute_stream": {"value": round(seqs / inline_s, 2), "ms_per_step": round(inline_s / args.steps * 1e3, 4),
-                                      "note": "Lightning's plain batch transfer: three .to(device, non_blocking=True) copies on "
-                                              "the compute stream itself, nothing prefetched"},
-            **({"ragged": ragged} if ragged else {}),
-            "cold_start": {"value": round(seqs / cold_s, 2), "ms_per_step": round(cold_s / args.steps * 1e3, 4),
-                           "note": f"the first {args.steps} steps after {args.warmup} warm-up steps only, before the spin-up"},
-            "roofline": roofline,
+            **extra,
         }
         if world > 1:  # what a scaling record needs to explain itself
             be = torch.distributed.get_backend()
@@ -807,7 +852,7 @@ def main():
                                      "for (the overlapped half shows only as far as it is NOT hidden)",
                 "ms_per_step_per_rank": per_rank_ms,
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(result), flush=True)
     if world > 1:

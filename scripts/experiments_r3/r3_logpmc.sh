@@ -7,7 +7,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 PMC="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES"
 timeout -k 10 200 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/harness -o h -- python3 $ROOT/scripts/bench_logging.py --reps 4 > $OUT/harness.log 2>&1 || exit 1
-timeout -k 10 300 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/bench -o b -- python3 $ROOT/bench.py --steps 5 --warmup 2 --spinup-steps 0 --no-cpu-baseline --overlap off --graph off > $OUT/bench.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --pmc $PMC --kernel-trace --output-format csv -d $OUT/bench -o b -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 --spinup-steps 0 --no-cpu-baseline --overlap off --graph off > $OUT/bench.log 2>&1 || exit 1
 cd $ROOT
 python - <<'PY'
 import csv,glob,collections

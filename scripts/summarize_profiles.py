@@ -62,7 +62,7 @@ def main():
             main_steps = n_steps
         md = subprocess.run([sys.executable, str(ROOT / "scripts" / "rocpd_stats.py"), stats, "--steps", str(n_steps),
                              "--top", "40", "--md"], capture_output=True, text=True, check=True).stdout
-        head = (f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --spinup-steps 0 --no-cpu-baseline"
+        head = (f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --spinup-steps 0 --no-cpu-baseline"
                 f"{' --overlap on' if suffix else ' --overlap off'}  ({a.tag}; {n_steps} steps profiled)\n")
         (prof / f"{a.tag}_kernel_stats{suffix}.md").write_text(head + md)
     for v, what in (("config4", "--preset config4"), ("config5", "--preset config5"), ("b32", "--batch 32")):
@@ -72,7 +72,7 @@ def main():
         n_steps = a.steps or steps_in(stats, 48)
         md = subprocess.run([sys.executable, str(ROOT / "scripts" / "rocpd_stats.py"), stats, "--steps", str(n_steps),
                              "--top", "30", "--md"], capture_output=True, text=True, check=True).stdout
-        head = (f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --spinup-steps 0 --no-cpu-baseline "
+        head = (f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --spinup-steps 0 --no-cpu-baseline "
                 f"--overlap off --graph off {what}  ({a.tag}; {n_steps} steps profiled)\n")
         (prof / f"{a.tag}_{v}_kernel_stats.md").write_text(head + md)
     f = find(src / "pmc_FETCH_SIZE" / "**" / "*counter_collection.csv")

@@ -388,6 +388,35 @@ def test_bench_presets_name_the_baseline_configs(monkeypatch):
     assert bench.METRIC.startswith("user-sequences/sec")
 
 
+def test_bench_plain_run_is_lean_and_dumps_float32_outputs(monkeypatch, tmp_path):
+    """A plain bench run measures `value` only (--full is off by default); --dump-outputs writes one float32 .npy per
+    output, and an array above the size cap as the same seeded sample in every run."""
+    import importlib
+    import sys
+
+    import numpy as np
+    import torch
+
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    assert (bench.parse().full, bench.parse().dump_outputs) == (True, str(tmp_path))
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMENTS", 64)
+    flat = torch.arange(1000, dtype=torch.float32)
+    logged = {"loss/InfoNCELoss": torch.tensor(2.5), "batch/size": 4}
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, torch.tensor(2.5), logged, flat)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["logged_batch_size.npy", "logged_loss_InfoNCELoss.npy", "loss.npy", "params.npy"]
+    for n in names:
+        x = np.load(tmp_path / "a" / n)
+        assert x.dtype == np.float32 and np.array_equal(x, np.load(tmp_path / "b" / n))
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.shape == (64,) and np.all(np.diff(p) > 0) and set(p.tolist()) <= set(flat.tolist())
+
+
 def test_bench_gpus_n_launches_its_own_ranks():
     """`python bench.py --gpus N` started as ONE process must start N ranks itself (torch.distributed.run, one process
     per GPU) and relay rank 0's line; a world size that disagrees with --gpus is an error, never a silent 1-GPU run
