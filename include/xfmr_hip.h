@@ -66,6 +66,10 @@ enum { XFMR_PREC_F32 = 0, XFMR_PREC_BF16 = 1 };
 /* Self-attention mask. CAUSAL is what the reference builds (BertConfig(is_decoder=True), xfmr_rec/models.py:355);
  * BIDIRECTIONAL is BertConfig.is_decoder=False: the key-padding mask alone (TF:masking_utils.py bidirectional mask). */
 enum { XFMR_ATTN_CAUSAL = 0, XFMR_ATTN_BIDIRECTIONAL = 1 };
+/* OR-ed into attn_mode: run the key-streaming form of the generic attention kernels (fp32 policy, head size 64) at any
+ * L, instead of the whole-panel form where that fits LDS. Same results, bit for bit; meant for tests and timing. The
+ * bf16 policy at head size 32 ignores it. The streaming form runs anyway where the panel does not fit. */
+enum { XFMR_ATTN_STREAM_KEYS = 2 };
 /* xfmr_encoder_cfg.flags. The *_UNFUSED / DW_INLINE bits select the separate-launch forms of fused kernels (A/B
  * measurements, parity of fused vs unfused forms in tests/): the forward and the backward of a step get the same cfg, so
  * they agree on what the saved activations hold. */
@@ -311,7 +315,8 @@ int xfmr_attn_bwd(const float* qkv, const uint8_t* key_mask, const float* ctx, c
                   const float* d_ctx, float* d_qkv, int32_t B, int32_t L, int32_t A, int32_t H, float dropout_p,
                   uint64_t seed, uint32_t site, int32_t precision, void* stream);
 /* The same pair with the mask selectable: attn_mode = XFMR_ATTN_CAUSAL is exactly the pair above;
- * XFMR_ATTN_BIDIRECTIONAL drops the `k <= q` condition (key k is visible to every query iff key_mask[b,k]). */
+ * XFMR_ATTN_BIDIRECTIONAL drops the `k <= q` condition (key k is visible to every query iff key_mask[b,k]).
+ * Either may carry XFMR_ATTN_STREAM_KEYS; any other bit is XFMR_EINVAL. */
 int xfmr_attn_fwd_mode(const float* qkv, const uint8_t* key_mask, float* ctx, float* lse, int32_t B, int32_t L,
                        int32_t A, int32_t H, float dropout_p, uint64_t seed, uint32_t site, int32_t precision,
                        int32_t attn_mode, void* stream);

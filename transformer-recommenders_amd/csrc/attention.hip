@@ -9,7 +9,8 @@
 //   O^T  += V^T  P^T      dQ^T += K^T dS^T      dV^T += dO^T (P.D)      dK^T += Q^T dS
 // One workgroup = 4 waves = 128 consecutive rows (queries, or keys for dK/dV) of one (batch, head);
 // the whole K/V (or Q/dO) panel of that head that the causal mask can reach is staged once into LDS
-// (L <= 512 keeps it under 160 KiB), so there is a single barrier per kernel.
+// (while it fits 160 KiB), so there is a single barrier per kernel; longer sequences run the key-streaming forms of
+// the generic kernels, which pass the panel through LDS in fixed-size chunks.
 #include "internal.h"
 
 namespace {
@@ -341,6 +342,313 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs a_in) 
       P::tile_xb(dk[j], sQT, ldt, 32 * j, row0, s);
     }
   }
+  float* sc_w = scratch + wid * 32 * 33;
+#pragma unroll
+  for (int j = 0; j < ND; ++j) {
+    xf_store_tile_T_at<S16>(sc_w, dk[j], attn_scale<DHT>(), a.d_qkv, tok0 * 3 * H + H + h * DHT + 32 * j, 3 * H, k0, L);
+    xf_store_tile_T_at<S16>(sc_w, dv[j], 1.f, a.d_qkv, tok0 * 3 * H + 2 * H + h * DHT + 32 * j, 3 * H, k0, L);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ key streaming
+// Key-streaming forms of the three generic kernels: the same workgroups (128 queries, or 128 keys for dK/dV), the same
+// 32-row blocks in the same order and the same per-block code, but the K/V (Q/dO) panel passes through LDS in chunks
+// of CH rows instead of being staged whole, so LDS use does not depend on L. Single-buffered: per chunk, stage ->
+// barrier -> every wave runs the blocks of the chunk its (causal) range reaches -> barrier. A wave with nothing left
+// (rows past L, or past its causal end) still stages and waits at every barrier. After the last chunk the 4 x 32 x 33
+// fp32 output-transposition scratch aliases the chunk images. Results are bit-identical to the panel kernels.
+//   CH = 128 rows (fp32 policy at head size 32, bf16 policy at head size 64), 64 rows (fp32 at head size 64):
+//                  fwd (K, V^T, mask)   dQ (K, V, K^T, mask)   dK/dV (Q, dO, Q^T, dO^T, lse, delta)
+//   fp32, 32       35 456 B             53 888 B               71 680 B
+//   fp32, 64       34 880 B             52 288 B               70 144 B
+//   bf16, 64       35 456 B             53 888 B               71 680 B
+// (<= 80 KiB: two workgroups per CU; the launchers check every instantiation against kLdsLimit.)
+template <class P, int DHT>
+struct AttnStream {
+  using elem = typename P::elem;
+  static constexpr int CH = (sizeof(elem) == 2 || DHT == 32) ? 128 : 64;  // panel rows per chunk
+  static constexpr int LDR = xf_ld<P>(DHT);                                // row images [CH][LDR]
+  static constexpr int LDT = CH + 4;                                       // transposed images [DHT][LDT] (see AttnSmem)
+  static constexpr size_t kRow = (size_t)CH * LDR * sizeof(elem);
+  static constexpr size_t kT = (size_t)DHT * LDT * sizeof(elem);
+  static constexpr size_t kScratch = 4 * 32 * 33 * sizeof(float);
+  static constexpr size_t at_least_scratch(size_t x) { return x > kScratch ? x : kScratch; }
+  static constexpr size_t kFwdImg = at_least_scratch(kRow + kT);        // then CH mask bytes
+  static constexpr size_t kDqImg = at_least_scratch(2 * kRow + kT);     // then CH mask bytes
+  static constexpr size_t kDkvImg = at_least_scratch(2 * kRow + 2 * kT);  // then CH lse + CH delta floats
+  static constexpr size_t fwd_bytes() { return kFwdImg + CH; }
+  static constexpr size_t dq_bytes() { return kDqImg + CH; }
+  static constexpr size_t dkv_bytes() { return kDkvImg + 2 * CH * sizeof(float); }
+  static_assert(kRow % 16 == 0 && kT % 16 == 0, "16-byte aligned images");
+  static_assert(fwd_bytes() <= 80 * 1024 && dq_bytes() <= 80 * 1024 && dkv_bytes() <= 80 * 1024,
+                "two workgroups per CU");
+};
+
+template <class P, int DHT, bool S16>
+__global__ __launch_bounds__(256) void attn_fwd_stream_kernel(const AttnArgs a_in) {
+  AttnArgs a = a_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
+  XF_CHAIN_PRIO();
+  a.drop = xf_drop_resolve(a.drop);
+  using elem = typename P::elem;
+  using ST = AttnStream<P, DHT>;
+  constexpr int ND = DHT / 32, CH = ST::CH;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int L = a.L, H = a.H;
+  const int b = blockIdx.y / a.A, h = blockIdx.y % a.A;
+  const int qblk0 = blockIdx.x * 128;
+  const int nkeys = a.causal ? min(((L + 31) / 32) * 32, qblk0 + 128) : ((L + 31) / 32) * 32;
+  elem* sK = reinterpret_cast<elem*>(smem_raw);
+  elem* sVT = reinterpret_cast<elem*>(smem_raw + ST::kRow);
+  float* scratch = reinterpret_cast<float*>(smem_raw);  // after the last chunk
+  uint8_t* sMask = smem_raw + ST::kFwdImg;
+
+  const int64_t tok0 = (int64_t)b * L;
+  const int64_t koff = tok0 * 3 * H + H + h * DHT, voff = tok0 * 3 * H + 2 * H + h * DHT;
+  const int lane = xf_lane(), wid = threadIdx.x >> 6;
+  const int q0 = qblk0 + wid * 32;
+  const bool active = q0 < L;  // (wave-uniform)
+  const int q = q0 + (lane & 31);
+  RegRows<P, DHT> qreg;
+  load_reg_rows<P, DHT, S16>(qreg, a.qkv, (tok0 + q) * 3 * H + h * DHT, q < L);
+
+  const float sc = attn_scale<DHT>() * kLog2e;
+  float m = -INFINITY, lsum = 0.f;
+  f32x16 o[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[j][r] = 0.f;
+  const uint32_t rowkey = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blockIdx.y * L + q));
+
+  const int kb_end = !active ? -1 : a.causal ? min((q0 + 31) / 32, nkeys / 32 - 1) : nkeys / 32 - 1;
+  for (int c0 = 0; c0 < nkeys; c0 += CH) {
+    const int nr = min(CH, nkeys - c0);
+    stage_rows<P, DHT, S16>(sK, ST::LDR, a.qkv, koff, 3 * H, c0, nr, L);
+    stage_rows_T<P, DHT, S16>(sVT, ST::LDT, a.qkv, voff, 3 * H, c0, nr, L);
+    for (int t = threadIdx.x; t < nr; t += blockDim.x) sMask[t] = (c0 + t < L) ? a.key_mask[tok0 + c0 + t] : 0;
+    __syncthreads();
+    const int kb_hi = min(kb_end, (c0 + nr) / 32 - 1);
+    for (int kb = c0 / 32; kb <= kb_hi; ++kb) {
+      f32x16 s;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = 0.f;
+      P::tile_nreg(s, sK, ST::LDR, kb * 32 - c0, qreg.regs(), DHT);
+      float bmax = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = kb * 32 + xf_acc_row(r, lane);
+        const bool vis = (key <= q || !a.causal) && sMask[key - c0];
+        s[r] = vis ? s[r] * sc : -INFINITY;
+        bmax = fmaxf(bmax, s[r]);
+      }
+      bmax = fmaxf(bmax, xf_half_swap(bmax));
+      const float mnew = fmaxf(m, bmax);
+      if (__all(mnew == -INFINITY)) continue;  // nothing visible yet for any query of this wave
+      const float msafe = (mnew == -INFINITY) ? 0.f : mnew;
+      const float alpha = exp2f(m - msafe);  // m = -inf -> 0
+      float psum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = exp2f(s[r] - msafe);  // masked: exp2(-inf) = 0
+        psum += p;
+        s[r] = a.drop.on ? p * xf_keep_scale_rc(a.drop, rowkey, (uint32_t)(kb * 32 + xf_acc_row(r, lane)) * kDropColMul) : p;
+      }
+      lsum = lsum * alpha + psum;
+#pragma unroll
+      for (int j = 0; j < ND; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[j][r] *= alpha;
+      m = mnew;
+#pragma unroll
+      for (int j = 0; j < ND; ++j) P::tile_xb(o[j], sVT, ST::LDT, 32 * j, kb * 32 - c0, s);
+    }
+    __syncthreads();  // every wave is done with the chunk (and, after the last one, with the images the scratch aliases)
+  }
+  if (!active) return;
+  const float ltot = lsum + xf_half_swap(lsum);
+  const float inv = ltot > 0.f ? 1.f / ltot : 0.f;
+#pragma unroll
+  for (int j = 0; j < ND; ++j)
+    xf_store_tile_T_at<S16>(scratch + wid * 32 * 33, o[j], inv, a.ctx, tok0 * H + h * DHT + 32 * j, H, q0, L);
+  if (lane < 32 && q < L)
+    a.lse[((int64_t)blockIdx.y) * L + q] = ltot > 0.f ? (m + log2f(ltot)) * kLn2 : INFINITY;
+}
+
+template <class P, int DHT, bool S16>
+__global__ __launch_bounds__(256) void attn_bwd_dq_stream_kernel(const AttnArgs a_in) {
+  AttnArgs a = a_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
+  XF_CHAIN_PRIO();
+  a.drop = xf_drop_resolve(a.drop);
+  using elem = typename P::elem;
+  using ST = AttnStream<P, DHT>;
+  constexpr int ND = DHT / 32, CH = ST::CH;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int L = a.L, H = a.H;
+  const int b = blockIdx.y / a.A, h = blockIdx.y % a.A;
+  const int qblk0 = blockIdx.x * 128;
+  const int nkeys = a.causal ? min(((L + 31) / 32) * 32, qblk0 + 128) : ((L + 31) / 32) * 32;
+  elem* sK = reinterpret_cast<elem*>(smem_raw);
+  elem* sV = reinterpret_cast<elem*>(smem_raw + ST::kRow);
+  elem* sKT = reinterpret_cast<elem*>(smem_raw + 2 * ST::kRow);
+  float* scratch = reinterpret_cast<float*>(smem_raw);  // after the last chunk
+  uint8_t* sMask = smem_raw + ST::kDqImg;
+
+  const int64_t tok0 = (int64_t)b * L;
+  const int64_t koff = tok0 * 3 * H + H + h * DHT, voff = tok0 * 3 * H + 2 * H + h * DHT;
+  const int lane = xf_lane(), wid = threadIdx.x >> 6;
+  const int q0 = qblk0 + wid * 32;
+  const bool active = q0 < L;  // (wave-uniform)
+  const int q = q0 + (lane & 31);
+  const bool qv = q < L;
+  RegRows<P, DHT> qreg, doreg;
+  load_reg_rows<P, DHT, S16>(qreg, a.qkv, (tok0 + q) * 3 * H + h * DHT, qv);
+  load_reg_rows<P, DHT, S16>(doreg, a.d_ctx, (tok0 + q) * H + h * DHT, qv);
+  float delta = 0.f;  // as attn_bwd_dq_kernel
+  if (qv) {
+    const int64_t o0 = (tok0 + q) * H + h * DHT + (DHT / 2) * (lane >> 5);
+#pragma unroll
+    for (int u = 0; u < DHT / 8; ++u) {
+      const float4 x = xf_ld4<S16>(a.ctx, o0 + 4 * u);
+      const float4 y = xf_ld4<S16>(a.d_ctx, o0 + 4 * u);
+      delta += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
+    }
+  }
+  delta += xf_half_swap(delta);
+  const float lse2 = qv ? a.lse[(int64_t)blockIdx.y * L + q] * kLog2e : INFINITY;
+  const float sc = attn_scale<DHT>() * kLog2e;
+  const uint32_t rowkey = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blockIdx.y * L + q));
+
+  f32x16 dq[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dq[j][r] = 0.f;
+  const int kb_end = !active ? -1 : a.causal ? min((q0 + 31) / 32, nkeys / 32 - 1) : nkeys / 32 - 1;
+  for (int c0 = 0; c0 < nkeys; c0 += CH) {
+    const int nr = min(CH, nkeys - c0);
+    stage_rows<P, DHT, S16>(sK, ST::LDR, a.qkv, koff, 3 * H, c0, nr, L);
+    stage_rows<P, DHT, S16>(sV, ST::LDR, a.qkv, voff, 3 * H, c0, nr, L);
+    stage_rows_T<P, DHT, S16>(sKT, ST::LDT, a.qkv, koff, 3 * H, c0, nr, L);
+    for (int t = threadIdx.x; t < nr; t += blockDim.x) sMask[t] = (c0 + t < L) ? a.key_mask[tok0 + c0 + t] : 0;
+    __syncthreads();
+    const int kb_hi = min(kb_end, (c0 + nr) / 32 - 1);
+    for (int kb = c0 / 32; kb <= kb_hi; ++kb) {
+      f32x16 s, dp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+      P::tile_nreg(s, sK, ST::LDR, kb * 32 - c0, qreg.regs(), DHT);
+      P::tile_nreg(dp, sV, ST::LDR, kb * 32 - c0, doreg.regs(), DHT);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = kb * 32 + xf_acc_row(r, lane);
+        const bool vis = (key <= q || !a.causal) && sMask[key - c0];
+        const float p = vis ? exp2f(s[r] * sc - lse2) : 0.f;
+        float dpv = dp[r];
+        if (a.drop.on) dpv *= xf_keep_scale_rc(a.drop, rowkey, (uint32_t)key * kDropColMul);
+        s[r] = p * (dpv - delta);
+      }
+#pragma unroll
+      for (int j = 0; j < ND; ++j) P::tile_xb(dq[j], sKT, ST::LDT, 32 * j, kb * 32 - c0, s);
+    }
+    __syncthreads();  // every wave is done with the chunk (and, after the last one, with the images the scratch aliases)
+  }
+  if (!active) return;
+#pragma unroll
+  for (int j = 0; j < ND; ++j)
+    xf_store_tile_T_at<S16>(scratch + wid * 32 * 33, dq[j], attn_scale<DHT>(), a.d_qkv, tok0 * 3 * H + h * DHT + 32 * j, 3 * H,
+                            q0, L);
+}
+
+template <class P, int DHT, bool S16>
+__global__ __launch_bounds__(256) void attn_bwd_dkv_stream_kernel(const AttnArgs a_in) {
+  AttnArgs a = a_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
+  XF_CHAIN_PRIO();
+  a.drop = xf_drop_resolve(a.drop);
+  using elem = typename P::elem;
+  using ST = AttnStream<P, DHT>;
+  constexpr int ND = DHT / 32, CPR = DHT / 4, CH = ST::CH;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int L = a.L, H = a.H;
+  const int b = blockIdx.y / a.A, h = blockIdx.y % a.A;
+  const int kblk0 = blockIdx.x * 128;   // first key of this workgroup
+  const int qs = a.causal ? kblk0 : 0;  // first query its keys are visible to
+  const int Lp = ((L + 31) / 32) * 32;  // queries [qs, Lp) stream through in chunks; image row = q - c0
+  elem* sQ = reinterpret_cast<elem*>(smem_raw);
+  elem* sDO = reinterpret_cast<elem*>(smem_raw + ST::kRow);
+  elem* sQT = reinterpret_cast<elem*>(smem_raw + 2 * ST::kRow);
+  elem* sDOT = reinterpret_cast<elem*>(smem_raw + 2 * ST::kRow + ST::kT);
+  float* scratch = reinterpret_cast<float*>(smem_raw);  // after the last chunk
+  float* sLse = reinterpret_cast<float*>(smem_raw + ST::kDkvImg);  // [CH] log2-scaled lse
+  float* sDelta = sLse + CH;                                         // [CH]
+
+  const int64_t tok0 = (int64_t)b * L;
+  const int64_t qoff = tok0 * 3 * H + h * DHT, dooff = tok0 * H + h * DHT;
+  const int lane = xf_lane(), wid = threadIdx.x >> 6;
+  const int k0 = kblk0 + wid * 32;
+  const bool active = k0 < L;  // (wave-uniform)
+  const int key = k0 + (lane & 31);
+  const bool kvis = key < L && a.key_mask[tok0 + (key < L ? key : 0)];
+  RegRows<P, DHT> kreg, vreg;
+  load_reg_rows<P, DHT, S16>(kreg, a.qkv, (tok0 + key) * 3 * H + H + h * DHT, key < L);
+  load_reg_rows<P, DHT, S16>(vreg, a.qkv, (tok0 + key) * 3 * H + 2 * H + h * DHT, key < L);
+  const float sc = attn_scale<DHT>() * kLog2e;
+
+  f32x16 dk[ND], dv[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dk[j][r] = 0.f; dv[j][r] = 0.f; }
+  const int qb_lo = !active ? Lp / 32 : a.causal ? k0 / 32 : 0;
+  for (int c0 = qs; c0 < Lp; c0 += CH) {
+    const int nr = min(CH, Lp - c0);
+    stage_rows<P, DHT, S16>(sQ, ST::LDR, a.qkv, qoff, 3 * H, c0, nr, L);
+    stage_rows<P, DHT, S16>(sDO, ST::LDR, a.d_ctx, dooff, H, c0, nr, L);
+    stage_rows_T<P, DHT, S16>(sQT, ST::LDT, a.qkv, qoff, 3 * H, c0, nr, L);
+    stage_rows_T<P, DHT, S16>(sDOT, ST::LDT, a.d_ctx, dooff, H, c0, nr, L);
+    for (int c = threadIdx.x; c < nr * CPR; c += blockDim.x) {  // delta: CPR consecutive lanes share a row
+      const int r = c / CPR, dd = (c % CPR) * 4;
+      float part = 0.f;
+      if (c0 + r < L) {
+        const float4 x = xf_ld4<S16>(a.ctx, dooff + (int64_t)(c0 + r) * H + dd);
+        const float4 y = xf_ld4<S16>(a.d_ctx, dooff + (int64_t)(c0 + r) * H + dd);
+        part = x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
+      }
+#pragma unroll
+      for (int o = 1; o < CPR; o <<= 1) part += __shfl_xor(part, o, 64);
+      if ((c % CPR) == 0) {
+        sDelta[r] = part;
+        sLse[r] = (c0 + r < L) ? a.lse[(int64_t)blockIdx.y * L + c0 + r] * kLog2e : INFINITY;
+      }
+    }
+    __syncthreads();
+    const int qb_hi = (c0 + nr) / 32;
+    for (int qb = max(qb_lo, c0 / 32); qb < qb_hi; ++qb) {
+      const int row0 = qb * 32 - c0;
+      f32x16 s, dp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+      P::tile_nreg(s, sQ, ST::LDR, row0, kreg.regs(), DHT);
+      P::tile_nreg(dp, sDO, ST::LDR, row0, vreg.regs(), DHT);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qi = row0 + xf_acc_row(r, lane);
+        const int q = qi + c0;
+        const bool vis = kvis && (key <= q || !a.causal);
+        const float p = vis ? exp2f(s[r] * sc - sLse[qi]) : 0.f;  // q >= L: lse = +inf -> 0
+        float keep = 1.f;
+        if (a.drop.on) keep = xf_keep_scale_rc(a.drop, xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blockIdx.y * L + q)), (uint32_t)key * kDropColMul);
+        s[r] = p * (dp[r] * keep - sDelta[qi]);  // dS
+        dp[r] = p * keep;                        // P.D
+      }
+#pragma unroll
+      for (int j = 0; j < ND; ++j) {
+        P::tile_xb(dv[j], sDOT, ST::LDT, 32 * j, row0, dp);
+        P::tile_xb(dk[j], sQT, ST::LDT, 32 * j, row0, s);
+      }
+    }
+    __syncthreads();  // every wave is done with the chunk (and, after the last one, with the images the scratch aliases)
+  }
+  if (!active) return;
   float* sc_w = scratch + wid * 32 * 33;
 #pragma unroll
   for (int j = 0; j < ND; ++j) {
@@ -1520,11 +1828,22 @@ int launch_bwd_bf16(const AttnArgs& a, hipStream_t st) {
 }
 
 // The generic kernels: fp32 policy at head size 32, and both policies at head size 64 (operands fp32, or bf16 when S16).
+// Where the whole panel fits LDS the panel kernels run; beyond that -- or with stream_keys (XFMR_ATTN_STREAM_KEYS, the
+// tests' streaming-vs-panel comparison) -- the key-streaming forms, whose LDS use does not depend on L.
 template <class P, int DHT, bool S16>
-int launch_fwd_generic(const AttnArgs& a, hipStream_t st) {
+int launch_fwd_generic(const AttnArgs& a, hipStream_t st, bool stream_keys) {
   dim3 grid((a.L + 127) / 128, a.B * a.A);
   const size_t sm = fwd_smem<P, DHT>(a.L);
-  if (sm > kLdsLimit) return XFMR_EUNSUPPORTED;
+  if (stream_keys || sm > kLdsLimit) {
+    using ST = AttnStream<P, DHT>;
+    static_assert(ST::fwd_bytes() <= kLdsLimit, "streaming forward LDS");
+    if (hipFuncSetAttribute((const void*)attn_fwd_stream_kernel<P, DHT, S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)ST::fwd_bytes()) != hipSuccess)
+      return XFMR_EHIP;
+    hipLaunchKernelGGL((attn_fwd_stream_kernel<P, DHT, S16>), grid, dim3(256), ST::fwd_bytes(), st, a);
+    XF_LAUNCH_CHECK();
+    return XFMR_OK;
+  }
   if (hipFuncSetAttribute((const void*)attn_fwd_kernel<P, DHT, S16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) !=
       hipSuccess)
     return XFMR_EHIP;
@@ -1533,10 +1852,23 @@ int launch_fwd_generic(const AttnArgs& a, hipStream_t st) {
   return XFMR_OK;
 }
 template <class P, int DHT, bool S16>
-int launch_bwd_generic(const AttnArgs& a, hipStream_t st) {
+int launch_bwd_generic(const AttnArgs& a, hipStream_t st, bool stream_keys) {
   dim3 grid((a.L + 127) / 128, a.B * a.A);
   const size_t s1 = dq_smem<P, DHT>(a.L), s2 = dkv_smem<P, DHT>(a.L);
-  if (s1 > kLdsLimit || s2 > kLdsLimit) return XFMR_EUNSUPPORTED;
+  if (stream_keys || s1 > kLdsLimit || s2 > kLdsLimit) {
+    using ST = AttnStream<P, DHT>;
+    static_assert(ST::dq_bytes() <= kLdsLimit && ST::dkv_bytes() <= kLdsLimit, "streaming backward LDS");
+    if (hipFuncSetAttribute((const void*)attn_bwd_dq_stream_kernel<P, DHT, S16>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ST::dq_bytes()) != hipSuccess ||
+        hipFuncSetAttribute((const void*)attn_bwd_dkv_stream_kernel<P, DHT, S16>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ST::dkv_bytes()) != hipSuccess)
+      return XFMR_EHIP;
+    hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<P, DHT, S16>), grid, dim3(256), ST::dq_bytes(), st, a);
+    XF_LAUNCH_CHECK();
+    hipLaunchKernelGGL((attn_bwd_dkv_stream_kernel<P, DHT, S16>), grid, dim3(256), ST::dkv_bytes(), st, a);
+    XF_LAUNCH_CHECK();
+    return XFMR_OK;
+  }
   if (hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<P, DHT, S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)s1) != hipSuccess ||
       hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<P, DHT, S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1549,26 +1881,30 @@ int launch_bwd_generic(const AttnArgs& a, hipStream_t st) {
   return XFMR_OK;
 }
 // precision x storage x head size -> kernel family
-int dispatch_fwd(const AttnArgs& a, int precision, bool s16, hipStream_t st) {
+int dispatch_fwd(const AttnArgs& a, int precision, bool s16, hipStream_t st, bool stream_keys) {
   const int dh = a.H / a.A;
   if (a.offs && !(precision == XFMR_PREC_BF16 && dh == 32)) return XFMR_EUNSUPPORTED;  // packed rows: production kernels only
   if (precision == XFMR_PREC_BF16) {
     if (dh == 32) return s16 ? launch_fwd_bf16<true>(a, st) : launch_fwd_bf16<false>(a, st);
-    return s16 ? launch_fwd_generic<PrecBF16, 64, true>(a, st) : launch_fwd_generic<PrecBF16, 64, false>(a, st);
+    return s16 ? launch_fwd_generic<PrecBF16, 64, true>(a, st, stream_keys)
+               : launch_fwd_generic<PrecBF16, 64, false>(a, st, stream_keys);
   }
   if (precision == XFMR_PREC_F32 && !s16)
-    return dh == 32 ? launch_fwd_generic<PrecF32, 32, false>(a, st) : launch_fwd_generic<PrecF32, 64, false>(a, st);
+    return dh == 32 ? launch_fwd_generic<PrecF32, 32, false>(a, st, stream_keys)
+                    : launch_fwd_generic<PrecF32, 64, false>(a, st, stream_keys);
   return XFMR_EINVAL;
 }
-int dispatch_bwd(const AttnArgs& a, int precision, bool s16, hipStream_t st) {
+int dispatch_bwd(const AttnArgs& a, int precision, bool s16, hipStream_t st, bool stream_keys) {
   const int dh = a.H / a.A;
   if (a.offs && !(precision == XFMR_PREC_BF16 && dh == 32)) return XFMR_EUNSUPPORTED;
   if (precision == XFMR_PREC_BF16) {
     if (dh == 32) return s16 ? launch_bwd_bf16<true>(a, st) : launch_bwd_bf16<false>(a, st);
-    return s16 ? launch_bwd_generic<PrecBF16, 64, true>(a, st) : launch_bwd_generic<PrecBF16, 64, false>(a, st);
+    return s16 ? launch_bwd_generic<PrecBF16, 64, true>(a, st, stream_keys)
+               : launch_bwd_generic<PrecBF16, 64, false>(a, st, stream_keys);
   }
   if (precision == XFMR_PREC_F32 && !s16)
-    return dh == 32 ? launch_bwd_generic<PrecF32, 32, false>(a, st) : launch_bwd_generic<PrecF32, 64, false>(a, st);
+    return dh == 32 ? launch_bwd_generic<PrecF32, 32, false>(a, st, stream_keys)
+                    : launch_bwd_generic<PrecF32, 64, false>(a, st, stream_keys);
   return XFMR_EINVAL;
 }
 
@@ -1584,7 +1920,7 @@ extern "C" {
 
 int xf_attn_fwd_ex(const void* qkv, const uint8_t* key_mask, void* ctx, float* lse, int32_t B, int32_t L, int32_t A,
                    int32_t H, float dropout_p, XfSeed seed, uint32_t site, int32_t precision, bool s16,
-                   bool causal, hipStream_t st, const int32_t* seq_offsets) {
+                   bool causal, hipStream_t st, const int32_t* seq_offsets, bool stream_keys) {
   if (!qkv || !key_mask || !ctx || !lse) return XFMR_EINVAL;
   if (int rc = check_shape(B, L, A, H)) return rc;
   if (!xf_aligned16(qkv) || !xf_aligned16(ctx)) return XFMR_EALIGN;
@@ -1592,7 +1928,7 @@ int xf_attn_fwd_ex(const void* qkv, const uint8_t* key_mask, void* ctx, float* l
   a.qkv = (const float*)qkv; a.key_mask = key_mask; a.ctx = (float*)ctx; a.lse = lse; a.B = B; a.L = L; a.A = A;
   a.H = H; a.causal = causal; a.offs = seq_offsets;
   a.drop = xf_make_dropout(dropout_p, seed, site);
-  return dispatch_fwd(a, precision, s16, st);
+  return dispatch_fwd(a, precision, s16, st, stream_keys);
 }
 
 int xfmr_attn_fwd(const float* qkv, const uint8_t* key_mask, float* ctx, float* lse, int32_t B, int32_t L,
@@ -1604,14 +1940,16 @@ int xfmr_attn_fwd(const float* qkv, const uint8_t* key_mask, float* ctx, float* 
 int xfmr_attn_fwd_mode(const float* qkv, const uint8_t* key_mask, float* ctx, float* lse, int32_t B, int32_t L,
                        int32_t A, int32_t H, float dropout_p, uint64_t seed, uint32_t site, int32_t precision,
                        int32_t attn_mode, void* stream) {
-  if (attn_mode != XFMR_ATTN_CAUSAL && attn_mode != XFMR_ATTN_BIDIRECTIONAL) return XFMR_EINVAL;
+  if (attn_mode & ~(XFMR_ATTN_BIDIRECTIONAL | XFMR_ATTN_STREAM_KEYS)) return XFMR_EINVAL;
   return xf_attn_fwd_ex(qkv, key_mask, ctx, lse, B, L, A, H, dropout_p, seed, site, precision, false,
-                        attn_mode == XFMR_ATTN_CAUSAL, (hipStream_t)stream);
+                        !(attn_mode & XFMR_ATTN_BIDIRECTIONAL), (hipStream_t)stream, nullptr,
+                        (attn_mode & XFMR_ATTN_STREAM_KEYS) != 0);
 }
 
 int xf_attn_bwd_ex(const void* qkv, const uint8_t* key_mask, const void* ctx, const float* lse, const void* d_ctx,
                    void* d_qkv, int32_t B, int32_t L, int32_t A, int32_t H, float dropout_p, XfSeed seed,
-                   uint32_t site, int32_t precision, bool s16, bool causal, hipStream_t st, const int32_t* seq_offsets) {
+                   uint32_t site, int32_t precision, bool s16, bool causal, hipStream_t st, const int32_t* seq_offsets,
+                   bool stream_keys) {
   if (!qkv || !key_mask || !ctx || !lse || !d_ctx || !d_qkv) return XFMR_EINVAL;
   if (int rc = check_shape(B, L, A, H)) return rc;
   if (!xf_aligned16(qkv) || !xf_aligned16(ctx) || !xf_aligned16(d_ctx) || !xf_aligned16(d_qkv)) return XFMR_EALIGN;
@@ -1620,7 +1958,7 @@ int xf_attn_bwd_ex(const void* qkv, const uint8_t* key_mask, const void* ctx, co
   a.lse = const_cast<float*>(lse); a.d_ctx = (const float*)d_ctx; a.d_qkv = (float*)d_qkv;
   a.B = B; a.L = L; a.A = A; a.H = H; a.causal = causal; a.offs = seq_offsets;
   a.drop = xf_make_dropout(dropout_p, seed, site);
-  return dispatch_bwd(a, precision, s16, st);
+  return dispatch_bwd(a, precision, s16, st, stream_keys);
 }
 
 int xfmr_attn_bwd(const float* qkv, const uint8_t* key_mask, const float* ctx, const float* lse,
@@ -1632,9 +1970,10 @@ int xfmr_attn_bwd(const float* qkv, const uint8_t* key_mask, const float* ctx, c
 int xfmr_attn_bwd_mode(const float* qkv, const uint8_t* key_mask, const float* ctx, const float* lse,
                        const float* d_ctx, float* d_qkv, int32_t B, int32_t L, int32_t A, int32_t H, float dropout_p,
                        uint64_t seed, uint32_t site, int32_t precision, int32_t attn_mode, void* stream) {
-  if (attn_mode != XFMR_ATTN_CAUSAL && attn_mode != XFMR_ATTN_BIDIRECTIONAL) return XFMR_EINVAL;
+  if (attn_mode & ~(XFMR_ATTN_BIDIRECTIONAL | XFMR_ATTN_STREAM_KEYS)) return XFMR_EINVAL;
   return xf_attn_bwd_ex(qkv, key_mask, ctx, lse, d_ctx, d_qkv, B, L, A, H, dropout_p, seed, site, precision, false,
-                        attn_mode == XFMR_ATTN_CAUSAL, (hipStream_t)stream);
+                        !(attn_mode & XFMR_ATTN_BIDIRECTIONAL), (hipStream_t)stream, nullptr,
+                        (attn_mode & XFMR_ATTN_STREAM_KEYS) != 0);
 }
 
 }  // extern "C"

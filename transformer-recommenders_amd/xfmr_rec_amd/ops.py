@@ -135,30 +135,35 @@ def colsum(a):
     return out
 
 
-def attn_fwd(qkv, key_mask, heads, *, dropout_p=0.0, seed=0, site=0, precision="bf16", causal=True):
+def attn_fwd(qkv, key_mask, heads, *, dropout_p=0.0, seed=0, site=0, precision="bf16", causal=True, stream_keys=False):
+    """stream_keys: the key-streaming form of the generic kernels (fp32 policy, head size 64) even where the whole-panel
+    form fits LDS -- bit-identical results; the bf16 policy at head size 32 ignores it."""
     B, L, H3 = qkv.shape
     H = H3 // 3
     ctx, lse = _empty((B, L, H), qkv), _empty((B, heads, L), qkv)
     lib = N.load()
     head = (N.ptr(qkv), N.ptr(key_mask), N.ptr(ctx), N.ptr(lse), B, L, heads, H, dropout_p, seed, site,
             N.precision_id(precision))
-    if causal:
+    if causal and not stream_keys:
         N.check(lib.xfmr_attn_fwd(*head, N.stream()), "xfmr_attn_fwd")
     else:
-        N.check(lib.xfmr_attn_fwd_mode(*head, N.ATTN_BIDIRECTIONAL, N.stream()), "xfmr_attn_fwd_mode")
+        mode = (N.ATTN_CAUSAL if causal else N.ATTN_BIDIRECTIONAL) | (N.ATTN_STREAM_KEYS if stream_keys else 0)
+        N.check(lib.xfmr_attn_fwd_mode(*head, mode, N.stream()), "xfmr_attn_fwd_mode")
     return ctx, lse
 
 
-def attn_bwd(qkv, key_mask, ctx, lse, d_ctx, heads, *, dropout_p=0.0, seed=0, site=0, precision="bf16", causal=True):
+def attn_bwd(qkv, key_mask, ctx, lse, d_ctx, heads, *, dropout_p=0.0, seed=0, site=0, precision="bf16", causal=True,
+             stream_keys=False):
     B, L, H3 = qkv.shape
     d_qkv = torch.empty_like(qkv)
     lib = N.load()
     head = (N.ptr(qkv), N.ptr(key_mask), N.ptr(ctx), N.ptr(lse), N.ptr(d_ctx), N.ptr(d_qkv), B, L, heads, H3 // 3,
             dropout_p, seed, site, N.precision_id(precision))
-    if causal:
+    if causal and not stream_keys:
         N.check(lib.xfmr_attn_bwd(*head, N.stream()), "xfmr_attn_bwd")
     else:
-        N.check(lib.xfmr_attn_bwd_mode(*head, N.ATTN_BIDIRECTIONAL, N.stream()), "xfmr_attn_bwd_mode")
+        mode = (N.ATTN_CAUSAL if causal else N.ATTN_BIDIRECTIONAL) | (N.ATTN_STREAM_KEYS if stream_keys else 0)
+        N.check(lib.xfmr_attn_bwd_mode(*head, mode, N.stream()), "xfmr_attn_bwd_mode")
     return d_qkv
 
 
