@@ -348,6 +348,13 @@ int xfmr_pool(const float* tok, const uint8_t* key_mask, float* out, int32_t B, 
               void* stream);
 int xfmr_mean_pool(const float* tok, const uint8_t* key_mask, float* out, int32_t B, int32_t L, int32_t H,
                    void* stream);
+/* xfmr_pool over the PACKED layout (xfmr_encoder_cfg.seq_offsets): tok (rows,H) holds each sequence's own rows only,
+ * sequence b = rows [seq_offsets[b], seq_offsets[b+1]) (int32, B+1 entries, as xfmr_pack_rows writes them); out (B,H).
+ * normalize != 0 applies xfmr_l2_normalize_fwd (eps) to every output row in the same launch. On a non-empty sequence the
+ * result is bit-identical to xfmr_pool (+ xfmr_l2_normalize_fwd) on the right-padded layout; an EMPTY sequence gives a
+ * zero row (normalised: still zero). */
+int xfmr_pool_rows(const float* tok, const int32_t* seq_offsets, float* out, int32_t B, int32_t H, int32_t mode,
+                   int32_t normalize, float eps, void* stream);
 
 /* Row-wise L2 normalisation y = x / max(|x|, eps) and its backward: torch.nn.functional.normalize on the query
  * embeddings when ModelConfig.is_normalized (xfmr_rec/models.py:393-394, eps 1e-12) and the sentence-transformers
@@ -539,6 +546,23 @@ int xfmr_topk(const float* query, const float* table, const float* table_rnorm, 
               int64_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes, void* stream);
 int xfmr_retrieval_metrics(const int64_t* rec_idx, const int64_t* targets, const int64_t* target_offsets, int32_t n_query,
                            int32_t k, int32_t top_k, float* out, uint8_t* valid, void* stream);
+/* xfmr_topk_tiled: the same search as xfmr_topk for MANY queries, with no per-(query, item) workspace. Arguments and
+ * results as xfmr_topk, except:
+ *   - table_sqnorm (n_rows): squared row norms (xfmr_table_sqnorm), read by the l2 metric only (may be NULL otherwise);
+ *     table_rnorm is read by the cosine metric only;
+ *   - each query's exclude list must be SORTED ascending (duplicates and out-of-range ids are harmless);
+ *   - only finite scores are returned;
+ *   - k <= 128, n_rows < 2^31, n_query < 2^31; H a multiple of 4, <= 1024; query and table 16-byte aligned.
+ * Scores are exact f32 MFMA dot products: they differ from xfmr_topk's only by summation order. The result is
+ * bit-identical from run to run. Workspace: xfmr_topk_tiled_workspace bytes = O(n_query * k * slices), slices <= 16.
+ * xfmr_topk stays the kernel for one or a few queries (one workgroup spread over each query). */
+size_t xfmr_topk_tiled_workspace(int64_t n_query, int64_t n_rows, int32_t k);
+int xfmr_topk_tiled(const float* query, const float* table, const float* table_rnorm, const float* table_sqnorm,
+                    int64_t n_rows, int64_t n_query, int32_t H, const int64_t* exclude, const int64_t* exclude_offsets,
+                    int32_t k, int32_t metric, int64_t* out_idx, float* out_score, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* table_sqnorm[r] = |table[r]|^2 (the l2 metric's item term). */
+int xfmr_table_sqnorm(const float* table, float* table_sqnorm, int64_t n_rows, int32_t H, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K18: AdamW over the flat buffer (torch.optim.AdamW as configured at xfmr_rec/trainer.py:327-332:

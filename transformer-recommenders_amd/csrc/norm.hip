@@ -387,6 +387,51 @@ __global__ void pool_kernel(const float* tok, const uint8_t* mask, float* out, i
   out[(int64_t)b * H + c] = r;
 }
 
+// pool_kernel over the packed layout (sequence b = rows [off[b], off[b+1]) of tok), with the row normalisation of
+// l2norm_fwd_kernel fused. One wave per sequence, lane c owns columns c, c + 64, ...: each column's sum runs over the
+// sequence's rows in the order pool_kernel adds them, and the squared norm in l2norm_fwd_kernel's order, so the result
+// is bit-identical to the padded pair (padding rows add exact zeros to pool_kernel's mean). Empty sequence: zero row.
+__global__ __launch_bounds__(256) void pool_rows_kernel(const float* tok, const int32_t* off, float* out, int B, int H,
+                                                        int mode, int normalize, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int64_t r0 = off[b];
+  const int n = off[b + 1] - off[b];
+  float* o = out + (int64_t)b * H;
+  for (int c = lane; c < H; c += 64) {
+    const float* x = tok + r0 * H + c;
+    float r = 0.f;
+    if (n <= 0) {
+      r = 0.f;
+    } else if (mode == XFMR_POOL_MEAN) {
+      float s = 0.f, cnt = 0.f;
+      for (int t = 0; t < n; ++t) {
+        s += x[(int64_t)t * H];
+        cnt += 1.f;
+      }
+      r = s / fmaxf(cnt, 1e-9f);
+    } else if (mode == XFMR_POOL_MAX) {
+      r = -INFINITY;
+      for (int t = 0; t < n; ++t) r = fmaxf(r, x[(int64_t)t * H]);
+    } else if (mode == XFMR_POOL_CLS) {
+      r = x[0];
+    } else {
+      r = x[(int64_t)(n - 1) * H];
+    }
+    o[c] = r;
+  }
+  if (!normalize) return;
+  float s = 0.f;
+  for (int c = lane; c < H; c += 64) {
+    const float v = o[c];
+    s += v * v;
+  }
+  s = xf_wave_sum(s);
+  const float inv = 1.f / fmaxf(sqrtf(s), eps);
+  for (int c = lane; c < H; c += 64) o[c] = o[c] * inv;
+}
+
 // y = x / max(|x|, eps) per row (torch.nn.functional.normalize, models.py:393-394; sentence-transformers
 // Normalize, models.py:146-147). One wave per row.
 __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* x, float* y, float* inv_norm, int64_t rows, int H,
@@ -774,6 +819,17 @@ int xfmr_pool(const float* tok, const uint8_t* key_mask, float* out, int32_t B, 
 int xfmr_mean_pool(const float* tok, const uint8_t* key_mask, float* out, int32_t B, int32_t L, int32_t H,
                    void* stream) {
   return xfmr_pool(tok, key_mask, out, B, L, H, XFMR_POOL_MEAN, stream);
+}
+
+int xfmr_pool_rows(const float* tok, const int32_t* seq_offsets, float* out, int32_t B, int32_t H, int32_t mode,
+                   int32_t normalize, float eps, void* stream) {
+  if (!tok || !seq_offsets || !out || B <= 0 || H <= 0) return XFMR_EINVAL;
+  if (mode < XFMR_POOL_MEAN || mode > XFMR_POOL_LASTTOKEN) return XFMR_EINVAL;
+  if (normalize && !(eps > 0.f)) return XFMR_EINVAL;
+  hipLaunchKernelGGL(pool_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tok, seq_offsets,
+                     out, B, H, mode, normalize, eps);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
 }
 
 int xfmr_l2_normalize_fwd(const float* x, float* y, float* inv_norm, int64_t rows, int32_t H, float eps, void* stream) {

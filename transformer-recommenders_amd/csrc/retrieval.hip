@@ -7,6 +7,8 @@
 //   topk_kernel     one workgroup per query: scores for every item (16 lanes per item, 16-byte pieces), the query's
 //                   history and the padding row masked out, the k-th largest score by a 4-pass radix select, ordered
 //                   compaction (ties: lower item index first), bitonic sort of the k survivors, best first
+//   topk_tiled_kernel + topk_merge_kernel  the same search for many queries at once (MFMA score tiles, streaming
+//                   top-k, no per-(query, item) workspace): see the comment above topk_tiled_kernel
 //   metrics_kernel  one thread per query: nDCG, MAP, AUROC, precision, recall, hit rate, MRR at k from the ranked
 //                   list and the user's target set, with torchmetrics' definitions for a strictly decreasing score
 //                   vector over [recommendations | missing targets] (metrics.py:66-79)
@@ -248,6 +250,301 @@ __global__ void metrics_kernel(const int64_t* rec, const int64_t* tgt, const int
   o[6] = rr;
 }
 
+
+// ---- tiled top-k: score tiles on the matrix cores and a streaming top-k (xfmr_topk_tiled) --------------------------
+// topk_kernel above is one workgroup per query: every query re-reads the whole table through VALU dot products and
+// keeps an n_query x n_rows score workspace. That is the right kernel for ONE query (a single query spread over a whole
+// workgroup; here it would fill one row of a 32-row MFMA tile) and the wrong one for a whole user set (6 040 users x a
+// 6 MB table = 36 GB of table reads). topk_tiled_kernel instead:
+//   - a workgroup owns TT_Q = 32 queries and one slice of the catalogue; its four waves score 32 x 32 blocks of
+//     (query, item) with v_mfma_f32_32x32x2_f32 -- exact f32, bit for bit a k-ordered fmaf chain, so the scores differ
+//     from topk_kernel's only in summation order. 32 queries rather than 64 because each query's candidate list and
+//     running top-k (double-buffered) live in LDS: 96 KB at k = 128. Operands are read straight from global memory,
+//     not staged through LDS: the 32 query rows are shared by the four waves (L1 hits), every item row is read by one
+//     wave once per query tile, and the f32 MFMA rate (64 FLOP/clk/SIMD) needs only 16 B/clk per CU of item rows.
+//   - the epilogue applies topk_kernel's formulas, masks row 0, rows past the slice and non-finite scores, and keeps a
+//     per-query threshold (the current k-th best, ties broken by the lower item index). Only scores that beat it are
+//     checked against the query's SORTED exclusion list (binary search) and appended to an LDS candidate list; when a
+//     list fills, or at the end of the slice, the candidates are sorted and merged into the running top-k. A tile
+//     whose candidates overflowed a list is re-offered after the merge (against the new threshold).
+//   - grid = (query tiles, slices), slices chosen so that the grid covers the chip; topk_merge_kernel then merges each
+//     query's per-slice lists into the final sorted k. Scratch: n_query x slices x k (score, index) pairs, no
+//     per-(query, item) workspace. No float atomics: the candidate order inside a list depends on LDS atomics, the
+//     result does not (every list is sorted by (score desc, index asc), a total order), so runs are bit-identical.
+constexpr int TT_Q = 32;         // queries per workgroup (one 32-row MFMA tile)
+constexpr int TT_N = 128;        // items per tile (4 waves x 32)
+constexpr int TT_C = 128;        // candidate list per query (a power of two: bitonic sort)
+constexpr int TT_KMAX = 128;
+constexpr int TT_MAX_SPLITS = 16;
+constexpr int TT_TARGET_WG = 512;  // 256 CUs x 2 resident workgroups
+constexpr int TT_IDX_NONE = 0x7fffffff;
+
+struct TiledPlan { int splits; int64_t slice; };
+
+static TiledPlan tiled_plan(int64_t n_query, int64_t n_rows) {
+  const int64_t qtiles = (n_query + TT_Q - 1) / TT_Q;
+  const int64_t itiles = (n_rows + TT_N - 1) / TT_N;
+  int64_t s = (TT_TARGET_WG + qtiles - 1) / qtiles;
+  if (s > TT_MAX_SPLITS) s = TT_MAX_SPLITS;
+  if (s > itiles) s = itiles;
+  if (s < 1) s = 1;
+  TiledPlan p;
+  p.slice = ((itiles + s - 1) / s) * TT_N;
+  p.splits = (int)((n_rows + p.slice - 1) / p.slice);
+  return p;
+}
+
+static int tiled_kp(int k) {
+  int kp = 1;
+  while (kp < k) kp <<= 1;
+  return kp;
+}
+
+static size_t tiled_lds_bytes(int kp) {
+  return (size_t)TT_Q * TT_C * 8 + (size_t)2 * TT_Q * kp * 8;
+}
+
+struct TiledArgs {
+  const float* q; const float* table; const float* rnorm; const float* sqnorm; int n_rows; int n_query;
+  const int64_t* excl; const int64_t* excl_off;
+  float* ws_score; int* ws_idx;  // [n_query][splits][k]
+  int H, k, kp, metric, splits;
+  int64_t slice;  // items per slice, a multiple of TT_N
+};
+
+__device__ __forceinline__ bool tt_better(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
+
+// number of entries of the best-first list (s, ix)[0..n) that are better than (v, iv)
+__device__ __forceinline__ int tt_count_better(const float* s, const int* ix, int n, float v, int iv) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tt_better(s[mid], ix[mid], v, iv)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// item `it` in the sorted list ex[lo..hi)
+__device__ __forceinline__ bool tt_excluded(const int64_t* ex, int64_t lo, int64_t hi, int it) {
+  const int64_t end = hi;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (ex[mid] < it) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < end && ex[lo] == it;
+}
+
+// Sorts every query's candidates and merges them into its running list (buffer `cur` -> 1 - cur); new thresholds.
+// Called by all threads of the workgroup; returns the new buffer index.
+__device__ int tt_merge(const TiledArgs& a, float* cS, int* cI, float* lS, int* lI, int cur, int* cnt, float* thrS,
+                        int* thrI, int* flag) {
+  const int tid = threadIdx.x, kp = a.kp;
+  for (int x = tid; x < TT_Q * TT_C; x += 256) {
+    const int i = x / TT_C, e = x % TT_C;
+    if (e >= min(cnt[i], TT_C)) { cS[x] = -INFINITY; cI[x] = TT_IDX_NONE; }
+  }
+  __syncthreads();
+  for (int size = 2; size <= TT_C; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int x = tid; x < TT_Q * TT_C / 2; x += 256) {
+        const int i = x / (TT_C / 2), p = x % (TT_C / 2);
+        const int e = 2 * p - (p & (stride - 1)), f = e + stride;
+        const bool up = (e & size) == 0;  // "up" blocks hold the better element first
+        float* s = cS + i * TT_C;
+        int* ix = cI + i * TT_C;
+        const float se = s[e], sf = s[f];
+        const int ie = ix[e], jf = ix[f];
+        if (tt_better(sf, jf, se, ie) == up) { s[e] = sf; s[f] = se; ix[e] = jf; ix[f] = ie; }
+      }
+      __syncthreads();
+    }
+  }
+  // merge path: rank of an entry = its place in its own list + the entries of the other list that are better
+  const int nxt = 1 - cur;
+  for (int x = tid; x < TT_Q * (kp + TT_C); x += 256) {
+    const int i = x / (kp + TT_C), e = x % (kp + TT_C);
+    const float* ls = lS + (cur * TT_Q + i) * kp;
+    const int* li = lI + (cur * TT_Q + i) * kp;
+    const float* cs = cS + i * TT_C;
+    const int* ci = cI + i * TT_C;
+    float v; int iv, rank;
+    if (e < kp) { v = ls[e]; iv = li[e]; rank = e + tt_count_better(cs, ci, TT_C, v, iv); }
+    else { v = cs[e - kp]; iv = ci[e - kp]; rank = (e - kp) + tt_count_better(ls, li, kp, v, iv); }
+    if (rank < kp) { lS[(nxt * TT_Q + i) * kp + rank] = v; lI[(nxt * TT_Q + i) * kp + rank] = iv; }
+  }
+  __syncthreads();
+  if (tid < TT_Q) {
+    thrS[tid] = lS[(nxt * TT_Q + tid) * kp + a.k - 1];
+    thrI[tid] = lI[(nxt * TT_Q + tid) * kp + a.k - 1];
+    cnt[tid] = 0;
+  }
+  if (tid == 0) *flag = 0;
+  __syncthreads();
+  return nxt;
+}
+
+__global__ __launch_bounds__(256) void topk_tiled_kernel(TiledArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tt_lds[];
+  __shared__ float sQQ[TT_Q], sRQ[TT_Q], thrS[TT_Q];
+  __shared__ int thrI[TT_Q], cnt[TT_Q], flag;
+  float* cS = reinterpret_cast<float*>(tt_lds);
+  int* cI = reinterpret_cast<int*>(cS + TT_Q * TT_C);
+  float* lS = reinterpret_cast<float*>(cI + TT_Q * TT_C);
+  int* lI = reinterpret_cast<int*>(lS + 2 * TT_Q * a.kp);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int H = a.H;
+  const int q0 = blockIdx.x * TT_Q;
+  const int split = blockIdx.y;
+  const int64_t lo = split * a.slice;
+  const int64_t hi = lo + a.slice < a.n_rows ? lo + a.slice : a.n_rows;
+  // ---- query norms: 8 threads per query ------------------------------------------------------------------------
+  {
+    const int i = tid >> 3, part = tid & 7;
+    float qq = 0.f;
+    if (q0 + i < a.n_query) {
+      const float* qr = a.q + (int64_t)(q0 + i) * H;
+      for (int h = 4 * part; h < H; h += 32) {
+        const float4 v = *reinterpret_cast<const float4*>(qr + h);
+        qq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, qq))));
+      }
+    }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) qq += __shfl_xor(qq, o, 64);
+    if (part == 0) {
+      sQQ[i] = qq;
+      sRQ[i] = 1.f / fmaxf(sqrtf(qq), 1e-8f);
+      thrS[i] = -INFINITY;
+      thrI[i] = TT_IDX_NONE;
+      cnt[i] = 0;
+    }
+  }
+  for (int x = tid; x < TT_Q * a.kp; x += 256) { lS[x] = -INFINITY; lI[x] = TT_IDX_NONE; }
+  if (tid == 0) flag = 0;
+  __syncthreads();
+  int cur = 0;
+  const int h2 = lane >> 5;
+  const float* qa = a.q + (int64_t)min(q0 + (lane & 31), a.n_query - 1) * H + 4 * h2;
+  for (int64_t t0 = lo; t0 < hi; t0 += TT_N) {
+    const int64_t j64 = t0 + 32 * w + (lane & 31);  // this lane's item (accumulator column)
+    const bool jok = j64 >= 1 && j64 < hi;
+    const int j = jok ? (int)j64 : 0;
+    const float* eb = a.table + (int64_t)j * H + 4 * h2;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    // k-step order: dims 8c + 4h2 + {0..3} -- lane half h2 supplies k = h2 of each MFMA, both operands alike
+#pragma unroll 4
+    for (int c = 0; c < H; c += 8) {
+      float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
+      if (c + 4 * h2 < H) {
+        x = *reinterpret_cast<const float4*>(qa + c);
+        y = *reinterpret_cast<const float4*>(eb + c);
+      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, y.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, y.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, y.w, acc, 0, 0, 0);
+    }
+    // ---- epilogue: scores, masks, threshold, candidates ------------------------------------------------------------
+    float rn = 0.f, ee = 0.f;
+    if (jok) {
+      if (a.metric == XFMR_METRIC_COSINE) rn = a.rnorm[j];
+      else if (a.metric == XFMR_METRIC_L2) ee = a.sqnorm[j];
+    }
+    float sc[16];
+    unsigned pending = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = xf_acc_row(r, lane);
+      const float dot = acc[r];
+      float s;
+      if (a.metric == XFMR_METRIC_COSINE) s = dot * sRQ[i] * rn;
+      else if (a.metric == XFMR_METRIC_DOT) s = dot;
+      else s = 1.f - (sQQ[i] - 2.f * dot + ee);
+      sc[r] = s;
+      if (jok && q0 + i < a.n_query && s > -INFINITY && s < INFINITY) pending |= 1u << r;
+    }
+    while (true) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (!((pending >> r) & 1u)) continue;
+        const int i = xf_acc_row(r, lane);
+        bool drop = !tt_better(sc[r], j, thrS[i], thrI[i]);
+        if (!drop && a.excl) drop = tt_excluded(a.excl, a.excl_off[q0 + i], a.excl_off[q0 + i + 1], j);
+        if (!drop) {
+          const int pos = atomicAdd(&cnt[i], 1);
+          if (pos < TT_C) { cS[i * TT_C + pos] = sc[r]; cI[i * TT_C + pos] = j; }
+          else { flag = 1; continue; }  // list full: offered again after the merge
+        }
+        pending &= ~(1u << r);
+      }
+      __syncthreads();
+      if (!flag) break;
+      __syncthreads();
+      cur = tt_merge(a, cS, cI, lS, lI, cur, cnt, thrS, thrI, &flag);
+    }
+  }
+  cur = tt_merge(a, cS, cI, lS, lI, cur, cnt, thrS, thrI, &flag);
+  for (int x = tid; x < TT_Q * a.k; x += 256) {
+    const int i = x / a.k, e = x % a.k;
+    if (q0 + i >= a.n_query) continue;
+    const int64_t o = ((int64_t)(q0 + i) * a.splits + split) * a.k + e;
+    a.ws_score[o] = lS[(cur * TT_Q + i) * a.kp + e];
+    a.ws_idx[o] = lI[(cur * TT_Q + i) * a.kp + e];
+  }
+}
+
+// one workgroup per query: the query's splits x k (score, index) pairs -> bitonic sort -> the best k
+constexpr int TT_MERGE_MAX = TT_MAX_SPLITS * TT_KMAX;
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* ws_score, const int* ws_idx, int splits, int k,
+                                                         int64_t* out_idx, float* out_score) {
+  __shared__ float sS[TT_MERGE_MAX];
+  __shared__ int sI[TT_MERGE_MAX];
+  const int tid = threadIdx.x;
+  const int64_t qi = blockIdx.x;
+  const int n = splits * k;
+  int np2 = 1;
+  while (np2 < n) np2 <<= 1;
+  for (int x = tid; x < np2; x += 256) {
+    if (x < n) { sS[x] = ws_score[qi * n + x]; sI[x] = ws_idx[qi * n + x]; }
+    else { sS[x] = -INFINITY; sI[x] = TT_IDX_NONE; }
+  }
+  __syncthreads();
+  for (int size = 2; size <= np2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int p = tid; p < np2 / 2; p += 256) {
+        const int e = 2 * p - (p & (stride - 1)), f = e + stride;
+        const bool up = (e & size) == 0;
+        const float se = sS[e], sf = sS[f];
+        const int ie = sI[e], jf = sI[f];
+        if (tt_better(sf, jf, se, ie) == up) { sS[e] = sf; sS[f] = se; sI[e] = jf; sI[f] = ie; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int e = tid; e < k; e += 256) {
+    const bool real = sI[e] != TT_IDX_NONE;  // (only finite scores ever enter a list)
+    out_idx[qi * k + e] = real ? (int64_t)sI[e] : -1;
+    out_score[qi * k + e] = real ? sS[e] : -INFINITY;
+  }
+}
+
+// squared row norms for the l2 metric, one wave per row
+__global__ __launch_bounds__(256) void table_sqnorm_kernel(const float* table, float* out, int64_t n_rows, int H) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;
+  float s = 0.f;
+  for (int c = lane; c < H; c += 64) {
+    const float v = table[row * H + c];
+    s += v * v;
+  }
+  s = xf_wave_sum(s);
+  if (lane == 0) out[row] = s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,6 +578,56 @@ int xfmr_retrieval_metrics(const int64_t* rec_idx, const int64_t* targets, const
     return XFMR_EINVAL;
   hipLaunchKernelGGL(metrics_kernel, dim3((n_query + 63) / 64), dim3(64), 0, (hipStream_t)stream, rec_idx, targets,
                      target_offsets, n_query, k, top_k, out, valid);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
+
+
+size_t xfmr_topk_tiled_workspace(int64_t n_query, int64_t n_rows, int32_t k) {
+  if (n_query <= 0 || n_rows <= 0 || k <= 0) return 0;
+  const TiledPlan p = tiled_plan(n_query, n_rows);
+  const size_t n = (size_t)n_query * (size_t)p.splits * (size_t)k;
+  return n * sizeof(float) + n * sizeof(int);
+}
+
+int xfmr_topk_tiled(const float* query, const float* table, const float* table_rnorm, const float* table_sqnorm,
+                    int64_t n_rows, int64_t n_query, int32_t H, const int64_t* exclude, const int64_t* exclude_offsets,
+                    int32_t k, int32_t metric, int64_t* out_idx, float* out_score, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  if (!query || !table || !out_idx || !out_score || !workspace) return XFMR_EINVAL;
+  if (n_rows <= 0 || n_query <= 0 || H <= 0 || k <= 0) return XFMR_EINVAL;
+  if ((exclude == nullptr) != (exclude_offsets == nullptr)) return XFMR_EINVAL;
+  if (metric < XFMR_METRIC_COSINE || metric > XFMR_METRIC_L2) return XFMR_EINVAL;
+  if (metric == XFMR_METRIC_COSINE && !table_rnorm) return XFMR_EINVAL;
+  if (metric == XFMR_METRIC_L2 && !table_sqnorm) return XFMR_EINVAL;
+  if ((H & 3) || H > TOPK_MAX_H || k > TT_KMAX || n_rows >= (1ll << 31) || n_query >= (1ll << 31))
+    return XFMR_EUNSUPPORTED;
+  if (!xf_aligned16(query) || !xf_aligned16(table) || !xf_aligned16(workspace)) return XFMR_EALIGN;
+  if (workspace_bytes < xfmr_topk_tiled_workspace(n_query, n_rows, k)) return XFMR_EWORKSPACE;
+  const TiledPlan p = tiled_plan(n_query, n_rows);
+  const size_t n = (size_t)n_query * (size_t)p.splits * (size_t)k;
+  TiledArgs a{};
+  a.q = query; a.table = table; a.rnorm = table_rnorm; a.sqnorm = table_sqnorm; a.n_rows = (int)n_rows;
+  a.n_query = (int)n_query; a.excl = exclude; a.excl_off = exclude_offsets;
+  a.ws_score = (float*)workspace; a.ws_idx = (int*)((float*)workspace + n);
+  a.H = H; a.k = k; a.kp = tiled_kp(k); a.metric = metric; a.splits = p.splits; a.slice = p.slice;
+  const size_t lds = tiled_lds_bytes(a.kp);
+  if (hipFuncSetAttribute((const void*)topk_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+      hipSuccess)
+    return XFMR_EHIP;
+  const unsigned qtiles = (unsigned)((n_query + TT_Q - 1) / TT_Q);
+  hipLaunchKernelGGL(topk_tiled_kernel, dim3(qtiles, (unsigned)p.splits), dim3(256), lds, (hipStream_t)stream, a);
+  XF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)n_query), dim3(256), 0, (hipStream_t)stream, a.ws_score,
+                     a.ws_idx, p.splits, k, out_idx, out_score);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
+
+int xfmr_table_sqnorm(const float* table, float* table_sqnorm, int64_t n_rows, int32_t H, void* stream) {
+  if (!table || !table_sqnorm || n_rows <= 0 || H <= 0) return XFMR_EINVAL;
+  hipLaunchKernelGGL(table_sqnorm_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     table, table_sqnorm, n_rows, H);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
 }

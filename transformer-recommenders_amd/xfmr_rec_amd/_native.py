@@ -135,6 +135,7 @@ _SIGNATURES = {
     "xfmr_encoder_bwd": (C.c_int, [C.POINTER(EncoderCfg), _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "xfmr_mean_pool": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "xfmr_pool": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "xfmr_pool_rows": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
     "xfmr_l2_normalize_fwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
     "xfmr_l2_normalize_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
     "xfmr_sampled_loss_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64]),
@@ -164,6 +165,10 @@ _SIGNATURES = {
     "xfmr_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P,
                             C.c_size_t, _P]),
     "xfmr_retrieval_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "xfmr_topk_tiled_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "xfmr_topk_tiled": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P,
+                                  _P, C.c_size_t, _P]),
+    "xfmr_table_sqnorm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     "xfmr_adamw": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                              C.c_int64, C.c_float, _P]),
     "xfmr_adamw_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,

@@ -28,6 +28,7 @@ import json
 import pathlib
 from typing import Literal
 
+import numpy as np
 import pydantic
 import torch
 
@@ -101,6 +102,15 @@ def flat_layout(H: int, I: int, max_pos: int, num_layers: int):
             n *= d
         o += n
     return names, shapes, offsets, o
+
+
+def truncate_histories(histories, max_len: int) -> list[list[int]]:
+    """The last ``max_len`` table rows of EACH history (what ``_encode_tokens`` keeps of one row: ``item_idx[:, -L:]``)."""
+    out = []
+    for h in histories:
+        h = [int(x) for x in (h.tolist() if torch.is_tensor(h) else h)]
+        out.append(h[-max_len:] if max_len > 0 else [])
+    return out
 
 
 class RecommenderModel(torch.nn.Module):
@@ -391,6 +401,45 @@ class RecommenderModel(torch.nn.Module):
             if self.config.is_normalized:
                 sent = ops.l2_normalize(sent)
         return {"token_embeddings": tok, "sentence_embedding": sent, "attention_mask": key_mask.long()}
+
+    @torch.no_grad()
+    def encode_batch(self, histories) -> torch.Tensor:
+        """Sentence embeddings (B, H) of a list of histories (lists of table rows), in eval mode: each history truncated
+        to its own last ``max_seq_length`` rows, as ``self(idx[None])["sentence_embedding"]`` would encode it alone.
+        The packed layout (each sequence's own rows, pooled by xfmr_pool_rows with the normalisation fused) where
+        ``supports_packed_rows`` allows, else one right-padded forward + xfmr_pool. An empty history gives a zero row."""
+        rows = truncate_histories(histories, self.max_seq_length)
+        B, H, dev = len(rows), self.config.hidden_size, self.device
+        out = torch.zeros((B, H), dtype=torch.float32, device=dev)
+        keep = [b for b, r in enumerate(rows) if r]
+        if not keep:
+            return out
+        rows = [rows[b] for b in keep]
+        lens = [len(r) for r in rows]
+        L = max(lens)
+        lens_np = np.asarray(lens, dtype=np.int64)
+        hist_np = np.zeros((len(rows), L), dtype=np.int64)  # right-padded with the padding row 0
+        hist_np[np.arange(L)[None, :] < lens_np[:, None]] = np.concatenate([np.asarray(r, dtype=np.int64) for r in rows])
+        hist = torch.from_numpy(hist_np).to(dev)
+        was_training = self.training
+        self.eval()
+        try:
+            if self.supports_packed_rows(L):
+                order, offs64 = ops.length_order(lens)
+                order = order.to(dev)
+                packed = ops.pack_rows(hist, hist, None, offs64.to(dev), int(offs64[-1]), order=order)
+                packed |= {"batch": len(rows), "seq_len": L}
+                tok, _ = self._encode_tokens(packed=packed)
+                sent = ops.pool_rows(tok, packed["seq_offsets"], self.config.pooling_mode,
+                                     normalize=bool(self.config.is_normalized))
+                emb = torch.empty_like(sent)
+                emb[order] = sent  # packed slot b holds history order[b]
+            else:
+                emb = self(hist)["sentence_embedding"]
+        finally:
+            self.train(was_training)
+        out[torch.as_tensor(keep, dtype=torch.int64, device=dev)] = emb
+        return out
 
     def encode(self, item_ids: list[str]) -> torch.Tensor:
         """Pooled embedding of a list of item ids; unknown ids are dropped (``models.py:347-364``)."""

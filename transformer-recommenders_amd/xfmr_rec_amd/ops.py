@@ -201,6 +201,25 @@ def pool(tok, key_mask, mode: str = "mean"):
     return out
 
 
+def pool_rows(tok, seq_offsets, mode: str = "mean", *, normalize: bool = False, eps: float = 1e-12):
+    """:func:`pool` over the PACKED layout: tok (rows, H), seq_offsets (B + 1) int32 on the device (ops.pack_rows's
+    ``seq_offsets``); ``normalize`` fuses :func:`l2_normalize`. Returns (B, H); an empty sequence gives a zero row.
+    Forward only."""
+    B, H = seq_offsets.numel() - 1, tok.shape[-1]
+    out = _empty((B, H), tok)
+    N.check(N.load().xfmr_pool_rows(N.ptr(tok), N.ptr(seq_offsets), N.ptr(out), B, H, N.POOL_MODES[mode],
+                                    int(bool(normalize)), float(eps), N.stream()), "xfmr_pool_rows")
+    return out
+
+
+def table_sqnorm(table):
+    """Squared row norms of the item table (the l2 metric's item term of xfmr_topk_tiled)."""
+    out = _empty((table.shape[0],), table)
+    N.check(N.load().xfmr_table_sqnorm(N.ptr(table), N.ptr(out), table.shape[0], table.shape[1], N.stream()),
+            "xfmr_table_sqnorm")
+    return out
+
+
 class L2NormalizeFunction(torch.autograd.Function):
     """``torch.nn.functional.normalize(x, dim=-1)`` (``models.py:393-394``) on (rows, H)."""
 

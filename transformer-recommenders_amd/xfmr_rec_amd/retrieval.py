@@ -3,7 +3,8 @@
 Mirrors what ``RecommenderLightningModule.recommend / predict_step / compute_metrics`` do through LanceDB and
 torchmetrics (``xfmr_rec/trainer.py:186-211, 266-314``, ``index.py:214-255``, ``metrics.py:17-79``), for a batch of
 users at once: ``ExactItemIndex.search`` = exact top-k over the item table with each user's history excluded;
-``compute_retrieval_metrics`` = the seven metrics under the reference's names.
+``compute_retrieval_metrics`` = the seven metrics under the reference's names. ``ExactItemIndex.search_batch`` is the
+same search for a whole user set (xfmr_topk_tiled: no per-(user, item) workspace).
 """
 
 from __future__ import annotations
@@ -28,6 +29,16 @@ def _csr(lists, device):
     return torch.from_numpy(flat).to(device), torch.from_numpy(off).to(device)
 
 
+def sorted_exclusion_csr(lists):
+    """Host side of xfmr_topk_tiled's exclusions: each query's list sorted ascending with duplicates removed, as one
+    flat int64 array + (B + 1) int64 offsets (numpy). The kernel binary-searches each list."""
+    rows = [np.unique(np.asarray(x, dtype=np.int64).reshape(-1)) for x in lists]
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum([r.size for r in rows], out=off[1:])
+    flat = np.concatenate(rows) if off[-1] else np.zeros(1, dtype=np.int64)
+    return flat, off
+
+
 class ExactItemIndex:
     """``LanceIndex.search`` (``index.py:214-255``) as an exact scan of the item table (row 0 = padding)."""
 
@@ -37,6 +48,16 @@ class ExactItemIndex:
         self.table = table.contiguous()
         self.rnorm = table_rnorm if table_rnorm is not None else ops.table_rnorm(self.table)
         self.metric = METRICS[index_metric]
+        self._sqnorm = None
+
+    @property
+    def sqnorm(self) -> torch.Tensor:
+        """Squared item norms (the l2 metric's item term of :meth:`search_batch`), computed once."""
+        if self._sqnorm is None:
+            from . import ops
+
+            self._sqnorm = ops.table_sqnorm(self.table)
+        return self._sqnorm
 
     def search(self, embedding: torch.Tensor, exclude_item_idx=None, top_k: int = 20):
         """embedding (B,H) or (H,); exclude_item_idx: per-query lists of item indices (the users' histories).
@@ -54,6 +75,36 @@ class ExactItemIndex:
             lib.xfmr_topk(N.ptr(q), N.ptr(self.table), N.ptr(self.rnorm), self.table.shape[0], B, H, N.ptr(ex),
                           N.ptr(exo), top_k, self.metric, N.ptr(idx), N.ptr(score), N.ptr(ws), nbytes, N.stream()),
             "xfmr_topk",
+        )
+        return idx, score
+
+    def search_batch(self, embedding: torch.Tensor, exclude_item_idx=None, top_k: int = 20):
+        """:meth:`search` for a batch of users through xfmr_topk_tiled: score tiles on the matrix cores and a streaming
+        top-k, no (B, n_items) workspace. Same results as :meth:`search` up to the summation order of the scores (so up
+        to near-tied scores at the k-th place). top_k <= 128."""
+        q = embedding.reshape(-1, embedding.shape[-1]).contiguous().to(torch.float32)
+        B, H = q.shape
+        dev = q.device
+        idx = torch.empty((B, top_k), dtype=torch.int64, device=dev)
+        score = torch.empty((B, top_k), dtype=torch.float32, device=dev)
+        if B == 0:
+            return idx, score
+        ex = exo = None
+        if exclude_item_idx is not None:
+            if len(exclude_item_idx) != B:
+                raise ValueError(f"exclude_item_idx has {len(exclude_item_idx)} lists for {B} queries")
+            flat, off = sorted_exclusion_csr(exclude_item_idx)
+            ex, exo = torch.from_numpy(flat).to(dev), torch.from_numpy(off).to(dev)
+        n_rows = self.table.shape[0]
+        rnorm = self.rnorm if self.metric == METRICS["cosine"] else None
+        sqnorm = self.sqnorm if self.metric == METRICS["l2"] else None
+        lib = N.load()
+        nbytes = lib.xfmr_topk_tiled_workspace(B, n_rows, top_k)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        N.check(
+            lib.xfmr_topk_tiled(N.ptr(q), N.ptr(self.table), N.ptr(rnorm), N.ptr(sqnorm), n_rows, B, H, N.ptr(ex),
+                                N.ptr(exo), top_k, self.metric, N.ptr(idx), N.ptr(score), N.ptr(ws), nbytes, N.stream()),
+            "xfmr_topk_tiled",
         )
         return idx, score
 

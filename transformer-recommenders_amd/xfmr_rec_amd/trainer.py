@@ -387,6 +387,59 @@ class RecommenderLightningModule(_Base):
         hist = list(row["history"]["item_id"])
         return self.recommend(hist, top_k=self.config.top_k, exclude_item_ids=hist)
 
+    def _to_idx_or_empty(self, item_ids) -> list[int]:
+        return self._to_idx(item_ids) if len(item_ids) else []
+
+    @torch.no_grad()
+    def recommend_batch(self, item_ids_lists, *, top_k: int = 0, exclude_item_ids=None):
+        """:meth:`recommend` for many users in one pass: one batched encoder forward (``encode_batch``) and one
+        xfmr_topk_tiled search. Returns ``{"item_idx": (B, k), "score": (B, k)}``; a history that is empty (also after
+        unknown ids are dropped) gets all -1 / -inf."""
+        hists = [self._to_idx_or_empty(list(x)) for x in item_ids_lists]
+        excl = None if exclude_item_ids is None else [self._to_idx_or_empty(list(x)) for x in exclude_item_ids]
+        emb = self.model.encode_batch(hists)
+        idx, score = self.items_index.search_batch(emb, excl, top_k=top_k or self.config.top_k)
+        empty = [b for b, h in enumerate(hists) if not h]
+        if empty:
+            e = torch.as_tensor(empty, dtype=torch.int64, device=idx.device)
+            idx.index_fill_(0, e, -1)
+            score.index_fill_(0, e, float("-inf"))
+        return {"item_idx": idx, "score": score}
+
+    def predict_batch(self, rows):
+        """:meth:`predict_step` for a list of rows: each row's history excluded from its recommendations."""
+        hists = [list(r["history"]["item_id"]) for r in rows]
+        return self.recommend_batch(hists, top_k=self.config.top_k, exclude_item_ids=hists)
+
+    @torch.no_grad()
+    def evaluate(self, rows, stage: str = "val", batch_size: int = 1024) -> dict[str, float]:
+        """The epoch means of the seven retrieval metrics over ``rows`` (the reference's format: ``{"history":
+        {"item_id"}, "target": {"item_id", "label"}}``), batch_size rows per pass. Each mean is over the rows with at
+        least one positive target and a non-empty history -- what Lightning logs from ``validation_step(...,
+        batch_size=1)``, where a row without a target logs nothing (metrics.py:58-59) -- and
+        ``{stage}/num_rows`` is their number."""
+        import numpy as np
+
+        from .retrieval import METRIC_NAMES, retrieval_metrics
+
+        rows = list(rows)
+        total = np.zeros(len(METRIC_NAMES), dtype=np.float64)
+        n = 0
+        for b0 in range(0, len(rows), max(1, int(batch_size))):
+            chunk = rows[b0 : b0 + max(1, int(batch_size))]
+            recs = self.predict_batch(chunk)["item_idx"]
+            tgts = [self._to_idx_or_empty([i for i, l in zip(r["target"]["item_id"], r["target"]["label"]) if l])
+                    for r in chunk]
+            vals, valid = retrieval_metrics(recs, tgts, self.config.top_k)
+            vals, valid = vals.cpu().numpy().astype(np.float64), valid.cpu().numpy()
+            has_hist = np.asarray([bool(self._to_idx_or_empty(list(r["history"]["item_id"]))) for r in chunk])
+            use = valid & has_hist
+            total += vals[use].sum(axis=0)
+            n += int(use.sum())
+        out = {f"{stage}/{name}": (float(total[i] / n) if n else float("nan")) for i, name in enumerate(METRIC_NAMES)}
+        out[f"{stage}/num_rows"] = n
+        return out
+
     def compute_metrics(self, row, stage: str = "val") -> dict[str, torch.Tensor]:
         """``trainer.py:266-286``: the seven retrieval metrics of one validation row under ``{stage}/<name>``."""
         from .retrieval import compute_retrieval_metrics
