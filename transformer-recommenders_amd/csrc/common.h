@@ -197,6 +197,18 @@ struct RegRows<PrecBF16, K> {
     }
     return sq * z;
   }
+  // bf16 storage, `row` dereferenceable even when !valid (the result is then zero): every load issued up front
+  __device__ __forceinline__ void load_safe(const __bf16* row, bool valid) {
+    const int h = xf_lane() >> 5;
+#pragma unroll
+    for (int s = 0; s < K / 16; ++s) v[s] = *reinterpret_cast<const bf16x8*>(row + 16 * s + 8 * h);
+    if (!valid) {
+#pragma unroll
+      for (int s = 0; s < K / 16; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[s][j] = (__bf16)0.f;
+    }
+  }
   __device__ __forceinline__ void load(const __bf16* row, bool valid) {  // bf16 storage: no conversion
     const int h = xf_lane() >> 5;
 #pragma unroll

@@ -818,6 +818,7 @@ struct Plan {
   size_t off_dump, off_tau, off_qinfo; int64_t dump_ld;  // num_hard_negatives only
   size_t off_hist, off_dcnt, off_negmul; int ndblocks;    // distinct-item compaction
   size_t off_counts, off_blockcnt, off_neg, off_qrow, off_qpos, off_part, off_partO, off_block, total;
+  size_t off_qimg, off_qaux;  // bf16 image of the query rows + {|q|^2, q . e_pos} per query (loss_qprep_kernel)
   int nblocks;
 };
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -864,6 +865,8 @@ Plan make_plan(int64_t T, int H, int64_t n_rows, bool hard = false, int ns_overr
   p.off_partO = o; o += up256((size_t)ns * T * H * 4);
   p.off_block = o; o += up256((size_t)p.nblocks * BP * 8);
   p.off_tot = o; o += 256;
+  p.off_qimg = o; o += up256((size_t)T * H * 2);
+  p.off_qaux = o; o += up256((size_t)T * sizeof(float2));
   p.off_dump = p.off_tau = p.off_qinfo = 0;
   p.dump_ld = ((cols + BN - 1) / BN) * BN;  // whole tiles: the dump writes 16-byte runs
   if (hard) {
@@ -897,6 +900,16 @@ int launch_main_h(const LossArgs& a, int H, bool all, dim3 grid, hipStream_t st)
   else return XFMR_EUNSUPPORTED;
   XF_LAUNCH_CHECK();
   return XFMR_OK;
+}
+
+int launch_qprep_h(const LossArgs& a, __bf16* qimg, float2* qaux, int H, dim3 grid, hipStream_t st) {
+  switch (H) {
+    case 64: return xf_launch_loss_qprep_64(a, qimg, qaux, grid, st);
+    case 128: return xf_launch_loss_qprep_128(a, qimg, qaux, grid, st);
+    case 256: return xf_launch_loss_qprep_256(a, qimg, qaux, grid, st);
+    case 384: return xf_launch_loss_qprep_384(a, qimg, qaux, grid, st);
+    default: return XFMR_EUNSUPPORTED;
+  }
 }
 
 int launch_dma_h(const LossArgs& a, const void* tbf, int H, int head, dim3 grid, hipStream_t st) {
@@ -934,7 +947,7 @@ size_t xfmr_sampled_loss_workspace_cfg(const xfmr_loss_cfg* cfg, int64_t positio
 
 static int run_loss(const xfmr_loss_cfg* cfg, const float* tok, const float* table, const float* table_rnorm,
                     const void* table_bf16, int64_t n_rows, int T, int32_t H, float* losses, float* stats, float* d_tok, unsigned char* ws,
-                    const Plan& p, hipStream_t st) {
+                    size_t ws_bytes, const Plan& p, hipStream_t st) {
   int* counts = (int*)(ws + p.off_counts);
   int* neg_item = (int*)(ws + p.off_neg);
   int* qrow = (int*)(ws + p.off_qrow);
@@ -1037,11 +1050,33 @@ static int run_loss(const xfmr_loss_cfg* cfg, const float* tok, const float* tab
       a.nsplit = ns_part = ns_grad;
       if (ns_grad == 1 && !col_parts) { a.d_tok = d_tok; fused_finish = true; }
     }
+    // Query rows as bf16, converted once per call: a launch with n > 1 column splits would read and round every fp32 query
+    // row n times (and gather and multiply its positive's row n times); it stages them from the image instead, which
+    // loss_qprep_kernel writes in front of the first such launch. A launch with one split reads the fp32 rows itself --
+    // once. XFMR_LOSS_Q_FP32=1 (read per call) keeps every launch on the fp32 rows: the results are the same bit for bit
+    // (tests/test_gpu_loss_bf16_rows.py).
+    const char* q_env = getenv("XFMR_LOSS_Q_FP32");
+    const bool q_fp32 = q_env && q_env[0] && !(q_env[0] == '0' && !q_env[1]);
+    bool img_ready = false;
+    auto with_image = [&](LossArgs& l) -> int {
+      if (q_fp32 || l.nsplit <= 1) return XFMR_OK;
+      if (p.off_qimg + (size_t)T * H * 2 > ws_bytes || p.off_qaux + (size_t)T * sizeof(float2) > ws_bytes)
+        return XFMR_EWORKSPACE;  // (the image lives in the caller's workspace: no allocation inside the step)
+      __bf16* qimg = (__bf16*)(ws + p.off_qimg);
+      float2* qaux = (float2*)(ws + p.off_qaux);
+      if (!img_ready) {
+        if (int e = launch_qprep_h(a, qimg, qaux, H, grid, st)) return e;
+        img_ready = true;
+      }
+      l.qimg = qimg; l.qaux = qaux;
+      return XFMR_OK;
+    };
     if (pinned) {
       LossArgs b = a;
       b.nsplit = p.nsplit; b.d_tok = nullptr;
       b.part = (float*)(ws + p.off_part2);
       b.need_grad = 0;
+      if ((rc = with_image(b))) return rc;
       if (lev0 && hipEventRecord(lev0, st) != hipSuccess) return XFMR_EHIP;
       rc = launch_dma_h(b, table_bf16, H, -2, grid, st);  // (the InfoNCE value comes from the gradient records)
       if (rc) return rc;
@@ -1050,12 +1085,14 @@ static int run_loss(const xfmr_loss_cfg* cfg, const float* tok, const float* tab
       lse_from_grad = true;
       a.pin_part = b.part;
       a.pin_nsplit = p.nsplit;
+      if ((rc = with_image(a))) return rc;
       if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return XFMR_EHIP;
       rc = launch_dma_h(a, table_bf16, H, cfg->train_head, ggrid, st);
       if (rc) return rc;
       if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return XFMR_EHIP;
     } else {
     if (grad_pass) {
+      if ((rc = with_image(a))) return rc;
       if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return XFMR_EHIP;
       rc = launch_dma_h(a, table_bf16, H, cfg->train_head, ggrid, st);
       if (rc) return rc;
@@ -1073,6 +1110,7 @@ static int run_loss(const xfmr_loss_cfg* cfg, const float* tok, const float* tab
       const bool lse_elsewhere = cfg->train_head == XFMR_LOSS_INFONCE && (grad_pass || cfg->all_heads == 2);
       lse_from_grad = lse_elsewhere && grad_pass;
       const int code = lse_elsewhere ? -2 : -1;
+      if ((rc = with_image(b))) return rc;
       if (lev0 && hipEventRecord(lev0, st) != hipSuccess) return XFMR_EHIP;
       rc = launch_dma_h(b, table_bf16, H, code, grid, st);
       if (rc) return rc;
@@ -1185,7 +1223,7 @@ int xfmr_sampled_loss_prepared(const xfmr_loss_cfg* cfg, const float* tok, const
   if (d_tok && !zeroed && xf_zero_async(d_tok, (size_t)positions * H * sizeof(float), st) != hipSuccess) return XFMR_EHIP;
   if (table_bf16 && !xf_aligned16(table_bf16)) return XFMR_EALIGN;
   return run_loss(cfg, tok, table, table_rnorm, table_bf16, n_rows, (int)positions, H, losses, stats, d_tok,
-                  (unsigned char*)workspace, p, st);
+                  (unsigned char*)workspace, workspace_bytes, p, st);
 }
 
 int xfmr_sampled_loss(const xfmr_loss_cfg* cfg, const float* tok, const uint8_t* key_mask, const int64_t* pos_idx,
@@ -1238,7 +1276,7 @@ int xfmr_sampled_loss_lists(const xfmr_loss_cfg* cfg, const float* query, const 
     if (int rc = launch_distinct(ws, p, n_rows, table_rnorm, st)) return rc;
   }
   if (table_bf16 && !xf_aligned16(table_bf16)) return XFMR_EALIGN;
-  return run_loss(cfg, query, table, table_rnorm, table_bf16, n_rows, T, H, losses, stats, d_query, ws, p, st);
+  return run_loss(cfg, query, table, table_rnorm, table_bf16, n_rows, T, H, losses, stats, d_query, ws, workspace_bytes, p, st);
 }
 
 int xfmr_table_prepare(const float* table, float* table_rnorm, void* table_bf16, int64_t n_rows, int32_t H,

@@ -51,6 +51,10 @@ struct LossArgs {
   // dL/dquery written straight to d_tok rows (qrow), no (split, query, H) partials, no gradient work left for the
   // combine kernel. Null: write the partials to partO as before.
   float* d_tok;
+  // bf16 image of the query rows in COMPACTED order (row qi = the rounded tok row qrow[qi]) and {|q|^2, q . e_pos} per
+  // query, written once per call by loss_qprep_kernel (loss_dma.inc) for launches that walk the queries once per column
+  // split. Null: the prologue reads the fp32 rows (a launch with one split: that IS reading them once).
+  const __bf16* qimg; const float2* qaux;
   int T; int nsplit;
   int H;                  // generic kernel: the rows' real width (= their stride); <= the kernel's template width, % 32 == 0
   int train_head, mask_fn, mode, need_grad;
@@ -543,6 +547,11 @@ using namespace xfl;
 
 // launchers of the LDS-DMA main kernel, one translation unit per hidden size (compile time)
 // head: XFMR_LOSS_* = gradient pass of that head; -1 = logging pass (all heads + statistics, values only)
+// ... and of loss_qprep_kernel (a.qimg / a.qaux are the OUTPUTS there); grid.x = query blocks of QB
+int xf_launch_loss_qprep_64(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st);
+int xf_launch_loss_qprep_128(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st);
+int xf_launch_loss_qprep_256(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st);
+int xf_launch_loss_qprep_384(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st);
 int xf_launch_loss_dma_64(const LossArgs& a, const void* table_bf16, int head, dim3 grid, hipStream_t st);
 int xf_launch_loss_dma_128(const LossArgs& a, const void* table_bf16, int head, dim3 grid, hipStream_t st);
 int xf_launch_loss_dma_256(const LossArgs& a, const void* table_bf16, int head, dim3 grid, hipStream_t st);

@@ -84,7 +84,41 @@ constexpr int loss_dma_waves() {
 // or three such workgroups per slot, 454 at two per CU. Equal workgroups started together stay in phase -- prologues,
 // side-data chunks and gather waits of a CU's three workgroups coincide instead of hiding behind each other's
 // arithmetic -- and that costs more than the 0.17 of a round the plain grid leaves empty. Removed.)
-template <int H, int HEAD_CODE>
+// The per-query half of loss_main_dma_kernel's prologue, once per call instead of once per column split: query qi's fp32 row
+// rounded to bf16 into row qi of `qimg` (RegRows' own conversion), and {|q|^2, q . e_pos} into qaux[qi]. Same lane map
+// (lane & 31 = the query, lane >> 5 = the half of the row) and the same RegRows calls in the same order as that
+// prologue, compiled in the same translation unit with the same flags: the values are the ones it computes.
+template <int H>
+__global__ __launch_bounds__(256) void loss_qprep_kernel(LossArgs a, __bf16* qimg, float2* qaux) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int Nq = a.counts[1];
+  const int qi = blockIdx.x * QB + (tid >> 6) * 32 + (lane & 31);
+  if ((int)blockIdx.x * QB >= Nq) return;
+  const bool qvalid = qi < Nq;
+  const int row = qvalid ? a.qrow[qi] : 0;
+  const int pos_item = qvalid ? a.qpos[qi] : -2;
+  RegRows<PrecBF16, H> qreg, preg;
+  float qq = qreg.load_safe_sq(a.tok + (int64_t)row * H, qvalid);
+  preg.load_safe(a.table + (int64_t)(qvalid ? pos_item : 0) * H, qvalid);
+  float pos_dot = qreg.dot_partial(preg);
+  pos_dot += xf_half_swap(pos_dot);
+  qq += xf_half_swap(qq);
+  if (qvalid) {
+    qreg.store_image(qimg + (int64_t)qi * H);
+    if (lane < 32) qaux[qi] = make_float2(qq, pos_dot);
+  }
+}
+template <int H>
+int xf_launch_loss_qprep_t(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((loss_qprep_kernel<H>), dim3(grid.x), dim3(256), 0, st, a, qimg, qaux);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
+
+// QIMG: the query rows come from the bf16 image (LossArgs::qimg). A compile-time form: with both prologues behind a
+// run-time test in one kernel the masked logging pass at H = 128 needed 168 registers and spilled 64 B per lane (143
+// and none with either prologue alone), and the H = 256 logging kernels spilled 170-220 B.
+template <int H, int HEAD_CODE, bool QIMG>
 __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_main_dma_kernel(
     LossArgs a, const __bf16* tbf) {
   constexpr bool PINNED = HEAD_CODE == HEAD_INFONCE_PINNED;  // unmasked InfoNCE, row maximum known (loss_common.h)
@@ -144,8 +178,21 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
   RegRows<PrecBF16, H> qreg;
   // (the query row is read ONCE: operand and |q|^2 from the same fp32 pieces -- round 2 read it again for the norm: with
   //  two column splits 4 x the algorithmic bytes, VERDICT r2)
-  float pos_dot, qq = qreg.load_safe_sq(a.tok + (int64_t)row * H, qvalid);  // row 0 / item 0 stand in for lanes past the end
-  {
+  float pos_dot, qq;
+  if constexpr (QIMG) {
+    // several column splits walk these queries: the operand comes from the bf16 image loss_qprep_kernel wrote once for
+    // the call (the same rounding of the same fp32 pieces, so every logit keeps its bits), |q|^2 and the positive's dot
+    // product -- functions of the query alone, taken there with the arithmetic of the other branch -- from its record:
+    // half the bytes per split, no fp32 -> bf16 conversion, no positive row gathered and multiplied per split.
+    // Nothing below needs the fp32 row itself (the in-kernel finish of a one-split gradient pass does; it never runs
+    // with the image).
+    const int qs = qvalid ? qi : 0;
+    qreg.load_safe(a.qimg + (int64_t)qs * H, qvalid);
+    const float2 ax = a.qaux[qs];
+    qq = qvalid ? ax.x : 0.f;
+    pos_dot = qvalid ? ax.y : 0.f;
+  } else {
+    qq = qreg.load_safe_sq(a.tok + (int64_t)row * H, qvalid);  // row 0 / item 0 stand in for lanes past the end
     RegRows<PrecBF16, H> preg;
     preg.load_safe(a.table + (int64_t)(qvalid ? pos_item : 0) * H, qvalid);
     pos_dot = qreg.dot_partial(preg);
@@ -339,7 +386,7 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
   write_partial(ms, a.part + ((int64_t)split * a.T + qi) * REC, lane < 32 && qvalid && hpart == 0, pos_dot, rq, qq);
   if (GRAD && do_grad) {
     __syncthreads();  // sScratch aliases the tile buffers other waves may still be reading
-    if (HP == 1 && a.d_tok != nullptr) {
+    if (!QIMG && HP == 1 && a.d_tok != nullptr) {  // (one split: never launched with the image)
       // ---- one column split: finish the rows here (the arithmetic of loss_combine_kernel, on the accumulators) -----
       // The lane holds, of its query's dQ^T, the h-runs h0 = 32 i + 8 g + 4 hh .. + 3 (i < NO, g < 4); the other half of
       // the row is with lane ^ 32.
@@ -421,4 +468,10 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
     for (int i = 0; i < NO; ++i)
       xf_store_tile_T(sScratch + wid * 32 * 33, o[i], 1.f, base + (hpart * NO + i) * 32, H, qb0 + wid * 32, Nq);
   }
+}
+
+template <int H, int HEAD_CODE>
+void xfl_launch_dma(const LossArgs& a, const __bf16* tbf, dim3 grid, dim3 block, hipStream_t st) {
+  if (a.qimg != nullptr) hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, true>), grid, block, 0, st, a, tbf);
+  else hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, false>), grid, block, 0, st, a, tbf);
 }
