@@ -412,6 +412,33 @@ __device__ __forceinline__ void xf_drop4(const XfDropout& d, uint32_t row, uint3
   v.z *= xf_keep_scale_rc(d, rk, cm + 2 * kDropColMul); v.w *= xf_keep_scale_rc(d, rk, cm + 3 * kDropColMul);
 }
 
+// LayerNorm output from what every LayerNorm producer stores for its backward: the input `pre`, the row's mean and rstd,
+// gamma and beta. The producers (ln_fwd_v4_kernel, the EPI_DROP_RES_LN epilogue) and the kernels that RE-DERIVE that output as
+// their residual operand instead of loading a stored fp32 copy go through these, so both round identically: one subtraction,
+// one multiply, one explicit fma -- never left to the compiler's contraction. xf_ln_affine4 takes the centred value
+// (pre - mean), which the producers hold already.
+__device__ __forceinline__ float xf_ln_affine(float d, float rstd, float g, float b) { return __builtin_fmaf(d * rstd, g, b); }
+__device__ __forceinline__ float4 xf_ln_affine4(const float4& d, float rstd, const float4& g, const float4& b) {
+  return make_float4(xf_ln_affine(d.x, rstd, g.x, b.x), xf_ln_affine(d.y, rstd, g.y, b.y),
+                     xf_ln_affine(d.z, rstd, g.z, b.z), xf_ln_affine(d.w, rstd, g.w, b.w));
+}
+__device__ __forceinline__ float4 xf_ln_out4(const float4& pre, float mean, float rstd, const float4& g, const float4& b) {
+  return xf_ln_affine4(make_float4(pre.x - mean, pre.y - mean, pre.z - mean, pre.w - mean), rstd, g, b);
+}
+// ... followed by the dropout of that output (the embedding site: ln_fwd_v4_kernel applies xf_drop4 to what it stores). The
+// product is made opaque: a consumer that adds it to something else must add the ROUNDED product, as the stored copy was,
+// not contract the two into one fma.
+template <bool DROP>
+__device__ __forceinline__ float4 xf_ln_out_drop4(const float4& pre, float mean, float rstd, const float4& g, const float4& b,
+                                                  const XfDropout& d, uint32_t row, uint32_t col) {
+  float4 o = xf_ln_out4(pre, mean, rstd, g, b);
+  if (DROP) {
+    xf_drop4(d, row, col, o);
+    asm volatile("" : "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(o.w));
+  }
+  return o;
+}
+
 // Zero-fill as a KERNEL launch (bytes % 4 == 0, p 4-byte aligned): hipMemsetAsync nodes captured into a hipGraph were
 // not re-executed by later replays on this runtime (ROCm 7.x with torch 2.10: the multiplicity histogram of the loss
 // doubled from the second replay on -- scripts/probe/graph_debug.py), and the training step must replay as a graph.

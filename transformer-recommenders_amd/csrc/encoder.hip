@@ -59,7 +59,8 @@ LayerParams layer_params(const xfmr_encoder_cfg* c, int i) {
 struct LayerActs {
   void *qkv, *ctx, *f1, *g;                                           // bf16 when mixed
   float *lse, *pre1, *mean1, *rstd1, *x1, *pre2, *mean2, *rstd2, *x2;  // always fp32
-  void *x1b, *x2b;  // mixed storage: bf16 copies of the LayerNorm outputs (GEMM operands; x1 / x2 stay the residuals)
+  void *x1b, *x2b;  // mixed storage: bf16 copies of the LayerNorm outputs (GEMM operands; x1 / x2 stay the residuals -- or go
+                    // unwritten where the residual is re-derived: ln_store_x)
 };
 // Per-layer reduction inputs of the backward pass, reduced by ONE launch at its end (xf_multi_rowsum): split-K slabs
 // of the four weight gradients, partial rows of the two bias gradients that are column sums (b1, bqkv -- produced by
@@ -117,6 +118,14 @@ bool ln_fused(const xfmr_encoder_cfg* c, int64_t T) {
   //  separate GEMMs; at batch 32 nothing in it, 0.662 against 0.661-0.672. XFMR_LN_FUSED_MIN_TOKENS for experiments.)
   static const int64_t min_tokens = [] { const char* e = getenv("XFMR_LN_FUSED_MIN_TOKENS"); return e ? (int64_t)atoll(e) : (int64_t)12288; }();
   return mixed_storage(c) && c->hidden == 128 && T >= min_tokens && !(c->flags & XFMR_ENC_LN_UNFUSED);
+}
+// Under the LayerNorm-fused forms the fp32 LayerNorm outputs x0, x1 and x2 (of every layer but the last) are not stored: the
+// backward never reads them, and their one reader -- the next kernel's residual operand -- re-derives them from pre / mean /
+// rstd, which are stored for the backward anyway (XfLnResidual). XFMR_LN_STORE_X=1 (read per call: tests, A/B timing)
+// stores them and loads the residual as before; results are bit-identical either way.
+bool ln_store_x() {
+  const char* e = getenv("XFMR_LN_STORE_X");
+  return e && *e && *e != '0';
 }
 bool ffn_fused(const xfmr_encoder_cfg* c, int64_t T) {
   // (the fused FFN pair keeps its 16 384 tokens: at 12 800 it measured 0.887 against 0.876 ms for the separate GEMMs)
@@ -349,17 +358,23 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
   const XfSeed sd(cfg->seed, cfg->step_device);
   ParamLayout pl;
   layer_base(cfg, 0, &pl);
+  const bool fuse_ln = ln_fused(cfg, Tplan);  // LayerNorm in the out-proj / FFN2 GEMM epilogues
+  const bool fuse_ffn = ffn_fused(cfg, Tplan);
+  const bool rederive = fuse_ln && !ln_store_x();  // fp32 LayerNorm outputs not stored; residuals re-derived
+  float* const x0 = rederive ? nullptr : a.x0;
   if (offs) {
     XF_TRY(xf_embed_ln_fwd_packed_ex(item_idx, table, n_rows, params + pl.pos, params + pl.type, params + pl.eg,
-                                     params + pl.eb, a.x0, mix ? a.x0b : nullptr, a.emb_pre, a.emb_mean, a.emb_rstd, key_mask,
+                                     params + pl.eb, x0, mix ? a.x0b : nullptr, a.emb_pre, a.emb_mean, a.emb_rstd, key_mask,
                                      T, cfg->row_pos, H, cfg->ln_eps, cfg->hidden_dropout, sd, SITE_EMB, st));
   } else {
     XF_TRY(xf_embed_ln_fwd_ex(item_idx, table, n_rows, params + pl.pos, params + pl.type, params + pl.eg,
-                              params + pl.eb, a.x0, mix ? a.x0b : nullptr, a.emb_pre, a.emb_mean, a.emb_rstd, key_mask, B,
+                              params + pl.eb, x0, mix ? a.x0b : nullptr, a.emb_pre, a.emb_mean, a.emb_rstd, key_mask, B,
                               L, H, cfg->ln_eps, cfg->hidden_dropout, sd, SITE_EMB, st));
   }
   if (cfg->embed_event && hipEventRecord((hipEvent_t)cfg->embed_event, st) != hipSuccess) return XFMR_EHIP;  // key_mask is written
-  const float* x = a.x0;
+  const float* x = x0;
+  // the layer input as a re-derived residual: the embedding LayerNorm's dropped-out output, then each layer's LayerNorm 2
+  XfLnResidual xr{a.emb_pre, a.emb_mean, a.emb_rstd, params + pl.eg, params + pl.eb, cfg->hidden_dropout, SITE_EMB};
   const void* xg = mix ? a.x0b : (const void*)a.x0;  // the same activations as the GEMM operand
   const uint32_t sA = mix ? XF_S16_A : 0;
   if (mix) {
@@ -369,8 +384,6 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
     XF_LAUNCH_CHECK();
   }
   const uint32_t sB = mix ? XF_S16_B : 0;
-  const bool fuse_ln = ln_fused(cfg, Tplan);  // LayerNorm in the out-proj / FFN2 GEMM epilogues
-  const bool fuse_ffn = ffn_fused(cfg, Tplan);
   auto W = [&](int64_t off) -> const float* {  // weight operand: the bf16 copy under mixed storage
     return mix ? reinterpret_cast<const float*>((const __bf16*)a.wbf + off) : params + off;
   };
@@ -378,14 +391,20 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
     LayerActs l;
     carve(cfg, base, i, &l);
     const LayerParams p = layer_params(cfg, i);
-    float* out = (i == cfg->layers - 1) ? tok : l.x2;
+    const bool last = i == cfg->layers - 1;
+    float* out = last ? tok : (rederive ? nullptr : l.x2);
+    const XfLnResidual x1r{l.pre1, l.mean1, l.rstd1, params + p.ln1g, params + p.ln1b, 0.f, 0};
     XF_TRY(xf_linear_fwd_ex(xg, W(p.wqkv), params + p.bqkv, l.qkv, T, 3 * H, H, XFMR_EPI_BIAS, nullptr, nullptr,
                             0.f, 0, 0, prec, (mix ? XF_S16_C : 0) | sA | sB, st));
     XF_TRY(prof(cfg, XFMR_PROF_ATTN_FWD, i, 0, st));
     XF_TRY(xf_attn_fwd_ex(l.qkv, key_mask, l.ctx, l.lse, B, L, A, H, cfg->attn_dropout, sd, site_attn(i), prec,
                           mix, causal, st, offs));
     XF_TRY(prof(cfg, XFMR_PROF_ATTN_FWD, i, 1, st));
-    if (fuse_ln) {  // LayerNorm in the GEMM epilogue (the tile spans whole rows)
+    if (rederive) {
+      XF_TRY(xf_linear_ln_fwd_re(l.ctx, W(p.wo), params + p.bo, l.pre1, T, H, H, &xr, cfg->hidden_dropout, sd,
+                                 site_out(i), params + p.ln1g, params + p.ln1b, cfg->ln_eps, nullptr, l.x1b, l.mean1,
+                                 l.rstd1, prec, XF_S16_A | sB, st));
+    } else if (fuse_ln) {  // LayerNorm in the GEMM epilogue (the tile spans whole rows)
       XF_TRY(xf_linear_ln_fwd_ex(l.ctx, W(p.wo), params + p.bo, l.pre1, T, H, H, x, cfg->hidden_dropout, sd,
                                  site_out(i), params + p.ln1g, params + p.ln1b, cfg->ln_eps, l.x1, l.x1b, l.mean1,
                                  l.rstd1, prec, XF_S16_A | sB, st));
@@ -395,21 +414,37 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
       XF_TRY(xf_layernorm_fwd_ex(l.pre1, params + p.ln1g, params + p.ln1b, l.x1, mix ? l.x1b : nullptr, l.mean1,
                                  l.rstd1, T, H, cfg->ln_eps, st));
     }
-    const bool last = i == cfg->layers - 1;
     XF_TRY(prof(cfg, XFMR_PROF_FFN_FWD, i, 0, st));
+    // what the next layer takes as its input: the GEMM operand, and the residual -- loaded (x) or re-derived (xr)
+    auto next_input = [&]() {
+      x = out;
+      xg = mix ? (const void*)l.x2b : (const void*)out;
+      xr = XfLnResidual{l.pre2, l.mean2, l.rstd2, params + p.ln2g, params + p.ln2b, 0.f, 0};
+    };
+    if (fuse_ffn && rederive) {
+      XF_TRY(xf_ffn_fwd_fused_re(l.x1b, W(p.w1), params + p.b1, W(p.w2), params + p.b2, l.f1, l.g, l.pre2, T, H, I, &x1r,
+                                 cfg->hidden_dropout, sd, site_ffn(i), params + p.ln2g, params + p.ln2b,
+                                 cfg->ln_eps, out, last ? nullptr : l.x2b, l.mean2, l.rstd2, st));
+      XF_TRY(prof(cfg, XFMR_PROF_FFN_FWD, i, 1, st));
+      next_input();
+      continue;
+    }
     if (fuse_ffn) {  // FFN1 -> GELU -> FFN2 -> dropout + residual + LayerNorm in one kernel; f1 <- the PRE-activation, g <- gelu
       XF_TRY(xf_ffn_fwd_fused_ex(l.x1b, W(p.w1), params + p.b1, W(p.w2), params + p.b2, l.f1, l.g, l.pre2, T, H, I, l.x1,
                                  cfg->hidden_dropout, sd, site_ffn(i), params + p.ln2g, params + p.ln2b,
                                  cfg->ln_eps, out, last ? nullptr : l.x2b, l.mean2, l.rstd2, st));
       XF_TRY(prof(cfg, XFMR_PROF_FFN_FWD, i, 1, st));
-      x = out;
-      xg = mix ? (const void*)l.x2b : (const void*)out;
+      next_input();
       continue;
     }
     XF_TRY(xf_linear_fwd_ex(mix ? (const void*)l.x1b : (const void*)l.x1, W(p.w1), params + p.b1, l.g, T, I, H,
                             XFMR_EPI_BIAS_GELU, nullptr, l.f1, 0.f, 0, 0, prec,
                             (mix ? XF_S16_C : 0) | sA | sB | XF_AUX_GELU_GRAD, st));  // f1 <- gelu'(pre)
-    if (fuse_ln) {
+    if (rederive) {
+      XF_TRY(xf_linear_ln_fwd_re(l.g, W(p.w2), params + p.b2, l.pre2, T, H, I, &x1r, cfg->hidden_dropout, sd,
+                                 site_ffn(i), params + p.ln2g, params + p.ln2b, cfg->ln_eps, out,
+                                 last ? nullptr : l.x2b, l.mean2, l.rstd2, prec, XF_S16_A | sB, st));
+    } else if (fuse_ln) {
       XF_TRY(xf_linear_ln_fwd_ex(l.g, W(p.w2), params + p.b2, l.pre2, T, H, I, l.x1, cfg->hidden_dropout, sd,
                                  site_ffn(i), params + p.ln2g, params + p.ln2b, cfg->ln_eps, out,
                                  last ? nullptr : l.x2b, l.mean2, l.rstd2, prec, XF_S16_A | sB, st));
@@ -420,8 +455,7 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
                                  l.mean2, l.rstd2, T, H, cfg->ln_eps, st));
     }
     XF_TRY(prof(cfg, XFMR_PROF_FFN_FWD, i, 1, st));
-    x = out;
-    xg = mix ? (const void*)l.x2b : (const void*)out;
+    next_input();
   }
   return XFMR_OK;
 }

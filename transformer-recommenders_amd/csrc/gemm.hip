@@ -72,8 +72,15 @@ namespace {
 // EPI_DX_LNBWD: a dX GEMM (+ residual gradient) whose output rows are the gradient of a LayerNorm OUTPUT: the LayerNorm
 // backward runs in the epilogue -- C = gradient of the LayerNorm input, D16 = its dropout-scaled bf16 copy (the
 // gradient of the Linear that fed the LayerNorm), one partial record [3][128] (d gamma, d beta, d bias) per workgroup.
+// EPI_DROP_RES_LN_RE / _RED: EPI_DROP_RES_LN whose residual operand is not loaded from a stored fp32 tensor but RE-DERIVED
+// from what the LayerNorm that produced it stored for its backward (its input, mean, rstd; gamma, beta) -- xf_ln_out_drop4;
+// _RED: ... followed by the dropout of that output (layer 0: the residual is the embedding LayerNorm's dropped-out output).
+// Separate instantiations: the variants cost registers the plain form does not pay.
 enum { EPI_STORE = 0, EPI_GELU = 1, EPI_DROP_RES = 2, EPI_GELU_GRAD = 3, EPI_SPLITK = 4, EPI_DROP_RES_LN = 5,
-       EPI_DX_LNBWD = 6 };
+       EPI_DX_LNBWD = 6, EPI_DROP_RES_LN_RE = 7, EPI_DROP_RES_LN_RED = 8 };
+constexpr bool epi_res_ln(int epi) { return epi == EPI_DROP_RES_LN || epi == EPI_DROP_RES_LN_RE || epi == EPI_DROP_RES_LN_RED; }
+// residual operand of the EPI_DROP_RES_LN family: 0 = loaded (GemmArgs.R), 1 = re-derived, 2 = re-derived + dropout
+constexpr int epi_res_mode(int epi) { return epi == EPI_DROP_RES_LN_RE ? 1 : epi == EPI_DROP_RES_LN_RED ? 2 : 0; }
 
 struct GemmArgs {
   const void* A; const void* B; void* C;  // fp32, or bf16 where the storage mask says so
@@ -94,7 +101,10 @@ struct GemmArgs {
   XfDropout drop;
   // EPI_DROP_RES_LN
   const float* ln_gamma; const float* ln_beta; float ln_eps;
-  float* Y; void* Y16; float* ln_mean; float* ln_rstd;
+  float* Y; void* Y16; float* ln_mean; float* ln_rstd;  // (Y null: the fp32 output is not stored)
+  // EPI_DROP_RES_LN_RE / _RED: the residual = LayerNorm(rp_pre; rp_mean, rp_rstd, rp_gamma, rp_beta), then rp_drop (_RED)
+  const float* rp_pre; const float* rp_mean; const float* rp_rstd; const float* rp_gamma; const float* rp_beta;
+  XfDropout rp_drop;
   // EPI_DX_LNBWD (ln_gamma as above; `drop` = the dropout of the Linear that fed the LayerNorm)
   const float* lnb_x; const float* lnb_mean; const float* lnb_rstd;  // saved LayerNorm input and statistics
   void* D16; float* lnb_partials;
@@ -356,6 +366,7 @@ static void xf_plan_row_tiles(GemmArgs& g, int BM) {
 // columns, acc[j] = its 32 x 32 block j): bias + dropout + residual -> C (the pre-LayerNorm sum, kept for the backward),
 // LayerNorm -> Y (fp32) / Y16 (bf16 GEMM operand), mean / rstd per row. `smem`: >= 4 strips of 16 x 68 floats + 128
 // floats, free of live data (the callers alias their operand images after a barrier).
+template <int RES>  // epi_res_mode
 __device__ __forceinline__ void epi_drop_res_ln_64x128(const f32x16 (&acc)[2], unsigned char* smem, const GemmArgs& g,
                                                        const int64_t m0, const int wid, const int lane) {
   // The wave owns 32 rows x 64 columns; a row's other 64 columns are with the partner wave (wc ^ 1). Lane ->
@@ -368,16 +379,29 @@ __device__ __forceinline__ void epi_drop_res_ln_64x128(const f32x16 (&acc)[2], u
   const int prow = lane / LPRL, li = lane % LPRL, c0 = li * 4;
   const int n = wc * WN + c0;  // (n0 == 0: one N tile)
   const float4 bias = g.bias ? *reinterpret_cast<const float4*>(g.bias + n) : make_float4(0, 0, 0, 0);
+  float4 gp = make_float4(0, 0, 0, 0), bp = gp;  // gamma / beta of the LayerNorm whose output is the residual
+  if constexpr (RES != 0) {
+    gp = *reinterpret_cast<const float4*>(g.rp_gamma + n);
+    bp = *reinterpret_cast<const float4*>(g.rp_beta + n);
+  }
   float4 vv[2][NPL];
 #pragma unroll
   for (int hf = 0; hf < 2; ++hf) {
     const int64_t mb = m0 + wr * WM + 16 * hf;
     float4 aux[NPL];
+    float amu[NPL], ars[NPL];
 #pragma unroll
     for (int ps = 0; ps < NPL; ++ps) {
       aux[ps] = make_float4(0, 0, 0, 0);
+      amu[ps] = ars[ps] = 0.f;
       const int64_t m = mb + prow + RPPL * ps;
-      if (m < g.M) aux[ps] = *reinterpret_cast<const float4*>(g.R + m * LDC + n);
+      if constexpr (RES == 0) {
+        if (m < g.M) aux[ps] = *reinterpret_cast<const float4*>(g.R + m * LDC + n);
+      } else if (m < g.M) {
+        aux[ps] = *reinterpret_cast<const float4*>(g.rp_pre + m * LDC + n);
+        amu[ps] = g.rp_mean[m];
+        ars[ps] = g.rp_rstd[m];
+      }
     }
 #pragma unroll
     for (int j = 0; j < NI; ++j)
@@ -395,7 +419,13 @@ __device__ __forceinline__ void epi_drop_res_ln_64x128(const f32x16 (&acc)[2], u
       if (g.drop.on) {
         xf_drop4(g.drop, (uint32_t)m, (uint32_t)(n), v);
       }
-      v.x += aux[ps].x; v.y += aux[ps].y; v.z += aux[ps].z; v.w += aux[ps].w;
+      float4 res = aux[ps];
+      if constexpr (RES != 0) {
+        XF_PIN_SCALAR(amu[ps]);  // (per-row scalars broadcast into four-wide arithmetic: see XF_PIN_SCALAR)
+        XF_PIN_SCALAR(ars[ps]);
+        res = xf_ln_out_drop4<RES == 2>(res, amu[ps], ars[ps], gp, bp, g.rp_drop, (uint32_t)m, (uint32_t)(n));
+      }
+      v.x += res.x; v.y += res.y; v.z += res.z; v.w += res.w;
       if (m >= g.M) v = make_float4(0, 0, 0, 0);
       else *reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + m * LDC + n) = v;
       vv[hf][ps] = v;
@@ -445,11 +475,8 @@ __device__ __forceinline__ void epi_drop_res_ln_64x128(const f32x16 (&acc)[2], u
       const float var = (red[(wr * 2) * 32 + rr] + red[(wr * 2 + 1) * 32 + rr]) * (1.f / 128.f);
       const float rs = rsqrtf(var + g.ln_eps);
       if (m >= g.M) continue;
-      const float4 d = vv[hf][ps];
-      float4 o;
-      o.x = d.x * rs * gm.x + bt.x; o.y = d.y * rs * gm.y + bt.y;
-      o.z = d.z * rs * gm.z + bt.z; o.w = d.w * rs * gm.w + bt.w;
-      *reinterpret_cast<float4*>(g.Y + m * LDC + n) = o;
+      const float4 o = xf_ln_affine4(vv[hf][ps], rs, gm, bt);
+      if (g.Y) *reinterpret_cast<float4*>(g.Y + m * LDC + n) = o;  // (null: the consumer re-derives it)
       if (g.Y16) xf_st4<true>(g.Y16, m * LDC + n, o);
       if (wc == 0 && li == 0) {
         g.ln_mean[m] = mean[hf][ps];
@@ -595,6 +622,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g_in, const int bid) {
   GemmArgs g = g_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
   if (EPI != EPI_SPLITK) XF_CHAIN_PRIO();
   g.drop = xf_drop_resolve(g.drop); g.drop2 = xf_drop_resolve(g.drop2);
+  if constexpr (EPI == EPI_DROP_RES_LN_RED) g.rp_drop = xf_drop_resolve(g.rp_drop);
   using elem = typename P::elem;
   using TileA = OperandTile<P, BM, BK, TA>;
   using TileB = OperandTile<P, BN, BK, TB>;
@@ -608,7 +636,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g_in, const int bid) {
   // the LayerNorm-fused epilogues keep their exchange records BEHIND the four scratch strips: row sums [4 waves][32]
   // (EPI_DROP_RES_LN); [2 hf][2 wr][2 wc][16][2] row sums + [2 wr][3][128] column records (EPI_DX_LNBWD). With 32-deep
   // K slices the operand images are smaller than strips + records, so the records are part of the size.
-  constexpr size_t RED_BYTES = EPI == EPI_DROP_RES_LN ? (size_t)4 * 32 * sizeof(float)
+  constexpr size_t RED_BYTES = epi_res_ln(EPI) ? (size_t)4 * 32 * sizeof(float)
                                : EPI == EPI_DX_LNBWD  ? (size_t)(2 * 2 * 2 * 16 * 2 + 2 * 3 * 128) * sizeof(float)
                                                       : 0;
   constexpr size_t EPI_BYTES = SCR_BYTES + RED_BYTES;
@@ -621,7 +649,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g_in, const int bid) {
   constexpr int WM = BM / 2, WN = BN / 2, MI = WM / 32, NI = WN / 32;
   const TileIdx tix = tile_of(g.nt_n, g.nt_m, g.nt_z, bid);
   if (!tix.valid) return;  // (whole workgroup: the grid is padded to a multiple of 8 M-tiles / K splits)
-  const int64_t m0 = (EPI == EPI_DROP_RES_LN || EPI == EPI_DX_LNBWD) ? xf_tile_rows(g, tix.m, BM) : (int64_t)tix.m * BM;
+  const int64_t m0 = (epi_res_ln(EPI) || EPI == EPI_DX_LNBWD) ? xf_tile_rows(g, tix.m, BM) : (int64_t)tix.m * BM;
   const int n0 = tix.n * BN;
   int kbeg = 0, kend = g.K;
   if (g.k_chunk > 0) {
@@ -691,8 +719,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g_in, const int bid) {
   // covers the wave's whole column range: full 128-byte lines even for bf16 outputs when the wave owns 64 columns
   // (one wave instruction = 4-8 rows x 128-256 B instead of 2 rows x 32 scattered 4- or 2-byte elements).
   __syncthreads();  // everyone is done with the operand images the scratch aliases
-  if constexpr (EPI == EPI_DROP_RES_LN) {
-    if constexpr (BM == 64 && BN == 128) epi_drop_res_ln_64x128(acc[0], smem, g, m0, wid, lane);
+  if constexpr (epi_res_ln(EPI)) {
+    if constexpr (BM == 64 && BN == 128) epi_drop_res_ln_64x128<epi_res_mode(EPI)>(acc[0], smem, g, m0, wid, lane);
     return;
   }
   if constexpr (EPI == EPI_DX_LNBWD) {
@@ -831,7 +859,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g_in, const int bid) {
   }
 }
 template <class P, int BM, int BN, int BK, bool TA, bool TB, int EPI, uint32_t S>
-__global__ __launch_bounds__(256, (EPI == EPI_DROP_RES_LN || EPI == EPI_DX_LNBWD) ? XF_LN_EPI_MIN_WAVES : 1) void gemm_kernel(const GemmArgs g_in) {
+__global__ __launch_bounds__(256, (epi_res_ln(EPI) || EPI == EPI_DX_LNBWD) ? XF_LN_EPI_MIN_WAVES : 1) void gemm_kernel(const GemmArgs g_in) {
   gemm_body<P, BM, BN, BK, TA, TB, EPI, S>(g_in, (int)blockIdx.x);
 }
 // Up to four GEMMs of one tile configuration in one launch: workgroups [start[i], start[i + 1]) are GEMM i's. The
@@ -901,7 +929,9 @@ struct WeightChunk {
   }
 };
 
-template <int CH>  // columns of I per chunk: 128 (two workgroups' worth of registers) or 64
+// CH: columns of I per chunk: 128 (two workgroups' worth of registers) or 64. RE: the residual (this layer's LayerNorm 1
+// output) is re-derived from pre1 / mean1 / rstd1 in the epilogue (EPI_DROP_RES_LN_RE) instead of loaded.
+template <int CH, bool RE = false>
 __global__ __launch_bounds__(256, CH == 128 ? XF_FFN_MIN_WAVES : 3) void ffn_fwd_fused_kernel(const FfnFwdArgs f_in) {
   FfnFwdArgs f = f_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
   XF_CHAIN_PRIO();
@@ -1031,7 +1061,7 @@ __global__ __launch_bounds__(256, CH == 128 ? XF_FFN_MIN_WAVES : 3) void ffn_fwd
   XF_STAMP(14);
   __syncthreads();  // everyone is done with sW: the epilogue's scratch aliases it
   XF_STAMP(15);
-  epi_drop_res_ln_64x128(accy, reinterpret_cast<unsigned char*>(sW), f.e, m0, wid, lane);
+  epi_drop_res_ln_64x128<RE ? 1 : 0>(accy, reinterpret_cast<unsigned char*>(sW), f.e, m0, wid, lane);
   XF_STAMP(16);
 }
 
@@ -1358,7 +1388,7 @@ int launch_gemm_bk(const GemmArgs& g, int splits, hipStream_t st) {
   // are co-resident, not by the matrix core. Many small workgroups win -- 64x64 tiles with
   // 64-deep slices for the forward / dX GEMMs (64x128 once N >= 256), 128-deep slices only for the split-K dW GEMMs.
   int bm = 64, bn = (g.N >= 256 && EPI != EPI_GELU_GRAD) ? 128 : 64;
-  if (EPI == EPI_DROP_RES_LN || EPI == EPI_DX_LNBWD) bn = 128;  // whole rows (N == 128, checked by the caller)
+  if (epi_res_ln(EPI) || EPI == EPI_DX_LNBWD) bn = 128;  // whole rows (N == 128, checked by the caller)
   if (EPI == EPI_SPLITK && g.M > 64 && g.N > 64) {
     // 128 x 64: twice the workgroups of 128 x 128 at half the LDS and registers each -- the split-K GEMMs are a
     // latency chain of a dozen K slices per workgroup and want co-resident workgroups (measured +1.4 ... 2 % of the
@@ -1372,13 +1402,13 @@ int launch_gemm_bk(const GemmArgs& g, int splits, hipStream_t st) {
     if (dw.bm) { bm = dw.bm; bn = dw.bn; }
   }
   const TileOverride ov = tile_override();
-  if (ov.bm && EPI != EPI_DROP_RES_LN && EPI != EPI_DX_LNBWD) { bm = ov.bm; bn = ov.bn; }
+  if (ov.bm && !epi_res_ln(EPI) && EPI != EPI_DX_LNBWD) { bm = ov.bm; bn = ov.bn; }
   dim3 block(256);
   static const int pad_lds = [] { const char* e = getenv("XFMR_GEMM_PAD_LDS"); return e ? atoi(e) : 0; }();
   GemmArgs ga = g;
   ga.nt_n = (int)((g.N + bn - 1) / bn);
   ga.nt_m = (int)((g.M + bm - 1) / bm);
-  if (EPI == EPI_DROP_RES_LN || EPI == EPI_DX_LNBWD) xf_plan_row_tiles(ga, bm);  // (whole-row tiles: bm = 64, one N-tile)
+  if (epi_res_ln(EPI) || EPI == EPI_DX_LNBWD) xf_plan_row_tiles(ga, bm);  // (whole-row tiles: bm = 64, one N-tile)
   ga.nt_z = splits;
   // one-dimensional launch, padded so that every XCD gets whole groups (see tile_of)
   const int64_t groups = splits > 1 ? (splits + 7) / 8 : (ga.nt_m + 7) / 8;
@@ -1458,6 +1488,79 @@ int dw_split_bound(int64_t M, int N, int K) {
   return bound > plan ? (int)bound : plan;
 }
 
+// residual operand of the EPI_DROP_RES_LN family: `residual` (loaded) or `res` (re-derived) -- exactly one
+int set_ln_residual(GemmArgs& g, const float* residual, const XfLnResidual* res, XfSeed seed) {
+  if ((residual != nullptr) == (res != nullptr)) return XFMR_EINVAL;
+  g.R = residual;
+  if (!res) return xf_aligned16(residual) ? XFMR_OK : XFMR_EALIGN;
+  if (!res->pre || !res->mean || !res->rstd || !res->gamma || !res->beta) return XFMR_EINVAL;
+  if (!xf_aligned16(res->pre) || !xf_aligned16(res->gamma) || !xf_aligned16(res->beta)) return XFMR_EALIGN;
+  g.rp_pre = res->pre; g.rp_mean = res->mean; g.rp_rstd = res->rstd; g.rp_gamma = res->gamma; g.rp_beta = res->beta;
+  g.rp_drop = xf_make_dropout(res->dropout_p, seed, res->site);
+  return XFMR_OK;
+}
+
+int linear_ln_fwd(const void* x, const float* w, const float* bias, float* pre, int64_t M, int32_t N, int32_t K,
+                  const float* residual, const XfLnResidual* res, float dropout_p, XfSeed seed, uint32_t site,
+                  const float* gamma, const float* beta, float eps, float* y, void* y16, float* mean, float* rstd,
+                  int32_t precision, uint32_t s16, hipStream_t st) {
+  if (!x || !w || !pre || !gamma || !beta || (!y && !y16) || !mean || !rstd || M <= 0 || K <= 0) return XFMR_EINVAL;
+  if (N != 128 || (K & 7)) return XFMR_EUNSUPPORTED;  // the tile spans one whole 128-column row
+  if (precision != XFMR_PREC_BF16) return XFMR_EUNSUPPORTED;
+  if (!xf_aligned16(x) || !xf_aligned16(w) || !xf_aligned16(pre) || (y && !xf_aligned16(y))) return XFMR_EALIGN;
+  GemmArgs g{};
+  g.A = x; g.B = w; g.C = pre; g.lda = K; g.ldb = K; g.ldc = N; g.M = M; g.N = N; g.K = K; g.k_chunk = 0;
+  g.bias = bias; g.s16 = s16 & (XF_S16_A | XF_S16_B);
+  if (const int rc = set_ln_residual(g, residual, res, seed)) return rc;
+  g.drop = xf_make_dropout(dropout_p, seed, site);
+  g.ln_gamma = gamma; g.ln_beta = beta; g.ln_eps = eps; g.Y = y; g.Y16 = y16; g.ln_mean = mean; g.ln_rstd = rstd;
+  if (!res) return dispatch_gemm<false, false, EPI_DROP_RES_LN, XF_S16_A, (XF_S16_A | XF_S16_B)>(g, 1, precision, st);
+  // (the re-derived forms exist for the storage the encoder runs them with: bf16 A and B operands)
+  if (g.s16 != (XF_S16_A | XF_S16_B)) return XFMR_EUNSUPPORTED;
+  if (g.rp_drop.on) return launch_gemm<PrecBF16, false, false, EPI_DROP_RES_LN_RED, (XF_S16_A | XF_S16_B)>(g, 1, st);
+  return launch_gemm<PrecBF16, false, false, EPI_DROP_RES_LN_RE, (XF_S16_A | XF_S16_B)>(g, 1, st);
+}
+
+int ffn_fwd_fused(const void* x16, const void* w1_16, const float* b1, const void* w2_16, const float* b2, void* u16,
+                  void* g16, float* pre, int64_t M, int32_t H, int32_t I, const float* residual, const XfLnResidual* res,
+                  float dropout_p, XfSeed seed, uint32_t site, const float* gamma, const float* beta, float eps, float* y,
+                  void* y16, float* mean, float* rstd, hipStream_t st) {
+  if (!x16 || !w1_16 || !b1 || !w2_16 || !pre || !gamma || !beta || (!y && !y16) || !mean || !rstd || M <= 0)
+    return XFMR_EINVAL;
+  if (H != 128 || I <= 0 || (I % 128) || I > 1024) return XFMR_EUNSUPPORTED;  // (b1 is staged in 4 KB of LDS)
+  if (res && res->dropout_p > 0.f) return XFMR_EUNSUPPORTED;
+  if (!xf_aligned16(x16) || !xf_aligned16(w1_16) || !xf_aligned16(w2_16) || !xf_aligned16(pre) ||
+      (y && !xf_aligned16(y)) || (u16 && !xf_aligned16(u16)) || (g16 && !xf_aligned16(g16)) || (y16 && !xf_aligned16(y16)) || !xf_aligned16(b1) ||
+      (b2 && !xf_aligned16(b2)) || !xf_aligned16(gamma) || !xf_aligned16(beta))
+    return XFMR_EALIGN;
+  FfnFwdArgs f{};
+  f.X = (const __bf16*)x16; f.W1 = (const __bf16*)w1_16; f.b1 = b1; f.W2 = (const __bf16*)w2_16; f.U = (__bf16*)u16; f.G = (__bf16*)g16;
+  f.I = I;
+#ifdef XF_FFN_STAMP
+  if (const char* e = getenv("XFMR_FFN_STAMPS")) f.stamps = (unsigned long long*)strtoull(e, nullptr, 0);
+#endif
+  GemmArgs& g = f.e;
+  g.C = pre; g.ldc = H; g.M = M; g.N = H; g.K = I; g.bias = b2;
+  if (const int rc = set_ln_residual(g, residual, res, seed)) return rc;
+  g.drop = xf_make_dropout(dropout_p, seed, site);
+  g.ln_gamma = gamma; g.ln_beta = beta; g.ln_eps = eps; g.Y = y; g.Y16 = y16; g.ln_mean = mean; g.ln_rstd = rstd;
+  g.nt_n = 1; g.nt_z = 1;
+  xf_plan_row_tiles(g, 64);
+  const int64_t groups = (g.nt_m + 7) / 8;
+  if (groups * 8 > 0x7fffffffll) return XFMR_EUNSUPPORTED;
+  // XFMR_FFN_CHUNK=128 (tiling only -- what the kernel stores does not depend on it; read per call so that one test process
+  // can cover both): the wider chunk, two workgroups per CU -- measured slower
+  const char* ce = getenv("XFMR_FFN_CHUNK");
+  const int chunk = ce ? atoi(ce) : 64;
+  const dim3 grid((unsigned)(groups * 8));
+  if (chunk == 64 && res) hipLaunchKernelGGL((ffn_fwd_fused_kernel<64, true>), grid, dim3(256), 0, st, f);
+  else if (chunk == 64) hipLaunchKernelGGL((ffn_fwd_fused_kernel<64, false>), grid, dim3(256), 0, st, f);
+  else if (res) hipLaunchKernelGGL((ffn_fwd_fused_kernel<128, true>), grid, dim3(256), 0, st, f);
+  else hipLaunchKernelGGL((ffn_fwd_fused_kernel<128, false>), grid, dim3(256), 0, st, f);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
+
 }  // namespace
 
 
@@ -1512,17 +1615,17 @@ int xf_linear_ln_fwd_ex(const void* x, const float* w, const float* bias, float*
                         const float* residual, float dropout_p, XfSeed seed, uint32_t site, const float* gamma,
                         const float* beta, float eps, float* y, void* y16, float* mean, float* rstd, int32_t precision,
                         uint32_t s16, hipStream_t st) {
-  if (!x || !w || !pre || !residual || !gamma || !beta || !y || !mean || !rstd || M <= 0 || K <= 0)
-    return XFMR_EINVAL;
-  if (N != 128 || (K & 7)) return XFMR_EUNSUPPORTED;  // the tile spans one whole 128-column row
-  if (precision != XFMR_PREC_BF16) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(x) || !xf_aligned16(w) || !xf_aligned16(pre) || !xf_aligned16(y)) return XFMR_EALIGN;
-  GemmArgs g{};
-  g.A = x; g.B = w; g.C = pre; g.lda = K; g.ldb = K; g.ldc = N; g.M = M; g.N = N; g.K = K; g.k_chunk = 0;
-  g.bias = bias; g.R = residual; g.s16 = s16 & (XF_S16_A | XF_S16_B);
-  g.drop = xf_make_dropout(dropout_p, seed, site);
-  g.ln_gamma = gamma; g.ln_beta = beta; g.ln_eps = eps; g.Y = y; g.Y16 = y16; g.ln_mean = mean; g.ln_rstd = rstd;
-  return dispatch_gemm<false, false, EPI_DROP_RES_LN, XF_S16_A, (XF_S16_A | XF_S16_B)>(g, 1, precision, st);
+  if (!residual || !y) return XFMR_EINVAL;
+  return linear_ln_fwd(x, w, bias, pre, M, N, K, residual, nullptr, dropout_p, seed, site, gamma, beta, eps, y, y16, mean,
+                       rstd, precision, s16, st);
+}
+int xf_linear_ln_fwd_re(const void* x, const float* w, const float* bias, float* pre, int64_t M, int32_t N, int32_t K,
+                        const XfLnResidual* res, float dropout_p, XfSeed seed, uint32_t site, const float* gamma,
+                        const float* beta, float eps, float* y, void* y16, float* mean, float* rstd, int32_t precision,
+                        uint32_t s16, hipStream_t st) {
+  if (!res) return XFMR_EINVAL;
+  return linear_ln_fwd(x, w, bias, pre, M, N, K, nullptr, res, dropout_p, seed, site, gamma, beta, eps, y, y16, mean, rstd,
+                       precision, s16, st);
 }
 
 int xfmr_linear_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int32_t N, int32_t K,
@@ -1536,35 +1639,17 @@ int xf_ffn_fwd_fused_ex(const void* x16, const void* w1_16, const float* b1, con
                         void* u16, void* g16, float* pre, int64_t M, int32_t H, int32_t I, const float* residual, float dropout_p,
                         XfSeed seed, uint32_t site, const float* gamma, const float* beta, float eps, float* y,
                         void* y16, float* mean, float* rstd, hipStream_t st) {
-  if (!x16 || !w1_16 || !b1 || !w2_16 || !pre || !residual || !gamma || !beta || !y || !mean || !rstd || M <= 0)
-    return XFMR_EINVAL;
-  if (H != 128 || I <= 0 || (I % 128) || I > 1024) return XFMR_EUNSUPPORTED;  // (b1 is staged in 4 KB of LDS)
-  if (!xf_aligned16(x16) || !xf_aligned16(w1_16) || !xf_aligned16(w2_16) || !xf_aligned16(pre) || !xf_aligned16(residual) ||
-      !xf_aligned16(y) || (u16 && !xf_aligned16(u16)) || (g16 && !xf_aligned16(g16)) || (y16 && !xf_aligned16(y16)) || !xf_aligned16(b1) ||
-      (b2 && !xf_aligned16(b2)) || !xf_aligned16(gamma) || !xf_aligned16(beta))
-    return XFMR_EALIGN;
-  FfnFwdArgs f{};
-  f.X = (const __bf16*)x16; f.W1 = (const __bf16*)w1_16; f.b1 = b1; f.W2 = (const __bf16*)w2_16; f.U = (__bf16*)u16; f.G = (__bf16*)g16;
-  f.I = I;
-#ifdef XF_FFN_STAMP
-  if (const char* e = getenv("XFMR_FFN_STAMPS")) f.stamps = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
-  GemmArgs& g = f.e;
-  g.C = pre; g.ldc = H; g.M = M; g.N = H; g.K = I; g.bias = b2; g.R = residual;
-  g.drop = xf_make_dropout(dropout_p, seed, site);
-  g.ln_gamma = gamma; g.ln_beta = beta; g.ln_eps = eps; g.Y = y; g.Y16 = y16; g.ln_mean = mean; g.ln_rstd = rstd;
-  g.nt_n = 1; g.nt_z = 1;
-  xf_plan_row_tiles(g, 64);
-  const int64_t groups = (g.nt_m + 7) / 8;
-  if (groups * 8 > 0x7fffffffll) return XFMR_EUNSUPPORTED;
-  // XFMR_FFN_CHUNK=128 (tiling only -- what the kernel stores does not depend on it; read per call so that one test process
-  // can cover both): the wider chunk, two workgroups per CU -- measured slower
-  const char* ce = getenv("XFMR_FFN_CHUNK");
-  const int chunk = ce ? atoi(ce) : 64;
-  if (chunk == 64) hipLaunchKernelGGL(ffn_fwd_fused_kernel<64>, dim3((unsigned)(groups * 8)), dim3(256), 0, st, f);
-  else hipLaunchKernelGGL(ffn_fwd_fused_kernel<128>, dim3((unsigned)(groups * 8)), dim3(256), 0, st, f);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  if (!residual || !y) return XFMR_EINVAL;
+  return ffn_fwd_fused(x16, w1_16, b1, w2_16, b2, u16, g16, pre, M, H, I, residual, nullptr, dropout_p, seed, site, gamma,
+                       beta, eps, y, y16, mean, rstd, st);
+}
+int xf_ffn_fwd_fused_re(const void* x16, const void* w1_16, const float* b1, const void* w2_16, const float* b2,
+                        void* u16, void* g16, float* pre, int64_t M, int32_t H, int32_t I, const XfLnResidual* res,
+                        float dropout_p, XfSeed seed, uint32_t site, const float* gamma, const float* beta, float eps,
+                        float* y, void* y16, float* mean, float* rstd, hipStream_t st) {
+  if (!res) return XFMR_EINVAL;
+  return ffn_fwd_fused(x16, w1_16, b1, w2_16, b2, u16, g16, pre, M, H, I, nullptr, res, dropout_p, seed, site, gamma, beta,
+                       eps, y, y16, mean, rstd, st);
 }
 
 int xf_ffn_bwd_dx_fused_ex(const void* dy16, const void* w2_16, const void* u16, const void* w1_16, void* di16, int64_t M,

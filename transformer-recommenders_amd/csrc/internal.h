@@ -25,6 +25,24 @@ int xf_ffn_fwd_fused_ex(const void* x16, const void* w1_16, const float* b1, con
                         void* u16, void* g16, float* pre, int64_t M, int32_t H, int32_t I, const float* residual, float dropout_p,
                         XfSeed seed, uint32_t site, const float* gamma, const float* beta, float eps, float* y,
                         void* y16, float* mean, float* rstd, hipStream_t st);
+// The residual operand of the two LayerNorm-fused forward kernels as "re-derived": the OUTPUT of an earlier LayerNorm,
+// recomputed from what that LayerNorm stored for its backward (xf_ln_out_drop4) instead of loaded from a stored fp32 copy.
+// dropout_p / site: dropout that was applied to that output (the embedding LayerNorm); 0: none.
+struct XfLnResidual {
+  const float* pre; const float* mean; const float* rstd; const float* gamma; const float* beta;
+  float dropout_p; uint32_t site;
+};
+// xf_ffn_fwd_fused_ex / xf_linear_ln_fwd_ex with residual = *res; y may be null (the fp32 output is not stored: y16 is then
+// required -- whoever takes the output as ITS residual re-derives it the same way). The fused FFN takes no dropout on its
+// residual (it is always a layer's own LayerNorm 1 output).
+int xf_ffn_fwd_fused_re(const void* x16, const void* w1_16, const float* b1, const void* w2_16, const float* b2,
+                        void* u16, void* g16, float* pre, int64_t M, int32_t H, int32_t I, const XfLnResidual* res,
+                        float dropout_p, XfSeed seed, uint32_t site, const float* gamma, const float* beta, float eps,
+                        float* y, void* y16, float* mean, float* rstd, hipStream_t st);
+int xf_linear_ln_fwd_re(const void* x, const float* w, const float* bias, float* pre, int64_t M, int32_t N, int32_t K,
+                        const XfLnResidual* res, float dropout_p, XfSeed seed, uint32_t site, const float* gamma,
+                        const float* beta, float eps, float* y, void* y16, float* mean, float* rstd, int32_t precision,
+                        uint32_t s16, hipStream_t st);
 // The dX chain of the FFN backward in one kernel (bf16 storage, H = 128, I a multiple of 64; after the fused forward:
 // u16 = the saved pre-activation): di16 <- (dy16 W2) * gelu'(u16), then exactly xf_linear_bwd_dx_lnbwd_ex on di16 / W1.
 int xf_ffn_bwd_dx_fused_ex(const void* dy16, const void* w2_16, const void* u16, const void* w1_16, void* di16, int64_t M,

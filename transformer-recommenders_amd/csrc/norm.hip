@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a_in) {
     if (c < H) {
       float o = (v[i] - mean) * rstd * a.gamma[c] + a.beta[c];
       if (a.drop.on) o *= xf_keep_scale_2d(a.drop, (uint32_t)row, (uint32_t)c);
-      a.y[row * H + c] = o;
+      if (a.y) a.y[row * H + c] = o;
       if (a.y16) a.y16[row * H + c] = (__bf16)o;
     }
   }
@@ -222,12 +222,11 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(const LnFwdArgs a_in) {
   }
   const float4 g = *reinterpret_cast<const float4*>(a.gamma + c);
   const float4 b = *reinterpret_cast<const float4*>(a.beta + c);
-  float4 o;
-  o.x = dx * rstd * g.x + b.x; o.y = dy * rstd * g.y + b.y; o.z = dz * rstd * g.z + b.z; o.w = dw * rstd * g.w + b.w;
+  float4 o = xf_ln_affine4(make_float4(dx, dy, dz, dw), rstd, g, b);
   if (a.drop.on) {
     xf_drop4(a.drop, (uint32_t)row, (uint32_t)(c), o);
   }
-  *reinterpret_cast<float4*>(a.y + row * H + c) = o;
+  if (a.y) *reinterpret_cast<float4*>(a.y + row * H + c) = o;  // (null: the consumer re-derives it -- xf_ln_out_drop4)
   if (a.y16) xf_st4<true>(a.y16, row * H + c, o);
 }
 
@@ -669,7 +668,8 @@ int xf_embed_ln_fwd_ex(const int64_t* item_idx, const float* table, int64_t n_ro
                        const float* type_emb, const float* gamma, const float* beta, float* out, void* out16,
                        float* pre, float* mean, float* rstd, uint8_t* key_mask, int32_t B, int32_t L, int32_t H,
                        float eps, float dropout_p, XfSeed seed, uint32_t site, hipStream_t stream) {
-  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || !out || !pre || !mean || !rstd || !key_mask)
+  // (out may be null when out16 is given: the fp32 output is not stored -- its consumer re-derives it, xf_ln_out_drop4)
+  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !pre || !mean || !rstd || !key_mask)
     return XFMR_EINVAL;
   if (B <= 0 || L <= 0 || H <= 0 || n_rows <= 0) return XFMR_EINVAL;
   LnFwdArgs a{};
@@ -686,7 +686,7 @@ int xf_embed_ln_fwd_packed_ex(const int64_t* item_idx, const float* table, int64
                               const float* type_emb, const float* gamma, const float* beta, float* out, void* out16,
                               float* pre, float* mean, float* rstd, uint8_t* key_mask, int64_t rows, const int32_t* row_pos,
                               int32_t H, float eps, float dropout_p, XfSeed seed, uint32_t site, hipStream_t stream) {
-  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || !out || !pre || !mean || !rstd || !key_mask || !row_pos)
+  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !pre || !mean || !rstd || !key_mask || !row_pos)
     return XFMR_EINVAL;
   if (rows <= 0 || H <= 0 || n_rows <= 0) return XFMR_EINVAL;
   LnFwdArgs a{};
