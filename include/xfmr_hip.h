@@ -582,6 +582,67 @@ int xfmr_adamw_dev(float* params, const float* grads, float* exp_avg, float* exp
 int xfmr_step_advance(uint32_t* step_device, void* stream); /* *step_device += 1 (one thread) */
 
 /* ------------------------------------------------------------------------------------------------
+ * K18b: the optimizer step's options -- gradient clipping, gradient scaling for accumulated micro-batches and
+ * learning-rate schedules -- produced and consumed ON THE DEVICE, so that a clipped or scheduled step has no
+ * host-computed argument that changes from step to step (it can be captured and replayed like xfmr_adamw_dev).
+ *
+ *   xfmr_opt_prepare   grads -> ctl: the norm, max |g| and non-finite count of grad_scale * g, the clip
+ *                      coefficient and the step's learning rate (two launches)
+ *   xfmr_adamw_ctl     the AdamW update of xfmr_adamw / xfmr_adamw_dev with the gradient clipped as `ctl` says and
+ *                      the learning rate read from ctl->lr (one launch; grads themselves are left as they are)
+ *
+ * Semantics matched (torch): clip_grad_norm_ (error_if_nonfinite=False: clip_coef = min(1, clip_val / (norm + 1e-6)),
+ * a NaN / inf norm propagates), clip_grad_value_ (clamp to +-clip_val), LambdaLR stepped once per optimizer step with
+ * the lr_lambda of transformers.optimization.get_{constant,linear,cosine}_schedule_with_warmup: with s = step - 1
+ * completed steps, W = warmup_steps, T = total_steps
+ *   constant          1
+ *   warmup-constant   s / max(1, W) for s < W, else 1
+ *   warmup-linear     the same ramp, then max(0, (T - s) / max(1, T - W))
+ *   warmup-cosine     the same ramp, then max(0, 0.5 * (1 + cos(pi * (s - W) / max(1, T - W))))
+ * evaluated in fp64 and rounded once to fp32; ctl->lr = lr * that value.
+ * ---------------------------------------------------------------------------------------------- */
+enum { XFMR_CLIP_NONE = 0, XFMR_CLIP_NORM = 1, XFMR_CLIP_VALUE = 2 };
+enum { XFMR_SCHED_CONSTANT = 0, XFMR_SCHED_WARMUP_CONSTANT = 1, XFMR_SCHED_WARMUP_LINEAR = 2, XFMR_SCHED_WARMUP_COSINE = 3 };
+
+typedef struct xfmr_opt_cfg {
+  float lr, beta1, beta2, eps, weight_decay;
+  float grad_scale;     /* multiplies the gradient first: 1 / (world_size * accumulated micro-batches)               */
+  int32_t clip_mode;    /* XFMR_CLIP_*                                                                               */
+  float clip_val;       /* > 0 unless clip_mode is XFMR_CLIP_NONE                                                    */
+  int32_t sched;        /* XFMR_SCHED_*                                                                              */
+  int32_t step_offset;  /* with step_device: step = *step_device + step_offset                                       */
+  int64_t warmup_steps; /* W >= 0                                                                                    */
+  int64_t total_steps;  /* T >= 0 (the two decaying schedules)                                                       */
+  int64_t step;         /* 1-based step, used when step_device is NULL                                               */
+  const uint32_t* step_device; /* device counter of completed steps (the pair xfmr_adamw_dev takes), or NULL         */
+} xfmr_opt_cfg;
+
+/* 32 bytes in device memory, written by xfmr_opt_prepare and read by xfmr_adamw_ctl */
+typedef struct xfmr_opt_ctl {
+  float grad_norm;     /* L2 norm of grad_scale * g (fp64 accumulation, rounded once)   */
+  float grad_max_abs;  /* max |grad_scale * g| over the finite and infinite elements    */
+  float clip_coef;     /* norm mode: min(1, clip_val / (grad_norm + 1e-6)); otherwise 1 */
+  float lr;            /* the step's learning rate                                      */
+  uint32_t nonfinite;  /* number of NaN / inf elements                                  */
+  uint32_t pad[3];
+} xfmr_opt_ctl;
+
+/* The schedule's factor for s completed steps: the host form of what the device evaluates (same arithmetic). */
+float xfmr_lr_lambda(int32_t sched, int64_t warmup_steps, int64_t total_steps, int64_t completed_steps);
+
+/* Launch (a): a fixed grid of at most 256 workgroups strides over grads with 16-byte loads, squares accumulated in fp64,
+ * one record per workgroup into `workspace`; launch (b): one workgroup adds the records in a fixed order and writes ctl.
+ * No atomics: the same input gives the same bits on every launch. grads 16-byte aligned (XFMR_EALIGN otherwise). */
+size_t xfmr_opt_workspace(int64_t n);
+int xfmr_opt_prepare(const xfmr_opt_cfg* cfg, const float* grads, int64_t n, void* workspace, xfmr_opt_ctl* ctl,
+                     void* stream);
+/* With clip_mode XFMR_CLIP_NONE and a constant schedule: the bits of xfmr_adamw / xfmr_adamw_dev on the same inputs. */
+int xfmr_adamw_ctl(const xfmr_opt_cfg* cfg, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                   int64_t n, const xfmr_opt_ctl* ctl, void* stream);
+/* acc = first ? grads : acc + grads (gradient accumulation over micro-batches); both 16-byte aligned. */
+int xfmr_grad_accumulate(float* acc, const float* grads, int64_t n, int32_t first, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K19: the data-parallel exchange (SURVEY section 8b `allreduce_flat`, 8e): what torch DDP does for the reference
  * (config.yaml:5-6,35 -- Lightning `strategy: auto`): g <- SUM over ranks of the flat gradient buffer, in place, fp32, on
  * the caller's stream; the 1 / world factor is xfmr_adamw's grad_scale. RCCL does the transport (rings over xGMI); it is

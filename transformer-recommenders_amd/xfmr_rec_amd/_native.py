@@ -72,6 +72,23 @@ class LossCfg(C.Structure):
     ]
 
 
+CLIP_NONE, CLIP_NORM, CLIP_VALUE = 0, 1, 2  # xfmr_opt_cfg.clip_mode
+CLIP_MODES = {None: CLIP_NONE, "none": CLIP_NONE, "norm": CLIP_NORM, "value": CLIP_VALUE}
+# xfmr_opt_cfg.sched: a LambdaLR with the lr_lambda of transformers.optimization.get_*_schedule_with_warmup
+SCHEDULES = {"constant": 0, "warmup_constant": 1, "warmup_linear": 2, "warmup_cosine": 3}
+# the words of the xfmr_opt_ctl record (nonfinite is a uint32: read it through an int32 view)
+CTL = dict(grad_norm=0, grad_max_abs=1, clip_coef=2, lr=3, nonfinite=4)
+
+
+class OptCfg(C.Structure):
+    _fields_ = [
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+        ("grad_scale", C.c_float), ("clip_mode", C.c_int32), ("clip_val", C.c_float), ("sched", C.c_int32),
+        ("step_offset", C.c_int32), ("warmup_steps", C.c_int64), ("total_steps", C.c_int64), ("step", C.c_int64),
+        ("step_device", C.c_void_p),
+    ]
+
+
 class Seed(C.Structure):
     """csrc/common.h XfSeed, by value: the dropout seed argument of the library's INTERNAL entry points (xf_*_ex; tests and
     probes call a few of them directly). A plain int converts to (seed, no device-side counter)."""
@@ -174,6 +191,11 @@ _SIGNATURES = {
     "xfmr_adamw_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                  _P, C.c_int32, C.c_float, _P]),
     "xfmr_step_advance": (C.c_int, [_P, _P]),
+    "xfmr_lr_lambda": (C.c_float, [C.c_int32, C.c_int64, C.c_int64, C.c_int64]),
+    "xfmr_opt_workspace": (C.c_size_t, [C.c_int64]),
+    "xfmr_opt_prepare": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
+    "xfmr_adamw_ctl": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "xfmr_grad_accumulate": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     "xfmr_scale_by_device_scalar": (C.c_int, [_P, C.c_int64, _P, _P]),
     "xfmr_selftest_mfma": (C.c_int, [_P, _P]),
     "xfmr_comm_unique_id": (C.c_int, [_P]),

@@ -272,6 +272,80 @@ def step_advance_(step_device):
     N.check(N.load().xfmr_step_advance(N.ptr(step_device), N.stream()), "xfmr_step_advance")
 
 
+# ---- the optimizer step's options on the device (include/xfmr_hip.h K18b): clip, gradient scale, lr schedule
+def _schedule_ids(schedule) -> tuple[int, int, int]:
+    """``{"name", "warmup_steps", "total_steps"}`` (or None = constant) -> (XFMR_SCHED_*, W, T)."""
+    if schedule is None:
+        return N.SCHEDULES["constant"], 0, 0
+    unknown = set(schedule) - {"name", "warmup_steps", "total_steps"}
+    if unknown:
+        raise ValueError(f"schedule: unknown keys {sorted(unknown)}")
+    name = schedule.get("name", "constant")
+    if name not in N.SCHEDULES:
+        raise ValueError(f"schedule name must be one of {sorted(N.SCHEDULES)}; got {name!r}")
+    W, T = int(schedule.get("warmup_steps") or 0), int(schedule.get("total_steps") or 0)
+    if W < 0 or T < 0:
+        raise ValueError(f"schedule: warmup_steps / total_steps must be >= 0, got {W}, {T}")
+    if name in ("warmup_linear", "warmup_cosine") and "total_steps" not in schedule:
+        raise ValueError(f"schedule {name!r} needs total_steps")
+    return N.SCHEDULES[name], W, T
+
+
+def lr_lambda(schedule, completed_steps: int) -> float:
+    """The schedule's factor after ``completed_steps`` optimizer steps: the library's host form of what its kernel
+    evaluates (fp64 arithmetic, rounded once to fp32)."""
+    sched, W, T = _schedule_ids(schedule)
+    return float(N.load().xfmr_lr_lambda(sched, W, T, int(completed_steps)))
+
+
+def make_opt_cfg(*, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, clip_mode=None,
+                 clip_val=None, schedule=None, step=1, step_device=None) -> N.OptCfg:
+    """xfmr_opt_cfg. ``step_device`` (int32 device tensor = completed steps): the step is read on the device (``step``
+    ignored), as in :func:`adamw_`. The caller keeps ``step_device`` alive while the record is in use."""
+    if clip_mode not in N.CLIP_MODES:
+        raise ValueError(f"clip_mode must be one of 'norm', 'value' or None; got {clip_mode!r}")
+    mode = N.CLIP_MODES[clip_mode]
+    if mode != N.CLIP_NONE and not (clip_val is not None and float(clip_val) > 0.0):
+        raise ValueError(f"clip_mode={clip_mode!r} needs clip_val > 0, got {clip_val!r}")
+    sched, W, T = _schedule_ids(schedule)
+    return N.OptCfg(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
+                    clip_mode=mode, clip_val=float(clip_val) if mode != N.CLIP_NONE else 0.0, sched=sched, step_offset=1,
+                    warmup_steps=W, total_steps=T, step=int(step), step_device=N.ptr(step_device))
+
+
+def opt_buffers(grads: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(ctl, workspace) for a gradient buffer of this size: the 32-byte xfmr_opt_ctl record as 8 fp32 words (N.CTL names
+    them) and the first launch's per-workgroup records."""
+    ctl = torch.zeros(8, dtype=f32, device=grads.device)
+    return ctl, _bytes(N.load().xfmr_opt_workspace(grads.numel()), grads)
+
+
+def opt_prepare_(cfg: N.OptCfg, grads, workspace, ctl):
+    """grads -> ctl (norm, max |g|, clip coefficient, learning rate, non-finite count); two launches, no atomics."""
+    if workspace.numel() < N.load().xfmr_opt_workspace(grads.numel()) or ctl.numel() * ctl.element_size() < 32:
+        raise ValueError("opt_prepare_: workspace / ctl too small for this gradient buffer (ops.opt_buffers)")
+    N.check(N.load().xfmr_opt_prepare(C.byref(cfg), N.ptr(grads), grads.numel(), N.ptr(workspace), N.ptr(ctl), N.stream()),
+            "xfmr_opt_prepare")
+    return ctl
+
+
+def adamw_ctl_(cfg: N.OptCfg, params, grads, exp_avg, exp_avg_sq, ctl):
+    """The update of :func:`adamw_` with the gradient clipped as ``ctl`` says and the learning rate read from it."""
+    if not (params.numel() == grads.numel() == exp_avg.numel() == exp_avg_sq.numel()):
+        raise ValueError("adamw_ctl_: params, grads and the moments must have the same number of elements")
+    N.check(N.load().xfmr_adamw_ctl(C.byref(cfg), N.ptr(params), N.ptr(grads), N.ptr(exp_avg), N.ptr(exp_avg_sq),
+                                    params.numel(), N.ptr(ctl), N.stream()), "xfmr_adamw_ctl")
+
+
+def grad_accumulate_(acc, grads, first: bool):
+    """acc = grads if first else acc + grads."""
+    if acc.numel() != grads.numel():
+        raise ValueError("grad_accumulate_: acc and grads must have the same number of elements")
+    N.check(N.load().xfmr_grad_accumulate(N.ptr(acc), N.ptr(grads), acc.numel(), 1 if first else 0, N.stream()),
+            "xfmr_grad_accumulate")
+    return acc
+
+
 def _plan_flags(nsplit: int = 0, nsplit_grad: int = 0) -> int:
     """XFMR_LOSS_NSPLIT(n) | XFMR_LOSS_NSPLIT_GRAD(n): launch-plan overrides inside xfmr_loss_cfg.flags (0 = library's plan)."""
     assert 0 <= nsplit < 256 and 0 <= nsplit_grad < 256

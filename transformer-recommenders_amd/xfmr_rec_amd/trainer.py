@@ -64,13 +64,45 @@ class FusedAdamW(torch.optim.Optimizer):
     from it (``xfmr_adamw_dev``) and advances it afterwards (``xfmr_step_advance``) -- no host-computed argument changes
     from step to step, so the step can be captured into a hipGraph and replayed."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, step_device=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, step_device=None,
+                 clip_mode=None, clip_val=None, schedule=None):
+        """``clip_mode``: None, "norm" (``clip_grad_norm_``) or "value" (``clip_grad_value_``) with ``clip_val``;
+        ``schedule``: ``{"name": "constant" | "warmup_constant" | "warmup_linear" | "warmup_cosine", "warmup_steps",
+        "total_steps"}`` -- a ``LambdaLR`` stepped once per optimizer step. With either set the step is
+        ``xfmr_opt_prepare`` + ``xfmr_adamw_ctl``: norm, clip coefficient and learning rate are produced and consumed on
+        the device (``self.ctl``), so the step stays capturable. The clip is folded into the update: ``p.grad`` itself is
+        left unclipped. Neither is part of ``state_dict()``: the schedule is a function of the step
+        count that is."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale))
         self.step_device = step_device
+        ops.make_opt_cfg(lr=lr, clip_mode=clip_mode, clip_val=clip_val, schedule=schedule)  # (validates, loudly, now)
+        self.clip_mode, self.clip_val = clip_mode, clip_val
+        self.schedule = dict(schedule) if schedule is not None else None
+        self._opt_bufs: dict = {}  # parameter -> (ctl, workspace), created at the first step
+
+    @property
+    def has_options(self) -> bool:
+        return self.clip_mode is not None or (self.schedule is not None and self.schedule.get("name", "constant") != "constant")
+
+    @property
+    def ctl(self) -> torch.Tensor | None:
+        """The xfmr_opt_ctl record of the last step as 8 fp32 device words (``_native.CTL`` names them); None before the
+        first step with an option set."""
+        return next(iter(self._opt_bufs.values()))[0] if self._opt_bufs else None
+
+    def ctl_log_dict(self) -> dict[str, torch.Tensor]:
+        """``grad/norm``, ``grad/clip_coef`` and ``lr`` of the last step: 0-dim device views of ``ctl``, no host sync."""
+        ctl = self.ctl
+        if ctl is None:
+            return {}
+        return {"grad/norm": ctl[N.CTL["grad_norm"]], "grad/clip_coef": ctl[N.CTL["clip_coef"]], "lr": ctl[N.CTL["lr"]]}
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        options = self.has_options
+        if options and self.clip_mode == "norm" and sum(p.grad is not None for g in self.param_groups for p in g["params"]) > 1:
+            raise ValueError("clip_mode='norm' clips by the norm of ONE flat gradient buffer; this optimizer holds several")
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
@@ -82,9 +114,20 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["exp_avg"] = torch.zeros_like(p)
                     st["exp_avg_sq"] = torch.zeros_like(p)
                 st["step"] += 1
-                ops.adamw_(p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], lr=group["lr"], beta1=b1,
-                           beta2=b2, eps=group["eps"], weight_decay=group["weight_decay"], step=st["step"],
-                           grad_scale=group["grad_scale"], step_device=self.step_device)
+                if not options:
+                    ops.adamw_(p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], lr=group["lr"], beta1=b1,
+                               beta2=b2, eps=group["eps"], weight_decay=group["weight_decay"], step=st["step"],
+                               grad_scale=group["grad_scale"], step_device=self.step_device)
+                    continue
+                grad = p.grad.contiguous()
+                if p not in self._opt_bufs:
+                    self._opt_bufs[p] = ops.opt_buffers(grad)
+                ctl, ws = self._opt_bufs[p]
+                cfg = ops.make_opt_cfg(lr=group["lr"], beta1=b1, beta2=b2, eps=group["eps"], weight_decay=group["weight_decay"],
+                                       grad_scale=group["grad_scale"], clip_mode=self.clip_mode, clip_val=self.clip_val,
+                                       schedule=self.schedule, step=st["step"], step_device=self.step_device)
+                ops.opt_prepare_(cfg, grad, ws, ctl)
+                ops.adamw_ctl_(cfg, p.data, grad, st["exp_avg"], st["exp_avg_sq"], ctl)
         if self.step_device is not None:
             ops.step_advance_(self.step_device)
         return loss
@@ -606,11 +649,73 @@ class RecommenderLightningModule(_Base):
         self.model.save(str(path))
 
 
+# lr_scheduler class paths of a reference config (LightningCLI: {"class_path", "init_args"}) -> FusedAdamW schedule names
+_REFERENCE_SCHEDULERS = {
+    "get_constant_schedule": "constant",
+    "get_constant_schedule_with_warmup": "warmup_constant",
+    "get_linear_schedule_with_warmup": "warmup_linear",
+    "get_cosine_schedule_with_warmup": "warmup_cosine",
+}
+
+
+def reference_trainer_options(cfg: dict) -> dict:
+    """The :class:`Trainer` arguments a parsed reference ``config.yaml`` asks for (``Trainer.from_reference_config``)."""
+    block = cfg.get("trainer") or {}
+    if not isinstance(block, dict):
+        raise ValueError(f"trainer: expected a mapping, got {type(block).__name__}")
+    algo = block.get("gradient_clip_algorithm")
+    if algo not in (None, "norm", "value"):
+        raise ValueError(f"trainer.gradient_clip_algorithm: {algo!r} is not supported ('norm', 'value' or null)")
+    clip = block.get("gradient_clip_val")
+    if clip is not None and (isinstance(clip, bool) or not isinstance(clip, (int, float)) or not clip >= 0):
+        raise ValueError(f"trainer.gradient_clip_val: {clip!r} is not a number >= 0")
+    acc = block.get("accumulate_grad_batches")
+    acc = 1 if acc is None else acc
+    if isinstance(acc, bool) or not isinstance(acc, int) or acc < 1:
+        raise ValueError(f"trainer.accumulate_grad_batches: {acc!r} is not an integer >= 1")
+    if cfg.get("optimizer") is not None:  # (the module's configure_optimizers is AdamW, as the reference's)
+        raise ValueError(f"optimizer: {cfg['optimizer']!r} cannot be honoured (the step is the module's fused AdamW)")
+    sched = cfg.get("lr_scheduler")
+    schedule = None
+    if sched is not None:
+        if not isinstance(sched, dict):
+            raise ValueError(f"lr_scheduler: expected a mapping, got {sched!r}")
+        if "class_path" in sched:
+            name = _REFERENCE_SCHEDULERS.get(str(sched["class_path"]).rsplit(".", 1)[-1])
+            if name is None:
+                raise ValueError(f"lr_scheduler: class_path {sched['class_path']!r} is not supported (one of "
+                                 f"transformers.optimization.{{{', '.join(_REFERENCE_SCHEDULERS)}}})")
+            args = dict(sched.get("init_args") or {})
+            schedule = {"name": name}
+            if name != "constant":
+                schedule["warmup_steps"] = args.pop("num_warmup_steps", 0)
+            if name in ("warmup_linear", "warmup_cosine"):
+                if "num_training_steps" not in args:
+                    raise ValueError(f"lr_scheduler: {sched['class_path']} needs init_args.num_training_steps")
+                schedule["total_steps"] = args.pop("num_training_steps")
+            left = {k: v for k, v in args.items() if not (k == "last_epoch" and v == -1) and not (k == "num_cycles" and v == 0.5)}
+            if left:
+                raise ValueError(f"lr_scheduler: init_args {sorted(left)} cannot be honoured")
+        else:
+            schedule = dict(sched)
+        try:
+            ops._schedule_ids(schedule)
+        except ValueError as e:
+            raise ValueError(f"lr_scheduler: {e}") from None
+    return dict(gradient_clip_val=clip, gradient_clip_algorithm=algo, accumulate_grad_batches=acc, lr_scheduler=schedule)
+
+
 class Trainer:
     """Minimal stand-in for Lightning's automatic optimisation (``zero_grad -> training_step -> backward ->
     [all-reduce] -> optimizer.step``), single process or one process per GPU (``torch.distributed``)."""
 
-    def __init__(self, module: RecommenderLightningModule, *, world_size: int = 1, process_group=None):
+    def __init__(self, module: RecommenderLightningModule, *, world_size: int = 1, process_group=None,
+                 gradient_clip_val: float | None = None, gradient_clip_algorithm: str | None = None,
+                 accumulate_grad_batches: int = 1, lr_scheduler: dict | None = None):
+        """``gradient_clip_val`` / ``gradient_clip_algorithm`` / ``accumulate_grad_batches``: Lightning's ``Trainer``
+        arguments of the same names (algorithm None = "norm"; 0 or None = no clipping). ``lr_scheduler``: ``{"name",
+        "warmup_steps", "total_steps"}`` (:class:`FusedAdamW`), stepped once per optimizer step. All of them act inside
+        the optimizer's launches; with none set the step is what it is without them."""
         self.module = module
         module.configure_model()
         self.optimizer = module.configure_optimizers()
@@ -618,11 +723,34 @@ class Trainer:
         self.process_group = process_group
         self.exchange = None
         self.default_stream_steps = 0  # eager steps this trainer ran on the device's DEFAULT stream
+        if gradient_clip_algorithm not in (None, "norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm', 'value' or None (= 'norm'); got {gradient_clip_algorithm!r}")
+        if isinstance(accumulate_grad_batches, bool) or not isinstance(accumulate_grad_batches, int) or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1; got {accumulate_grad_batches!r}")
+        if gradient_clip_val is not None and not float(gradient_clip_val) >= 0.0:
+            raise ValueError(f"gradient_clip_val must be >= 0 or None; got {gradient_clip_val!r}")
+        self.accumulate_grad_batches = accumulate_grad_batches
+        self._micro = 0          # micro-batches accumulated since the last optimizer step
+        self._grad_acc = None    # their gradient sum (accumulate_grad_batches > 1), persistent
+        clip = float(gradient_clip_val) if gradient_clip_val else None  # (Lightning: 0 and None both mean "off")
+        if clip is not None or lr_scheduler is not None:
+            if not isinstance(self.optimizer, FusedAdamW):
+                raise ValueError("gradient_clip_val / lr_scheduler act inside FusedAdamW's launches; configure_optimizers() "
+                                 f"returned {type(self.optimizer).__name__}")
+            ops.make_opt_cfg(lr=1.0, clip_mode=(gradient_clip_algorithm or "norm") if clip is not None else None,
+                             clip_val=clip, schedule=lr_scheduler)  # (validates)
+            if clip is not None:
+                self.optimizer.clip_mode, self.optimizer.clip_val = gradient_clip_algorithm or "norm", clip
+            self.optimizer.schedule = dict(lr_scheduler) if lr_scheduler is not None else None
+        if accumulate_grad_batches > 1:
+            for g in self.optimizer.param_groups:
+                g["grad_scale"] = 1.0 / accumulate_grad_batches  # the optimizer sees the MEAN of the micro-batch gradients
         if world_size > 1:
             import os
 
             for g in self.optimizer.param_groups:
-                g["grad_scale"] = 1.0 / world_size  # DDP averages gradients: SUM all-reduce then / W
+                # DDP averages gradients: SUM all-reduce then / W (times 1 / k for k accumulated micro-batches)
+                g["grad_scale"] = 1.0 / (world_size * accumulate_grad_batches)
             # One message behind the backward by default. XFMR_ALLREDUCE_HALVES=1: two halves, the upper layers' underneath
             # the lower layers' backward (distributed.HalvedAllReduce) -- its event ordering is tested on one GPU
             # (tests/test_gpu_ddp.py), but RCCL's transport has never run under it (no multi-GPU box was available to the
@@ -630,6 +758,9 @@ class Trainer:
             if os.environ.get("XFMR_ALLREDUCE_HALVES", "0") == "1" and os.environ.get("XFMR_ALLREDUCE_SINGLE", "0") != "1":
                 from .distributed import HalvedAllReduce
 
+                if accumulate_grad_batches > 1:
+                    raise ValueError("XFMR_ALLREDUCE_HALVES=1 exchanges halves of the backward's own buffer underneath the "
+                                     "backward; accumulate_grad_batches > 1 exchanges the accumulated sum once instead")
                 self.exchange = HalvedAllReduce(module.model, process_group)
             elif os.environ.get("XFMR_ALLREDUCE", "") == "abi" and module.model.flat.is_cuda:
                 # the exchange through the C ABI (xfmr_allreduce_flat: RCCL underneath, no torch collective in the step)
@@ -661,10 +792,34 @@ class Trainer:
         self.optimizer.zero_grad(set_to_none=True)
         loss = m.training_step(batch, 0)
         m.backward(loss)
+        k = self.accumulate_grad_batches
+        if k > 1:
+            # one call = one micro-batch: its gradient joins the persistent sum; the k-th call exchanges the sum once and
+            # steps on it (grad_scale = 1 / (W k)). Calls 1 .. k-1 leave parameters, moments and step count alone.
+            flat = m.model.flat
+            if self._grad_acc is None:
+                self._grad_acc = torch.empty_like(flat.grad)
+            ops.grad_accumulate_(self._grad_acc, flat.grad.contiguous(), first=self._micro == 0)
+            self._micro += 1
+            if self._micro < k:
+                m.on_train_batch_end(loss, batch, 0)
+                return loss.detach()
+            self._micro = 0
+            flat.grad = self._grad_acc  # (what the optimizer reads; the next zero_grad drops the reference, not the buffer)
         self.allreduce_(m.model.flat.grad)
         self.optimizer.step()
+        if getattr(self.optimizer, "has_options", False):
+            m.log_dict(self.optimizer.ctl_log_dict())  # grad/norm, grad/clip_coef, lr: device views, no host sync
         m.on_train_batch_end(loss, batch, 0)  # joins the logging stream (leaving the pass to finish underneath the next
         return loss.detach()                  # step's forward measured no gain: 3.411 vs 3.414 ms)
+
+    @classmethod
+    def from_reference_config(cls, module: RecommenderLightningModule, cfg: dict, **kwargs) -> "Trainer":
+        """A trainer from a parsed reference ``config.yaml``: its ``trainer:`` block's ``gradient_clip_val``,
+        ``gradient_clip_algorithm`` and ``accumulate_grad_batches`` and the top-level ``lr_scheduler``. The block's other
+        keys are orchestration (devices, epochs, logging, checkpointing: the caller's loop) and are not read. A non-null
+        value that changes the optimisation and cannot be honoured raises a ``ValueError`` that names its key."""
+        return cls(module, **reference_trainer_options(cfg), **kwargs)
 
     def fit(self, batches, max_steps: int | None = None, *, ring_slots: int = 6, graph: str = "off",
             graph_probe_steps: int = 20) -> list[float]:
@@ -683,6 +838,8 @@ class Trainer:
 
         if graph not in ("off", "on", "auto"):
             raise ValueError(f"graph must be 'off', 'on' or 'auto', got {graph!r}")
+        if graph != "off" and self.accumulate_grad_batches > 1:
+            raise ValueError(_NO_ACCUMULATED_CAPTURE)
         if self.world_size != 1:
             graph = "off"  # (the all-reduce of a data-parallel step is not captured)
         defer_before = getattr(self.module, "defer_logging", "auto")
@@ -779,6 +936,11 @@ class Trainer:
         return [float(v) for v in out]  # (one host sync at the end, not one per step)
 
 
+_NO_ACCUMULATED_CAPTURE = ("a captured step cannot accumulate micro-batches (accumulate_grad_batches > 1): the device-side step "
+                           "counter advances once per OPTIMIZER step, so the micro-batches of one step would share their "
+                           "dropout masks; run accumulated steps eagerly (graph='off')")
+
+
 def _refuse_capture_after_default_stream_steps(trainer: "Trainer") -> None:
     """torch's capture protocol: autograd's AccumulateGrad node of a parameter is bound to the stream of the first backward
     that used it and synchronises with that stream from then on; eager steps on the device's DEFAULT (legacy) stream
@@ -821,6 +983,8 @@ class GraphedStep:
         m = trainer.module
         if trainer.world_size != 1:
             raise ValueError("GraphedStep captures a single-process step")
+        if getattr(trainer, "accumulate_grad_batches", 1) > 1:
+            raise ValueError(_NO_ACCUMULATED_CAPTURE)
         _refuse_capture_after_default_stream_steps(trainer)
         self.trainer, self.keys = trainer, SEQ_BATCH_KEYS
         dev = m.model.device
