@@ -655,6 +655,22 @@ struct SwzImg {
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.f, b, acc, 0, 0, 0);
     }
   }
+  // B operand of a "contract over the image's ROW index" product in the register order of gemm.hip's
+  // Frag<PrecBF16, true>: lane (i = l & 31, h = l >> 5) gets IMG[k0 + 8 h + 0..7][col0 + i] -- the same two transposed
+  // block reads per 16-lane group, the chunk position taken through the swizzle.
+  __device__ static __forceinline__ bf16x8 frag_tr(const __bf16* img, int col0, int k0) {
+    const int l = xf_lane(), g16 = l >> 4, li = l & 15, q = li >> 2, p = li & 3;
+    const int col = col0 + 16 * (g16 & 1) + 4 * p;
+    const int c = col >> 3, within = col & 7;
+    union { xf_s16x4 v[2]; bf16x8 f; } a;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int row = k0 + 8 * (g16 >> 1) + 4 * t + q;
+      a.v[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) xf_s16x4*)(img + off(row, c) + within));
+    }
+    return a.f;
+  }
   // One wave instruction of the gather: lane -> (row = row0 + lane / CPR, position = lane % CPR);
   // returns the SOURCE chunk index this lane must fetch so that position holds chunk (position ^ swizzle).
   __device__ static __forceinline__ int gather_row(int row0) { return row0 + xf_lane() / CPR; }
@@ -682,6 +698,11 @@ __device__ __forceinline__ void xf_glds16_raw_so(const void* sbase, uint32_t vof
                : "=&s"(keep)
                : "v"(voff), "s"(sbase), "s"(dst)
                : "memory");
+}
+// s_waitcnt vmcnt(N) only (gfx9 encoding: expcnt / lgkmcnt fields all ones): the hand-placed wait of the asm-issued DMA
+template <int N>
+__device__ __forceinline__ void xf_wait_vm() {
+  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (7 << 4) | (0xF << 8));
 }
 __device__ __forceinline__ void xf_glds16_raw(const void* gsrc, void* lds_base) {
   const unsigned dst = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)lds_base;

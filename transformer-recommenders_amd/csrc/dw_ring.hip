@@ -77,11 +77,6 @@ __device__ __forceinline__ bf16x8 frag_tr(const __bf16* img, const int hsub, con
   return a.f;
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {  // s_waitcnt vmcnt(N) only (gfx9 encoding: expcnt / lgkmcnt fields all ones)
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (7 << 4) | (0xF << 8));
-}
-
 __global__ __launch_bounds__(512, (RT * NST <= 128) ? 4 : 2) void dw_ring_kernel(const DwRingArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __bf16* const sA = reinterpret_cast<__bf16*>(smem_raw);        // [NST][64][128] dy pieces
@@ -141,9 +136,9 @@ __global__ __launch_bounds__(512, (RT * NST <= 128) ? 4 : 2) void dw_ring_kernel
   for (int s = 0; s < nst; ++s) {
     // this wave's pieces of stage s have landed once at most the later stages' are outstanding
     const int later = (nst - 1 - s) < (NST - 2) ? (nst - 1 - s) : (NST - 2);
-    if (NST >= 4 && later >= 2) wait_vm<2 * IPW>();
-    else if (NST >= 3 && later >= 1) wait_vm<IPW>();
-    else wait_vm<0>();
+    if (NST >= 4 && later >= 2) xf_wait_vm<2 * IPW>();
+    else if (NST >= 3 && later >= 1) xf_wait_vm<IPW>();
+    else xf_wait_vm<0>();
     __syncthreads();  // everyone's pieces of stage s are in LDS; everyone is done reading stage s - 1's buffer
     const __bf16* const a = sA + (s % NST) * IMG_ELEMS;
     const __bf16* const bm = sB + (s % NST) * IMG_ELEMS;

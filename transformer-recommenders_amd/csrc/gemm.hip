@@ -1072,10 +1072,25 @@ __global__ __launch_bounds__(256, CH == 128 ? XF_FFN_MIN_WAVES : 3) void ffn_fwd
 // order as the two launches it replaces (the FFN2 dX GEMM with the gelu' epilogue, the FFN1 dX GEMM with the LayerNorm
 // backward epilogue): bit-identical dI, dx, d_lin and partial records. Per layer at T = 102 400, I = 512: 418 MB instead of
 // 523 MB.
+// Two forms of the weight staging (template parameter RING, picked per launch: xf_ffn_bwd_dx_fused_ex). Per tile both run
+// the same MFMAs on the same operands in the same order and the same epilogue: every output is bit-identical.
+//   RING = false, the register-staged form (XFMR_FFN_REG_STAGE=1): a W2 / W1 chunk travels global -> registers ->
+//   ds_write into a padded image, one image buffer for both.
 //   LDS: sF [64][68] fp32 (dy W2 chunk: accumulator layout -> row-major) + sG [64][72] (the dI chunk: A operand of the
 //   second GEMM; the u chunk never goes through LDS: a thread multiplies the piece it loaded) + sW 24 KB (the W2 chunk as
 //   a [128 k][64 + 32] image, then the W1 chunk as [64 k][128 + 32]: both are B operands stored k-major, read through
 //   ds_read_b64_tr_b16; the dy tile before the first chunk, the epilogue's scratch after the last) = 51 KB.
+//   RING = true (the default): the chunks come by global_load_lds_dwordx4 (dw_ring.hip's helpers) into UNPADDED images
+//   swizzled on the source address (SwzImg<64> for the [128 k][64] W2 chunk, SwzImg<128> for the [64 k][128] W1 chunk), each
+//   one chunk ahead of its use: W2 (c + 1) is issued behind the barrier that ends chunk c's row-major pass and lands in
+//   sF's bytes (dead from that pass to the next dG store) while GEMM 2 of chunk c runs; W1 (c) is issued at the top of
+//   chunk c into its own 16 KB and lands during GEMM 1 and the gelu' arithmetic. No weight ever sits in a VGPR.
+//   LDS: one array, sF 17 KB (= the W2 image + 1 KB) + sG 9 KB + the W1 image 16 KB = 42 KB; the dy tile is staged over
+//   sG and the head of the W1 image, the epilogue's scratch over sF and sG.
+//   Waits: the DMA is asm-issued, outside hipcc's s_waitcnt bookkeeping, and the chunk loop's barriers do not wait on
+//   vmcnt. Every wait for an image is s_waitcnt vmcnt(0) at a point where nothing else of this wave that matters is in
+//   flight (in front of the dI stores; at the top of the chunk, where the u chunk is needed too), followed by a barrier
+//   before anyone reads the image.
 struct FfnBwdArgs {
   const __bf16* DY;   // [M][128] gradient of the FFN2 Linear's output
   const __bf16* W2;   // [128][I]
@@ -1086,20 +1101,14 @@ struct FfnBwdArgs {
   GemmArgs e;         // epi_dx_lnbwd_64x128's arguments
 };
 
+template <bool RING>
 __global__ __launch_bounds__(256, 3) void ffn_bwd_dx_fused_kernel(const FfnBwdArgs f_in) {
   FfnBwdArgs f = f_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
   XF_CHAIN_PRIO();
   f.e.drop = xf_drop_resolve(f.e.drop); f.e.drop2 = xf_drop_resolve(f.e.drop2);
   constexpr int H = 128, BM = 64, CH = 64, LDH = H + 8, LDC = CH + 8;
-  constexpr int LD1 = CH + 32;  // W2 chunk image [128 k][CH rows]
-  constexpr int LD2 = H + 32;   // W1 chunk image [CH k][128 rows]
-  constexpr int W_ELEMS = H * LD1 > CH * LD2 ? H * LD1 : CH * LD2;
   constexpr int LDF = CH + 4;
-  __shared__ __attribute__((aligned(16))) float sF[BM * LDF];  // dG = dy W2 chunk, fp32, accumulator layout -> row-major
-  __shared__ __attribute__((aligned(16))) __bf16 sG[BM * LDC];
-  __shared__ __attribute__((aligned(16))) __bf16 sW[W_ELEMS];
-  static_assert(W_ELEMS >= BM * LDH, "the dy tile is staged through sW");
-  static_assert(W_ELEMS * 2 >= (4 * 16 * 68 + 2 * 2 * 2 * 16 * 2 + 2 * 3 * 128) * 4, "the epilogue's scratch aliases sW");
+  constexpr int EPI_BYTES = (4 * 16 * 68 + 2 * 2 * 2 * 16 * 2 + 2 * 3 * 128) * 4;  // epi_dx_lnbwd_64x128's scratch
   using FN = Frag<PrecBF16, false>;
   using FT = Frag<PrecBF16, true>;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, tid = threadIdx.x;
@@ -1110,35 +1119,7 @@ __global__ __launch_bounds__(256, 3) void ffn_bwd_dx_fused_kernel(const FfnBwdAr
   const int64_t M = f.e.M;
   const int I = f.I, nchunk = I / CH;
 
-  bf16x8 wa[4], wb[4], ur[2];  // W2 chunk, W1 chunk, u chunk in flight (native vectors: see WeightChunk)
-  auto load_w2 = [&](int c) {  // W2[k][c CH + j]: 128 rows of 8 pieces
-    xf_static_for<4>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      const int p = tid + i * 256, k = p >> 3, ch = p & 7;
-      wa[i] = *reinterpret_cast<const bf16x8*>(f.W2 + (int64_t)k * I + c * CH + ch * 8);
-    });
-  };
-  auto commit_w2 = [&]() {
-    xf_static_for<4>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      const int p = tid + i * 256, k = p >> 3, ch = p & 7;
-      *reinterpret_cast<bf16x8*>(sW + k * LD1 + ch * 8) = wa[i];
-    });
-  };
-  auto load_w1 = [&](int c) {  // W1[c CH + k][n]: 64 rows of 16 pieces
-    xf_static_for<4>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      const int p = tid + i * 256, k = p >> 4, ch = p & 15;
-      wb[i] = *reinterpret_cast<const bf16x8*>(f.W1 + (int64_t)(c * CH + k) * H + ch * 8);
-    });
-  };
-  auto commit_w1 = [&]() {
-    xf_static_for<4>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      const int p = tid + i * 256, k = p >> 4, ch = p & 15;
-      *reinterpret_cast<bf16x8*>(sW + k * LD2 + ch * 8) = wb[i];
-    });
-  };
+  bf16x8 ur[2];  // u chunk in flight (native vectors: see WeightChunk)
   auto load_u = [&](int c) {  // u[m0 + row][c CH + ..]: 64 rows of 8 pieces
     xf_static_for<2>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
@@ -1150,29 +1131,25 @@ __global__ __launch_bounds__(256, 3) void ffn_bwd_dx_fused_kernel(const FfnBwdAr
       ur[i] = z;
     });
   };
-
-  // dy tile -> sW (as a [64][136] image) -> this wave's A fragments of all 8 k-steps
-  {
-    uint4 yr[4];
+  // piece i of the row-major pass, 8 columns: dI = dG * gelu'(u) with u straight from the registers it was loaded into
+  auto di_piece = [&](const float* sF, const int i) {
+    const int p = tid + i * 256, row = p >> 3, ch = p & 7;
+    const float4 g0 = *reinterpret_cast<const float4*>(sF + row * LDF + ch * 8);
+    const float4 g1 = *reinterpret_cast<const float4*>(sF + row * LDF + ch * 8 + 4);
+    const bf16x8 u8 = ur[i];
+    bf16x8 d8;
+    d8[0] = (__bf16)(g0.x * xf_gelu_grad((float)u8[0])); d8[1] = (__bf16)(g0.y * xf_gelu_grad((float)u8[1]));
+    d8[2] = (__bf16)(g0.z * xf_gelu_grad((float)u8[2])); d8[3] = (__bf16)(g0.w * xf_gelu_grad((float)u8[3]));
+    d8[4] = (__bf16)(g1.x * xf_gelu_grad((float)u8[4])); d8[5] = (__bf16)(g1.y * xf_gelu_grad((float)u8[5]));
+    d8[6] = (__bf16)(g1.z * xf_gelu_grad((float)u8[6])); d8[7] = (__bf16)(g1.w * xf_gelu_grad((float)u8[7]));
+    return d8;
+  };
+  // dG (fp32, accumulator layout: element r of lane l = row (r&3) + 8 (r>>2) + 4 (l>>5), col l&31) -> sF
+  auto store_dg = [&](float* sF, const f32x16& accg) {
+    const int col = wc * 32 + (lane & 31);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int p = tid + i * 256, row = p >> 4, ch = p & 15;
-      yr[i] = make_uint4(0u, 0u, 0u, 0u);
-      if (m0 + row < M) yr[i] = *reinterpret_cast<const uint4*>(f.DY + (m0 + row) * H + ch * 8);
-    }
-    load_w2(0);
-    load_u(0);
-    load_w1(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int p = tid + i * 256, row = p >> 4, ch = p & 15;
-      *reinterpret_cast<uint4*>(sW + row * LDH + ch * 8) = yr[i];
-    }
-  }
-  __syncthreads();
-  bf16x8 ya[H / 16];
-#pragma unroll
-  for (int ks = 0; ks < H / 16; ++ks) ya[ks] = FN::get(sW, LDH, wr * 32, ks * 16);
+    for (int r = 0; r < 16; ++r) sF[(wr * 32 + xf_acc_row(r, lane)) * LDF + col] = accg[r];
+  };
 
   f32x16 accx[2];
 #pragma unroll
@@ -1180,51 +1157,193 @@ __global__ __launch_bounds__(256, 3) void ffn_bwd_dx_fused_kernel(const FfnBwdAr
 #pragma unroll
     for (int r = 0; r < 16; ++r) accx[j][r] = 0.f;
 
-  for (int c = 0; c < nchunk; ++c) {
-    XF_LOOP_BARRIER();  // the previous chunk's second GEMM (or the fragment reads above) is done with sW and sG
-    commit_w2();
-    XF_LOOP_BARRIER();
-    if (c + 1 < nchunk) load_w2(c + 1);
-    f32x16 accg;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accg[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < H / 16; ++ks) accg = xf_mma(ya[ks], FT::get(sW, LD1, wc * 32, ks * 16), accg);
-    // dG (fp32, accumulator layout: element r of lane l = row (r&3) + 8 (r>>2) + 4 (l>>5), col l&31) -> sF
+  if constexpr (RING) {
+    constexpr int F_BYTES = BM * LDF * 4, G_BYTES = BM * LDC * 2, W2_BYTES = H * CH * 2, W1_BYTES = CH * H * 2;
+    // ONE shared array (a second __shared__ object next to an LDS-DMA target makes hipcc serialise on vmcnt(0))
+    __shared__ __attribute__((aligned(16))) unsigned char smem[F_BYTES + G_BYTES + W1_BYTES];
+    static_assert(W2_BYTES <= F_BYTES, "the W2 chunk image lands in sF's bytes");
+    static_assert(BM * LDH * 2 <= G_BYTES + W1_BYTES, "the dy tile is staged over sG and the W1 image");
+    static_assert(EPI_BYTES <= F_BYTES + G_BYTES, "the epilogue's scratch aliases sF and sG");
+    static_assert(F_BYTES % 1024 == 0 && G_BYTES % 1024 == 0, "DMA targets on 1-KiB instruction boundaries");
+    float* const sF = reinterpret_cast<float*>(smem);
+    __bf16* const sW2 = reinterpret_cast<__bf16*>(smem);
+    __bf16* const sG = reinterpret_cast<__bf16*>(smem + F_BYTES);
+    __bf16* const sW1 = reinterpret_cast<__bf16*>(smem + F_BYTES + G_BYTES);
+    __bf16* const sY = sG;
+    using I2 = SwzImg<CH>;  // W2 chunk image [128 k][64]: 8 rows per 1-KiB instruction
+    using I1 = SwzImg<H>;   // W1 chunk image [64 k][128]: 4 rows per instruction
+    const int w = __builtin_amdgcn_readfirstlane(wid);
+    // four instructions per wave and image: wave w fetches image rows [32 w, +32) of W2[k][c CH + ..] ...
+    auto issue_w2 = [&](int c) {
+      xf_static_for<4>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const int row0 = 32 * w + I2::kRowsPerInstr * j, k = I2::gather_row(row0);
+        xf_glds16_raw_so(f.W2, (uint32_t)(k * I + c * CH + 8 * I2::gather_src_chunk(k)) * 2u, sW2 + row0 * CH);
+      });
+    };
+    // ... and rows [16 w, +16) of W1[c CH + k][..]
+    auto issue_w1 = [&](int c) {
+      xf_static_for<4>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const int row0 = 16 * w + I1::kRowsPerInstr * j, k = I1::gather_row(row0);
+        xf_glds16_raw_so(f.W1, (uint32_t)((c * CH + k) * H + 8 * I1::gather_src_chunk(k)) * 2u, sW1 + row0 * H);
+      });
+    };
+
+    // dy tile -> sY (a [64][136] image) -> this wave's A fragments of all 8 k-steps; the first W2 chunk is on its way
+    issue_w2(0);
     {
-      const int col = wc * 32 + (lane & 31);
+      uint4 yr[4];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) sF[(wr * 32 + xf_acc_row(r, lane)) * LDF + col] = accg[r];
+      for (int i = 0; i < 4; ++i) {
+        const int p = tid + i * 256, row = p >> 4, ch = p & 15;
+        yr[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (m0 + row < M) yr[i] = *reinterpret_cast<const uint4*>(f.DY + (m0 + row) * H + ch * 8);
+      }
+      load_u(0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int p = tid + i * 256, row = p >> 4, ch = p & 15;
+        *reinterpret_cast<uint4*>(sY + row * LDH + ch * 8) = yr[i];
+      }
     }
-    XF_LOOP_BARRIER();  // sF holds dG; every wave is done with the W2 chunk
-    // row-major pass, 8 columns per thread and piece: dI = dG * gelu'(u) with u straight from the registers it was
-    // loaded into -> HBM (16-byte pieces: a wave instruction = 8 rows x 128 B) and -> sG, the second GEMM's A operand
-    xf_static_for<2>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      const int p = tid + i * 256, row = p >> 3, ch = p & 7;
-      const float4 g0 = *reinterpret_cast<const float4*>(sF + row * LDF + ch * 8);
-      const float4 g1 = *reinterpret_cast<const float4*>(sF + row * LDF + ch * 8 + 4);
-      const bf16x8 u8 = ur[i];
-      bf16x8 d8;
-      d8[0] = (__bf16)(g0.x * xf_gelu_grad((float)u8[0])); d8[1] = (__bf16)(g0.y * xf_gelu_grad((float)u8[1]));
-      d8[2] = (__bf16)(g0.z * xf_gelu_grad((float)u8[2])); d8[3] = (__bf16)(g0.w * xf_gelu_grad((float)u8[3]));
-      d8[4] = (__bf16)(g1.x * xf_gelu_grad((float)u8[4])); d8[5] = (__bf16)(g1.y * xf_gelu_grad((float)u8[5]));
-      d8[6] = (__bf16)(g1.z * xf_gelu_grad((float)u8[6])); d8[7] = (__bf16)(g1.w * xf_gelu_grad((float)u8[7]));
-      if (m0 + row < M) *reinterpret_cast<bf16x8*>(f.DI + (m0 + row) * I + c * CH + ch * 8) = d8;
-      *reinterpret_cast<bf16x8*>(sG + row * LDC + ch * 8) = d8;
-    });
-    commit_w1();
     XF_LOOP_BARRIER();
-    if (c + 1 < nchunk) { load_w1(c + 1); load_u(c + 1); }
+    bf16x8 ya[H / 16];
 #pragma unroll
-    for (int ks = 0; ks < CH / 16; ++ks) {
-      const bf16x8 fa = FN::get(sG, LDC, wr * 32, ks * 16);
+    for (int ks = 0; ks < H / 16; ++ks) ya[ks] = FN::get(sY, LDH, wr * 32, ks * 16);
+
+    for (int c = 0; c < nchunk; ++c) {
+      xf_wait_vm<0>();    // this wave's pieces of W2 chunk c (and its u chunk) have landed
+      XF_LOOP_BARRIER();  // ... everyone's; the previous chunk's second GEMM (or the fragment reads above) is done with sW1 and sG
+      issue_w1(c);
+      f32x16 accg;
 #pragma unroll
-      for (int j = 0; j < 2; ++j) accx[j] = xf_mma(fa, FT::get(sW, LD2, wc * 64 + j * 32, ks * 16), accx[j]);
+      for (int r = 0; r < 16; ++r) accg[r] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < H / 16; ++ks) accg = xf_mma(ya[ks], I2::frag_tr(sW2, wc * 32, ks * 16), accg);
+      XF_LOOP_BARRIER();  // every wave is done with the W2 image: sF takes its bytes
+      store_dg(sF, accg);
+      XF_LOOP_BARRIER();  // sF holds dG
+      // row-major pass -> sG, the second GEMM's A operand, and -> HBM (16-byte pieces: a wave instruction = 8 rows x 128 B)
+      bf16x8 d8[2];
+      xf_static_for<2>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const int p = tid + i * 256, row = p >> 3, ch = p & 7;
+        d8[i] = di_piece(sF, i);
+        *reinterpret_cast<bf16x8*>(sG + row * LDC + ch * 8) = d8[i];
+      });
+      xf_wait_vm<0>();  // this wave's pieces of W1 chunk c (issued a GEMM and the gelu' arithmetic ago); the stores go after it
+      xf_static_for<2>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const int p = tid + i * 256, row = p >> 3, ch = p & 7;
+        if (m0 + row < M) *reinterpret_cast<bf16x8*>(f.DI + (m0 + row) * I + c * CH + ch * 8) = d8[i];
+      });
+      XF_LOOP_BARRIER();  // sG holds dI, the W1 image is whole, everyone is done with sF
+      if (c + 1 < nchunk) { issue_w2(c + 1); load_u(c + 1); }
+#pragma unroll
+      for (int ks = 0; ks < CH / 16; ++ks) {
+        const bf16x8 fa = FN::get(sG, LDC, wr * 32, ks * 16);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) accx[j] = xf_mma(fa, I1::frag_tr(sW1, wc * 64 + j * 32, ks * 16), accx[j]);
+      }
     }
+    __syncthreads();  // everyone is done with the images: the epilogue's scratch aliases them
+    epi_dx_lnbwd_64x128(accx, smem, f.e, m0, tix.m, wid, lane);
+  } else {
+    constexpr int LD1 = CH + 32;  // W2 chunk image [128 k][CH rows]
+    constexpr int LD2 = H + 32;   // W1 chunk image [CH k][128 rows]
+    constexpr int W_ELEMS = H * LD1 > CH * LD2 ? H * LD1 : CH * LD2;
+    __shared__ __attribute__((aligned(16))) float sF[BM * LDF];  // dG = dy W2 chunk, fp32, accumulator layout -> row-major
+    __shared__ __attribute__((aligned(16))) __bf16 sG[BM * LDC];
+    __shared__ __attribute__((aligned(16))) __bf16 sW[W_ELEMS];
+    static_assert(W_ELEMS >= BM * LDH, "the dy tile is staged through sW");
+    static_assert(W_ELEMS * 2 >= EPI_BYTES, "the epilogue's scratch aliases sW");
+    bf16x8 wa[4], wb[4];  // W2 chunk, W1 chunk in flight
+    auto load_w2 = [&](int c) {  // W2[k][c CH + j]: 128 rows of 8 pieces
+      xf_static_for<4>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const int p = tid + i * 256, k = p >> 3, ch = p & 7;
+        wa[i] = *reinterpret_cast<const bf16x8*>(f.W2 + (int64_t)k * I + c * CH + ch * 8);
+      });
+    };
+    auto commit_w2 = [&]() {
+      xf_static_for<4>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const int p = tid + i * 256, k = p >> 3, ch = p & 7;
+        *reinterpret_cast<bf16x8*>(sW + k * LD1 + ch * 8) = wa[i];
+      });
+    };
+    auto load_w1 = [&](int c) {  // W1[c CH + k][n]: 64 rows of 16 pieces
+      xf_static_for<4>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const int p = tid + i * 256, k = p >> 4, ch = p & 15;
+        wb[i] = *reinterpret_cast<const bf16x8*>(f.W1 + (int64_t)(c * CH + k) * H + ch * 8);
+      });
+    };
+    auto commit_w1 = [&]() {
+      xf_static_for<4>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const int p = tid + i * 256, k = p >> 4, ch = p & 15;
+        *reinterpret_cast<bf16x8*>(sW + k * LD2 + ch * 8) = wb[i];
+      });
+    };
+
+    // dy tile -> sW (as a [64][136] image) -> this wave's A fragments of all 8 k-steps
+    {
+      uint4 yr[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int p = tid + i * 256, row = p >> 4, ch = p & 15;
+        yr[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (m0 + row < M) yr[i] = *reinterpret_cast<const uint4*>(f.DY + (m0 + row) * H + ch * 8);
+      }
+      load_w2(0);
+      load_u(0);
+      load_w1(0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int p = tid + i * 256, row = p >> 4, ch = p & 15;
+        *reinterpret_cast<uint4*>(sW + row * LDH + ch * 8) = yr[i];
+      }
+    }
+    __syncthreads();
+    bf16x8 ya[H / 16];
+#pragma unroll
+    for (int ks = 0; ks < H / 16; ++ks) ya[ks] = FN::get(sW, LDH, wr * 32, ks * 16);
+
+    for (int c = 0; c < nchunk; ++c) {
+      XF_LOOP_BARRIER();  // the previous chunk's second GEMM (or the fragment reads above) is done with sW and sG
+      commit_w2();
+      XF_LOOP_BARRIER();
+      if (c + 1 < nchunk) load_w2(c + 1);
+      f32x16 accg;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accg[r] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < H / 16; ++ks) accg = xf_mma(ya[ks], FT::get(sW, LD1, wc * 32, ks * 16), accg);
+      store_dg(sF, accg);
+      XF_LOOP_BARRIER();  // sF holds dG; every wave is done with the W2 chunk
+      // row-major pass -> HBM (16-byte pieces: a wave instruction = 8 rows x 128 B) and -> sG, the second GEMM's A operand
+      xf_static_for<2>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const int p = tid + i * 256, row = p >> 3, ch = p & 7;
+        const bf16x8 d8 = di_piece(sF, i);
+        if (m0 + row < M) *reinterpret_cast<bf16x8*>(f.DI + (m0 + row) * I + c * CH + ch * 8) = d8;
+        *reinterpret_cast<bf16x8*>(sG + row * LDC + ch * 8) = d8;
+      });
+      commit_w1();
+      XF_LOOP_BARRIER();
+      if (c + 1 < nchunk) { load_w1(c + 1); load_u(c + 1); }
+#pragma unroll
+      for (int ks = 0; ks < CH / 16; ++ks) {
+        const bf16x8 fa = FN::get(sG, LDC, wr * 32, ks * 16);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) accx[j] = xf_mma(fa, FT::get(sW, LD2, wc * 64 + j * 32, ks * 16), accx[j]);
+      }
+    }
+    __syncthreads();  // everyone is done with sW: the epilogue's scratch aliases it
+    epi_dx_lnbwd_64x128(accx, reinterpret_cast<unsigned char*>(sW), f.e, m0, tix.m, wid, lane);
   }
-  __syncthreads();  // everyone is done with sW: the epilogue's scratch aliases it
-  epi_dx_lnbwd_64x128(accx, reinterpret_cast<unsigned char*>(sW), f.e, m0, tix.m, wid, lane);
 }
 
 // Deterministic column sums of a [rows, cols] fp32 matrix: block (x, y) sums rows [y*rows_per, (y+1)*rows_per)
@@ -1678,7 +1797,12 @@ int xf_ffn_bwd_dx_fused_ex(const void* dy16, const void* w2_16, const void* u16,
   *blocks_out = g.nt_m;
   const int64_t groups = (g.nt_m + 7) / 8;
   if (groups * 8 > 0x7fffffffll) return XFMR_EUNSUPPORTED;
-  hipLaunchKernelGGL(ffn_bwd_dx_fused_kernel, dim3((unsigned)(groups * 8)), dim3(256), 0, st, f);
+  // XFMR_FFN_REG_STAGE=1 (read per call: tests, A/B timing inside one library): the register-staged weight chunks
+  const char* const reg_stage = getenv("XFMR_FFN_REG_STAGE");
+  if (reg_stage && *reg_stage && *reg_stage != '0')
+    hipLaunchKernelGGL(ffn_bwd_dx_fused_kernel<false>, dim3((unsigned)(groups * 8)), dim3(256), 0, st, f);
+  else
+    hipLaunchKernelGGL(ffn_bwd_dx_fused_kernel<true>, dim3((unsigned)(groups * 8)), dim3(256), 0, st, f);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
 }
