@@ -546,6 +546,21 @@ int xfmr_topk(const float* query, const float* table, const float* table_rnorm, 
               int64_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes, void* stream);
 int xfmr_retrieval_metrics(const int64_t* rec_idx, const int64_t* targets, const int64_t* target_offsets, int32_t n_query,
                            int32_t k, int32_t top_k, float* out, uint8_t* valid, void* stream);
+/* The metrics of xfmr_retrieval_metrics and their SUMS in one call: what a validation pass reads back is 64 bytes.
+ * rec_idx, targets, target_offsets, k, top_k as above; `use` picks the rows that are summed. The optional per-row outputs
+ * hold the same bits as the per-row call's (one device function computes both) and are written for every row, used or
+ * not. Two launches: 256-row workgroups reduce their rows in fp64 (wave shuffles, then the four waves in a fixed order)
+ * to one 8-double record each in `workspace`; one workgroup adds the records in index order. No atomics: the same input
+ * gives the same eight doubles on every launch. n_query < 2^31 (XFMR_EUNSUPPORTED); a workspace smaller than the size
+ * query's bytes is XFMR_EWORKSPACE. Nothing is read back to the host. */
+size_t xfmr_retrieval_metrics_sum_workspace(int64_t n_query);
+int xfmr_retrieval_metrics_sum(const int64_t* rec_idx, const int64_t* targets, const int64_t* target_offsets,
+                               const uint8_t* use,      /* (n_query) or NULL: rows with use[q] == 0 are left out */
+                               int64_t n_query, int32_t k, int32_t top_k,
+                               double* sums,            /* device, 8: [0..6] sums of the XFMR_RM_* values over the rows
+                                                           that are valid (>= 1 target) and used; [7] their number  */
+                               float* out, uint8_t* valid, /* optional per-row outputs, as xfmr_retrieval_metrics; may be NULL */
+                               void* workspace, size_t workspace_bytes, void* stream);
 /* xfmr_topk_tiled: the same search as xfmr_topk for MANY queries, with no per-(query, item) workspace. Arguments and
  * results as xfmr_topk, except:
  *   - table_sqnorm (n_rows): squared row norms (xfmr_table_sqnorm), read by the l2 metric only (may be NULL otherwise);

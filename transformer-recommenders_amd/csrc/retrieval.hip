@@ -12,6 +12,8 @@
 //   metrics_kernel  one thread per query: nDCG, MAP, AUROC, precision, recall, hit rate, MRR at k from the ranked
 //                   list and the user's target set, with torchmetrics' definitions for a strictly decreasing score
 //                   vector over [recommendations | missing targets] (metrics.py:66-79)
+//   metrics_sum_kernel + metrics_sum_final_kernel  the same per-row values and, in the same call, their fp64 sums over
+//                   the rows that count (xfmr_retrieval_metrics_sum: nothing of a validation pass is summed on the host)
 // metric: cosine (reference default, index.py:47), dot, or l2; score = 1 - distance as index.py:248-251 appends it.
 #include "common.h"
 
@@ -198,16 +200,14 @@ __global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
   }
 }
 
-// rec (B,k) ranked item indices (-1 = padding), targets CSR; out (B,7): ndcg, map, auroc, precision, recall, hit, mrr;
-// valid[b] = 0 when the user has no target (the reference returns {} for it, metrics.py:58-59)
-__global__ void metrics_kernel(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off, int B, int k, int top_k,
-                               float* out, uint8_t* valid) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
+// One query's seven metrics: rec (B,k) ranked item indices (-1 = padding), targets CSR; v = ndcg, map, auroc, precision,
+// recall, hit, mrr. Returns false (v all zero) when the user has no target (the reference returns {} for it,
+// metrics.py:58-59). metrics_kernel and metrics_sum_kernel both call it: their per-row values are the same bits.
+__device__ __forceinline__ bool metrics_row(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off, int64_t b, int k,
+                                            int top_k, float v[7]) {
   const int64_t* t = tgt + tgt_off[b];
   const int nt_raw = (int)(tgt_off[b + 1] - tgt_off[b]);
-  float* o = out + (int64_t)b * 7;
-  for (int i = 0; i < 7; ++i) o[i] = 0.f;
+  for (int i = 0; i < 7; ++i) v[i] = 0.f;
   // distinct targets (target_ids = set(target_ids), metrics.py:66)
   int nt = 0;
   for (int i = 0; i < nt_raw; ++i) {
@@ -215,9 +215,8 @@ __global__ void metrics_kernel(const int64_t* rec, const int64_t* tgt, const int
     for (int j = 0; j < i; ++j) dup |= t[j] == t[i];
     nt += dup ? 0 : 1;
   }
-  valid[b] = nt > 0;
-  if (nt == 0) return;
-  const int64_t* r = rec + (int64_t)b * k;
+  if (nt == 0) return false;
+  const int64_t* r = rec + b * k;
   // the list torchmetrics sees: max(len(rec), top_k) slots of recommendations (padding never matches a target), then
   // the missing targets. Every metric below only looks at the first top_k slots (+ the number of targets).
   const int K = top_k;
@@ -235,19 +234,91 @@ __global__ void metrics_kernel(const int64_t* rec, const int64_t* tgt, const int
       if (rr == 0.f) rr = 1.f / (float)(i + 1);
     } else {
       ++neg_seen;
+      pairs += hits;  // each earlier positive outranks this negative
     }
-    if (rel) pairs += 0;  // (positives above this point are counted when the negatives below them arrive)
-    else pairs += hits;   // each earlier positive outranks this negative
   }
   float idcg = 0.f;
   for (int i = 0; i < (nt < K ? nt : K); ++i) idcg += 1.f / log2f((float)i + 2.f);
-  o[0] = idcg > 0.f ? dcg / idcg : 0.f;
-  o[1] = hits > 0 ? ap_sum / (float)hits : 0.f;
-  o[2] = (hits > 0 && neg_seen > 0) ? (float)pairs / ((float)hits * (float)neg_seen) : 0.f;
-  o[3] = (float)hits / (float)K;
-  o[4] = (float)hits / (float)nt;
-  o[5] = hits > 0 ? 1.f : 0.f;
-  o[6] = rr;
+  v[0] = idcg > 0.f ? dcg / idcg : 0.f;
+  v[1] = hits > 0 ? ap_sum / (float)hits : 0.f;
+  v[2] = (hits > 0 && neg_seen > 0) ? (float)pairs / ((float)hits * (float)neg_seen) : 0.f;
+  v[3] = (float)hits / (float)K;
+  v[4] = (float)hits / (float)nt;
+  v[5] = hits > 0 ? 1.f : 0.f;
+  v[6] = rr;
+  return true;
+}
+
+// one thread per query: out (B,7), valid[b] = 0 when the user has no target
+__global__ void metrics_kernel(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off, int B, int k, int top_k,
+                               float* out, uint8_t* valid) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float v[7];
+  valid[b] = metrics_row(rec, tgt, tgt_off, b, k, top_k, v);
+  float* o = out + (int64_t)b * 7;
+  for (int i = 0; i < 7; ++i) o[i] = v[i];
+}
+
+// ---- the metrics and their sums in one call (xfmr_retrieval_metrics_sum) ---------------------------------------------
+// metrics_sum_kernel: 256-row workgroups, one row per lane. The seven values and the count of the rows that are valid and
+// used go to fp64 (lanes past n_query and rows left out: exact zeros), are added across the wave by xor shuffles (a fixed
+// tree), across the four waves through LDS in a fixed order, and leave as ONE 8-double record per workgroup.
+// metrics_sum_final_kernel: one workgroup adds the records in index order (lane t takes records t, t + 256, ...) and
+// finishes with the same tree. No atomics, no dependence on which workgroup finishes first: the same input gives the same
+// eight doubles on every launch.
+constexpr int MS_ROWS = 256;
+constexpr int MS_VALS = 8;  // XFMR_NUM_RM sums + the number of rows
+
+__device__ __forceinline__ void ms_block_sum(double acc[MS_VALS], double (*sP)[MS_VALS], double* dst) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+  for (int i = 0; i < MS_VALS; ++i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc[i] += __shfl_xor(acc[i], o, 64);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < MS_VALS; ++i) sP[w][i] = acc[i];
+  }
+  __syncthreads();
+  if (tid < MS_VALS) dst[tid] = (sP[0][tid] + sP[1][tid]) + (sP[2][tid] + sP[3][tid]);
+}
+
+__global__ __launch_bounds__(MS_ROWS) void metrics_sum_kernel(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off,
+                                                              const uint8_t* use, int64_t B, int k, int top_k, float* out,
+                                                              uint8_t* valid, double* partial) {
+  __shared__ double sP[MS_ROWS / 64][MS_VALS];
+  const int64_t b = (int64_t)blockIdx.x * MS_ROWS + threadIdx.x;
+  double acc[MS_VALS];
+#pragma unroll
+  for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
+  if (b < B) {
+    float v[7];
+    const bool ok = metrics_row(rec, tgt, tgt_off, b, k, top_k, v);
+    if (out) {
+      for (int i = 0; i < 7; ++i) out[b * 7 + i] = v[i];
+    }
+    if (valid) valid[b] = ok;
+    if (ok && (!use || use[b])) {
+#pragma unroll
+      for (int i = 0; i < 7; ++i) acc[i] = (double)v[i];
+      acc[7] = 1.0;
+    }
+  }
+  ms_block_sum(acc, sP, partial + (int64_t)blockIdx.x * MS_VALS);
+}
+
+__global__ __launch_bounds__(MS_ROWS) void metrics_sum_final_kernel(const double* partial, int64_t n_partial, double* sums) {
+  __shared__ double sP[MS_ROWS / 64][MS_VALS];
+  double acc[MS_VALS];
+#pragma unroll
+  for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
+  for (int64_t p = threadIdx.x; p < n_partial; p += MS_ROWS) {
+#pragma unroll
+    for (int i = 0; i < MS_VALS; ++i) acc[i] += partial[p * MS_VALS + i];
+  }
+  ms_block_sum(acc, sP, sums);
 }
 
 
@@ -582,6 +653,29 @@ int xfmr_retrieval_metrics(const int64_t* rec_idx, const int64_t* targets, const
   return XFMR_OK;
 }
 
+
+size_t xfmr_retrieval_metrics_sum_workspace(int64_t n_query) {
+  if (n_query <= 0) return 0;
+  return (size_t)((n_query + MS_ROWS - 1) / MS_ROWS) * MS_VALS * sizeof(double);
+}
+
+int xfmr_retrieval_metrics_sum(const int64_t* rec_idx, const int64_t* targets, const int64_t* target_offsets,
+                               const uint8_t* use, int64_t n_query, int32_t k, int32_t top_k, double* sums, float* out,
+                               uint8_t* valid, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!rec_idx || !targets || !target_offsets || !sums || !workspace || n_query <= 0 || k <= 0 || top_k <= 0)
+    return XFMR_EINVAL;
+  if (n_query >= (1ll << 31)) return XFMR_EUNSUPPORTED;  // (xfmr_retrieval_metrics takes an int32 row count)
+  if (workspace_bytes < xfmr_retrieval_metrics_sum_workspace(n_query)) return XFMR_EWORKSPACE;
+  const int64_t n_partial = (n_query + MS_ROWS - 1) / MS_ROWS;
+  double* partial = (double*)workspace;
+  hipLaunchKernelGGL(metrics_sum_kernel, dim3((unsigned)n_partial), dim3(MS_ROWS), 0, (hipStream_t)stream, rec_idx, targets,
+                     target_offsets, use, n_query, k, top_k, out, valid, partial);
+  XF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(metrics_sum_final_kernel, dim3(1), dim3(MS_ROWS), 0, (hipStream_t)stream, (const double*)partial,
+                     n_partial, sums);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
 
 size_t xfmr_topk_tiled_workspace(int64_t n_query, int64_t n_rows, int32_t k) {
   if (n_query <= 0 || n_rows <= 0 || k <= 0) return 0;

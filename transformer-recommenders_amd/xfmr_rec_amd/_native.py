@@ -182,6 +182,9 @@ _SIGNATURES = {
     "xfmr_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P,
                             C.c_size_t, _P]),
     "xfmr_retrieval_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "xfmr_retrieval_metrics_sum_workspace": (C.c_size_t, [C.c_int64]),
+    "xfmr_retrieval_metrics_sum": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_size_t,
+                                             _P]),
     "xfmr_topk_tiled_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
     "xfmr_topk_tiled": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P,
                                   _P, C.c_size_t, _P]),

@@ -124,6 +124,38 @@ def retrieval_metrics(rec_idx: torch.Tensor, target_idx, top_k: int):
     return out, valid.bool()
 
 
+def retrieval_metrics_sum(rec_idx: torch.Tensor, targets_csr, use: torch.Tensor | None = None, *, top_k: int,
+                          per_row: bool = False):
+    """:func:`retrieval_metrics` and its sums in one call (xfmr_retrieval_metrics_sum), nothing read back: returns the
+    device tensor of 8 doubles -- ``[0..6]`` the sums of the METRIC_NAMES values over the rows that have a target and are
+    used, ``[7]`` their number. ``targets_csr``: ``(flat, offsets)`` int64 DEVICE tensors (offsets: B + 1 entries; a view
+    into a longer offsets array with absolute values is fine); ``use`` (B,) uint8 / bool on the device or None = every
+    row. ``per_row=True`` returns ``(sums, values (B,7), valid (B,) bool)``: the bits of :func:`retrieval_metrics`."""
+    B, k = rec_idx.shape
+    dev = rec_idx.device
+    tg, tgo = targets_csr
+    if tgo.numel() != B + 1:
+        raise ValueError(f"targets_csr offsets have {tgo.numel()} entries for {B} rows")
+    if use is not None:
+        if use.numel() != B:
+            raise ValueError(f"use has {use.numel()} entries for {B} rows")
+        use = use.view(torch.uint8) if use.dtype == torch.bool else use
+        if use.dtype != torch.uint8:
+            raise ValueError(f"use must be uint8 or bool, got {use.dtype}")
+    sums = torch.empty((8,), dtype=torch.float64, device=dev)
+    out = torch.empty((B, len(METRIC_NAMES)), dtype=torch.float32, device=dev) if per_row else None
+    valid = torch.empty((B,), dtype=torch.uint8, device=dev) if per_row else None
+    lib = N.load()
+    nbytes = lib.xfmr_retrieval_metrics_sum_workspace(B)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    N.check(
+        lib.xfmr_retrieval_metrics_sum(N.ptr(rec_idx.contiguous()), N.ptr(tg), N.ptr(tgo), N.ptr(use), B, k, top_k,
+                                       N.ptr(sums), N.ptr(out), N.ptr(valid), N.ptr(ws), nbytes, N.stream()),
+        "xfmr_retrieval_metrics_sum",
+    )
+    return (sums, out, valid.bool()) if per_row else sums
+
+
 def compute_retrieval_metrics(rec_idx, target_idx, top_k: int) -> dict[str, torch.Tensor]:
     """``metrics.py:17-79`` for ONE ranked list (item indices instead of id strings): {} when there is no target."""
     rec = torch.as_tensor(rec_idx, dtype=torch.int64, device="cuda").reshape(1, -1)

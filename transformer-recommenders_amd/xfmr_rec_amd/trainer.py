@@ -16,6 +16,8 @@ HIP kernels from ``libxfmr_hip.so``; torch supplies memory, streams, autograd bo
 from __future__ import annotations
 
 import contextlib
+import math
+import pathlib
 import time
 
 import torch
@@ -24,7 +26,7 @@ from . import _native as N
 from . import ops
 from .losses import LOSS_CLASSES, LossConfig, LossType, stats_to_dict
 from .models import ModelConfig, RecommenderModel
-from .params import TOP_K
+from .params import METRIC, TOP_K
 
 try:  # pragma: no cover - lightning is not installed in the build image
     import lightning.pytorch as _lp
@@ -705,6 +707,57 @@ def reference_trainer_options(cfg: dict) -> dict:
     return dict(gradient_clip_val=clip, gradient_clip_algorithm=algo, accumulate_grad_batches=acc, lr_scheduler=schedule)
 
 
+class EarlyStopping:
+    """Lightning's ``EarlyStopping`` rule on one monitored value: ``update(value)`` returns True when the loop should stop.
+
+    A value improves when ``value - min_delta > best`` (mode "max"; ``value + min_delta < best`` for "min"); the first value
+    always does. A value that does not improve (a NaN never does) adds one to ``wait``; the loop stops once
+    ``wait >= patience``. ``patience=None`` never stops: the object then only tracks the best value. ``improved`` says
+    whether the last value did."""
+
+    def __init__(self, mode: str = "max", patience: int | None = 3, min_delta: float = 0.0):
+        if mode not in ("max", "min"):
+            raise ValueError(f"mode must be 'max' or 'min'; got {mode!r}")
+        if patience is not None and (isinstance(patience, bool) or not isinstance(patience, int) or patience < 1):
+            raise ValueError(f"patience must be an integer >= 1 (or None); got {patience!r}")
+        if not float(min_delta) >= 0.0:
+            raise ValueError(f"min_delta must be >= 0; got {min_delta!r}")
+        self.mode, self.patience, self.min_delta = mode, patience, float(min_delta)
+        self.best: float | None = None
+        self.wait = 0
+        self.improved = False
+
+    def update(self, value: float) -> bool:
+        v = float(value)
+        if self.best is None:
+            better = not math.isnan(v)
+        elif self.mode == "max":
+            better = v - self.min_delta > self.best
+        else:
+            better = v + self.min_delta < self.best
+        self.improved = better
+        if better:
+            self.best, self.wait = v, 0
+        else:
+            self.wait += 1
+        return self.patience is not None and self.wait >= self.patience
+
+
+def _early_stopping_from(arg, mode: str) -> EarlyStopping | None:
+    """``Trainer.fit``'s ``early_stopping`` argument: None / False (off), True (Lightning's defaults: patience 3, min_delta 0)
+    or ``{"patience", "min_delta"}``."""
+    if arg is None or arg is False:
+        return None
+    if arg is True:
+        return EarlyStopping(mode)
+    if isinstance(arg, dict):
+        extra = set(arg) - {"patience", "min_delta"}
+        if extra:
+            raise ValueError(f"early_stopping: unknown keys {sorted(extra)} ('patience', 'min_delta')")
+        return EarlyStopping(mode, patience=arg.get("patience", 3), min_delta=arg.get("min_delta", 0.0))
+    raise ValueError(f"early_stopping must be None, True or a dict; got {arg!r}")
+
+
 class Trainer:
     """Minimal stand-in for Lightning's automatic optimisation (``zero_grad -> training_step -> backward ->
     [all-reduce] -> optimizer.step``), single process or one process per GPU (``torch.distributed``)."""
@@ -821,8 +874,22 @@ class Trainer:
         value that changes the optimisation and cannot be honoured raises a ``ValueError`` that names its key."""
         return cls(module, **reference_trainer_options(cfg), **kwargs)
 
+    def _check_val(self, val) -> None:
+        if val is not None and self.world_size > 1:
+            raise ValueError("validation inside a data-parallel run (world_size > 1) is not supported: a sharded validation "
+                             "set has never run on more than one GPU")
+
+    def validate(self, val, stage: str = "val") -> dict:
+        """One validation pass over ``val`` (a :class:`~xfmr_rec_amd.evalset.DeviceEvalSet`) outside ``fit``: the dict of
+        ``DeviceEvalSet.evaluate``, also handed to ``module.log_dict``."""
+        self._check_val(val)
+        metrics = val.evaluate(stage)
+        self.module.log_dict(metrics)
+        return metrics
+
     def fit(self, batches, max_steps: int | None = None, *, ring_slots: int = 6, graph: str = "off",
-            graph_probe_steps: int = 20) -> list[float]:
+            graph_probe_steps: int = 20, val=None, val_check_interval: int | None = None, monitor: dict = METRIC,
+            early_stopping=None, checkpoint_dir=None) -> list[float]:
         """Steps over an iterable of collated batches. Batches that arrive in HOST memory (the reference's DataLoader
         output, ``data.py:915-927``) are handed over through a :class:`~xfmr_rec_amd.data.PinnedBatchRing`: the copy of
         batch i + 1 runs underneath step i; device-resident batches (``DeviceSeqDataset.sample_batch``) are used as they are.
@@ -833,8 +900,42 @@ class Trainer:
         form runs the rest (replay wins where the host's launch rate bounds the step -- BASELINE config 1's shape: 0.31
         against 0.48 ms -- and changes nothing where the GPU does: DESIGN.md section 5). Every probe step is a real
         training step on its own batch. Batches of another shape (a short last batch) take the eager step. Single
-        process only; ``self.graph_choice`` records what ran."""
+        process only; ``self.graph_choice`` records what ran.
+
+        ``val`` (a :class:`~xfmr_rec_amd.evalset.DeviceEvalSet`): validate inside the loop, as Lightning does with the
+        reference's ``ModelCheckpoint`` + ``EarlyStopping`` on ``val/retrieval_normalized_dcg`` (``trainer.py:334-341``).
+        ``val_check_interval=n``: a pass after every n-th batch (a multiple of ``accumulate_grad_batches``); None: one pass
+        after the last batch. A pass runs between steps on the loop's stream, never inside a capture (under ``graph`` it is
+        enqueued eagerly between replays) and its time is taken out of the "auto" probe's windows. ``monitor``: ``{"name",
+        "mode"}``. ``early_stopping``: None, True (patience 3, min_delta 0) or ``{"patience", "min_delta"}``
+        (:class:`EarlyStopping`). ``checkpoint_dir``: every strict improvement of the monitor overwrites
+        ``checkpoint_dir / "best"`` with ``module.save`` (``ModelCheckpoint(save_top_k=1)``; ``RecommenderModel.load`` reads
+        it). Afterwards: ``val_history`` (``{"step": batches done, **metrics}`` per pass), ``best_score``, ``best_step``,
+        ``best_model_path``, ``stopped_early`` and ``val_elapsed`` (seconds in validation passes: a host clock from a
+        stream sync in front of the pass to its read-back)."""
         from .data import SEQ_BATCH_KEYS, PinnedBatchRing
+
+        self._check_val(val)
+        if val_check_interval is not None:
+            if isinstance(val_check_interval, bool) or not isinstance(val_check_interval, int) or val_check_interval < 1:
+                raise ValueError(f"val_check_interval must be an integer >= 1 or None; got {val_check_interval!r}")
+            if val_check_interval % self.accumulate_grad_batches:
+                raise ValueError(f"val_check_interval = {val_check_interval} is not a multiple of accumulate_grad_batches = "
+                                 f"{self.accumulate_grad_batches}: a pass would fall between the micro-batches of one step")
+        if not isinstance(monitor, dict) or set(monitor) != {"name", "mode"}:
+            raise ValueError(f"monitor must be {{'name', 'mode'}}; got {monitor!r}")
+        stage, _, metric_name = str(monitor["name"]).rpartition("/")
+        tracker = EarlyStopping(monitor["mode"], patience=None)  # the best value: strict improvements (ModelCheckpoint)
+        stopper = _early_stopping_from(early_stopping, monitor["mode"])
+        if val is not None:
+            from .retrieval import METRIC_NAMES
+
+            if not stage or metric_name not in METRIC_NAMES:
+                raise ValueError(f"monitor name {monitor['name']!r}: expected '<stage>/<metric>' with a metric of {METRIC_NAMES}")
+        self.val_history: list[dict] = []
+        self.best_score = self.best_step = self.best_model_path = None
+        self.stopped_early = False
+        self.val_elapsed = 0.0
 
         if graph not in ("off", "on", "auto"):
             raise ValueError(f"graph must be 'off', 'on' or 'auto', got {graph!r}")
@@ -863,6 +964,31 @@ class Trainer:
         def _sync_time():
             torch.cuda.synchronize(self.module.model.device)
             return time.perf_counter()
+
+        def _validate(batches_done: int) -> bool:
+            """One pass between two steps; True when the loop should stop."""
+            dev_ = self.module.model.device
+            torch.cuda.current_stream(dev_).synchronize()  # the steps enqueued so far are not validation time
+            tv = time.perf_counter()
+            metrics = val.evaluate(stage)
+            self.val_elapsed += time.perf_counter() - tv
+            self.module.log_dict(metrics)
+            self.val_history.append({"step": batches_done, **metrics})
+            value = metrics[monitor["name"]]
+            tracker.update(value)
+            if tracker.improved:
+                self.best_score, self.best_step = tracker.best, batches_done
+                if checkpoint_dir is not None:
+                    path = pathlib.Path(checkpoint_dir) / "best"
+                    self.module.save(path)
+                    self.best_model_path = str(path)
+            stop = stopper.update(value) if stopper is not None else False
+            # the "auto" probe compares STEPS: whatever a pass (and its checkpoint) took leaves the open window
+            spent = time.perf_counter() - tv
+            for k0, k1 in (("eager_t0", "eager_ms"), ("graph_t0", "graph_ms")):
+                if k0 in probe and k1 not in probe:
+                    probe[k0] += spent
+            return stop
 
         out = []
         t0 = time.time()
@@ -923,6 +1049,11 @@ class Trainer:
                 else:
                     out.append(self.fit_step(dev_b))
                 i += 1
+                if val is not None and val_check_interval is not None and i % val_check_interval == 0 and _validate(i):
+                    self.stopped_early = True
+                    break
+            if val is not None and val_check_interval is None and i > 0:
+                _validate(i)
         if side is not None:
             cur.wait_stream(side)
         if graph != "off":
