@@ -14,8 +14,12 @@ plain functions over an HF-keyed parameter dict, following
 * self-output ``:282-293``  LN(dropout(dense(ctx)) + x)
 * FFN         ``:325-351``  LN(dropout(dense2(gelu_erf(dense1(x)))) + x)
 
-Dropout is applied only when ``dropout_p > 0`` (training-mode parity is not
-bit-reproducible; parity tests run with dropout off, as eval()).
+Dropout is applied only when ``dropout_p > 0`` and ``training``, through
+``_dropout`` at four kinds of site in a fixed order: embedding output; then per
+layer attention probabilities, attention output, FFN output. ``F.dropout``'s
+own stream matches no kernel's, so training-mode parity tests replace
+``_dropout`` for the call with the kernels' masks restated on the host
+(``tests/dropout_model.py``); the other parity tests run with dropout off.
 Sentence pooling follows sentence-transformers ``Pooling(mean)`` as wired at
 ``models.py:143-145``: sum(tok*m)/clamp(sum(m), 1e-9).
 """

@@ -6,7 +6,8 @@ test_fused_refs_host.py) instead of against each other:
   dropout of the LayerNorm OUTPUT (layer 0's call: the embedding LayerNorm)
 
 Inputs are bf16-representable, so the references see exactly the operands the MFMAs see. Dropout masks come from the FORWARD
-kernels that apply them (the Linear + dropout + residual epilogue; the embedding LayerNorm), never from the kernel under test.
+kernels that apply them (the Linear + dropout + residual epilogue; the embedding LayerNorm), never from the kernel under test,
+and are held to the host model of the mask (dropout_model.py) where they are extracted.
 Every output is pre-filled with 0xFF bytes (NaN as fp32 and as bf16) and has 64 guard rows behind it that must keep them.
 
 Limits. dI is bf16(fp32 accumulation): against bf16(fp64) it may differ by one bf16 ulp where the fp32 error (and the 1.5e-7 of
@@ -17,9 +18,11 @@ judged from the kernel's OWN dI, where only fp32 accumulation remains: helpers.T
 import ctypes as C
 import functools
 
+import numpy as np
 import pytest
 import torch
 
+import dropout_model as dm
 from fused_refs import dx_lnbwd_ref, ffn_bwd_dx_ref
 from helpers import assert_close
 from test_gpu_ffn_weight_ring import H, _inputs
@@ -79,6 +82,7 @@ def _keep(M, p):
     assert bool(((y == 0) | ((y - 1 / (1 - p)).abs() < 1e-6)).all())
     keep = (y != 0).double().cpu()
     assert 0 < float(keep.mean()) < 1
+    assert np.array_equal(keep.numpy(), dm.hidden_keep(SEED, SITE, M, H, p).astype(np.float64))  # = the host model's mask
     return keep
 
 
@@ -95,7 +99,9 @@ def _keep_out(M, p):
                            torch.zeros(H, device=DEV), torch.ones(H, device=DEV), dropout_p=p, seed=SEED, site=SITE_OUT)[0]
     out = out.view(M, H)
     assert bool(((out == 0) | ((out - 1 / (1 - p)).abs() < 1e-6)).all())
-    return (out != 0).double().cpu()
+    keep = (out != 0).double().cpu()
+    assert np.array_equal(keep.numpy(), dm.hidden_keep(SEED, SITE_OUT, M, H, p).astype(np.float64))  # = the host model's mask
+    return keep
 
 
 def _check_ln_stage(tag, o, ref, M, blocks, n_tiles, keep, p, with_dlin):

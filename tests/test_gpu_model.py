@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import dropout_model as dm
 from helpers import TOL, assert_close, grad_tol, loss_tol, ragged_batch, rel_l2, unit_table
 
 pytestmark = pytest.mark.gpu
@@ -206,14 +207,67 @@ def _perturbed_state(names_shapes, seed=7, scale=0.05):
 _ORACLE_CACHE = {}
 
 
-def _oracle_run(key, params, table, idx, A, L, is_decoder, w):
-    """Oracle forward + backward of sum(tok * w) over the valid rows, computed once per `key` and left unchanged."""
+class _MaskFeed:
+    """Stands in for oracle.encoder._dropout: hands out the host model's masks (dropout_model.py; each already times
+    1 / (1 - p)) in the oracle's fixed call order -- embedding, then per layer attention probabilities, attention output, FFN
+    output -- and checks every one against the tensor it is applied to."""
+
+    def __init__(self, masks):
+        self.masks, self.used = list(masks), 0
+
+    def __call__(self, x, p, training):
+        assert training and p > 0
+        assert self.used < len(self.masks), "the oracle asked for more dropout masks than the encoder has sites"
+        k = self.masks[self.used]
+        self.used += 1
+        assert tuple(k.shape) == tuple(x.shape), (self.used - 1, tuple(k.shape), tuple(x.shape))
+        return x * k.to(x.dtype)
+
+    def done(self):
+        assert self.used == len(self.masks), (self.used, len(self.masks))
+
+
+def _host_masks(seed, step, B, L, H, A, nL, p, rows_of=None, slot_of=None):
+    """The encoder's dropout masks of one forward from the host model, on the oracle's PADDED (B, L, ...) tensors. Padded
+    layout: hidden row b L + l, attention row (b A + h) L + q. Packed layout (`rows_of` (B, L): the packed row of each valid
+    position, `slot_of` (B,): the sequence's slot): hidden-state sites are keyed by the packed row, attention by the slot."""
+    rows = (torch.arange(B * L) if rows_of is None else rows_of.reshape(-1)).numpy()
+    sc = dm.scale(p)
+
+    def hidden(site):
+        return torch.from_numpy(dm.hidden_keep(seed, site, B * L, H, p, step, row_index=rows).astype(np.float64)).view(B, L, H) * sc
+
+    def attn(site):
+        slots = B if slot_of is None else int(slot_of.max()) + 1
+        k = torch.from_numpy(dm.attention_keep(seed, site, slots, A, L, p, step).astype(np.float64)) * sc
+        return k if slot_of is None else k[slot_of]
+
+    masks = [hidden(dm.SITE_EMB)]
+    for i in range(nL):
+        masks += [attn(dm.site_attn(i)), hidden(dm.site_out(i)), hidden(dm.site_ffn(i))]
+    return masks
+
+
+def _oracle_run(key, params, table, idx, A, L, is_decoder, w, feed=None, patch=None):
+    """Oracle forward + backward of sum(tok * w) over the valid rows, computed once per `key` and left unchanged. `feed`
+    (a _MaskFeed, with `patch` = the test's monkeypatch): the oracle in TRAINING mode under the feed's masks."""
     if key in _ORACLE_CACHE:
         return _ORACLE_CACHE[key]
     from oracle import model as OM
 
     params = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
-    ref = OM.forward(params, table, idx, num_heads=A, max_seq_length=L, causal=is_decoder)
+    kw = {}
+    if feed is not None:
+        import oracle.encoder
+        from xfmr_rec_amd import models
+
+        assert key is None
+        assert models.HIDDEN_DROPOUT_PROB == models.ATTENTION_PROBS_DROPOUT_PROB  # (the oracle takes one rate)
+        patch.setattr(oracle.encoder, "_dropout", feed)
+        kw = dict(dropout_p=models.HIDDEN_DROPOUT_PROB, training=True)
+    ref = OM.forward(params, table, idx, num_heads=A, max_seq_length=L, causal=is_decoder, **kw)
+    if feed is not None:
+        feed.done()
     valid = ref["attention_mask"].bool()
     (ref["token_embeddings"] * w.to(table.dtype) * valid[..., None]).sum().backward()
     out = dict(valid=valid, tok=ref["token_embeddings"].detach(), sent=ref["sentence_embedding"].detach(),
@@ -224,11 +278,15 @@ def _oracle_run(key, params, table, idx, A, L, is_decoder, w):
 
 
 def _encoder_shape_vs_oracle(X, prec, *, B, L, H, A, I, nL, V, lengths, is_decoder=True, state=None, scale=0.05,
-                             side_stream=None):
+                             side_stream=None, dropout=None, packed=False, device_step=None):
     """`state="perturbed"`: _perturbed_state's parameters instead of the constructor's, and the oracle in fp64 on the same
     tensors (shared between the cases of one shape). `side_stream`: a pytest monkeypatch -- the model runs in TRAINING mode
     with both dropout rates patched to 0, which is what gives the backward the model's xfmr_context (the side stream of the
-    weight-gradient GEMMs; eval mode passes none). Prints and returns the worst per-tensor gradient error."""
+    weight-gradient GEMMs; eval mode passes none). `dropout`: a pytest monkeypatch -- the model under m.train() with the
+    product's rates, the oracle in training mode under the host model's masks of that very forward (seed rule of
+    models.py::_cfg_kwargs; `device_step`: use_device_step(True) with the counter at that value; `packed`: the packed layout
+    through ops.pack_rows and _encode_tokens(packed=...), as the trainer runs it). Prints and returns the worst per-tensor
+    gradient error."""
     table = unit_table(V, H)
     batch, lengths = ragged_batch(B, L, V, lengths=lengths, seed=2)
     m = _model(X, H=H, A=A, I=I, nL=nL, Lmax=L, prec=prec, table=table, is_decoder=is_decoder)
@@ -246,17 +304,52 @@ def _encoder_shape_vs_oracle(X, prec, *, B, L, H, A, I, nL, V, lengths, is_decod
     dt = torch.float64 if state is not None else torch.float32
     params = {k: v.detach().cpu().to(dt) for k, v in m.encoder_state_dict().items()}
     w = torch.linspace(-1, 1, H)
-    ref = _oracle_run(key, params, table.to(dt), batch["history_item_idx"], A, L, is_decoder, w)
-    out = m(batch["history_item_idx"].to(DEV))
+    feed, pk, order = None, None, None
+    if packed:
+        from xfmr_rec_amd import ops
+
+        assert dropout is not None and m.supports_packed_rows(L)
+        order, offs = ops.length_order(lengths)  # longest first, as the trainer packs
+        idx_dev = batch["history_item_idx"].to(DEV)
+        pk = ops.pack_rows(idx_dev, idx_dev, None, offs.to(DEV), int(offs[-1]), order=order.to(DEV))
+        pk |= {"batch": B, "seq_len": L}
+    if dropout is not None:
+        from xfmr_rec_amd import models
+
+        key = None  # (masks differ from case to case: nothing to share)
+        m.train()
+        m._seed, m._step = 0x5DEECE66D, 6  # both halves of the 64-bit seed in use; the forward below is step 7
+        if device_step is not None:
+            m.use_device_step(True)
+            m.step_device.fill_(device_step)
+        seed = dm.model_seed(m._seed, m._step + 1, device_step is not None)
+        rows_of = slot_of = None
+        if packed:
+            slot_of = torch.empty(B, dtype=torch.int64)
+            slot_of[order] = torch.arange(B)
+            rows_of = (offs[:-1][slot_of][:, None] + torch.arange(L)[None, :]).clamp(max=int(offs[-1]) - 1)  # (padding: any row)
+        feed = _MaskFeed(_host_masks(seed, device_step, B, L, H, A, nL, models.HIDDEN_DROPOUT_PROB, rows_of, slot_of))
+    ref = _oracle_run(key, params, table.to(dt), batch["history_item_idx"], A, L, is_decoder, w, feed, dropout)
     valid = ref["valid"]
-    assert torch.equal(out["attention_mask"].cpu().bool(), valid)
-    e_tok = assert_close("tok", out["token_embeddings"].cpu()[valid], ref["tok"][valid], prec)
-    e_sent = assert_close("sentence_embedding", out["sentence_embedding"], ref["sent"], prec)
-    (out["token_embeddings"] * w.to(DEV) * valid.to(DEV)[..., None]).sum().backward()
+    if packed:
+        tok, km = m._encode_tokens(packed=pk)
+        sel = valid[order]
+        assert tok.shape == (int(sel.sum()), H) and bool(km.all())
+        e_tok = assert_close("tok", tok.cpu(), ref["tok"][order][sel], prec)
+        e_sent = float("nan")  # (pooling of packed rows: test_gpu_packed.py)
+        wrow = (w[None, None, :] * valid[..., None])[order][sel]
+        (tok * wrow.to(DEV)).sum().backward()
+    else:
+        out = m(batch["history_item_idx"].to(DEV))
+        assert torch.equal(out["attention_mask"].cpu().bool(), valid)
+        e_tok = assert_close("tok", out["token_embeddings"].cpu()[valid], ref["tok"][valid], prec)
+        e_sent = assert_close("sentence_embedding", out["sentence_embedding"], ref["sent"], prec)
+        (out["token_embeddings"] * w.to(DEV) * valid.to(DEV)[..., None]).sum().backward()
     got = m.grad_state_dict()
     errs = {k: rel_l2(got[k], g) for k, g in ref["grads"].items() if not k.endswith("key.bias")}
     worst = max(errs, key=errs.get)
-    print(f"FIG encoder B={B} L={L} H={H} I={I} {prec} state={state}: tok {e_tok:.2e}  sentence {e_sent:.2e}  "
+    mode = "" if dropout is None else f" dropout{' packed' if packed else ''}{'' if device_step is None else ' device-step'}"
+    print(f"FIG encoder B={B} L={L} H={H} I={I} {prec} state={state}{mode}: tok {e_tok:.2e}  sentence {e_sent:.2e}  "
           f"worst gradient {errs[worst]:.2e} ({worst})")
     for k, g in ref["grads"].items():
         if k.endswith("key.bias"):  # zero in exact arithmetic
@@ -330,6 +423,108 @@ def test_encoder_head_size_64_perturbed_vs_fp64_oracle(X):
 def test_bidirectional_encoder_config2_shape_perturbed_vs_fp64_oracle(X):
     _encoder_shape_vs_oracle(X, "bf16", B=3, L=200, H=128, A=4, I=512, nL=2, V=300, lengths=[200, 131, 17],
                              is_decoder=False, state="perturbed")
+
+
+# ------------------------------------------------------------------------------------------ training mode (dropout on)
+CONFIG2 = dict(B=3, L=200, H=128, A=4, I=512, nL=2, V=300, lengths=[200, 131, 17])
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_training_mode_encoder_config2_shape_vs_fp64_oracle(X, monkeypatch, prec):
+    """The whole encoder under m.train() -- hidden and attention dropout at the product's 0.1, which is what the benchmark
+    and Trainer.fit run -- against the fp64 oracle in training mode under the SAME masks, restated on the host
+    (dropout_model.py): token embeddings on the valid rows and every parameter tensor's gradient on its own, at the eval-mode
+    limits. Measured on an MI355X (token error; worst gradient rel-L2): fp32 1.5e-6; 3.9e-7 -- bf16 8.5e-3; 4.7e-3 --
+    bidirectional 1.0e-2; 3.9e-3 -- device step 9.1e-3; 4.6e-3 -- T = 82 x 200 1.3e-2; 3.5e-3 -- T = 62 x 200 1.2e-2; 3.7e-3 --
+    packed B = 3 / 82 8.5e-3; 4.9e-3 / 1.4e-2; 3.5e-3 -- L = 512 1.7e-2; 5.1e-3 -- head size 64 1.5e-2; 8.4e-3 (DESIGN.md
+    section 2)."""
+    _encoder_shape_vs_oracle(X, prec, state="perturbed", dropout=monkeypatch, **CONFIG2)
+
+
+def test_training_mode_bidirectional_encoder_vs_fp64_oracle(X, monkeypatch):
+    _encoder_shape_vs_oracle(X, "bf16", state="perturbed", dropout=monkeypatch, is_decoder=False, **CONFIG2)
+
+
+def test_training_mode_encoder_with_device_step_counter_vs_fp64_oracle(X, monkeypatch):
+    """use_device_step(True), the counter at 41: the host part of the seed is fixed and the kernels mix the counter into the
+    key (xf_drop_resolve) -- what a captured training step replays."""
+    _encoder_shape_vs_oracle(X, "bf16", state="perturbed", dropout=monkeypatch, device_step=41, **CONFIG2)
+
+
+@pytest.mark.parametrize("B", [82, 62])
+def test_training_mode_encoder_at_the_fused_thresholds_vs_fp64_oracle(X, monkeypatch, B):
+    """T = 82 x 200 (every fused plan: the LayerNorm epilogues, the one-kernel FFN, the re-derived residuals -- layer 0
+    REGENERATES the embedding mask --, the LayerNorm-fused dX GEMMs, ffn_bwd_dx_fused_kernel) and T = 62 x 200 (LayerNorm-fused
+    GEMMs, FFN unfused) with dropout on."""
+    _encoder_shape_vs_oracle(X, "bf16", B=B, lengths=_ragged_lengths(B, 200, B), state="perturbed", dropout=monkeypatch, **FUSED)
+
+
+@pytest.mark.parametrize("B", [3, 82])
+def test_training_mode_packed_encoder_vs_fp64_oracle(X, monkeypatch, B):
+    """The layout the trainer really runs: hidden-state masks keyed by the PACKED row, attention masks by the sequence's slot
+    (longest first) -- other masks than the padded layout's, by design."""
+    lengths = CONFIG2["lengths"] if B == 3 else _ragged_lengths(82, 200, 82)
+    _encoder_shape_vs_oracle(X, "bf16", B=B, lengths=lengths, state="perturbed", dropout=monkeypatch, packed=True, **FUSED)
+
+
+def test_training_mode_encoder_config5_shape_vs_fp64_oracle(X, monkeypatch):
+    """L = 512: the two-block attention forward and the dQ + dK/dV backward pair under dropout."""
+    _encoder_shape_vs_oracle(X, "bf16", B=3, L=512, H=256, A=8, I=1024, nL=2, V=300, lengths=[512, 300, 5],
+                             state="perturbed", dropout=monkeypatch)
+
+
+def test_training_mode_encoder_head_size_64_vs_fp64_oracle(X, monkeypatch):
+    _encoder_shape_vs_oracle(X, "bf16", B=3, L=40, H=384, A=6, I=96, nL=2, V=150, lengths=[40, 23, 3], state="perturbed",
+                             dropout=monkeypatch)
+
+
+def test_training_mode_step_packed_vs_oracle_under_the_same_masks(X, monkeypatch):
+    """compute_losses + backward in training mode, InfoNCE, through the packed layout the module chooses for a batch that
+    carries its lengths: the loss and the encoder gradients against the oracle's lean_loss in training mode under the host
+    model's masks (limits: loss_tol / grad_tol with flips, as every whole-step comparison of the default LossConfig)."""
+    import oracle.encoder
+    from oracle import model as OM
+    from xfmr_rec_amd import models, ops
+
+    B, L, H, A, I, nL, V, prec = 3, 24, 64, 2, 128, 2, 90, "bf16"
+    lengths = [17, 24, 5]  # slot order (longest first) differs from the batch's
+    table = unit_table(V, H)
+    batch, _ = ragged_batch(B, L, V, lengths=lengths, seed=5)
+    conf = X.LightningConfig(hidden_size=H, num_attention_heads=A, intermediate_size=I, num_hidden_layers=nL,
+                             max_seq_length=L, precision=prec, train_loss="InfoNCELoss")
+    mod = X.RecommenderLightningModule(conf)
+    mod.configure_model()
+    mod.model.set_table(table.to(DEV))
+    mod.model.load_encoder_state_dict(_perturbed_state([(k, v.shape) for k, v in mod.model.encoder_state_dict().items()]))
+    mod.train()
+    mod.model._seed, mod.model._step = 0x5DEECE66D, 2
+    packs = []
+    real_pack = ops.pack_rows
+    monkeypatch.setattr(ops, "pack_rows", lambda *a, **k: packs.append(1) or real_pack(*a, **k))
+    out = mod.compute_losses(batch | {"lengths": torch.tensor(lengths)})
+    assert packs == [1], "the module did not take the packed layout"
+    out["loss/InfoNCELoss"].backward()
+    order, offs = ops.length_order(lengths)
+    slot_of = torch.empty(B, dtype=torch.int64)
+    slot_of[order] = torch.arange(B)
+    rows_of = (offs[:-1][slot_of][:, None] + torch.arange(L)[None, :]).clamp(max=int(offs[-1]) - 1)
+    p = models.HIDDEN_DROPOUT_PROB
+    feed = _MaskFeed(_host_masks(dm.model_seed(mod.model._seed, 3), None, B, L, H, A, nL, p, rows_of, slot_of))
+    monkeypatch.setattr(oracle.encoder, "_dropout", feed)
+    params = {k: v.detach().cpu().double().requires_grad_(True) for k, v in mod.model.encoder_state_dict().items()}
+    want = OM.lean_loss(params, table.double(), batch, num_heads=A, max_seq_length=L, kind="InfoNCELoss", loss_cfg={},
+                        dropout_p=p)
+    feed.done()
+    want.backward()
+    wv = float(want.detach())
+    assert abs(float(out["loss/InfoNCELoss"]) - wv) <= loss_tol(prec, wv, flips=True), (float(out["loss/InfoNCELoss"]), wv)
+    got = mod.model.grad_state_dict()
+    errs = {k: rel_l2(got[k], p_.grad) for k, p_ in params.items() if not k.endswith("key.bias")}
+    worst = max(errs, key=errs.get)
+    print(f"FIG training step packed dropout: loss {float(out['loss/InfoNCELoss']):.5f} vs {wv:.5f}  worst gradient "
+          f"{errs[worst]:.2e} ({worst})")
+    for k, e in errs.items():
+        assert e <= grad_tol(prec, flips=True), (k, e)
 
 
 @pytest.mark.parametrize("mode,normalized", [("mean", False), ("max", True), ("cls", True), ("lasttoken", True)])

@@ -146,9 +146,10 @@ def test_embed_gather_layernorm_and_param_grads(ops):
     assert torch.count_nonzero(d_type[1]) == 0
 
 
-def _attention_reference(qkv, key_mask, A, causal=True):
+def _attention_reference(qkv, key_mask, A, causal=True, keep=None):
     """fp64 restatement of eager attention (TF:modeling_bert.py:111-136) with the causal+padding mask (causal=False:
-    the padding mask alone, BertConfig.is_decoder=False)."""
+    the padding mask alone, BertConfig.is_decoder=False). `keep`: (B, A, L, L) tensor of keep * 1/(1-p) (0 or the scale;
+    tests/dropout_model.py) -- attention-probability dropout where HF applies it, on the normalised probabilities."""
     B, L, H3 = qkv.shape
     H = H3 // 3
     dh = H // A
@@ -159,6 +160,8 @@ def _attention_reference(qkv, key_mask, A, causal=True):
     scores = scores.masked_fill(~allowed[:, None], float("-inf"))
     probs = torch.softmax(scores, dim=-1)
     probs = torch.nan_to_num(probs, nan=0.0)  # rows without any visible key -> zeros (documented)
+    if keep is not None:
+        probs = probs * keep.to(probs.dtype)
     return (probs @ v).transpose(1, 2).reshape(B, L, H)
 
 
@@ -200,14 +203,29 @@ def _bf16r(x):
     return x.to(torch.float32).to(torch.bfloat16).to(torch.float64)
 
 
-def _attention_bf16_emulation(qkv, key_mask, A, w, causal=True):
+def _attention_bf16_emulation(qkv, key_mask, A, w, causal=True, keep=None, fwd=None):
     """fp64 arithmetic with the bf16 kernels' ROUNDING POINTS (attention.hip, head size 32): operands Q / K / V / dO are
     bf16 values (the caller passes bf16-representable inputs, so staging rounds nothing); forward = online softmax over
     32-key blocks, p = 2^(s c - m_running) rounded to bf16 as the P V operand while the row sum takes the unrounded p;
     backward: P = exp(s / sqrt(dh) - lse) from the forward's lse, bf16(P) into dV, dS = P (dP - delta) rounded to bf16
     into dQ and dK, delta = rowsum(dO * ctx) in full precision. What is left between this and the kernels is fp32
     accumulation order and the 1-ulp exp2 -- parity at the fp32 level (1e-4) for the kernels no fp32-policy run reaches
-    (L > 256: the two-block forward and the dQ + dK/dV pair)."""
+    (L > 256: the two-block forward and the dQ + dK/dV pair).
+    `keep` ((B, A, L, L), keep * 1/(1-p)): dropout at the kernels' own points -- BEFORE each bf16 rounding, in fp32. Forward
+    (attn_fwd_bf16_kernel): the P V operand is bf16(p * keep) with p the unnormalised 2^(s c - m_running), the row sum takes
+    p without the mask. Backward (attn_bwd_dq_bf16_kernel, attn_bwd_dkv_bf16_kernel and the fused forms): the dV operand is
+    bf16(P * keep), dS = bf16(P * (dP * keep - delta)) with dP = dO V^T unrounded; delta = rowsum(dO * ctx) of the dropped-out
+    ctx.
+    `fwd` = (ctx, lse) as the FORWARD KERNEL stored them ((B, L, H) and (B, A, L), fp32): the backward is then modelled from
+    the backward kernels' own inputs and with the fp32 roundings of their exponent chain -- lse is an fp32 value in HBM,
+    lse2 = fp32(lse * log2e), the argument is ONE fp32 fma(s, fp32(1/sqrt(32) * log2e), -lse2) of the fp32 score, P is an fp32
+    value, P * keep an fp32 product before the bf16 rounding, and delta comes from the stored ctx. The fp64 form above places
+    P up to ~1e-6 (relative) from the kernel's, this form ~1e-7 (the MFMA's accumulation order of s and the 1-ulp exp2 are
+    left), so that many fewer probabilities fall on the other side of a bf16 rounding boundary than in the kernel. Only the
+    chain up to P and the product P * keep are rounded to fp32: the kernels' other fp32 steps in front of the bf16 rounding of
+    dS -- dP * keep, - delta, * P -- stay in fp64 here (the compiler may contract dP * keep - delta into one fma, so their
+    rounding is not fixed by the source; at ~1e-7 of a sum of O(1) terms they sit well inside the 1e-4 of the comparison).
+    Returns ctx, d_qkv and the model's own lse ((B, A, L), natural log), which a caller that passes `fwd` holds the kernel's to."""
     B, L, H3 = qkv.shape
     H = H3 // 3
     dh = H // A
@@ -227,21 +245,55 @@ def _attention_bf16_emulation(qkv, key_mask, A, w, causal=True):
         alpha = torch.exp2(m - msafe)
         p = torch.exp2(sb - msafe[..., None])
         lsum = lsum * alpha + p.sum(-1)
-        o = o * alpha[..., None] + _bf16r(p) @ v[:, :, k0:k0 + 32]
+        pk = p if keep is None else p * keep[..., k0:k0 + 32].double()
+        o = o * alpha[..., None] + _bf16r(pk) @ v[:, :, k0:k0 + 32]
         m = mnew
     ctx = o / lsum.clamp(min=1e-300)[..., None]
     ctx = torch.where((lsum > 0)[..., None], ctx, torch.zeros_like(ctx))
     lse = (m + torch.log2(lsum)) * 0.6931471805599453  # natural log, as the kernel stores it
-    pr = torch.exp(s * dh**-0.5 - lse[..., None]).masked_fill(~vis, 0.0)
-    pr = torch.nan_to_num(pr, nan=0.0)
+    f32 = lambda t: t.to(torch.float32).double()  # noqa: E731  (one fp32 rounding of an fp64 value)
+    if fwd is None:
+        pr = torch.exp(s * dh**-0.5 - lse[..., None]).masked_fill(~vis, 0.0)
+        pr = torch.nan_to_num(pr, nan=0.0)
+        ctx_b = ctx
+    else:
+        assert dh == 32
+        ctx_k, lse_k = (t.detach().cpu() for t in fwd)
+        sc32 = float(torch.tensor(0.17677669529663687, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32))
+        lse2 = (lse_k.to(torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32)).double()  # fp32 product
+        arg = f32(f32(s) * sc32 - lse2[..., None])  # fma: the product of two fp32 values is exact in fp64, one rounding
+        pr = f32(torch.exp2(arg)).masked_fill(~vis, 0.0)
+        pr = torch.nan_to_num(pr, nan=0.0)
+        ctx_b = ctx_k.double().view(B, L, A, dh).transpose(1, 2)
     dp = do @ v.transpose(2, 3)
-    delta = (do * ctx).sum(-1, keepdim=True)
+    delta = (do * ctx_b).sum(-1, keepdim=True)
+    if keep is not None:
+        dp = dp * keep.double()
     ds = _bf16r(pr * (dp - delta))
-    dv = _bf16r(pr).transpose(2, 3) @ do
+    pd = pr  # P.D, the dV operand
+    if keep is not None:
+        pd = pr * keep.double()
+        if fwd is not None:
+            pd = f32(pd)  # the kernel's fp32 product of the fp32 P and the fp32 scale
+    dv = _bf16r(pd).transpose(2, 3) @ do
     dq = (ds @ k) * dh**-0.5
     dk = (ds.transpose(2, 3) @ q) * dh**-0.5
     back = lambda t: t.transpose(1, 2).reshape(B, L, H)  # noqa: E731
-    return back(ctx), torch.cat([back(dq), back(dk), back(dv)], dim=-1)
+    return back(ctx), torch.cat([back(dq), back(dk), back(dv)], dim=-1), lse
+
+
+def fp32_level(name, got, want):
+    """rel-L2 <= 1e-4 over the tensor, and all but a handful of elements within 1e-4 * max(1, |x|). A probability that
+    lies within fp32 rounding (~1e-6 relative: the exponent's argument) of a bf16 rounding boundary lands on the other
+    side of it in the kernel than in the fp64 model -- a 2^-8 relative step of ONE probability, which a row with few
+    visible keys passes on almost undiluted (measured: 1.5-2.1e-4 on one or two elements of 51 200). The count-based
+    limit tolerates those; a slip in a tile's indexing moves whole 32 x 32 tiles and fails both."""
+    got, want = got.detach().double().cpu(), want.detach().double().cpu()
+    assert rel_l2(got, want) <= 1e-4, (name, rel_l2(got, want))
+    off = ((got - want).abs() > 1e-4 * want.abs().clamp(min=1.0)).double().mean().item()
+    assert off <= 2e-3, (name, off)
+    assert_close(name, got, want, "bf16")  # and nothing beyond the bf16 limit anywhere
+    return rel_l2(got, want), off
 
 
 @pytest.mark.parametrize("causal", [True, False], ids=["causal", "bidirectional"])
@@ -260,20 +312,8 @@ def test_bf16_attention_kernels_at_fp32_level_against_their_rounding_model(ops, 
         mask[1, 2] = 0
     w = (_rand(B, L, H, seed=14) * mask[..., None]).to(torch.bfloat16).float()
     ctx, lse = ops.attn_fwd(qkv.to(DEV), mask.to(DEV), A, precision="bf16", causal=causal)
-    want_ctx, want_d = _attention_bf16_emulation(qkv, mask, A, w, causal)
+    want_ctx, want_d, _lse_m = _attention_bf16_emulation(qkv, mask, A, w, causal)
     valid = mask.bool()
-
-    def fp32_level(name, got, want):
-        """rel-L2 <= 1e-4 over the tensor, and all but a handful of elements within 1e-4 * max(1, |x|). A probability that
-        lies within fp32 rounding (~1e-6 relative: the exponent's argument) of a bf16 rounding boundary lands on the other
-        side of it in the kernel than in the fp64 model -- a 2^-8 relative step of ONE probability, which a row with few
-        visible keys passes on almost undiluted (measured: 1.5-2.1e-4 on one or two elements of 51 200). The count-based
-        limit tolerates those; a slip in a tile's indexing moves whole 32 x 32 tiles and fails both."""
-        got, want = got.detach().double().cpu(), want.detach().double().cpu()
-        assert rel_l2(got, want) <= 1e-4, (name, rel_l2(got, want))
-        off = ((got - want).abs() > 1e-4 * want.abs().clamp(min=1.0)).double().mean().item()
-        assert off <= 2e-3, (name, off)
-        assert_close(name, got, want, "bf16")  # and nothing beyond the bf16 limit anywhere
 
     fp32_level("attn.ctx", ctx.cpu()[valid], want_ctx[valid])
     # the backward under test reads the FORWARD KERNEL's ctx / lse; the model used its own (equal to 1e-4 by the line above)
@@ -311,7 +351,7 @@ def test_attention_backward_roles_form_equals_the_lockstep_form(ops, monkeypatch
     # without dropout: the rounding model of the bf16 kernels
     ctx0, lse0 = ops.attn_fwd(qkv.to(DEV), mask.to(DEV), A, precision="bf16")
     d2 = ops.attn_bwd(qkv.to(DEV), mask.to(DEV), ctx0, lse0, w.to(DEV), A, precision="bf16")
-    _ctx_m, want_d = _attention_bf16_emulation(qkv, mask, A, w, True)
+    _ctx_m, want_d, _lse_m = _attention_bf16_emulation(qkv, mask, A, w, True)
     assert rel_l2(d2, want_d) <= 1e-4
 
 
@@ -561,6 +601,22 @@ def test_linear_with_layernorm_in_the_epilogue(ops, K, M, p_drop, bf16_storage):
     torch.testing.assert_close(rstd, rstd_ref, rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(y, y_ref, rtol=1e-5, atol=2e-6)
     assert torch.equal(y16, y.to(torch.bfloat16))
+    # and against fp64 with the host model's mask (dropout_model.py), not only against the sibling kernels: bf16 operands (the
+    # MFMA policy rounds fp32 storage on its way in), (acc + bias) * keep / (1 - p) + residual, then the LayerNorm. What is
+    # left is fp32 accumulation over K <= 512 products of O(1) sums and the hardware rsqrt (1 ulp): the limits of
+    # test_ffn_forward_in_one_kernel_vs_the_two_gemm_form's restatement.
+    import dropout_model as dm
+
+    ks = torch.from_numpy(dm.hidden_keep(5, 9, M, Nn, p_drop).astype("float64") * dm.scale(p_drop)).to(DEV)
+    xr, wr = x.to(torch.bfloat16).double(), w.to(torch.bfloat16).double()
+    pre64 = ks * (xr @ wr.T + b.double()) + res.double()
+    torch.testing.assert_close(pre.double(), pre64, rtol=2e-5, atol=2e-5)
+    if p_drop > 0:
+        assert torch.equal(pre == res, ks == 0)  # dropped: the residual alone, bit for bit
+    ln64 = torch.nn.functional.layer_norm(pre64, (Nn,), gamma.double(), beta.double(), 1e-12)
+    torch.testing.assert_close(y.double(), ln64, rtol=1e-4, atol=1e-4)
+    torch.testing.assert_close(mean.double(), pre64.mean(-1), rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(rstd.double(), (pre64.var(-1, unbiased=False) + 1e-12).rsqrt(), rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.parametrize("chunk", ["64", "128"])
@@ -639,14 +695,19 @@ def test_ffn_forward_in_one_kernel_vs_the_two_gemm_form(ops, M, I, p_drop, chunk
         assert rel_l2(a, b) <= 5e-3, k
     assert rel_l2(got["pre"], ref["pre"]) <= 2e-3 and rel_l2(got["y"], ref["y"]) <= 2e-3
     assert torch.equal(got["y16"], got["y"].to(torch.bfloat16))
-    # the fused kernel's own rounding points, restated in fp64 (without dropout: the mask is the shared hash)
-    if p_drop == 0.0:
+    # the fused kernel's own rounding points, restated in fp64, the dropout mask from the host model (dropout_model.py): the
+    # kernel scales (acc + bias) in fp32, then adds the residual. (The benchmark's row count is left to the comparisons above:
+    # M = 4113 has the partial tile, and 13 M fp64 products per chunk width are not worth their seconds.)
+    if M <= 8192:
+        import dropout_model as dm
+
+        ks = torch.from_numpy(dm.hidden_keep(5, 9, M, H, p_drop).astype("float64") * dm.scale(p_drop)).to(DEV)
         u = (x16.double() @ w1.double().T + b1.double()).to(torch.bfloat16)
         assert int((u != got["d"]).sum()) <= 2e-3 * u.numel()
         gg = torch.nn.functional.gelu(u.double()).to(torch.bfloat16)
         n_off = int((gg != got["g"]).sum())  # fp32-vs-fp64 accumulation flips a bf16 rounding now and then
         assert n_off <= 2e-3 * gg.numel(), n_off
-        pre = got["g"].double() @ w2.double().T + b2.double() + res.double()
+        pre = ks * (got["g"].double() @ w2.double().T + b2.double()) + res.double()
         torch.testing.assert_close(got["pre"].double(), pre, rtol=2e-5, atol=2e-5)
         ln = torch.nn.functional.layer_norm(pre, (H,), gamma.double(), beta.double(), 1e-12)
         torch.testing.assert_close(got["y"].double(), ln, rtol=1e-4, atol=1e-4)
