@@ -121,6 +121,10 @@ int xf_embed_ln_fwd_packed_ex(const int64_t* item_idx, const float* table, int64
                               int32_t H, float eps, float dropout_p, XfSeed seed, uint32_t site, hipStream_t stream);
 int xf_embed_param_grads_packed(const float* d_pre, float* d_pos, float* d_type, const int32_t* offs, int32_t B, int32_t L,
                                 int32_t H, int32_t max_pos, hipStream_t st);
+// encoder.hip: the forms a training step takes for this configuration (EncPlan), as integers: Tplan, T, mix, causal, fuse_ln,
+// fuse_ffn, rederive, fuse_ffn_bwd, dw_buffers_per_layer, dw_side, group_dw, lin_copy, half_layer, then zeros. Returns
+// check_cfg's code; reads the cfg's pointers only for being null or not.
+int xf_encoder_plan(const xfmr_encoder_cfg* cfg, int32_t out[16]);
 int xf_layernorm_bwd_impl(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                           float* dx, void* d_lin, bool lin16, float* d_gamma, float* d_beta, float* d_bias,
                           int64_t rows, int32_t H, XfDropout drop_out, XfDropout drop_lin, void* partials,
