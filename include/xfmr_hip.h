@@ -576,6 +576,41 @@ int xfmr_topk_tiled(const float* query, const float* table, const float* table_r
                     int64_t n_rows, int64_t n_query, int32_t H, const int64_t* exclude, const int64_t* exclude_offsets,
                     int32_t k, int32_t metric, int64_t* out_idx, float* out_score, void* workspace,
                     size_t workspace_bytes, void* stream);
+/* xfmr_target_ranks: the exact rank of every target among ALL eligible items, in one pass over the catalogue; no ranked
+ * list, so no limit on the cutoff a metric is taken at. query, table, table_rnorm, table_sqnorm, n_rows, n_query, H,
+ * metric and the SORTED exclusion CSR as xfmr_topk_tiled; targets / target_offsets (n_query + 1) as
+ * xfmr_retrieval_metrics_sum (repeats allowed, any number per query, offsets may be a view into a longer array).
+ * n_targets: at least target_offsets[n_query] - target_offsets[0]; it sizes the workspace.
+ *   Item j is ELIGIBLE for query q when 1 <= j < n_rows, j is not in q's exclusion list and its score is finite: the
+ *   items xfmr_topk_tiled can return. For the CSR entry e holding target t of query q
+ *     out_rank[e] = 1 + the eligible items that beat t (higher score first, then the lower index)   if t is eligible,
+ *     out_rank[e] = XFMR_RANK_NONE                                                                   otherwise
+ *   (e is the entry's index in `targets`: out_rank parallels that array). Repeats of a target share its rank.
+ *   out_target_score (may be NULL) parallels it too: the target's score, -inf where the rank is XFMR_RANK_NONE.
+ * Scores are xfmr_topk_tiled's bits (the same f32 MFMA tile; a target's own score by the fmaf chain the MFMA equals), so
+ * a target that xfmr_topk_tiled returns at place p has rank p + 1. Only integer counts are accumulated: two calls on the
+ * same input give the same bits. The cost per (query, item) does not grow with the number of targets up to 128 live
+ * targets per query; a 32-query tile holding more passes over its slice once per further 128.
+ * Limits as xfmr_topk_tiled (H a multiple of 4, <= 1024; 16-byte alignment; n_rows, n_query, n_targets < 2^31). */
+enum { XFMR_RANK_NONE = 0x7fffffff };
+size_t xfmr_target_ranks_workspace(int64_t n_query, int64_t n_rows, int64_t n_targets);
+int xfmr_target_ranks(const float* query, const float* table, const float* table_rnorm, const float* table_sqnorm,
+                      int64_t n_rows, int64_t n_query, int32_t H, const int64_t* exclude, const int64_t* exclude_offsets,
+                      const int64_t* targets, const int64_t* target_offsets, int64_t n_targets, int32_t metric,
+                      int32_t* out_rank, float* out_target_score, void* workspace, size_t workspace_bytes, void* stream);
+/* xfmr_rank_metrics_sum: the seven XFMR_RM_* metrics at up to 8 cutoffs from the ranks above, and their fp64 sums.
+ * ranks parallels `targets` (xfmr_target_ranks' out_rank); the CSR counts a row's DISTINCT targets and repeats are
+ * skipped; `use` as xfmr_retrieval_metrics_sum; cutoffs: HOST array of n_cutoffs (1..8) positive values, any size (also
+ * above n_rows), passed to the kernel by value. Per row and cutoff K the hits are the distinct targets of rank <= K in
+ * ascending rank, fed to the float expressions of xfmr_retrieval_metrics in its order: for K <= 128 the per-row values
+ * are the bits that call gives on xfmr_topk_tiled's list of K.
+ *   sums: device, n_cutoffs x 8 doubles: per cutoff the seven sums over valid and used rows, and their number;
+ *   out (n_query, n_cutoffs, 7) and valid (n_query): optional per-row outputs (may be NULL).
+ * The reduction is xfmr_retrieval_metrics_sum's (256-row records, then index order): no atomics. */
+size_t xfmr_rank_metrics_sum_workspace(int64_t n_query, int32_t n_cutoffs);
+int xfmr_rank_metrics_sum(const int32_t* ranks, const int64_t* targets, const int64_t* target_offsets, const uint8_t* use,
+                          int64_t n_query, const int32_t* cutoffs, int32_t n_cutoffs, double* sums, float* out,
+                          uint8_t* valid, void* workspace, size_t workspace_bytes, void* stream);
 /* table_sqnorm[r] = |table[r]|^2 (the l2 metric's item term). */
 int xfmr_table_sqnorm(const float* table, float* table_sqnorm, int64_t n_rows, int32_t H, void* stream);
 

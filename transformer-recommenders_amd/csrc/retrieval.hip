@@ -14,6 +14,8 @@
 //                   vector over [recommendations | missing targets] (metrics.py:66-79)
 //   metrics_sum_kernel + metrics_sum_final_kernel  the same per-row values and, in the same call, their fp64 sums over
 //                   the rows that count (xfmr_retrieval_metrics_sum: nothing of a validation pass is summed on the host)
+//   rank_prep_kernel + rank_tile_kernel + rank_finish_kernel  every target's exact rank over the whole catalogue
+//                   (xfmr_target_ranks), and rank_metrics_sum_kernel: the seven metrics at several cutoffs from those ranks
 // metric: cosine (reference default, index.py:47), dot, or l2; score = 1 - distance as index.py:248-251 appends it.
 #include "common.h"
 
@@ -616,6 +618,387 @@ __global__ __launch_bounds__(256) void table_sqnorm_kernel(const float* table, f
   if (lane == 0) out[row] = s;
 }
 
+// ---- full-catalogue target ranks (xfmr_target_ranks) and the metrics written from ranks (xfmr_rank_metrics_sum) ------
+// Every one of the seven metrics is a function of the ranks of a row's distinct targets among the eligible items and of
+// the number of distinct targets: no ranked list is needed, so no cutoff limit either. An item is ELIGIBLE for a query
+// when it is in [1, n_rows), not in the query's exclusion list and its score is finite (what topk_tiled_kernel can
+// return); rank(t) = 1 + the eligible items that are tt_better than t. Three launches:
+//   rank_prep_kernel    one workgroup per query. The scores of the query's targets by the k-ordered fmaf chain that
+//                       the f32 MFMA equals bit for bit (dims 8c + {0,4,1,5,2,6,3,7}) and topk_tiled_kernel's formulas;
+//                       the best-first order of the targets (a count per entry, ties between repeats by entry order;
+//                       targets that are not eligible go last and are "dead"); and a histogram of the query's distinct,
+//                       in-range excluded items with a finite score, binned by how many live targets beat them.
+//   rank_tile_kernel    topk_tiled_kernel's grid and MFMA loop. The epilogue masks row 0, rows past the slice and
+//                       non-finite scores and bins every remaining (query, item) by b = the live targets of the query that
+//                       beat the item (one comparison against the worst target: most items end there; else a binary
+//                       search over the sorted targets in LDS) with an integer LDS atomic. No exclusion lookup: excluded
+//                       items are counted in here and taken out by the prep histogram. RK_T live targets per pass; a
+//                       tile whose rows have more passes over its slice again for the next RK_T.
+//   rank_finish_kernel  per query: slices added in index order and prefix-summed over b within each pass, the excluded
+//                       items prefix-summed over the whole list. The m-th best live target t_m is beaten by exactly the
+//                       counted items of its pass with b <= m, less itself and less the excluded ones with b <= m:
+//                       rank = (sum_{b <= m} hist[b]) - 1 - (sum_{b <= m} exb[b]) + 1.
+// Integer counts only: two calls give the same bits.
+constexpr int RK_T = 128;
+constexpr int RK_NONE = 0x7fffffff;
+constexpr int RK_WS_ARRAYS = 6;  // per-entry arrays ahead of the per-query and per-slice ones
+
+struct RankArgs {
+  const float* q; const float* table; const float* rnorm; const float* sqnorm; int n_rows; int n_query;
+  const int64_t* excl; const int64_t* excl_off; const int64_t* tgt; const int64_t* tgt_off;
+  // workspace, indexed by CSR entry relative to tgt_off[0]
+  float* tS; int* tI;  // entry order: score and item (-inf, RK_NONE: dead)
+  float* sS; int* sI;  // each query's entries best first
+  int* pos;            // an entry's place in that order
+  int* exb;            // per place: excluded items in bin b; after the finish, the ranks by place
+  int* nlive;          // [n_query]
+  int* hist;           // [splits][n_targets]
+  int* out_rank; float* out_tscore;
+  int64_t n_targets;
+  int H, metric, splits;
+  int64_t slice;
+};
+
+__device__ __forceinline__ float rk_score(int metric, float dot, float rq, float qq, float rn, float ee) {
+  if (metric == XFMR_METRIC_COSINE) return dot * rq * rn;
+  if (metric == XFMR_METRIC_DOT) return dot;
+  return 1.f - (qq - 2.f * dot + ee);
+}
+
+// |q|^2 as topk_tiled_kernel's 8 threads per query compute it; every thread of an aligned group of 8 gets the value
+__device__ __forceinline__ float rk_query_sqnorm(const float* qr, int H, int part) {
+  float qq = 0.f;
+  for (int h = 4 * part; h < H; h += 32) {
+    const float4 v = *reinterpret_cast<const float4*>(qr + h);
+    qq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, qq))));
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) qq += __shfl_xor(qq, o, 64);
+  return qq;
+}
+
+// one (query, item) dot product in the k-step order of the 32x32x2 MFMA loop: lane half 0 supplies dims 8c + {0..3},
+// lane half 1 dims 8c + 4 + {0..3} (zeros past H), one MFMA per component
+__device__ __forceinline__ float rk_chain_dot(const float* sQ, const float* e, int H) {
+  float acc = 0.f;
+  for (int c = 0; c < H; c += 8) {
+    const float4 x0 = *reinterpret_cast<const float4*>(sQ + c), y0 = *reinterpret_cast<const float4*>(e + c);
+    float4 x1 = make_float4(0.f, 0.f, 0.f, 0.f), y1 = x1;
+    if (c + 4 < H) {
+      x1 = *reinterpret_cast<const float4*>(sQ + c + 4);
+      y1 = *reinterpret_cast<const float4*>(e + c + 4);
+    }
+    acc = fmaf(x0.x, y0.x, acc); acc = fmaf(x1.x, y1.x, acc);
+    acc = fmaf(x0.y, y0.y, acc); acc = fmaf(x1.y, y1.y, acc);
+    acc = fmaf(x0.z, y0.z, acc); acc = fmaf(x1.z, y1.z, acc);
+    acc = fmaf(x0.w, y0.w, acc); acc = fmaf(x1.w, y1.w, acc);
+  }
+  return acc;
+}
+
+__device__ __forceinline__ float rk_item_score(const RankArgs& a, const float* sQ, float rq, float qq, int it) {
+  const float dot = rk_chain_dot(sQ, a.table + (int64_t)it * a.H, a.H);
+  float rn = 0.f, ee = 0.f;
+  if (a.metric == XFMR_METRIC_COSINE) rn = a.rnorm[it];
+  else if (a.metric == XFMR_METRIC_L2) ee = a.sqnorm[it];
+  return rk_score(a.metric, dot, rq, qq, rn, ee);
+}
+
+__global__ __launch_bounds__(256) void rank_prep_kernel(RankArgs a) {
+  __shared__ __attribute__((aligned(16))) float sQ[TOPK_MAX_H];
+  __shared__ int sLive;
+  const int tid = threadIdx.x, H = a.H;
+  const int qi = blockIdx.x;
+  const float* qr = a.q + (int64_t)qi * H;
+  for (int h = tid; h < H; h += 256) sQ[h] = qr[h];
+  const float qq = rk_query_sqnorm(qr, H, tid & 7);
+  const float rq = 1.f / fmaxf(sqrtf(qq), 1e-8f);
+  const int64_t base = a.tgt_off[0];
+  const int64_t e0 = a.tgt_off[qi] - base, e1 = a.tgt_off[qi + 1] - base;
+  const int64_t x0 = a.excl ? a.excl_off[qi] : 0, x1 = a.excl ? a.excl_off[qi + 1] : 0;
+  if (tid == 0) sLive = 0;
+  __syncthreads();
+  // ---- the targets' scores ------------------------------------------------------------------------------------
+  int live = 0;
+  for (int64_t e = e0 + tid; e < e1; e += 256) {
+    const int64_t t = a.tgt[base + e];
+    float s = -INFINITY;
+    int it = RK_NONE;
+    if (t >= 1 && t < a.n_rows && !(a.excl && tt_excluded(a.excl, x0, x1, (int)t))) {
+      const float v = rk_item_score(a, sQ, rq, qq, (int)t);
+      if (v > -INFINITY && v < INFINITY) { s = v; it = (int)t; ++live; }
+    }
+    a.tS[e] = s;
+    a.tI[e] = it;
+    a.exb[e] = 0;
+    if (a.out_tscore) a.out_tscore[base + e] = s;
+  }
+  if (live) atomicAdd(&sLive, live);
+  __syncthreads();
+  const int nl = sLive;
+  if (tid == 0) a.nlive[qi] = nl;
+  // ---- best-first order: an entry's place = the entries that go before it ----------------------------------------
+  for (int64_t e = e0 + tid; e < e1; e += 256) {
+    const float s = a.tS[e];
+    const int it = a.tI[e];
+    int p = 0;
+    for (int64_t f = e0; f < e1; ++f) {
+      const float sf = a.tS[f];
+      const int jf = a.tI[f];
+      p += (tt_better(sf, jf, s, it) || (sf == s && jf == it && f < e)) ? 1 : 0;
+    }
+    a.pos[e] = p;
+    a.sS[e0 + p] = s;
+    a.sI[e0 + p] = it;
+  }
+  __syncthreads();
+  // ---- the excluded items that the tile pass will count: bin b = the live targets that beat them ------------------
+  if (a.excl && nl > 0) {
+    for (int64_t x = x0 + tid; x < x1; x += 256) {
+      const int64_t it = a.excl[x];
+      if (it < 1 || it >= a.n_rows || (x > x0 && a.excl[x - 1] == it)) continue;
+      const float v = rk_item_score(a, sQ, rq, qq, (int)it);
+      if (!(v > -INFINITY && v < INFINITY)) continue;
+      const int b = tt_count_better(a.sS + e0, a.sI + e0, nl, v, (int)it);
+      if (b < nl) atomicAdd(&a.exb[e0 + b], 1);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void rank_tile_kernel(RankArgs a) {
+  __shared__ float sQQ[TT_Q], sRQ[TT_Q];
+  __shared__ int sLive[TT_Q], sN[TT_Q];
+  __shared__ int64_t sE0[TT_Q];
+  __shared__ float tS[TT_Q * RK_T];
+  __shared__ int tI[TT_Q * RK_T], hist[TT_Q * RK_T];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int H = a.H;
+  const int q0 = blockIdx.x * TT_Q;
+  const int split = blockIdx.y;
+  const int64_t lo = split * a.slice;
+  const int64_t hi = lo + a.slice < a.n_rows ? lo + a.slice : a.n_rows;
+  {
+    const int i = tid >> 3, part = tid & 7;
+    const bool real = q0 + i < a.n_query;
+    const float qq = rk_query_sqnorm(a.q + (int64_t)(real ? q0 + i : 0) * H, H, part);
+    if (part == 0) {
+      sQQ[i] = real ? qq : 0.f;
+      sRQ[i] = 1.f / fmaxf(sqrtf(real ? qq : 0.f), 1e-8f);
+      sLive[i] = real ? a.nlive[q0 + i] : 0;
+      sE0[i] = real ? a.tgt_off[q0 + i] - a.tgt_off[0] : 0;
+    }
+  }
+  __syncthreads();
+  int maxlive = 0;
+  for (int i = 0; i < TT_Q; ++i) maxlive = max(maxlive, sLive[i]);
+  const int h2 = lane >> 5;
+  const float* qa = a.q + (int64_t)min(q0 + (lane & 31), a.n_query - 1) * H + 4 * h2;
+  for (int c0 = 0; c0 < maxlive; c0 += RK_T) {
+    for (int x = tid; x < TT_Q * RK_T; x += 256) {
+      const int i = x / RK_T, m = x % RK_T;
+      if (c0 + m < sLive[i]) { tS[x] = a.sS[sE0[i] + c0 + m]; tI[x] = a.sI[sE0[i] + c0 + m]; }
+      hist[x] = 0;
+    }
+    if (tid < TT_Q) sN[tid] = min(max(sLive[tid] - c0, 0), RK_T);
+    __syncthreads();
+    for (int64_t t0 = lo; t0 < hi; t0 += TT_N) {
+      const int64_t j64 = t0 + 32 * w + (lane & 31);  // this lane's item (accumulator column)
+      const bool jok = j64 >= 1 && j64 < hi;
+      const int j = jok ? (int)j64 : 0;
+      const float* eb = a.table + (int64_t)j * H + 4 * h2;
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      // topk_tiled_kernel's k-step order
+#pragma unroll 4
+      for (int c = 0; c < H; c += 8) {
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
+        if (c + 4 * h2 < H) {
+          x = *reinterpret_cast<const float4*>(qa + c);
+          y = *reinterpret_cast<const float4*>(eb + c);
+        }
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, y.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, y.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, y.w, acc, 0, 0, 0);
+      }
+      float rn = 0.f, ee = 0.f;
+      if (jok) {
+        if (a.metric == XFMR_METRIC_COSINE) rn = a.rnorm[j];
+        else if (a.metric == XFMR_METRIC_L2) ee = a.sqnorm[j];
+      }
+      if (jok) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = xf_acc_row(r, lane);
+          const int n = sN[i];  // (0 for the rows past n_query)
+          const float s = rk_score(a.metric, acc[r], sRQ[i], sQQ[i], rn, ee);
+          if (n == 0 || !(s > -INFINITY && s < INFINITY)) continue;
+          const float* ts = tS + i * RK_T;
+          const int* ti = tI + i * RK_T;
+          if (tt_better(ts[n - 1], ti[n - 1], s, j)) continue;  // behind every target of this pass: no bin
+          atomicAdd(&hist[i * RK_T + tt_count_better(ts, ti, n - 1, s, j)], 1);
+        }
+      }
+    }
+    __syncthreads();
+    for (int x = tid; x < TT_Q * RK_T; x += 256) {
+      const int i = x / RK_T, m = x % RK_T;
+      if (m < sN[i]) a.hist[(int64_t)split * a.n_targets + sE0[i] + c0 + m] = hist[x];
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void rank_finish_kernel(RankArgs a) {
+  __shared__ int sScan[256], sExcl[256];
+  __shared__ int sCarry;
+  static_assert(256 % RK_T == 0, "the scan restarts at multiples of RK_T");
+  const int tid = threadIdx.x;
+  const int qi = blockIdx.x;
+  const int64_t base = a.tgt_off[0];
+  const int64_t e0 = a.tgt_off[qi] - base, e1 = a.tgt_off[qi + 1] - base;
+  const int nl = a.nlive[qi];
+  if (tid == 0) sCarry = 0;
+  __syncthreads();
+  for (int m0 = 0; m0 < nl; m0 += 256) {
+    const int m = m0 + tid;
+    int v = 0, x = 0;
+    if (m < nl) {
+      for (int s = 0; s < a.splits; ++s) v += a.hist[(int64_t)s * a.n_targets + e0 + m];
+      x = a.exb[e0 + m];
+    }
+    // a pass of the tile kernel bins against its own RK_T targets only (its bin 0 holds every item ahead of the pass's
+    // first target): the counted items restart at every pass, the excluded ones (binned over the whole list) do not
+    sScan[tid] = v;
+    sExcl[tid] = x;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+      const int t = (tid >= o && (tid - o) / RK_T == tid / RK_T) ? sScan[tid - o] : 0;
+      const int u = tid >= o ? sExcl[tid - o] : 0;
+      __syncthreads();
+      sScan[tid] += t;
+      sExcl[tid] += u;
+      __syncthreads();
+    }
+    if (m < nl) a.exb[e0 + m] = sScan[tid] - (sCarry + sExcl[tid]);
+    __syncthreads();
+    if (tid == 255) sCarry += sExcl[255];
+    __syncthreads();
+  }
+  for (int64_t e = e0 + tid; e < e1; e += 256)
+    a.out_rank[base + e] = a.tI[e] != RK_NONE ? a.exb[e0 + a.pos[e]] : RK_NONE;
+}
+
+// ---- the seven metrics at up to 8 cutoffs from the ranks (xfmr_rank_metrics_sum) ---------------------------------
+// One thread per row, metrics_sum_kernel's layout and reduction. The hits of a row at cutoff K are its distinct targets
+// with rank <= K in ascending rank (distinct eligible items have distinct ranks and the repeats of one target share a
+// rank: picking the next larger rank each time skips repeats); they are walked ONCE, every cutoff that still reaches the
+// rank takes the hit with metrics_row's float expressions in metrics_row's order, so the per-row values are its bits.
+constexpr int RK_MAX_CUTOFFS = 8;
+struct RankCutoffs { int k[RK_MAX_CUTOFFS]; int n; };
+
+__global__ __launch_bounds__(MS_ROWS) void rank_metrics_sum_kernel(const int* ranks, const int64_t* tgt,
+                                                                   const int64_t* tgt_off, const uint8_t* use, int64_t B,
+                                                                   RankCutoffs c, float* out, uint8_t* valid,
+                                                                   double* partial) {
+  __shared__ double sP[MS_ROWS / 64][MS_VALS];
+  const int64_t b = (int64_t)blockIdx.x * MS_ROWS + threadIdx.x;
+  float dcg[RK_MAX_CUTOFFS], ap_sum[RK_MAX_CUTOFFS], rr[RK_MAX_CUTOFFS];
+  int hits[RK_MAX_CUTOFFS];
+  int64_t rank_sum[RK_MAX_CUTOFFS];
+#pragma unroll
+  for (int ci = 0; ci < RK_MAX_CUTOFFS; ++ci) { dcg[ci] = ap_sum[ci] = rr[ci] = 0.f; hits[ci] = 0; rank_sum[ci] = 0; }
+  int nt = 0;
+  if (b < B) {
+    const int64_t e0 = tgt_off[b];
+    const int n = (int)(tgt_off[b + 1] - e0);
+    const int64_t* t = tgt + e0;
+    const int* rk = ranks + e0;
+    for (int i = 0; i < n; ++i) {  // distinct targets, eligible or not (target_ids = set(target_ids), metrics.py:66)
+      bool dup = false;
+      for (int j = 0; j < i; ++j) dup |= t[j] == t[i];
+      nt += dup ? 0 : 1;
+    }
+    int kmax = 0;
+#pragma unroll
+    for (int ci = 0; ci < RK_MAX_CUTOFFS; ++ci) kmax = ci < c.n ? max(kmax, c.k[ci]) : kmax;
+    int prev = 0;
+    while (nt > 0) {
+      int r = RK_NONE;
+      for (int i = 0; i < n; ++i) {
+        const int x = rk[i];
+        if (x > prev && x < r) r = x;
+      }
+      if (r == RK_NONE || r > kmax) break;
+#pragma unroll
+      for (int ci = 0; ci < RK_MAX_CUTOFFS; ++ci) {
+        if (ci < c.n && r <= c.k[ci]) {
+          ++hits[ci];
+          dcg[ci] += 1.f / log2f((float)(r - 1) + 2.f);
+          ap_sum[ci] += (float)hits[ci] / (float)r;
+          if (rr[ci] == 0.f) rr[ci] = 1.f / (float)r;
+          rank_sum[ci] += r;
+        }
+      }
+      prev = r;
+    }
+    if (valid) valid[b] = nt > 0;
+  }
+  const bool used = b < B && nt > 0 && (!use || use[b]);
+#pragma unroll
+  for (int ci = 0; ci < RK_MAX_CUTOFFS; ++ci) {
+    if (ci >= c.n) break;
+    double acc[MS_VALS];
+#pragma unroll
+    for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
+    if (b < B) {
+      float v[7];
+      for (int i = 0; i < 7; ++i) v[i] = 0.f;
+      if (nt > 0) {
+        const int K = c.k[ci], h = hits[ci];
+        const int64_t neg_seen = (int64_t)K - h;
+        // each hit outranks the non-hits behind it among the K slots: (K - r_j) - (h - 1 - j), summed over the hits
+        const int64_t pairs = (int64_t)h * K - rank_sum[ci] - (int64_t)h * (h - 1) / 2;
+        float idcg = 0.f;
+        for (int i = 0; i < (nt < K ? nt : K); ++i) idcg += 1.f / log2f((float)i + 2.f);
+        v[0] = idcg > 0.f ? dcg[ci] / idcg : 0.f;
+        v[1] = h > 0 ? ap_sum[ci] / (float)h : 0.f;
+        v[2] = (h > 0 && neg_seen > 0) ? (float)pairs / ((float)h * (float)neg_seen) : 0.f;
+        v[3] = (float)h / (float)K;
+        v[4] = (float)h / (float)nt;
+        v[5] = h > 0 ? 1.f : 0.f;
+        v[6] = rr[ci];
+      }
+      if (out) {
+        for (int i = 0; i < 7; ++i) out[(b * c.n + ci) * 7 + i] = v[i];
+      }
+      if (used) {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) acc[i] = (double)v[i];
+        acc[7] = 1.0;
+      }
+    }
+    if (ci) __syncthreads();  // (the previous cutoff's sP reads)
+    ms_block_sum(acc, sP, partial + ((int64_t)blockIdx.x * c.n + ci) * MS_VALS);
+  }
+}
+
+// workgroup ci adds cutoff ci's records in index order, as metrics_sum_final_kernel
+__global__ __launch_bounds__(MS_ROWS) void rank_metrics_final_kernel(const double* partial, int64_t n_partial, int n_cut,
+                                                                     double* sums) {
+  __shared__ double sP[MS_ROWS / 64][MS_VALS];
+  const int ci = blockIdx.x;
+  double acc[MS_VALS];
+#pragma unroll
+  for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
+  for (int64_t p = threadIdx.x; p < n_partial; p += MS_ROWS) {
+#pragma unroll
+    for (int i = 0; i < MS_VALS; ++i) acc[i] += partial[(p * n_cut + ci) * MS_VALS + i];
+  }
+  ms_block_sum(acc, sP, sums + (int64_t)ci * MS_VALS);
+}
+
 }  // namespace
 
 extern "C" {
@@ -714,6 +1097,75 @@ int xfmr_topk_tiled(const float* query, const float* table, const float* table_r
   XF_LAUNCH_CHECK();
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)n_query), dim3(256), 0, (hipStream_t)stream, a.ws_score,
                      a.ws_idx, p.splits, k, out_idx, out_score);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
+
+size_t xfmr_target_ranks_workspace(int64_t n_query, int64_t n_rows, int64_t n_targets) {
+  if (n_query <= 0 || n_rows <= 0 || n_targets < 0) return 0;
+  const TiledPlan p = tiled_plan(n_query, n_rows);
+  return ((size_t)(RK_WS_ARRAYS + p.splits) * (size_t)n_targets + (size_t)n_query) * sizeof(int);
+}
+
+int xfmr_target_ranks(const float* query, const float* table, const float* table_rnorm, const float* table_sqnorm,
+                      int64_t n_rows, int64_t n_query, int32_t H, const int64_t* exclude, const int64_t* exclude_offsets,
+                      const int64_t* targets, const int64_t* target_offsets, int64_t n_targets, int32_t metric,
+                      int32_t* out_rank, float* out_target_score, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!query || !table || !targets || !target_offsets || !out_rank || !workspace) return XFMR_EINVAL;
+  if (n_rows <= 0 || n_query <= 0 || H <= 0 || n_targets < 0) return XFMR_EINVAL;
+  if ((exclude == nullptr) != (exclude_offsets == nullptr)) return XFMR_EINVAL;
+  if (metric < XFMR_METRIC_COSINE || metric > XFMR_METRIC_L2) return XFMR_EINVAL;
+  if (metric == XFMR_METRIC_COSINE && !table_rnorm) return XFMR_EINVAL;
+  if (metric == XFMR_METRIC_L2 && !table_sqnorm) return XFMR_EINVAL;
+  if ((H & 3) || H > TOPK_MAX_H || n_rows >= (1ll << 31) || n_query >= (1ll << 31) || n_targets >= (1ll << 31))
+    return XFMR_EUNSUPPORTED;
+  if (!xf_aligned16(query) || !xf_aligned16(table) || !xf_aligned16(workspace)) return XFMR_EALIGN;
+  if (workspace_bytes < xfmr_target_ranks_workspace(n_query, n_rows, n_targets)) return XFMR_EWORKSPACE;
+  const TiledPlan p = tiled_plan(n_query, n_rows);
+  RankArgs a{};
+  a.q = query; a.table = table; a.rnorm = table_rnorm; a.sqnorm = table_sqnorm; a.n_rows = (int)n_rows;
+  a.n_query = (int)n_query; a.excl = exclude; a.excl_off = exclude_offsets; a.tgt = targets; a.tgt_off = target_offsets;
+  int* w = (int*)workspace;
+  a.tS = (float*)w; a.tI = w + n_targets; a.sS = (float*)(w + 2 * n_targets); a.sI = w + 3 * n_targets;
+  a.pos = w + 4 * n_targets; a.exb = w + 5 * n_targets; a.nlive = w + RK_WS_ARRAYS * n_targets;
+  a.hist = a.nlive + n_query;
+  a.out_rank = out_rank; a.out_tscore = out_target_score; a.n_targets = n_targets;
+  a.H = H; a.metric = metric; a.splits = p.splits; a.slice = p.slice;
+  const unsigned qtiles = (unsigned)((n_query + TT_Q - 1) / TT_Q);
+  hipLaunchKernelGGL(rank_prep_kernel, dim3((unsigned)n_query), dim3(256), 0, (hipStream_t)stream, a);
+  XF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rank_tile_kernel, dim3(qtiles, (unsigned)p.splits), dim3(256), 0, (hipStream_t)stream, a);
+  XF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)n_query), dim3(256), 0, (hipStream_t)stream, a);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
+
+size_t xfmr_rank_metrics_sum_workspace(int64_t n_query, int32_t n_cutoffs) {
+  if (n_query <= 0 || n_cutoffs <= 0) return 0;
+  return (size_t)((n_query + MS_ROWS - 1) / MS_ROWS) * (size_t)n_cutoffs * MS_VALS * sizeof(double);
+}
+
+int xfmr_rank_metrics_sum(const int32_t* ranks, const int64_t* targets, const int64_t* target_offsets, const uint8_t* use,
+                          int64_t n_query, const int32_t* cutoffs, int32_t n_cutoffs, double* sums, float* out,
+                          uint8_t* valid, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!ranks || !targets || !target_offsets || !cutoffs || !sums || !workspace || n_query <= 0) return XFMR_EINVAL;
+  if (n_cutoffs <= 0 || n_cutoffs > RK_MAX_CUTOFFS) return XFMR_EINVAL;
+  RankCutoffs c{};
+  c.n = n_cutoffs;
+  for (int i = 0; i < n_cutoffs; ++i) {
+    if (cutoffs[i] <= 0) return XFMR_EINVAL;
+    c.k[i] = cutoffs[i];
+  }
+  if (n_query >= (1ll << 31)) return XFMR_EUNSUPPORTED;
+  if (workspace_bytes < xfmr_rank_metrics_sum_workspace(n_query, n_cutoffs)) return XFMR_EWORKSPACE;
+  const int64_t n_partial = (n_query + MS_ROWS - 1) / MS_ROWS;
+  double* partial = (double*)workspace;
+  hipLaunchKernelGGL(rank_metrics_sum_kernel, dim3((unsigned)n_partial), dim3(MS_ROWS), 0, (hipStream_t)stream, ranks,
+                     targets, target_offsets, use, n_query, c, out, valid, partial);
+  XF_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rank_metrics_final_kernel, dim3((unsigned)n_cutoffs), dim3(MS_ROWS), 0, (hipStream_t)stream,
+                     (const double*)partial, n_partial, n_cutoffs, sums);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
 }

@@ -30,6 +30,8 @@ LOSS_DTOK_ZEROED = 1  # xfmr_loss_cfg.flags
 ABI_VERSION = 3
 ECOMM = -6  # XFMR_ECOMM: RCCL not loadable / an RCCL call failed (xfmr_comm_last_error has RCCL's text)
 NUM_LOSSES, NUM_STATS = 7, 16
+RANK_NONE = 0x7FFFFFFF  # XFMR_RANK_NONE: a target that is not eligible has no rank
+MAX_RANK_CUTOFFS = 8  # cutoffs per xfmr_rank_metrics_sum call
 LOSS_IDS = {
     "AlignmentLoss": 0,
     "AlignmentContrastiveLoss": 1,
@@ -188,6 +190,12 @@ _SIGNATURES = {
     "xfmr_topk_tiled_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
     "xfmr_topk_tiled": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P,
                                   _P, C.c_size_t, _P]),
+    "xfmr_target_ranks_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "xfmr_target_ranks": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32,
+                                    _P, _P, _P, C.c_size_t, _P]),
+    "xfmr_rank_metrics_sum_workspace": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "xfmr_rank_metrics_sum": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _P, _P, _P, _P,
+                                        C.c_size_t, _P]),
     "xfmr_table_sqnorm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
     "xfmr_adamw": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                              C.c_int64, C.c_float, _P]),

@@ -17,7 +17,7 @@ import torch
 
 from . import _native as N
 from . import ops
-from .retrieval import METRIC_NAMES, METRICS, retrieval_metrics_sum
+from .retrieval import METRIC_NAMES, METRICS, normalize_cutoffs, rank_metrics_sum, retrieval_metrics_sum
 
 
 @dataclasses.dataclass
@@ -117,12 +117,13 @@ class DeviceEvalSet:
     A pass makes no host -> device copy and loops over chunks, not rows. It runs in eval mode (the model's training flag is
     restored), so neither the dropout step count nor the optimizer is touched."""
 
-    def __init__(self, module, plan: EvalPlan):
+    def __init__(self, module, plan: EvalPlan, cutoffs_only: bool = False):
         model = module.model
         assert model is not None and model.embeddings is not None, "configure_model() and an item table come first"
         top_k = int(module.config.top_k)
-        if top_k > 128:
+        if top_k > 128 and not cutoffs_only:
             raise ValueError(f"top_k = {top_k}: the tiled top-k (xfmr_topk_tiled) returns at most 128 items per row")
+        self.cutoffs_only = bool(cutoffs_only)
         if plan.kept.size == 0:
             raise ValueError("no validation row has both a non-empty history and a positive target")
         self.module, self.plan, self.top_k = module, plan, top_k
@@ -152,18 +153,20 @@ class DeviceEvalSet:
         torch.cuda.synchronize(dev)  # (the uploads came from pageable numpy memory)
 
     @classmethod
-    def from_rows(cls, module, rows, batch_size: int = 1024) -> "DeviceEvalSet":
+    def from_rows(cls, module, rows, batch_size: int = 1024, cutoffs_only: bool = False) -> "DeviceEvalSet":
         """``rows`` in the reference's format: ``{"history": {"item_id"}, "target": {"item_id", "label"}}``. Ids go through
-        the module's own ``_to_idx`` (unknown ids are dropped), exactly as ``module.evaluate(rows)`` maps them."""
+        the module's own ``_to_idx`` (unknown ids are dropped), exactly as ``module.evaluate(rows)`` maps them.
+        ``cutoffs_only=True``: a set that is only ever evaluated with ``cutoffs`` (the rank path, which has no top_k
+        limit); ``recommend`` and ``evaluate()`` without cutoffs then refuse a ``top_k`` above 128."""
         if module.model is None:
             module.configure_model()
-        if int(module.config.top_k) > 128:
+        if int(module.config.top_k) > 128 and not cutoffs_only:
             raise ValueError(f"top_k = {module.config.top_k}: the tiled top-k (xfmr_topk_tiled) returns at most 128 items per row")
         hists, tgts = [], []
         for r in rows:
             hists.append(module._to_idx_or_empty(list(r["history"]["item_id"])))
             tgts.append(module._to_idx_or_empty([i for i, l in zip(r["target"]["item_id"], r["target"]["label"]) if l]))
-        return cls(module, plan_eval_rows(hists, tgts, module.model.max_seq_length, batch_size))
+        return cls(module, plan_eval_rows(hists, tgts, module.model.max_seq_length, batch_size), cutoffs_only=cutoffs_only)
 
     def __len__(self) -> int:
         return int(self.kept.size)
@@ -193,6 +196,9 @@ class DeviceEvalSet:
     def recommend(self, embedding: torch.Tensor | None = None):
         """``(item_idx (n_kept, k) int64, -1 padded; score (n_kept, k))``: xfmr_topk_tiled per chunk over the module's
         ``items_index`` (its metric, table and norms), each row's whole history excluded."""
+        if self.top_k > 128:
+            raise ValueError(f"top_k = {self.top_k}: the tiled top-k (xfmr_topk_tiled) returns at most 128 items per row; "
+                             "this set was built with cutoffs_only=True: evaluate it with cutoffs")
         emb = self.encode() if embedding is None else embedding
         index = self.module.items_index
         k, n_rows, H = self.top_k, index.table.shape[0], emb.shape[1]
@@ -220,9 +226,52 @@ class DeviceEvalSet:
         idx, _ = self.recommend()
         return retrieval_metrics_sum(idx, (self.targets, self.target_offsets), None, top_k=self.top_k)
 
-    def evaluate(self, stage: str = "val") -> dict[str, float]:
+    @torch.no_grad()
+    def target_ranks(self, embedding: torch.Tensor | None = None) -> torch.Tensor:
+        """The exact rank of every target of every kept row among the row's eligible items (int32, parallel to
+        ``self.targets``; ``_native.RANK_NONE`` where a target is in the row's history): one encode, then
+        ``ExactItemIndex.rank_targets`` per chunk into one resident tensor. No limit on ``top_k``."""
+        emb = self.encode() if embedding is None else embedding
+        index = self.module.items_index
+        ranks = torch.empty((self.targets.numel(),), dtype=torch.int32, device=self.device)
+        toff = self.plan.target_offsets
+        for c in self._chunks:
+            r0, r1 = c["rows"]
+            index.rank_targets(emb[r0:r1], (self.targets, self.target_offsets[r0 : r1 + 1]),
+                               (self.excl, c["excl_offsets"]), n_targets=int(toff[r1] - toff[r0]), out=ranks)
+        return ranks
+
+    def _cutoffs(self, cutoffs) -> tuple[int, ...]:
+        cut = normalize_cutoffs(cutoffs)
+        return cut if self.top_k in cut else cut + (self.top_k,)
+
+    @torch.no_grad()
+    def evaluate_ranks_device(self, cutoffs) -> torch.Tensor:
+        """One rank pass and one ``rank_metrics_sum``: ``(len(cutoffs), 8)`` doubles on the device, no host sync. The
+        cutoffs are taken as given (``config.top_k`` is not added here)."""
+        return rank_metrics_sum(self.target_ranks(), (self.targets, self.target_offsets), normalize_cutoffs(cutoffs))
+
+    def evaluate(self, stage: str = "val", cutoffs=None) -> dict[str, float]:
         """The keys of ``RecommenderLightningModule.evaluate``: ``{stage}/<metric>`` means and ``{stage}/num_rows``. One
-        read-back of 64 bytes."""
+        read-back of 64 bytes.
+
+        ``cutoffs`` (e.g. ``(5, 10, 20, 500)``): the rank path instead of the ranked list -- one pass over the catalogue
+        gives every target's exact rank, one launch pair the metrics at every cutoff, one read-back of 64 bytes per
+        cutoff. Adds ``{stage}/<metric>@<K>`` for every cutoff; the plain keys are those of cutoff ``config.top_k``
+        (added to the cutoffs when missing), equal to what the call without cutoffs returns."""
+        if cutoffs is not None:
+            cut = self._cutoffs(cutoffs)
+            sums = self.evaluate_ranks_device(cut).tolist()
+            out = {}
+            for K, s in zip(cut, sums):
+                n = int(s[7])
+                for i, name in enumerate(METRIC_NAMES):
+                    out[f"{stage}/{name}@{K}"] = s[i] / n if n else float("nan")
+                if K == self.top_k:
+                    for i, name in enumerate(METRIC_NAMES):
+                        out[f"{stage}/{name}"] = out[f"{stage}/{name}@{K}"]
+                    out[f"{stage}/num_rows"] = n
+            return out
         s = self.evaluate_device().tolist()
         n = int(s[7])
         out = {f"{stage}/{name}": (s[i] / n if n else float("nan")) for i, name in enumerate(METRIC_NAMES)}

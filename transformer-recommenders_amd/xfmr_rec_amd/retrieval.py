@@ -9,6 +9,8 @@ same search for a whole user set (xfmr_topk_tiled: no per-(user, item) workspace
 
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -107,6 +109,116 @@ class ExactItemIndex:
             "xfmr_topk_tiled",
         )
         return idx, score
+
+    def rank_targets(self, embedding: torch.Tensor, targets_csr, exclude_csr=None, *, n_targets: int | None = None,
+                     out: torch.Tensor | None = None, return_scores: bool = False):
+        """The exact rank of every target among all eligible items (xfmr_target_ranks): no ranked list, no cutoff limit.
+
+        ``targets_csr``: ``(flat, offsets)`` int64 DEVICE tensors, offsets with B + 1 entries (a view into a longer
+        offsets array with absolute values is fine); ``exclude_csr``: the same form, each row SORTED ascending
+        (:func:`sorted_exclusion_csr`), or None. Returns int32 ranks parallel to ``flat``: 1 = best; ``_native.RANK_NONE``
+        for a target that is excluded, out of [1, n_items) or has a non-finite score. ``n_targets``: an upper bound on the
+        entries the offsets cover (default: all of ``flat``; sizes the workspace); ``out``: an int32 tensor parallel to
+        ``flat`` to write into (entries outside the offsets are left alone). ``return_scores=True`` also returns the
+        targets' scores (float32, -inf where there is no rank): the bits :meth:`search_batch` reports for the item."""
+        q = embedding.reshape(-1, embedding.shape[-1]).contiguous().to(torch.float32)
+        B, H = q.shape
+        dev = q.device
+        tg, tgo = targets_csr
+        if tgo.numel() != B + 1:
+            raise ValueError(f"targets_csr offsets have {tgo.numel()} entries for {B} queries")
+        if tg.dtype != torch.int64 or tgo.dtype != torch.int64:
+            raise ValueError("targets_csr must be int64 tensors")
+        ex = exo = None
+        if exclude_csr is not None:
+            ex, exo = exclude_csr
+            if exo.numel() != B + 1:
+                raise ValueError(f"exclude_csr offsets have {exo.numel()} entries for {B} queries")
+            if ex.dtype != torch.int64 or exo.dtype != torch.int64:
+                raise ValueError("exclude_csr must be int64 tensors")
+        if out is None:
+            out = torch.full((tg.numel(),), N.RANK_NONE, dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or out.numel() != tg.numel():
+            raise ValueError(f"out must be int32 with {tg.numel()} entries")
+        score = torch.full((tg.numel(),), float("-inf"), dtype=torch.float32, device=dev) if return_scores else None
+        if B == 0:
+            return (out, score) if return_scores else out
+        nt = int(tg.numel() if n_targets is None else n_targets)
+        n_rows = self.table.shape[0]
+        rnorm = self.rnorm if self.metric == METRICS["cosine"] else None
+        sqnorm = self.sqnorm if self.metric == METRICS["l2"] else None
+        lib = N.load()
+        nbytes = lib.xfmr_target_ranks_workspace(B, n_rows, nt)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        N.check(
+            lib.xfmr_target_ranks(N.ptr(q), N.ptr(self.table), N.ptr(rnorm), N.ptr(sqnorm), n_rows, B, H, N.ptr(ex),
+                                  N.ptr(exo), N.ptr(tg), N.ptr(tgo), nt, self.metric, N.ptr(out), N.ptr(score), N.ptr(ws),
+                                  nbytes, N.stream()),
+            "xfmr_target_ranks",
+        )
+        return (out, score) if return_scores else out
+
+
+def normalize_cutoffs(cutoffs) -> tuple[int, ...]:
+    """The cutoffs as given, repeats dropped, each a positive int below 2^31 (ValueError otherwise)."""
+    if isinstance(cutoffs, (int, np.integer)) and not isinstance(cutoffs, bool):
+        cutoffs = (cutoffs,)
+    out = []
+    for k in cutoffs:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 < int(k) < 2**31:
+            raise ValueError(f"cutoffs must be positive integers below 2^31; got {k!r}")
+        if int(k) not in out:
+            out.append(int(k))
+    if not out:
+        raise ValueError("cutoffs is empty")
+    return tuple(out)
+
+
+def rank_metrics_sum(ranks: torch.Tensor, targets_csr, cutoffs, use: torch.Tensor | None = None, per_row: bool = False):
+    """The seven metrics at every cutoff from the ranks of :meth:`ExactItemIndex.rank_targets`
+    (xfmr_rank_metrics_sum), nothing read back: a device tensor ``(len(cutoffs), 8)`` of doubles -- per cutoff the sums of
+    the METRIC_NAMES values over the rows that have a target and are used, and their number. ``ranks`` parallels the
+    flat targets; ``targets_csr`` and ``use`` as :func:`retrieval_metrics_sum`; ``cutoffs``: positive ints in any order
+    (also above the catalogue size); more than 8 take one call per 8. ``per_row=True`` returns ``(sums, values (B,
+    len(cutoffs), 7), valid (B,) bool)``; for a cutoff K <= 128 the values are the bits of :func:`retrieval_metrics_sum`
+    on :meth:`ExactItemIndex.search_batch`'s list of K."""
+    cut = [int(k) for k in cutoffs]
+    if not cut or any(k <= 0 or k >= 2**31 for k in cut):
+        raise ValueError(f"cutoffs must be positive integers below 2^31; got {cutoffs!r}")
+    tg, tgo = targets_csr
+    B = tgo.numel() - 1
+    dev = ranks.device
+    if ranks.dtype != torch.int32 or ranks.numel() != tg.numel():
+        raise ValueError(f"ranks must be int32 with one entry per target ({tg.numel()}); got {ranks.dtype}, {ranks.numel()}")
+    if B < 1:
+        raise ValueError("targets_csr has no row")
+    if use is not None:
+        if use.numel() != B:
+            raise ValueError(f"use has {use.numel()} entries for {B} rows")
+        use = use.view(torch.uint8) if use.dtype == torch.bool else use
+        if use.dtype != torch.uint8:
+            raise ValueError(f"use must be uint8 or bool, got {use.dtype}")
+    nc = len(cut)
+    sums = torch.empty((nc, 8), dtype=torch.float64, device=dev)
+    vals = torch.empty((B, nc, len(METRIC_NAMES)), dtype=torch.float32, device=dev) if per_row else None
+    valid = torch.empty((B,), dtype=torch.uint8, device=dev) if per_row else None
+    lib = N.load()
+    for c0 in range(0, nc, N.MAX_RANK_CUTOFFS):
+        part = cut[c0 : c0 + N.MAX_RANK_CUTOFFS]
+        whole = len(part) == nc
+        part_vals = vals if whole or not per_row else torch.empty((B, len(part), len(METRIC_NAMES)), dtype=torch.float32,
+                                                                  device=dev)
+        nbytes = lib.xfmr_rank_metrics_sum_workspace(B, len(part))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        N.check(
+            lib.xfmr_rank_metrics_sum(N.ptr(ranks.contiguous()), N.ptr(tg), N.ptr(tgo), N.ptr(use), B,
+                                      (C.c_int32 * len(part))(*part), len(part), N.ptr(sums[c0 : c0 + len(part)]),
+                                      N.ptr(part_vals), N.ptr(valid), N.ptr(ws), nbytes, N.stream()),
+            "xfmr_rank_metrics_sum",
+        )
+        if per_row and not whole:
+            vals[:, c0 : c0 + len(part)] = part_vals
+    return (sums, vals, valid.bool()) if per_row else sums
 
 
 def retrieval_metrics(rec_idx: torch.Tensor, target_idx, top_k: int):

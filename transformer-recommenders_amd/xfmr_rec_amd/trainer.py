@@ -457,17 +457,24 @@ class RecommenderLightningModule(_Base):
         return self.recommend_batch(hists, top_k=self.config.top_k, exclude_item_ids=hists)
 
     @torch.no_grad()
-    def evaluate(self, rows, stage: str = "val", batch_size: int = 1024) -> dict[str, float]:
+    def evaluate(self, rows, stage: str = "val", batch_size: int = 1024, cutoffs=None) -> dict[str, float]:
         """The epoch means of the seven retrieval metrics over ``rows`` (the reference's format: ``{"history":
         {"item_id"}, "target": {"item_id", "label"}}``), batch_size rows per pass. Each mean is over the rows with at
         least one positive target and a non-empty history -- what Lightning logs from ``validation_step(...,
         batch_size=1)``, where a row without a target logs nothing (metrics.py:58-59) -- and
-        ``{stage}/num_rows`` is their number."""
+        ``{stage}/num_rows`` is their number.
+
+        ``cutoffs`` (e.g. ``(5, 10, 20, 500)``): the rank path -- per pass ``encode_batch``, every target's exact rank
+        over the whole catalogue (``ExactItemIndex.rank_targets``) and the metrics at every cutoff from the ranks. Adds
+        ``{stage}/<metric>@<K>`` per cutoff; the plain keys are those of cutoff ``config.top_k`` (added when missing), which
+        may then exceed 128."""
         import numpy as np
 
         from .retrieval import METRIC_NAMES, retrieval_metrics
 
         rows = list(rows)
+        if cutoffs is not None:
+            return self._evaluate_ranks(rows, stage, max(1, int(batch_size)), cutoffs)
         total = np.zeros(len(METRIC_NAMES), dtype=np.float64)
         n = 0
         for b0 in range(0, len(rows), max(1, int(batch_size))):
@@ -483,6 +490,43 @@ class RecommenderLightningModule(_Base):
             n += int(use.sum())
         out = {f"{stage}/{name}": (float(total[i] / n) if n else float("nan")) for i, name in enumerate(METRIC_NAMES)}
         out[f"{stage}/num_rows"] = n
+        return out
+
+    def _evaluate_ranks(self, rows, stage: str, batch_size: int, cutoffs) -> dict[str, float]:
+        import numpy as np
+
+        from .retrieval import METRIC_NAMES, normalize_cutoffs, rank_metrics_sum, sorted_exclusion_csr
+
+        cut = normalize_cutoffs(cutoffs)
+        top_k = int(self.config.top_k)
+        if top_k not in cut:
+            cut += (top_k,)
+        dev = self.model.device
+        total = np.zeros((len(cut), 8), dtype=np.float64)
+        for b0 in range(0, len(rows), batch_size):
+            chunk = rows[b0 : b0 + batch_size]
+            hists = [self._to_idx_or_empty(list(r["history"]["item_id"])) for r in chunk]
+            tgts = [self._to_idx_or_empty([i for i, l in zip(r["target"]["item_id"], r["target"]["label"]) if l])
+                    for r in chunk]
+            emb = self.model.encode_batch(hists)
+            ex, exo = sorted_exclusion_csr(hists)
+            tg = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in tgts] + [np.zeros(1, dtype=np.int64)])
+            tgo = np.zeros(len(tgts) + 1, dtype=np.int64)
+            np.cumsum([len(t) for t in tgts], out=tgo[1:])
+            csr = (torch.from_numpy(tg).to(dev), torch.from_numpy(tgo).to(dev))
+            ranks = self.items_index.rank_targets(emb, csr, (torch.from_numpy(ex).to(dev), torch.from_numpy(exo).to(dev)),
+                                                  n_targets=int(tgo[-1]))
+            use = torch.from_numpy(np.asarray([bool(h) for h in hists], dtype=np.uint8)).to(dev)
+            total += rank_metrics_sum(ranks, csr, cut, use).cpu().numpy()
+        out = {}
+        for K, s in zip(cut, total):
+            n = int(s[7])
+            for i, name in enumerate(METRIC_NAMES):
+                out[f"{stage}/{name}@{K}"] = float(s[i] / n) if n else float("nan")
+            if K == top_k:
+                for i, name in enumerate(METRIC_NAMES):
+                    out[f"{stage}/{name}"] = out[f"{stage}/{name}@{K}"]
+                out[f"{stage}/num_rows"] = n
         return out
 
     def compute_metrics(self, row, stage: str = "val") -> dict[str, torch.Tensor]:
@@ -879,17 +923,18 @@ class Trainer:
             raise ValueError("validation inside a data-parallel run (world_size > 1) is not supported: a sharded validation "
                              "set has never run on more than one GPU")
 
-    def validate(self, val, stage: str = "val") -> dict:
+    def validate(self, val, stage: str = "val", cutoffs=None) -> dict:
         """One validation pass over ``val`` (a :class:`~xfmr_rec_amd.evalset.DeviceEvalSet`) outside ``fit``: the dict of
-        ``DeviceEvalSet.evaluate``, also handed to ``module.log_dict``."""
+        ``DeviceEvalSet.evaluate``, also handed to ``module.log_dict``. ``cutoffs``: the rank path, with the
+        ``<metric>@<K>`` keys (``DeviceEvalSet.evaluate(stage, cutoffs=...)``)."""
         self._check_val(val)
-        metrics = val.evaluate(stage)
+        metrics = val.evaluate(stage) if cutoffs is None else val.evaluate(stage, cutoffs=cutoffs)
         self.module.log_dict(metrics)
         return metrics
 
     def fit(self, batches, max_steps: int | None = None, *, ring_slots: int = 6, graph: str = "off",
             graph_probe_steps: int = 20, val=None, val_check_interval: int | None = None, monitor: dict = METRIC,
-            early_stopping=None, checkpoint_dir=None) -> list[float]:
+            early_stopping=None, checkpoint_dir=None, val_cutoffs=None) -> list[float]:
         """Steps over an iterable of collated batches. Batches that arrive in HOST memory (the reference's DataLoader
         output, ``data.py:915-927``) are handed over through a :class:`~xfmr_rec_amd.data.PinnedBatchRing`: the copy of
         batch i + 1 runs underneath step i; device-resident batches (``DeviceSeqDataset.sample_batch``) are used as they are.
@@ -912,7 +957,12 @@ class Trainer:
         ``checkpoint_dir / "best"`` with ``module.save`` (``ModelCheckpoint(save_top_k=1)``; ``RecommenderModel.load`` reads
         it). Afterwards: ``val_history`` (``{"step": batches done, **metrics}`` per pass), ``best_score``, ``best_step``,
         ``best_model_path``, ``stopped_early`` and ``val_elapsed`` (seconds in validation passes: a host clock from a
-        stream sync in front of the pass to its read-back)."""
+        stream sync in front of the pass to its read-back).
+
+        ``val_cutoffs`` (e.g. ``(5, 10, 20, 500)``): every pass takes the rank path (``DeviceEvalSet.evaluate(stage,
+        cutoffs=val_cutoffs)``): the metrics at every cutoff under ``<stage>/<metric>@<K>`` next to the plain keys (those
+        of ``config.top_k``), all of them in ``val_history``. ``monitor["name"]`` may then be ``'<stage>/<metric>@<K>'`` for
+        a K among ``val_cutoffs``."""
         from .data import SEQ_BATCH_KEYS, PinnedBatchRing
 
         self._check_val(val)
@@ -927,11 +977,18 @@ class Trainer:
         stage, _, metric_name = str(monitor["name"]).rpartition("/")
         tracker = EarlyStopping(monitor["mode"], patience=None)  # the best value: strict improvements (ModelCheckpoint)
         stopper = _early_stopping_from(early_stopping, monitor["mode"])
+        if val_cutoffs is not None:
+            from .retrieval import normalize_cutoffs
+
+            val_cutoffs = normalize_cutoffs(val_cutoffs)
         if val is not None:
             from .retrieval import METRIC_NAMES
 
+            metric_name, at, at_k = metric_name.partition("@")
             if not stage or metric_name not in METRIC_NAMES:
                 raise ValueError(f"monitor name {monitor['name']!r}: expected '<stage>/<metric>' with a metric of {METRIC_NAMES}")
+            if at and (val_cutoffs is None or not at_k.isdecimal() or str(int(at_k)) != at_k or int(at_k) not in val_cutoffs):
+                raise ValueError(f"monitor name {monitor['name']!r}: '@<K>' needs K among val_cutoffs = {val_cutoffs!r}")
         self.val_history: list[dict] = []
         self.best_score = self.best_step = self.best_model_path = None
         self.stopped_early = False
@@ -970,7 +1027,7 @@ class Trainer:
             dev_ = self.module.model.device
             torch.cuda.current_stream(dev_).synchronize()  # the steps enqueued so far are not validation time
             tv = time.perf_counter()
-            metrics = val.evaluate(stage)
+            metrics = val.evaluate(stage) if val_cutoffs is None else val.evaluate(stage, cutoffs=val_cutoffs)
             self.val_elapsed += time.perf_counter() - tv
             self.module.log_dict(metrics)
             self.val_history.append({"step": batches_done, **metrics})
