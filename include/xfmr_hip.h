@@ -522,6 +522,25 @@ int xfmr_seq_sample(const int64_t* items, const uint8_t* labels, const int64_t* 
                     int32_t batch, int32_t width, int32_t max_seq_length, int32_t pos_lookahead, int64_t n_items,
                     int32_t max_history, uint64_t seed, int64_t* hist_out, int64_t* pos_out, int64_t* neg_out,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* The sampler of the epoch loop (xfmr_rec_amd/data.py: DeviceSeqLoader). Per-row semantics as xfmr_seq_sample; batch row
+ * b samples dataset row order[first + b] of a device-resident epoch order (n_order entries, each in [0, n_rows)), so a
+ * batch costs no upload. A batch row with first + b >= n_order -- or whose row index or history length (> max_history)
+ * is out of range -- is written as zeros with length 0 and reads nothing. len_out (batch, int32): the number of
+ * sampled positions of each row, min(n - 1, max_seq_length, width).
+ * Random stream: a function of (seed, epoch, dataset row, purpose, counter) alone -- a row samples the same values
+ * in every batch, slot and launch geometry; not the stream of xfmr_seq_sample.
+ * Negatives are drawn by the whole workgroup against a sorted copy of the row's distinct items in LDS: a draw is a
+ * uniform rank among the admissible items, mapped to the item by one binary search; duplicates between slots are
+ * resolved by slot index and round (deterministic), and after a fixed number of rounds, or at once when fewer than four
+ * admissible items per draw exist, by the exact selection the positions use. The workspace does not depend on
+ * n_items (nothing catalogue-sized exists; today it is 0 bytes and `workspace` may be NULL).
+ * Dynamic LDS: (2 max_history + 2 width + 9) words, <= 160 KB (XFMR_EUNSUPPORTED beyond; width <= 8192). */
+size_t xfmr_seq_sample_rows_workspace(int32_t batch, int32_t width);
+int xfmr_seq_sample_rows(const int64_t* items, const uint8_t* labels, const int64_t* offsets, int64_t n_rows,
+                         const int64_t* order, int64_t n_order, int64_t first, int32_t batch, int32_t width,
+                         int32_t max_seq_length, int32_t pos_lookahead, int64_t n_items, int32_t max_history,
+                         uint64_t seed, uint64_t epoch, int64_t* hist_out, int64_t* pos_out, int64_t* neg_out,
+                         int32_t* len_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Exact top-k retrieval and ranking metrics for validation: replaces the LanceDB

@@ -239,3 +239,319 @@ int xfmr_seq_sample(const int64_t* items, const uint8_t* labels, const int64_t* 
 }
 
 }  // extern "C"
+
+// ================================================================================================================
+// xfmr_seq_sample_rows: the sampler of the epoch loop (xfmr_rec_amd/data.py: DeviceSeqLoader). Same per-row semantics as
+// above; what differs:
+//   rows       batch row b samples dataset row order[first + b] of a device-resident epoch order: no per-batch upload.
+//              A batch row past n_order (or a row index / history length outside the dataset's limits) is written as
+//              zeros with length 0 and reads nothing.
+//   stream     a function of (seed, epoch, dataset row, purpose, counter) alone: a row samples the same values in every
+//              batch, slot and launch geometry.
+//   negatives  drawn by the whole workgroup, no catalogue-sized memory anywhere. The row's distinct items are sorted in
+//              LDS (bitonic, over the prefix-count / positive-list region once the positives are written). With D
+//              distinct items hs[0..D) the j-th admissible item (0-based, A = n_items - D of them) is
+//              j + 1 + #{i : hs[i] - 1 - i <= j} -- one binary search -- so a draw is a uniform RANK in [0, A) and never
+//              lands in the history. Regimes of data.py:743-747: A == 0 -> ranks over the whole catalogue (D := 0);
+//              fewer admissible items than draws -> every slot draws its own rank (with replacement); otherwise no
+//              duplicates: while A >= 4 cnt, rounds in which every open slot draws a rank and keeps it unless a filled
+//              slot, or an open slot of LOWER index, holds the same rank (a rule on slot and round: deterministic, and
+//              symmetric in the items, hence uniform over ordered draws without replacement; an open slot closes with
+//              probability > 3/4 per round). If A < 4 cnt, or a slot is still open after REJECT_ROUNDS rounds, the exact path
+//              runs instead: the cnt smallest hashed keys among ranks 0..A-1 (the positions' selection), in key order.
+//   outputs    len_out[b] = number of sampled positions of row b.
+namespace {
+
+constexpr int REJECT_ROUNDS = 32;
+constexpr size_t ROWS_MAX_LDS = 160 * 1024;
+
+struct RowsArgs {
+  const int64_t* items; const uint8_t* labels; const int64_t* offsets; const int64_t* order;
+  int64_t n_rows, n_order, first;
+  int64_t* hist_out; int64_t* pos_out; int64_t* neg_out; int32_t* len_out;
+  int B, width, max_len, lookahead, max_hist;
+  int64_t n_items;
+  uint64_t seed, epoch;
+};
+
+struct RowKey { uint32_t k0, k1; };
+
+__device__ __forceinline__ RowKey row_key(uint64_t seed, uint64_t epoch, int64_t row) {
+  uint32_t a = xf_hash32((uint32_t)seed ^ xf_hash32((uint32_t)(seed >> 32) + 0x9e3779b9u));
+  a = xf_hash32(a ^ (uint32_t)epoch * 0x85ebca6bu);
+  a = xf_hash32(a + (uint32_t)(epoch >> 32) * 0xc2b2ae35u);
+  uint32_t b = xf_hash32(a ^ 0x27d4eb2fu);
+  a = xf_hash32(a ^ (uint32_t)row);
+  b = xf_hash32(b + (uint32_t)((uint64_t)row >> 32) * 0x165667b1u + ((uint32_t)row * 0x9e3779b9u));
+  return RowKey{a, b};
+}
+__device__ __forceinline__ uint32_t rnd_row(RowKey k, uint32_t purpose, uint32_t ctr) {
+  const uint32_t x = xf_hash32(k.k0 ^ (purpose * 0xc2b2ae35u) ^ ctr);
+  return xf_hash32((x ^ k.k1) + 0x27d4eb2fu * ctr);
+}
+
+// exclusive count of `p` over the threads in front of this one, and the workgroup's total (uniform)
+__device__ __forceinline__ int block_excl(bool p, int* wcnt, int& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(p);
+  if (lane == 0) wcnt[w] = __popcll(bal);
+  __syncthreads();
+  int before = 0;
+  for (int k = 0; k < w; ++k) before += wcnt[k];
+  before += __popcll(bal & (lane == 0 ? 0ull : (~0ull >> (64 - lane))));
+  total = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+  __syncthreads();
+  return before;
+}
+
+// The `want` smallest keys rnd_row(key, purpose, i) among i in [0, m), ties by index: their indices, ascending, into
+// out[0..min(m, want)). Returns that count (uniform). out is LDS; a barrier stands behind the last write.
+__device__ int select_smallest(RowKey key, uint32_t purpose, int m, int want, int* out, int* red, int* wcnt) {
+  const int tid = threadIdx.x;
+  uint32_t T = 0xffffffffu;
+  int need_eq = 0;
+  if (m > want) {
+    uint32_t t = 0;  // smallest T with count(key <= T) >= want, bit by bit from the top
+    for (int bit = 31; bit >= 0; --bit) {
+      const uint32_t cand = t | ((1u << bit) - 1u);
+      int c = 0;
+      for (int i = tid; i < m; i += 256) c += rnd_row(key, purpose, (uint32_t)i) <= cand ? 1 : 0;
+      if (block_sum_i(c, red) < want) t |= 1u << bit;
+    }
+    T = t;
+    int lt = 0;
+    for (int i = tid; i < m; i += 256) lt += rnd_row(key, purpose, (uint32_t)i) < T ? 1 : 0;
+    need_eq = want - block_sum_i(lt, red);  // how many of the keys == T are taken (lowest indices first)
+  }
+  int n_sel = 0, n_eq = 0;
+  for (int i0 = 0; i0 < m && n_sel < want; i0 += 256) {
+    const int i = i0 + tid;
+    bool lt = false, eq = false;
+    if (i < m) {
+      if (m <= want) lt = true;
+      else {
+        const uint32_t k = rnd_row(key, purpose, (uint32_t)i);
+        lt = k < T;
+        eq = k == T;
+      }
+    }
+    int tot_eq, tot;
+    const int eq_before = n_eq + block_excl(eq, wcnt, tot_eq);
+    const bool take = lt || (eq && eq_before < need_eq);
+    const int at = n_sel + block_excl(take, wcnt, tot);
+    if (take && at < want) out[at] = i;
+    n_sel += tot;
+    n_eq += tot_eq;
+  }
+  __syncthreads();
+  return n_sel < want ? n_sel : want;
+}
+
+// rank (0-based) among the items of 1..n_items that are not in hs[0..D) -> the item
+__device__ __forceinline__ int64_t admissible_item(const uint32_t* hs, int D, uint32_t j) {
+  int lo = 0, hi = D;  // first i with hs[i] - 1 - i > j
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (hs[mid] - 1u - (uint32_t)mid <= j) lo = mid + 1; else hi = mid;
+  }
+  return (int64_t)j + 1 + lo;
+}
+
+__global__ __launch_bounds__(256) void seq_sample_rows_kernel(RowsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int smem[];
+  __shared__ int red[4], wcnt[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int64_t* ho = a.hist_out + (int64_t)b * a.width;
+  int64_t* po = a.pos_out + (int64_t)b * a.width;
+  int64_t* no = a.neg_out + (int64_t)b * a.width;
+  int64_t row = -1, o0 = 0;
+  int n = 0;
+  if (a.first + b < a.n_order) {
+    row = a.order[a.first + b];
+    if (row >= 0 && row < a.n_rows) {
+      o0 = a.offsets[row];
+      const int64_t len = a.offsets[row + 1] - o0;
+      n = len >= 1 && len <= a.max_hist ? (int)len : 0;
+    }
+  }
+  if (n == 0) {  // (uniform over the workgroup)
+    for (int k = tid; k < a.width; k += 256) { ho[k] = 0; po[k] = 0; no[k] = 0; }
+    if (tid == 0) a.len_out[b] = 0;
+    return;
+  }
+  const int64_t* h = a.items + o0;
+  const uint8_t* lab = a.labels + o0;
+  const RowKey key = row_key(a.seed, a.epoch, row);
+  int* P = smem;                                 // [n + 1] prefix count of positive labels
+  int* posidx = P + (n + 1);                     // [n] positions with a positive label, ascending
+  int* sel = smem + 2 * a.max_hist + 1;          // [width] sampled positions; later the negatives' ranks
+  uint32_t* nkey = (uint32_t*)(sel + a.width);   // [width] exact path: the selected ranks' keys
+  const int m = n - 1;  // candidate positions 0..m-1 (the last item only ever serves as a positive)
+  const int L = a.max_len < a.width ? a.max_len : a.width;
+
+  // ---- positions: data.py:669-688 ---------------------------------------------------------------------------------
+  const int cnt = select_smallest(key, 1u, m, L, sel, red, wcnt);  // = min(n - 1, L)
+
+  // ---- prefix count of positive labels + list of positive positions ----------------------------------------------
+  int n_pos = 0;
+  for (int i0 = 0; i0 < n; i0 += 256) {
+    const int i = i0 + tid;
+    const bool p = i < n && lab[i] != 0;
+    int tot;
+    const int before = n_pos + block_excl(p, wcnt, tot);
+    if (i < n) {
+      P[i] = before;
+      if (p) posidx[before] = i;
+    }
+    n_pos += tot;
+  }
+  if (tid == 0) P[n] = n_pos;
+  __syncthreads();
+
+  // ---- history + positives, right-padded: data.py:690-722 ---------------------------------------------------------
+  for (int k = tid; k < a.width; k += 256) {
+    int64_t hv = 0, pv = 0;
+    if (k < cnt) {
+      const int p = sel[k];
+      hv = h[p];
+      const int start = p + 1;
+      const int end = a.lookahead > 0 ? (start + a.lookahead < n ? start + a.lookahead : n) : n;
+      const int c = P[end] - P[start];
+      if (c > 0) pv = h[posidx[P[start] + (int)below(rnd_row(key, 2u, (uint32_t)k), (uint32_t)c)]];
+    }
+    ho[k] = hv;
+    po[k] = pv;
+  }
+  if (tid == 0) a.len_out[b] = cnt;
+  __syncthreads();  // P, posidx and sel are free from here on
+
+  // ---- the row's distinct items, sorted, over P / posidx ------------------------------------------------------------
+  uint32_t* hs = (uint32_t*)smem;
+  int N = 1;
+  while (N < n) N <<= 1;  // <= 2 n - 1 <= 2 max_hist words
+  for (int i = tid; i < N; i += 256) {
+    const int64_t v = i < n ? h[i] : 0;
+    hs[i] = v >= 1 && v <= a.n_items ? (uint32_t)v : 0xffffffffu;
+  }
+  __syncthreads();
+  for (int k = 2; k <= N; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (N >> 1); t += 256) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const uint32_t x = hs[i], y = hs[i | j];
+        if ((x > y) == ((i & k) == 0)) { hs[i] = y; hs[i | j] = x; }
+      }
+      __syncthreads();
+    }
+  // in-place order-preserving removal of duplicates and of the filler (a chunk writes at or below what it has read)
+  int D = 0;
+  for (int i0 = 0; i0 < N; i0 += 256) {
+    const int i = i0 + tid;
+    const uint32_t v = i < N ? hs[i] : 0xffffffffu;
+    const bool first = v != 0xffffffffu && (i == 0 || hs[i - 1] != v);
+    int tot;
+    const int at = D + block_excl(first, wcnt, tot);  // (its barriers stand between the reads above and the writes below)
+    if (first) hs[at] = v;
+    D += tot;
+    __syncthreads();
+  }
+
+  // ---- negatives: data.py:724-747 -----------------------------------------------------------------------------------
+  const bool any_item = a.n_items - D == 0;  // nothing left -> the whole catalogue
+  if (any_item) D = 0;
+  const uint32_t A = (uint32_t)(a.n_items - D);  // admissible items: ranks 0..A-1
+  uint32_t* val = (uint32_t*)sel;                // [cnt] a slot's rank; bit 31: the slot is filled
+  constexpr uint32_t FILLED = 0x80000000u;
+  bool exact = false;
+  if (A < (uint32_t)cnt) {  // with replacement
+    for (int k = tid; k < cnt; k += 256) val[k] = below(rnd_row(key, 3u, (uint32_t)k), A);
+  } else if ((uint64_t)A < 4ull * (uint64_t)cnt) {
+    exact = true;
+  } else {
+    for (int k = tid; k < cnt; k += 256) val[k] = 0;
+    int open = cnt;
+    for (int r = 0; r < REJECT_ROUNDS && open > 0; ++r) {
+      __syncthreads();
+      for (int k = tid; k < cnt; k += 256)
+        if (!(val[k] & FILLED)) val[k] = below(rnd_row(key, 16u + (uint32_t)r, (uint32_t)k), A);
+      __syncthreads();
+      uint32_t keep = 0;  // bit s: this thread's s-th slot closes this round (cnt <= width <= 256 * 32)
+      int still = 0, s = 0;
+      for (int k = tid; k < cnt; k += 256, ++s) {
+        const uint32_t x = val[k];
+        if (x & FILLED) continue;
+        bool ok = true;
+        for (int q = 0; q < cnt; ++q) {
+          const uint32_t y = val[q];
+          ok = ok && !((y & ~FILLED) == x && ((y & FILLED) || q < k));
+        }
+        if (ok) keep |= 1u << s; else ++still;
+      }
+      __syncthreads();
+      s = 0;
+      for (int k = tid; k < cnt; k += 256, ++s)
+        if (keep >> s & 1u) val[k] |= FILLED;
+      open = block_sum_i(still, red);
+    }
+    exact = open > 0;
+  }
+  __syncthreads();
+  if (exact) {
+    // the cnt smallest keys among the A ranks, then in key order (a uniform ordered draw without replacement)
+    select_smallest(key, 4u, (int)A, cnt, sel, red, wcnt);
+    for (int k = tid; k < cnt; k += 256) nkey[k] = rnd_row(key, 4u, (uint32_t)sel[k]);
+    __syncthreads();
+    for (int k = tid; k < cnt; k += 256) {
+      const uint32_t x = nkey[k];
+      int at = 0;
+      for (int q = 0; q < cnt; ++q) at += nkey[q] < x || (nkey[q] == x && q < k) ? 1 : 0;
+      no[at] = admissible_item(hs, D, (uint32_t)sel[k]);
+    }
+  } else {
+    for (int k = tid; k < cnt; k += 256) no[k] = admissible_item(hs, D, val[k] & ~FILLED);
+  }
+  for (int k = cnt + tid; k < a.width; k += 256) no[k] = 0;
+}
+
+size_t rows_lds_bytes(int32_t width, int32_t max_history) {
+  return ((size_t)2 * max_history + 1 + (size_t)2 * width + 8) * sizeof(int);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t xfmr_seq_sample_rows_workspace(int32_t batch, int32_t width) {
+  (void)batch; (void)width;
+  return 0;  // everything a row needs is held in LDS
+}
+
+int xfmr_seq_sample_rows(const int64_t* items, const uint8_t* labels, const int64_t* offsets, int64_t n_rows,
+                         const int64_t* order, int64_t n_order, int64_t first, int32_t batch, int32_t width,
+                         int32_t max_seq_length, int32_t pos_lookahead, int64_t n_items, int32_t max_history,
+                         uint64_t seed, uint64_t epoch, int64_t* hist_out, int64_t* pos_out, int64_t* neg_out,
+                         int32_t* len_out, void* workspace, size_t workspace_bytes, void* stream) {
+  (void)workspace;
+  if (!items || !labels || !offsets || !order || !hist_out || !pos_out || !neg_out || !len_out) return XFMR_EINVAL;
+  if (batch <= 0 || width <= 0 || max_seq_length <= 0 || pos_lookahead < 0 || n_items <= 0 || max_history <= 0 ||
+      n_rows <= 0 || n_order < 0 || first < 0)
+    return XFMR_EINVAL;
+  if (n_items >= (1ll << 31) || max_history > MAX_HIST) return XFMR_EUNSUPPORTED;
+  const size_t smem = rows_lds_bytes(width, max_history);
+  if (smem > ROWS_MAX_LDS || width > 256 * 32) return XFMR_EUNSUPPORTED;
+  if (workspace_bytes < xfmr_seq_sample_rows_workspace(batch, width)) return XFMR_EWORKSPACE;
+  RowsArgs a{};
+  a.items = items; a.labels = labels; a.offsets = offsets; a.order = order;
+  a.n_rows = n_rows; a.n_order = n_order; a.first = first;
+  a.hist_out = hist_out; a.pos_out = pos_out; a.neg_out = neg_out; a.len_out = len_out;
+  a.B = batch; a.width = width; a.max_len = max_seq_length; a.lookahead = pos_lookahead; a.max_hist = max_history;
+  a.n_items = n_items; a.seed = seed; a.epoch = epoch;
+  if (hipFuncSetAttribute((const void*)seq_sample_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
+      hipSuccess)
+    return XFMR_EHIP;
+  hipLaunchKernelGGL(seq_sample_rows_kernel, dim3(batch), dim3(256), smem, (hipStream_t)stream, a);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
+
+}  // extern "C"

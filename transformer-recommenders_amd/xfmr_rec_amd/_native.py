@@ -180,6 +180,10 @@ _SIGNATURES = {
     "xfmr_seq_sample_workspace": (C.c_size_t, [C.c_int32, C.c_int64]),
     "xfmr_seq_sample": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
                                   C.c_uint64, _P, _P, _P, _P, C.c_size_t, _P]),
+    "xfmr_seq_sample_rows_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "xfmr_seq_sample_rows": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P,
+                                       C.c_size_t, _P]),
     "xfmr_topk_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
     "xfmr_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P,
                             C.c_size_t, _P]),

@@ -4,7 +4,9 @@ The reference samples one row at a time on the host (numpy) inside DataLoader wo
 at the step rates of the MI355X path (> 6e4 sequences/s) that is the bottleneck. Here
 the processed histories live in HBM as one CSR (``items``, ``labels``, ``offsets``) and a whole batch -- sampled
 positions, positives, negatives, right-padded to the batch's longest row -- is produced by ONE kernel launch
-(``xfmr_seq_sample``), already resident where the training step reads it.
+(``xfmr_seq_sample``), already resident where the training step reads it. :class:`DeviceSeqLoader` is the reference's
+``train_dataloader`` over such a dataset (``data.py:886-927``): epochs, shuffling, sharding and one
+``xfmr_seq_sample_rows`` launch per batch, a batch ahead of the step.
 
 Not carried over: the ``*_item_text`` string lists of ``SeqBatch`` (``data.py:778-785``) -- the training step never
 reads them -- and the MovieLens download / polars ETL (``data.py:60-515``: out of scope).
@@ -265,3 +267,234 @@ class PinnedBatchRing:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+class DeviceSeqLoader:
+    """The reference's ``train_dataloader(shuffle=True, batch_size=...)`` (``data.py:886-927``) over a
+    :class:`DeviceSeqDataset`: epochs, shuffling, sharding and prefetch of batches that are sampled where they are read.
+
+    One epoch is a row order (:meth:`epoch_order`: a numpy permutation keyed by ``(seed, epoch)``, sharded as
+    ``DistributedSampler`` does), uploaded once; batch i is ONE launch of ``xfmr_seq_sample_rows`` over rows
+    ``order[i * batch_size : (i + 1) * batch_size]`` -- no per-batch upload or allocation: three slots of output
+    buffers, the lengths and the workspace are made at the first iteration. The random stream is keyed by
+    ``(seed, epoch, dataset row)``: what a row samples does not depend on the batch it lands in.
+
+    ``prefetch=True``: the launch runs on a stream of the loader's own, batch i + 1 underneath step i. Ordering is by
+    events in both directions (as :class:`PinnedBatchRing`): the consumer's stream waits for a slot's "ready" event;
+    the loader's stream waits, in front of the launch that rewrites a slot, for the "free" event the consumer's stream
+    recorded behind the step that read it. A yielded batch is valid until the batch after the next one is requested
+    (a consumer may look one batch ahead). ``prefetch=False`` launches on the consumer's stream; same bits.
+
+    Iteration yields ``{history_item_idx, pos_item_idx, neg_item_idx}`` (device views of a slot) and ``lengths`` (host):
+    what ``DeviceSeqDataset.sample_batch`` returns. ``fixed_width=True``: every batch is ``max_seq_length`` wide (one
+    shape for a captured step); ``False``: as wide as its longest row (``pad_sequence``). A short last batch is launched
+    with its own row count; ``drop_last=True`` leaves it out.
+
+        loader = DeviceSeqLoader(dataset, 512)
+        for epoch in range(3):
+            loader.set_epoch(epoch)
+            for batch in loader:
+                trainer.fit_step(batch)
+        loader.close()          # frees the stream and the events (``__del__`` makes no HIP call)
+    """
+
+    SLOTS = 3
+
+    def __init__(self, dataset: DeviceSeqDataset, batch_size: int, *, shuffle: bool = True, seed: int = 0,
+                 drop_last: bool = False, rank: int = 0, world_size: int = 1, fixed_width: bool = False,
+                 prefetch: bool = True):
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f"batch_size must be an integer >= 1; got {batch_size!r}")
+        if world_size < 1 or not 0 <= rank < world_size:
+            raise ValueError(f"rank {rank!r} is not in [0, world_size = {world_size!r})")
+        self.dataset = dataset
+        self.batch_size = batch_size
+        self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
+        self.rank, self.world_size = int(rank), int(world_size)
+        self.fixed_width, self.prefetch = bool(fixed_width), bool(prefetch)
+        self.epoch = 0
+        self.next_batch = 0  # the batch of `epoch` the next iteration starts with (state_dict)
+        self._order = None   # (epoch, this rank's rows) of the last epoch asked for
+        self._bufs = None    # device buffers, stream and events: made at the first iteration
+        self._ready_pending = [False] * self.SLOTS
+
+    # ------------------------------------------------------------------ host side: no device is touched
+    def epoch_order(self, epoch: int) -> np.ndarray:
+        """This rank's dataset rows of ``epoch``, in order: a permutation keyed by ``(seed, epoch)`` (the identity with
+        ``shuffle=False``), extended by wrapping to a multiple of ``world_size``; rank r takes every ``world_size``-th row
+        from r on (``torch.utils.data.DistributedSampler``). Every rank gets the same count."""
+        n = len(self.dataset)
+        if self.shuffle:
+            order = np.random.default_rng([self.seed & (2**63 - 1), int(epoch)]).permutation(n).astype(np.int64)
+        else:
+            order = np.arange(n, dtype=np.int64)
+        if self.world_size > 1:
+            total = -(-n // self.world_size) * self.world_size
+            order = np.resize(order, total)[self.rank :: self.world_size]
+        return np.ascontiguousarray(order)
+
+    def _rows(self) -> np.ndarray:
+        if self._order is None or self._order[0] != self.epoch:
+            self._order = (self.epoch, self.epoch_order(self.epoch))
+        return self._order[1]
+
+    @property
+    def rows_per_epoch(self) -> int:
+        return -(-len(self.dataset) // self.world_size)
+
+    def __len__(self) -> int:
+        n = self.rows_per_epoch
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def set_epoch(self, epoch: int) -> None:
+        """The epoch the next iteration runs, from its first batch."""
+        self.epoch = int(epoch)
+        self.next_batch = 0
+
+    def batch_rows(self, i: int) -> np.ndarray:
+        """The dataset rows of batch ``i`` of the current epoch."""
+        if not 0 <= i < len(self):
+            raise IndexError(f"batch {i} of {len(self)}")
+        return self._rows()[i * self.batch_size : (i + 1) * self.batch_size]
+
+    def batch_lengths(self, i: int) -> np.ndarray:
+        """Sampled positions per row of batch ``i``: ``min(len - 1, max_seq_length)`` (``data.py:669-688``)."""
+        return np.minimum(self.dataset.lengths[self.batch_rows(i)] - 1, self.dataset.config.max_seq_length)
+
+    def batch_width(self, i: int) -> int:
+        if self.fixed_width:
+            return int(self.dataset.config.max_seq_length)
+        return int(max(1, self.batch_lengths(i).max()))
+
+    def state_dict(self) -> dict:
+        return {"epoch": self.epoch, "next_batch": self.next_batch}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Continue where ``state`` was taken: the next iteration yields batches ``next_batch ...`` of ``epoch``."""
+        self.epoch, self.next_batch = int(state["epoch"]), int(state["next_batch"])
+
+    # ------------------------------------------------------------------ device side
+    def _make_buffers(self) -> dict:
+        import ctypes
+
+        ds = self.dataset
+        if ds.device.type != "cuda":
+            raise RuntimeError("DeviceSeqLoader samples on a HIP device (MI355X); the dataset lives on "
+                               f"{ds.device}. There is no CPU fallback.")
+        lib = N.load()
+        B, W = self.batch_size, int(ds.config.max_seq_length)
+        nbytes = lib.xfmr_seq_sample_rows_workspace(B, W)
+        bufs = {"lib": lib, "ws_bytes": nbytes, "stream": None, "ready": [], "free": [], "order_sent": False}
+        with torch.cuda.device(ds.device):
+            bufs["out"] = [torch.zeros((3, B * W), dtype=torch.int64, device=ds.device) for _ in range(self.SLOTS)]
+            bufs["len"] = [torch.zeros(B, dtype=torch.int32, device=ds.device) for _ in range(self.SLOTS)]
+            bufs["ws"] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=ds.device)
+            bufs["order"] = torch.zeros(max(self.rows_per_epoch, 1), dtype=torch.int64, device=ds.device)
+            bufs["order_pinned"] = torch.zeros(max(self.rows_per_epoch, 1), dtype=torch.int64).pin_memory()
+            h = ctypes.c_void_p()
+            N.check(lib.xfmr_stream_create(ctypes.byref(h)), "xfmr_stream_create")
+            bufs["stream"] = h.value
+            for _ in range(self.SLOTS):
+                for lst in (bufs["ready"], bufs["free"]):
+                    e = ctypes.c_void_p()
+                    N.check(lib.xfmr_event_create(ctypes.byref(e), 0), "xfmr_event_create")
+                    lst.append(e.value)
+            e = ctypes.c_void_p()
+            N.check(lib.xfmr_event_create(ctypes.byref(e), 0), "xfmr_event_create")
+            bufs["order_event"] = e.value
+        bufs["max_history"] = int(ds.lengths.max())
+        return bufs
+
+    def _launch(self, i: int, slot: int, stream: int) -> None:
+        ds, bf = self.dataset, self._bufs
+        first = i * self.batch_size
+        b = min(self.batch_size, self.rows_per_epoch - first)
+        out = bf["out"][slot]
+        N.check(
+            bf["lib"].xfmr_seq_sample_rows(
+                N.ptr(ds.items), N.ptr(ds.labels), N.ptr(ds.offsets), len(ds), N.ptr(bf["order"]), self.rows_per_epoch,
+                first, b, self.batch_width(i), ds.config.max_seq_length, ds.config.pos_lookahead, ds.n_items,
+                bf["max_history"], self.seed & (2**64 - 1), self.epoch, out[0].data_ptr(), out[1].data_ptr(),
+                out[2].data_ptr(), N.ptr(bf["len"][slot]), N.ptr(bf["ws"]) if bf["ws_bytes"] else None, bf["ws_bytes"],
+                stream),
+            "xfmr_seq_sample_rows",
+        )
+
+    def _views(self, i: int, slot: int) -> dict:
+        b, w = len(self.batch_rows(i)), self.batch_width(i)
+        out = self._bufs["out"][slot]
+        res = {k: out[j, : b * w].view(b, w) for j, k in enumerate(SEQ_BATCH_KEYS)}
+        res["lengths"] = torch.from_numpy(np.minimum(self.batch_lengths(i), w).astype(np.int64))
+        return res
+
+    def __iter__(self):
+        if self._bufs is None:
+            self._bufs = self._make_buffers()
+        bf, lib = self._bufs, self._bufs["lib"]
+        with torch.cuda.device(self.dataset.device):
+            # a sample left in flight by an abandoned iteration is in front of everything this one enqueues
+            for s in range(self.SLOTS):
+                if self._ready_pending[s]:
+                    N.check(lib.xfmr_stream_wait_event(N.stream(), bf["ready"][s]), "xfmr_stream_wait_event")
+                    self._ready_pending[s] = False
+            rows = self._rows()
+            if bf["order_sent"]:  # the last epoch's upload has left the page-locked block (returns at once, an epoch later)
+                N.check(lib.xfmr_event_synchronize(bf["order_event"]), "xfmr_event_synchronize")
+            bf["order_pinned"][: len(rows)].copy_(torch.from_numpy(rows))
+            bf["order"][: len(rows)].copy_(bf["order_pinned"][: len(rows)], non_blocking=True)  # once per epoch
+            N.check(lib.xfmr_event_record(bf["order_event"], N.stream()), "xfmr_event_record")
+            bf["order_sent"] = True
+            if self.prefetch:
+                # behind the upload -- and behind every step the consumer has enqueued on the slots so far
+                N.check(lib.xfmr_stream_wait_event(bf["stream"], bf["order_event"]), "xfmr_stream_wait_event")
+        nb, start = len(self), self.next_batch
+        used = [False] * self.SLOTS  # slot read by a step of this iteration (its free event has been recorded)
+
+        def enqueue(i: int) -> None:
+            s = i % self.SLOTS
+            if not self.prefetch:
+                self._launch(i, s, N.stream())
+                return
+            if used[s]:  # the step that read the slot (batch i - SLOTS) has finished before it is rewritten
+                N.check(lib.xfmr_stream_wait_event(bf["stream"], bf["free"][s]), "xfmr_stream_wait_event")
+            self._launch(i, s, bf["stream"])
+            N.check(lib.xfmr_event_record(bf["ready"][s], bf["stream"]), "xfmr_event_record")
+            self._ready_pending[s] = True
+
+        with torch.cuda.device(self.dataset.device):
+            if self.prefetch and start < nb:
+                enqueue(start)
+        for i in range(start, nb):
+            s = i % self.SLOTS
+            with torch.cuda.device(self.dataset.device):
+                if self.prefetch:
+                    if i - 2 >= start:
+                        # everything the consumer has enqueued when it asks for batch i includes the step on batch i - 2 (it may
+                        # hold batch i - 1 without having stepped on it yet): that slot is the one batch i + 1 goes into
+                        f = (i - 2) % self.SLOTS
+                        N.check(lib.xfmr_event_record(bf["free"][f], N.stream()), "xfmr_event_record")
+                        used[f] = True
+                    N.check(lib.xfmr_stream_wait_event(N.stream(), bf["ready"][s]), "xfmr_stream_wait_event")
+                    self._ready_pending[s] = False
+                    if i + 1 < nb:
+                        enqueue(i + 1)  # in flight while the consumer steps on batch i
+                else:
+                    enqueue(i)
+            self.next_batch = i + 1
+            yield self._views(i, s)
+        self.next_batch = 0
+
+    def close(self) -> None:
+        """Free the loader's stream and events (after the work enqueued on them has finished)."""
+        bf, self._bufs = self._bufs, None
+        if bf is None or bf["stream"] is None:
+            return
+        lib = bf["lib"]
+        for s in range(self.SLOTS):
+            if self._ready_pending[s]:
+                lib.xfmr_event_synchronize(bf["ready"][s])
+                self._ready_pending[s] = False
+        torch.cuda.synchronize(self.dataset.device)  # (the consumer's steps that read the slots)
+        for e in bf["ready"] + bf["free"] + [bf["order_event"]]:
+            lib.xfmr_event_destroy(e)
+        lib.xfmr_stream_destroy(bf["stream"])

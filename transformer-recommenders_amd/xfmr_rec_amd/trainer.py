@@ -751,6 +751,42 @@ def reference_trainer_options(cfg: dict) -> dict:
     return dict(gradient_clip_val=clip, gradient_clip_algorithm=algo, accumulate_grad_batches=acc, lr_scheduler=schedule)
 
 
+def reference_fit_options(cfg: dict) -> dict:
+    """What a parsed reference ``config.yaml`` asks of the epoch loop: the ``trainer:`` block's ``max_epochs``,
+    ``check_val_every_n_epoch``, ``limit_train_batches``, ``max_steps`` (-1 -> None) and ``val_check_interval`` --
+    :meth:`Trainer.fit`'s arguments of the same names -- and ``batch_size``, ``max_seq_length`` and ``pos_lookahead`` of
+    ``data.config`` (``DeviceSeqLoader`` / ``SeqDataConfig``). Lightning also takes fractions of an epoch for the two
+    batch limits; the loop counts batches, so a float raises a ``ValueError`` that names the key."""
+    block = cfg.get("trainer") or {}
+    if not isinstance(block, dict):
+        raise ValueError(f"trainer: expected a mapping, got {type(block).__name__}")
+
+    def _count(key, default, least):
+        v = block.get(key, default)
+        v = default if v is None else v
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < least):
+            raise ValueError(f"trainer.{key}: {v!r} is not an integer >= {least} (fractions of an epoch are not supported)")
+        return v
+
+    max_steps = block.get("max_steps", -1)
+    max_steps = -1 if max_steps is None else max_steps
+    if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < -1:
+        raise ValueError(f"trainer.max_steps: {max_steps!r} is not an integer >= -1")
+    max_epochs = block.get("max_epochs")
+    if max_epochs == -1 or (max_epochs is None and max_steps == -1):
+        raise ValueError(f"trainer.max_epochs: {max_epochs!r} with max_steps = -1 asks for an endless loop")
+    data = (cfg.get("data") or {}).get("config") or {}
+    out = dict(max_epochs=_count("max_epochs", None, 0), check_val_every_n_epoch=_count("check_val_every_n_epoch", 1, 1),
+               limit_train_batches=_count("limit_train_batches", None, 0), max_steps=None if max_steps == -1 else max_steps,
+               val_check_interval=_count("val_check_interval", None, 1))
+    for key, default in (("batch_size", 32), ("max_seq_length", 32), ("pos_lookahead", 0)):  # data.py:543-566
+        v = data.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, int) or v < (0 if key == "pos_lookahead" else 1):
+            raise ValueError(f"data.config.{key}: {v!r} is not a valid count")
+        out[key] = v
+    return out
+
+
 class EarlyStopping:
     """Lightning's ``EarlyStopping`` rule on one monitored value: ``update(value)`` returns True when the loop should stop.
 
@@ -914,7 +950,8 @@ class Trainer:
     def from_reference_config(cls, module: RecommenderLightningModule, cfg: dict, **kwargs) -> "Trainer":
         """A trainer from a parsed reference ``config.yaml``: its ``trainer:`` block's ``gradient_clip_val``,
         ``gradient_clip_algorithm`` and ``accumulate_grad_batches`` and the top-level ``lr_scheduler``. The block's other
-        keys are orchestration (devices, epochs, logging, checkpointing: the caller's loop) and are not read. A non-null
+        keys are orchestration (devices, logging, checkpointing: the caller's; the epoch loop's keys are read by
+        :func:`reference_fit_options` for :meth:`fit`) and are not read here. A non-null
         value that changes the optimisation and cannot be honoured raises a ``ValueError`` that names its key."""
         return cls(module, **reference_trainer_options(cfg), **kwargs)
 
@@ -934,7 +971,8 @@ class Trainer:
 
     def fit(self, batches, max_steps: int | None = None, *, ring_slots: int = 6, graph: str = "off",
             graph_probe_steps: int = 20, val=None, val_check_interval: int | None = None, monitor: dict = METRIC,
-            early_stopping=None, checkpoint_dir=None, val_cutoffs=None) -> list[float]:
+            early_stopping=None, checkpoint_dir=None, val_cutoffs=None, max_epochs: int | None = None,
+            check_val_every_n_epoch: int = 1, limit_train_batches: int | None = None) -> list[float]:
         """Steps over an iterable of collated batches. Batches that arrive in HOST memory (the reference's DataLoader
         output, ``data.py:915-927``) are handed over through a :class:`~xfmr_rec_amd.data.PinnedBatchRing`: the copy of
         batch i + 1 runs underneath step i; device-resident batches (``DeviceSeqDataset.sample_batch``) are used as they are.
@@ -962,10 +1000,35 @@ class Trainer:
         ``val_cutoffs`` (e.g. ``(5, 10, 20, 500)``): every pass takes the rank path (``DeviceEvalSet.evaluate(stage,
         cutoffs=val_cutoffs)``): the metrics at every cutoff under ``<stage>/<metric>@<K>`` next to the plain keys (those
         of ``config.top_k``), all of them in ``val_history``. ``monitor["name"]`` may then be ``'<stage>/<metric>@<K>'`` for
-        a K among ``val_cutoffs``."""
-        from .data import SEQ_BATCH_KEYS, PinnedBatchRing
+        a K among ``val_cutoffs``.
+
+        ``max_epochs`` (``batches`` must then be a :class:`~xfmr_rec_amd.data.DeviceSeqLoader`, built with this trainer's
+        ``world_size``): the epoch loop of the reference's ``trainer:`` block (:func:`reference_fit_options`). Epoch e is
+        ``loader.set_epoch(e)`` and one iteration of the loader, at most ``limit_train_batches`` batches of it; ``max_steps``
+        still caps the total, and the returned list holds every step's loss across the epochs. With ``val`` and no
+        ``val_check_interval`` a pass follows every ``check_val_every_n_epoch``-th epoch (Lightning's default; nothing
+        extra after the last batch); ``val_check_interval`` counts batches across epochs as before. ``val_history``
+        entries carry the ``"epoch"`` they ran in. Under ``graph != "off"`` the loader runs ``fixed_width`` for the call
+        and its batches are taken without their lengths: eager warm-up, probe and replays are one layout; the sample
+        launch itself stays outside the captured graph. A loader that was restored mid-epoch (``load_state_dict``)
+        continues there."""
+        from .data import SEQ_BATCH_KEYS, DeviceSeqLoader, PinnedBatchRing
 
         self._check_val(val)
+        loader = batches if isinstance(batches, DeviceSeqLoader) else None
+        if max_epochs is None:
+            if limit_train_batches is not None or check_val_every_n_epoch != 1:
+                raise ValueError("limit_train_batches / check_val_every_n_epoch belong to the epoch loop: pass max_epochs")
+        else:
+            if loader is None:
+                raise ValueError(f"max_epochs needs a DeviceSeqLoader to run epochs over; got {type(batches).__name__}")
+            for name, v, least in (("max_epochs", max_epochs, 0), ("check_val_every_n_epoch", check_val_every_n_epoch, 1),
+                                   ("limit_train_batches", limit_train_batches, 0)):
+                if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < least):
+                    raise ValueError(f"{name} must be an integer >= {least}; got {v!r}")
+        if loader is not None and loader.world_size != self.world_size:
+            raise ValueError(f"the loader shards its epochs over world_size = {loader.world_size}, this trainer runs "
+                             f"world_size = {self.world_size}")
         if val_check_interval is not None:
             if isinstance(val_check_interval, bool) or not isinstance(val_check_interval, int) or val_check_interval < 1:
                 raise ValueError(f"val_check_interval must be an integer >= 1 or None; got {val_check_interval!r}")
@@ -1030,7 +1093,8 @@ class Trainer:
             metrics = val.evaluate(stage) if val_cutoffs is None else val.evaluate(stage, cutoffs=val_cutoffs)
             self.val_elapsed += time.perf_counter() - tv
             self.module.log_dict(metrics)
-            self.val_history.append({"step": batches_done, **metrics})
+            self.val_history.append({"step": batches_done, **({"epoch": ep["epoch"]} if max_epochs is not None else {}),
+                                     **metrics})
             value = metrics[monitor["name"]]
             tracker.update(value)
             if tracker.improved:
@@ -1058,8 +1122,27 @@ class Trainer:
         side = torch.cuda.Stream(device=dev) if graph != "off" else None
         if side is not None:
             side.wait_stream(cur)
+        ep = {"epoch": 0, "last": False}  # the epoch loop's state at the batch in hand: its epoch, whether it ends it
+
+        def _epochs():
+            e0 = loader.epoch if loader.next_batch > 0 else 0  # (a loader restored mid-epoch goes on from there)
+            for e in range(e0, max_epochs):
+                if e > e0 or loader.next_batch == 0:
+                    loader.set_epoch(e)
+                n_b = len(loader) if limit_train_batches is None else min(len(loader), limit_train_batches)
+                it_e = iter(loader)
+                for j in range(loader.next_batch, n_b):
+                    b_ = next(it_e)
+                    ep["epoch"], ep["last"] = e, j + 1 == n_b
+                    yield b_
+                it_e.close()
+                loader.set_epoch(e)  # (an epoch cut short by limit_train_batches is over, not half done)
+
+        fixed_before = loader.fixed_width if loader is not None else None
+        if loader is not None and graph != "off":
+            loader.fixed_width = True  # one shape for the captured step -- and one layout for the steps around it
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            it = iter(batches)
+            it = iter(batches) if max_epochs is None else _epochs()
             nxt = next(it, None)
             i = 0
             while nxt is not None and (max_steps is None or i < max_steps):
@@ -1079,9 +1162,12 @@ class Trainer:
                         # a captured step has fixed launch sizes: it runs the padded layout, and so do the eager steps around
                         # it (one sequence of steps, one layout) -- the rows' lengths are not passed on
                         dev_b = {k: dev_b[k] for k in SEQ_BATCH_KEYS}
+                elif loader is not None and graph != "off":
+                    dev_b = {k: b[k] for k in SEQ_BATCH_KEYS}  # (as above: no lengths, the padded layout)
                 else:
                     dev_b = b
-                nxt = next(it, None)
+                if loader is None:
+                    nxt = next(it, None)
                 if nxt is not None and ring is not None and not nxt[SEQ_BATCH_KEYS[0]].is_cuda \
                         and nxt[SEQ_BATCH_KEYS[0]].shape[0] <= ring.shape[1] and nxt[SEQ_BATCH_KEYS[0]].shape[1] <= ring.shape[2]:
                     ring.stage(nxt)  # in flight while this step computes
@@ -1109,8 +1195,18 @@ class Trainer:
                 if val is not None and val_check_interval is not None and i % val_check_interval == 0 and _validate(i):
                     self.stopped_early = True
                     break
-            if val is not None and val_check_interval is None and i > 0:
+                if (val is not None and val_check_interval is None and max_epochs is not None and ep["last"]
+                        and (ep["epoch"] + 1) % check_val_every_n_epoch == 0 and _validate(i)):
+                    self.stopped_early = True
+                    break
+                if loader is not None:
+                    # a loader's slots are rewritten underneath the steps: the next batch is asked for once this step is enqueued
+                    # (and only if it will be stepped on: the loader's state then names the batch a resumed run starts with)
+                    nxt = next(it, None) if max_steps is None or i < max_steps else None
+            if val is not None and val_check_interval is None and max_epochs is None and i > 0:
                 _validate(i)
+        if loader is not None:
+            loader.fixed_width = fixed_before
         if side is not None:
             cur.wait_stream(side)
         if graph != "off":
