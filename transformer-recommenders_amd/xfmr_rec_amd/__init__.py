@@ -4,6 +4,7 @@ Host-side mirror of the reference's ``xfmr_rec.models`` / ``xfmr_rec.losses`` / 
 interfaces over hand-written gfx950 HIP kernels (``libxfmr_hip.so``, C ABI in ``include/xfmr_hip.h``).
 """
 
+from .checkpoint import parse_max_time, read_checkpoint, reference_checkpoint_options, write_checkpoint  # noqa: F401
 from .evalset import DeviceEvalSet, EvalPlan, plan_eval_rows  # noqa: F401
 from .losses import LOSS_CLASSES, EmbedLoss, LossConfig, LossType  # noqa: F401
 from .models import ModelConfig, RecommenderModel  # noqa: F401
@@ -12,4 +13,5 @@ from .trainer import EarlyStopping, FusedAdamW, GraphedStep, LightningConfig, Re
 __all__ = [
     "LOSS_CLASSES", "EmbedLoss", "LossConfig", "LossType", "ModelConfig", "RecommenderModel",
     "DeviceEvalSet", "EarlyStopping", "EvalPlan", "plan_eval_rows", "FusedAdamW", "GraphedStep", "LightningConfig", "RecommenderLightningModule", "Trainer",
+    "parse_max_time", "read_checkpoint", "reference_checkpoint_options", "write_checkpoint",
 ]

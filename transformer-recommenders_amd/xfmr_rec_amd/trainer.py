@@ -822,6 +822,15 @@ class EarlyStopping:
             self.wait += 1
         return self.patience is not None and self.wait >= self.patience
 
+    def state_dict(self) -> dict:
+        """What the rule has seen so far: ``best``, ``wait`` and ``improved``. The rule itself (mode, patience, min_delta) is
+        the constructor's: a resumed run may change its patience."""
+        return {"best": self.best, "wait": self.wait, "improved": self.improved}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.best = None if state["best"] is None else float(state["best"])
+        self.wait, self.improved = int(state["wait"]), bool(state["improved"])
+
 
 def _early_stopping_from(arg, mode: str) -> EarlyStopping | None:
     """``Trainer.fit``'s ``early_stopping`` argument: None / False (off), True (Lightning's defaults: patience 3, min_delta 0)
@@ -865,6 +874,8 @@ class Trainer:
         self.accumulate_grad_batches = accumulate_grad_batches
         self._micro = 0          # micro-batches accumulated since the last optimizer step
         self._grad_acc = None    # their gradient sum (accumulate_grad_batches > 1), persistent
+        self._loop = None        # fit's loop state as of its last checkpoint or its end (state_dict)
+        self._loader_fields = None  # identity of the DeviceSeqLoader the last fit / load_state_dict saw (None: an iterable)
         clip = float(gradient_clip_val) if gradient_clip_val else None  # (Lightning: 0 and None both mean "off")
         if clip is not None or lr_scheduler is not None:
             if not isinstance(self.optimizer, FusedAdamW):
@@ -969,10 +980,109 @@ class Trainer:
         self.module.log_dict(metrics)
         return metrics
 
+    # ------------------------------------------------------------------ full-state checkpoints
+    def _trainer_fields(self) -> dict:
+        opt = self.optimizer
+        return {"accumulate_grad_batches": self.accumulate_grad_batches,
+                "gradient_clip_algorithm": getattr(opt, "clip_mode", None), "gradient_clip_val": getattr(opt, "clip_val", None),
+                "lr_scheduler": getattr(opt, "schedule", None), "world_size": self.world_size}
+
+    def _optimizer_steps(self) -> int:
+        return int(max((st.get("step", 0) for st in self.optimizer.state.values()), default=0))
+
+    @staticmethod
+    def _empty_loop() -> dict:
+        return {"batches_done": 0, "epoch": 0, "next_batch": 0, "tracker": None, "stopper": None, "val_history": [],
+                "best_score": None, "best_step": None, "best_model_path": None, "train_seconds": 0.0}
+
+    def state_dict(self, loader=None) -> dict:
+        """Everything a run needs to go on as if it had not stopped (``checkpoint.py`` lists the keys): the module's weights
+        under the reference's keys, the optimizer's moments and step count, the dropout stream's position and whether it
+        is keyed on the device, the options that shape the optimisation, ``fit``'s loop state as of its last checkpoint
+        or its end, and the identity of ``loader`` (the :class:`~xfmr_rec_amd.data.DeviceSeqLoader` the run reads; by
+        default the one the last ``fit`` or ``load_state_dict`` saw, None for a plain iterable). Tensors are host copies: one stream sync, then the device-to-host copies. Refused between the
+        micro-batches of one optimizer step (``accumulate_grad_batches > 1``): the gradient sum is not part of it."""
+        from . import checkpoint as CK
+
+        if self._micro != 0:
+            raise ValueError(f"a checkpoint between the micro-batches of one optimizer step ({self._micro} of "
+                             f"accumulate_grad_batches = {self.accumulate_grad_batches} done) is refused: the gradient sum is "
+                             "not part of a checkpoint")
+        m, mdl = self.module, self.module.model
+        if mdl.flat.is_cuda:
+            torch.cuda.current_stream(mdl.device).synchronize()
+        optimizer = CK.plain(self.optimizer.state_dict(), "optimizer")  # (FusedAdamW reads its device-side step count first)
+        host = mdl.flat.detach().cpu()  # ONE copy: the HF-keyed tensors of the file are views of it (one storage in the file)
+        sd = {}
+        offsets = {CK.ENC_PREFIX + name: (off, shape) for name, shape, off in zip(mdl._names, mdl._shapes, mdl._offsets)}
+        for k, v in m.state_dict().items():
+            if k in offsets:
+                off, shape = offsets[k]
+                sd[k] = host[off : off + v.numel()].view(shape)
+            else:
+                sd[k] = v.detach().cpu()
+        loop = dict(self._loop) if self._loop is not None else self._empty_loop()
+        return {
+            "format": CK.FORMAT, "version": CK.VERSION, "state_dict": sd,
+            "hyper_parameters": {"config": CK.plain(m.config.model_dump(), "config")},
+            "epoch": loop["epoch"], "global_step": self._optimizer_steps(), "optimizer": optimizer,
+            "model": {"dropout_step": int(mdl._step), "seed": int(mdl._seed),
+                      "device_step": getattr(mdl, "step_device", None) is not None},
+            "trainer": CK.plain(self._trainer_fields(), "trainer"), "loop": CK.plain(loop, "loop"),
+            "loader": CK.loader_fields(loader) if loader is not None else self._loader_fields,
+        }
+
+    def load_state_dict(self, state: dict, loader=None) -> dict:
+        """Inverse of :meth:`state_dict`. Compatibility is checked before anything is touched
+        (``checkpoint.check_compatible``: a ``ValueError`` that names the field); then, in this order: module weights,
+        optimizer state, the dropout stream's position and seed, and the device-step mode -- a checkpoint taken with the
+        step counter on the device gets one again, filled with the restored step count and wired to the optimizer; one
+        taken without leaves it off. ``loader`` is positioned at the batch the run goes on with. Returns the ``loop``
+        state, which a later :meth:`fit` continues only when it is given the file (``ckpt_path``)."""
+        from . import checkpoint as CK
+
+        m, mdl = self.module, self.module.model
+        CK.check_compatible(state, flat_numel=mdl.flat.numel(), trainer=self._trainer_fields(), loader=CK.loader_fields(loader))
+        keys = m.load_state_dict(state["state_dict"], strict=False)
+        if keys.missing_keys:
+            raise ValueError(f"checkpoint state_dict: missing keys {keys.missing_keys[:4]}")
+        opt_state = {"state": state["optimizer"]["state"],
+                     "param_groups": [{k: (tuple(v) if k == "betas" else v) for k, v in g.items()}
+                                      for g in state["optimizer"]["param_groups"]]}
+        self.optimizer.load_state_dict(opt_state)
+        mdl._step, mdl._seed = int(state["model"]["dropout_step"]), int(state["model"]["seed"])
+        if state["model"]["device_step"] and getattr(mdl, "step_device", None) is None:
+            mdl.use_device_step(True)
+        if getattr(mdl, "step_device", None) is not None:
+            mdl.step_device.fill_(self._optimizer_steps())
+            self.optimizer.step_device = mdl.step_device
+        self._micro = 0
+        loop = {**self._empty_loop(), **state["loop"]}
+        self._loop, self._loader_fields = dict(loop), CK.loader_fields(loader)
+        self.val_history = [dict(h) for h in loop["val_history"]]
+        self.best_score, self.best_step, self.best_model_path = loop["best_score"], loop["best_step"], loop["best_model_path"]
+        if loader is not None and CK.loader_fields(loader) is not None:
+            loader.load_state_dict({"epoch": loop["epoch"], "next_batch": loop["next_batch"]})
+        return loop
+
+    def save_checkpoint(self, path, loader=None) -> int:
+        """:meth:`state_dict` written to ``path`` (``checkpoint.write_checkpoint``: a temporary name, fsync, then
+        ``os.replace``). Synchronous, on the calling thread. Returns the file's size in bytes."""
+        from . import checkpoint as CK
+
+        return CK.write_checkpoint(self.state_dict(loader), path)
+
+    def load_checkpoint(self, path, loader=None) -> dict:
+        """``checkpoint.read_checkpoint(path)`` into :meth:`load_state_dict`; returns the restored ``loop`` state."""
+        from . import checkpoint as CK
+
+        return self.load_state_dict(CK.read_checkpoint(path), loader=loader)
+
     def fit(self, batches, max_steps: int | None = None, *, ring_slots: int = 6, graph: str = "off",
             graph_probe_steps: int = 20, val=None, val_check_interval: int | None = None, monitor: dict = METRIC,
             early_stopping=None, checkpoint_dir=None, val_cutoffs=None, max_epochs: int | None = None,
-            check_val_every_n_epoch: int = 1, limit_train_batches: int | None = None) -> list[float]:
+            check_val_every_n_epoch: int = 1, limit_train_batches: int | None = None, ckpt_path=None,
+            save_last: bool = False, checkpoint_every_n_steps: int | None = None, max_time=None) -> list[float]:
         """Steps over an iterable of collated batches. Batches that arrive in HOST memory (the reference's DataLoader
         output, ``data.py:915-927``) are handed over through a :class:`~xfmr_rec_amd.data.PinnedBatchRing`: the copy of
         batch i + 1 runs underneath step i; device-resident batches (``DeviceSeqDataset.sample_batch``) are used as they are.
@@ -1011,10 +1121,50 @@ class Trainer:
         entries carry the ``"epoch"`` they ran in. Under ``graph != "off"`` the loader runs ``fixed_width`` for the call
         and its batches are taken without their lengths: eager warm-up, probe and replays are one layout; the sample
         launch itself stays outside the captured graph. A loader that was restored mid-epoch (``load_state_dict``)
-        continues there."""
+        continues there.
+
+        ``ckpt_path``: a file of :meth:`save_checkpoint`, loaded before the loop (:meth:`load_checkpoint` with this call's
+        loader: an incompatible trainer or loader is a ``ValueError``). The loop's counters continue: ``val_check_interval``
+        and ``check_val_every_n_epoch`` fall on the global batch numbers of the uninterrupted run, ``max_steps`` and
+        ``max_epochs`` cap the totals including the restored part (Lightning's meaning), ``val_history``, the best tracker
+        and the early-stopping rule start from their restored state. The returned list holds this call's losses only. The
+        resumed steps are the uninterrupted run's, bit for bit (tests/test_gpu_resume.py). A loader is put at the restored
+        position (the loop's own, not the loader's, which is a batch ahead); with a plain iterable the caller supplies the
+        batches from ``loop["batches_done"]`` on. ``checkpoint_every_n_steps=n`` (a multiple of
+        ``accumulate_grad_batches``; needs ``checkpoint_dir``): after every n-th global batch -- behind a validation pass
+        that falls on it, so that the file carries the pass -- ``checkpoint_dir / "last.ckpt"`` is rewritten.
+        ``save_last=True``: the same file is written when the loop ends, whatever ended it (not when it raises). A write is
+        synchronous, between two steps on the loop's stream, never inside a capture and on no other thread; its time
+        goes into ``ckpt_elapsed`` and out of the "auto" probe's windows.
+
+        ``max_time`` (``checkpoint.parse_max_time``: seconds, a ``timedelta``, ``"DD:HH:MM:SS"`` or a dict): the budget of
+        THIS call on the host's monotonic clock, from its start. It is looked at after each batch, without a device
+        sync; once it is spent the loop ends, ``stopped_on_time`` is True and ``save_last`` applies. A limit <= 0 still
+        runs one batch. This deviates from Lightning, whose ``Timer`` carries the elapsed time across a resume: there, a
+        run stopped on time and resumed with the same limit stops after one batch; here the resumed call has the whole
+        budget again. None of the four is supported under ``world_size > 1``."""
+        from . import checkpoint as CK
         from .data import SEQ_BATCH_KEYS, DeviceSeqLoader, PinnedBatchRing
 
+        t_fit = time.monotonic()
         self._check_val(val)
+        time_limit = CK.parse_max_time(max_time)
+        if self.world_size > 1 and (ckpt_path is not None or save_last or checkpoint_every_n_steps is not None
+                                    or max_time is not None):
+            raise ValueError("ckpt_path / save_last / checkpoint_every_n_steps / max_time inside a data-parallel run "
+                             "(world_size > 1) are not supported: ranks that read their own clocks would leave the all-reduce "
+                             "at different steps, and a multi-rank run has never executed (save_checkpoint / load_checkpoint "
+                             "work on any rank)")
+        if checkpoint_every_n_steps is not None:
+            n_ck = checkpoint_every_n_steps
+            if isinstance(n_ck, bool) or not isinstance(n_ck, int) or n_ck < 1:
+                raise ValueError(f"checkpoint_every_n_steps must be an integer >= 1 or None; got {n_ck!r}")
+            if n_ck % self.accumulate_grad_batches:
+                raise ValueError(f"checkpoint_every_n_steps = {n_ck} is not a multiple of accumulate_grad_batches = "
+                                 f"{self.accumulate_grad_batches}: a checkpoint would fall between the micro-batches of one step")
+        if (checkpoint_every_n_steps is not None or save_last) and checkpoint_dir is None:
+            raise ValueError("checkpoint_every_n_steps / save_last write checkpoint_dir / 'last.ckpt': pass checkpoint_dir")
+        last_path = pathlib.Path(checkpoint_dir) / "last.ckpt" if checkpoint_dir is not None else None
         loader = batches if isinstance(batches, DeviceSeqLoader) else None
         if max_epochs is None:
             if limit_train_batches is not None or check_val_every_n_epoch != 1:
@@ -1054,8 +1204,25 @@ class Trainer:
                 raise ValueError(f"monitor name {monitor['name']!r}: '@<K>' needs K among val_cutoffs = {val_cutoffs!r}")
         self.val_history: list[dict] = []
         self.best_score = self.best_step = self.best_model_path = None
-        self.stopped_early = False
-        self.val_elapsed = 0.0
+        self.stopped_early = self.stopped_on_time = False
+        self.val_elapsed = self.ckpt_elapsed = 0.0
+        # the loop's position is its OWN: batches done over all calls (`base` + this call's `i`) and the (epoch, batch) the
+        # next step reads -- the loader's state is a batch ahead of the step, and after a finished epoch e it reads
+        # (e, 0), which the epoch loop below takes for "start at epoch 0"
+        base, resumed, seconds_before = 0, False, 0.0
+        self._loader_fields = CK.loader_fields(loader)
+        if ckpt_path is not None:
+            loop = self.load_checkpoint(ckpt_path, loader=loader)  # (checks first; sets val_history and the best_* fields)
+            base, resumed, seconds_before = int(loop["batches_done"]), True, float(loop["train_seconds"])
+            pos = (int(loop["epoch"]), int(loop["next_batch"]))
+            if loop["tracker"] is not None:
+                tracker.load_state_dict(loop["tracker"])
+            if stopper is not None and loop["stopper"] is not None:
+                stopper.load_state_dict(loop["stopper"])
+        elif loader is not None:
+            pos = (loader.epoch if (loader.next_batch > 0 or max_epochs is None) else 0, loader.next_batch)
+        else:
+            pos = (0, 0)
 
         if graph not in ("off", "on", "auto"):
             raise ValueError(f"graph must be 'off', 'on' or 'auto', got {graph!r}")
@@ -1105,11 +1272,31 @@ class Trainer:
                     self.best_model_path = str(path)
             stop = stopper.update(value) if stopper is not None else False
             # the "auto" probe compares STEPS: whatever a pass (and its checkpoint) took leaves the open window
-            spent = time.perf_counter() - tv
+            _out_of_probe(time.perf_counter() - tv)
+            return stop
+
+        def _out_of_probe(spent: float) -> None:
             for k0, k1 in (("eager_t0", "eager_ms"), ("graph_t0", "graph_ms")):
                 if k0 in probe and k1 not in probe:
                     probe[k0] += spent
-            return stop
+
+        def _loop_state(batches_done: int) -> dict:
+            return {"batches_done": batches_done, "epoch": pos[0], "next_batch": pos[1], "tracker": tracker.state_dict(),
+                    "stopper": stopper.state_dict() if stopper is not None else None,
+                    "val_history": [dict(h) for h in self.val_history], "best_score": self.best_score,
+                    "best_step": self.best_step, "best_model_path": self.best_model_path,
+                    "train_seconds": seconds_before + (time.monotonic() - t_fit)}  # (for information only)
+
+        def _checkpoint(batches_done: int) -> None:
+            """``last.ckpt`` between two steps, on the loop's stream: one stream sync, the device-to-host copies, the write."""
+            assert not torch.cuda.is_current_stream_capturing()
+            torch.cuda.current_stream(self.module.model.device).synchronize()  # the steps enqueued so far are not its time
+            tc = time.perf_counter()
+            self._loop = _loop_state(batches_done)
+            self.save_checkpoint(last_path)
+            spent = time.perf_counter() - tc
+            self.ckpt_elapsed += spent
+            _out_of_probe(spent)
 
         out = []
         t0 = time.time()
@@ -1122,10 +1309,13 @@ class Trainer:
         side = torch.cuda.Stream(device=dev) if graph != "off" else None
         if side is not None:
             side.wait_stream(cur)
-        ep = {"epoch": 0, "last": False}  # the epoch loop's state at the batch in hand: its epoch, whether it ends it
+        # the epoch loop's state at the batch in hand: its epoch, its index in the epoch, whether it ends the epoch
+        ep = {"epoch": 0, "j": 0, "last": False}
 
         def _epochs():
-            e0 = loader.epoch if loader.next_batch > 0 else 0  # (a loader restored mid-epoch goes on from there)
+            # a loader restored mid-epoch goes on from there; a restored LOOP names its epoch itself (load_state_dict has put
+            # the loader there: after the last batch of epoch e that is (e + 1, 0))
+            e0 = pos[0] if resumed else (loader.epoch if loader.next_batch > 0 else 0)
             for e in range(e0, max_epochs):
                 if e > e0 or loader.next_batch == 0:
                     loader.set_epoch(e)
@@ -1133,19 +1323,26 @@ class Trainer:
                 it_e = iter(loader)
                 for j in range(loader.next_batch, n_b):
                     b_ = next(it_e)
-                    ep["epoch"], ep["last"] = e, j + 1 == n_b
+                    ep["epoch"], ep["j"], ep["last"] = e, j, j + 1 == n_b
                     yield b_
                 it_e.close()
                 loader.set_epoch(e)  # (an epoch cut short by limit_train_batches is over, not half done)
+
+        def _one_pass():
+            n_b = len(loader)
+            for j, b_ in enumerate(loader, loader.next_batch):  # what is left of the loader's current epoch
+                ep["epoch"], ep["j"], ep["last"] = loader.epoch, j, j + 1 == n_b
+                yield b_
 
         fixed_before = loader.fixed_width if loader is not None else None
         if loader is not None and graph != "off":
             loader.fixed_width = True  # one shape for the captured step -- and one layout for the steps around it
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            it = iter(batches) if max_epochs is None else _epochs()
-            nxt = next(it, None)
+            it = _epochs() if max_epochs is not None else (_one_pass() if loader is not None else iter(batches))
+            # `i` counts this call's batches (the capture's warm-up and the probe are this call's), `base + i` all of them
+            nxt = next(it, None) if (not resumed or max_steps is None or base < max_steps) else None
             i = 0
-            while nxt is not None and (max_steps is None or i < max_steps):
+            while nxt is not None and (max_steps is None or base + i < max_steps):
                 b = nxt
                 on_host = not b[SEQ_BATCH_KEYS[0]].is_cuda
                 if on_host:
@@ -1192,19 +1389,34 @@ class Trainer:
                 else:
                     out.append(self.fit_step(dev_b))
                 i += 1
-                if val is not None and val_check_interval is not None and i % val_check_interval == 0 and _validate(i):
+                done = base + i
+                if loader is None:
+                    pos = (0, done)
+                else:  # from the loop's own counters: the batch after the last one of epoch e is batch 0 of epoch e + 1
+                    pos = (ep["epoch"] + 1, 0) if ep["last"] else (ep["epoch"], ep["j"] + 1)
+                stop = False
+                if val is not None and val_check_interval is not None and done % val_check_interval == 0:
+                    stop = _validate(done)
+                elif (val is not None and val_check_interval is None and max_epochs is not None and ep["last"]
+                        and (ep["epoch"] + 1) % check_val_every_n_epoch == 0):
+                    stop = _validate(done)
+                if checkpoint_every_n_steps is not None and done % checkpoint_every_n_steps == 0:
+                    _checkpoint(done)  # behind the pass that fell on this batch: the file carries it
+                if stop:
                     self.stopped_early = True
                     break
-                if (val is not None and val_check_interval is None and max_epochs is not None and ep["last"]
-                        and (ep["epoch"] + 1) % check_val_every_n_epoch == 0 and _validate(i)):
-                    self.stopped_early = True
+                if time_limit is not None and time.monotonic() - t_fit >= time_limit:  # (a host clock: no device sync)
+                    self.stopped_on_time = True
                     break
                 if loader is not None:
                     # a loader's slots are rewritten underneath the steps: the next batch is asked for once this step is enqueued
                     # (and only if it will be stepped on: the loader's state then names the batch a resumed run starts with)
-                    nxt = next(it, None) if max_steps is None or i < max_steps else None
+                    nxt = next(it, None) if max_steps is None or done < max_steps else None
             if val is not None and val_check_interval is None and max_epochs is None and i > 0:
-                _validate(i)
+                _validate(base + i)
+            self._loop = _loop_state(base + i)
+            if save_last:
+                _checkpoint(base + i)
         if loader is not None:
             loader.fixed_width = fixed_before
         if side is not None:
