@@ -66,9 +66,11 @@ enum { XFMR_PREC_F32 = 0, XFMR_PREC_BF16 = 1 };
 /* Self-attention mask. CAUSAL is what the reference builds (BertConfig(is_decoder=True), xfmr_rec/models.py:355);
  * BIDIRECTIONAL is BertConfig.is_decoder=False: the key-padding mask alone (TF:masking_utils.py bidirectional mask). */
 enum { XFMR_ATTN_CAUSAL = 0, XFMR_ATTN_BIDIRECTIONAL = 1 };
-/* OR-ed into attn_mode: run the key-streaming form of the generic attention kernels (fp32 policy, head size 64) at any
- * L, instead of the whole-panel form where that fits LDS. Same results, bit for bit; meant for tests and timing. The
- * bf16 policy at head size 32 ignores it. The streaming form runs anyway where the panel does not fit. */
+/* OR-ed into attn_mode: run the key-streaming form of the attention kernels at any L, instead of the whole-panel form
+ * where that fits LDS. Generic kernels (fp32 policy, head size 64): same results as the panel form, bit for bit. bf16
+ * policy at head size 32: the key-streaming two-kernel form, bit-identical to the two-kernel panel form (and, where the
+ * default would be a one-workgroup form, equal to it within the bf16 tolerance only). Meant for tests and timing. The
+ * streaming form runs anyway where the panel does not fit. */
 enum { XFMR_ATTN_STREAM_KEYS = 2 };
 /* xfmr_encoder_cfg.flags. The *_UNFUSED / DW_INLINE bits select the separate-launch forms of fused kernels (A/B
  * measurements, parity of fused vs unfused forms in tests/): the forward and the backward of a step get the same cfg, so

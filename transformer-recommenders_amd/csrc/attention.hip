@@ -9,8 +9,8 @@
 //   O^T  += V^T  P^T      dQ^T += K^T dS^T      dV^T += dO^T (P.D)      dK^T += Q^T dS
 // One workgroup = 4 waves = 128 consecutive rows (queries, or keys for dK/dV) of one (batch, head);
 // the whole K/V (or Q/dO) panel of that head that the causal mask can reach is staged once into LDS
-// (while it fits 160 KiB), so there is a single barrier per kernel; longer sequences run the key-streaming forms of
-// the generic kernels, which pass the panel through LDS in fixed-size chunks.
+// (while it fits 160 KiB), so there is a single barrier per kernel; longer sequences run the key-streaming forms
+// (of the generic and of the production kernels), which pass the panel through LDS in fixed-size chunks.
 #include "internal.h"
 
 namespace {
@@ -1055,6 +1055,334 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_bf16_kernel(const AttnArg
   xf_store_tile_T_at<S16>(sc_w, dv, 1.f, a.d_qkv, tok0 * 3 * H + 2 * H + h * DH, 3 * H, k0, L);
 }
 
+// ---- key-streaming forms of the three kernels above: any sequence length ------------------------------------------
+// Same 128-row blocks through the same attn_block() mapping, the same 32-row tiles in the same order and the same
+// per-tile code (one swizzled image per operand, tile_nreg / tile_xb_tr, the interior fast path, xf_exp2, dropout by
+// the absolute key / row index), but the K/V (forward, dQ) or Q/dO + lse / delta / row-key (dK/dV) panel passes through
+// LDS in chunks of kBf16StreamCH rows, so LDS use does not depend on L. Single-buffered: per chunk, stage -> barrier ->
+// every wave runs the tiles of the chunk its (causal) range reaches -> barrier. A wave with nothing left (rows past L,
+// or past its causal end) still stages and waits at every barrier. After the last chunk the 4 x 32 x 33 fp32
+// output-transposition scratch aliases the chunk images. Results are bit-identical to the panel kernels.
+//   Chunk size: 256 rows, not 128. Every chunk costs two barriers and one exposed global-load latency (nothing is in
+//   flight while the waves wait for the images), so the fewer chunks the better; 128 rows would be 16 KiB of images,
+//   less than the 16.5 KiB scratch they have to hold anyway, while 256 rows is 32 KiB of images and still leaves the
+//   largest kernel (dK/dV: 35 840 B) under the 40 KiB at which four workgroups per CU share the 160 KiB.
+//                  fwd, dQ (K, V, key bits)   dK/dV (Q, dO, lse, delta, row keys)
+//   LDS            32 816 B                   35 840 B
+constexpr int kBf16StreamCH = 256;
+struct Bf16Stream {
+  static constexpr int CH = kBf16StreamCH;
+  static constexpr size_t kImg = (size_t)CH * DH * 2;  // one swizzled row image
+  static constexpr size_t kScratch = 4 * 32 * 33 * sizeof(float);
+  static constexpr size_t kBits = ((CH / 32 + 2) * sizeof(uint32_t) + 15) & ~(size_t)15;  // (slack words as bf16_smem_fwd)
+  static constexpr size_t fwd_bytes() { return 2 * kImg + kBits; }  // forward and dQ
+  static constexpr size_t dkv_bytes() { return 2 * kImg + 3 * (size_t)CH * sizeof(float); }
+  static_assert(CH % 64 == 0, "whole tiles and whole ballot words per chunk");
+  static_assert(2 * kImg >= kScratch, "the output-transposition scratch aliases the two chunk images");
+};
+static_assert(Bf16Stream::fwd_bytes() <= 40 * 1024 && Bf16Stream::dkv_bytes() <= 40 * 1024,
+              "four workgroups per CU in 160 KiB of LDS");
+
+template <bool S16>
+__global__ __launch_bounds__(256, 4) void attn_fwd_stream_bf16_kernel(const AttnArgs a_in) {
+  AttnArgs a = a_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
+  XF_CHAIN_PRIO();
+  a.drop = xf_drop_resolve(a.drop);
+  using ST = Bf16Stream;
+  constexpr int CH = ST::CH;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int L = a.L, H = a.H;
+  const AttnBlock blk = attn_block(a);
+  if (!blk.valid) return;  // (whole workgroup: the grid is padded to a multiple of 8 sequences)
+  const int b = blk.by / a.A, h = blk.by % a.A;
+  const int qblk0 = blk.bx * 128;
+  const int nkeys = a.causal ? min(((L + 31) / 32) * 32, qblk0 + 128) : ((L + 31) / 32) * 32;
+  __bf16* sK = reinterpret_cast<__bf16*>(smem_raw);
+  __bf16* sV = sK + CH * DH;
+  float* scratch = reinterpret_cast<float*>(smem_raw);  // after the last chunk
+  uint32_t* sBits = reinterpret_cast<uint32_t*>(smem_raw + 2 * ST::kImg);  // key mask of the chunk, one bit per key
+
+  const int64_t tok0 = (int64_t)b * L;
+  const int lane = xf_lane(), wid = threadIdx.x >> 6;
+  const int q0 = qblk0 + wid * 32;
+  const bool active = q0 < L;  // (wave-uniform) inactive waves still stage and take part in every barrier
+  const int q = q0 + (lane & 31);
+  RegRows<PrecBF16, DH> qreg;
+  qreg.load_at<S16>(a.qkv, (tok0 + q) * 3 * H + h * DH, active && q < L);
+  const float sc = 0.17677669529663687f * kLog2e;
+  float m = -INFINITY, lsum = 0.f;
+  f32x16 o;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) o[r] = 0.f;
+  const uint32_t rowkey = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * L + q));
+  const int kb_end = !active ? -1 : a.causal ? min((q0 + 31) / 32, nkeys / 32 - 1) : nkeys / 32 - 1;
+  for (int c0 = 0; c0 < nkeys; c0 += CH) {
+    const int nr = min(CH, nkeys - c0);
+    stage2_rows_swz<S16>(sK, a.qkv, tok0 * 3 * H + H + h * DH, 3 * H, sV, a.qkv, tok0 * 3 * H + 2 * H + h * DH, 3 * H, c0,
+                         nr, L);
+    stage_key_bits(sBits, a.key_mask + tok0 + c0, nr, L - c0);
+    __syncthreads();
+    const int kb_hi = min(kb_end, (c0 + nr) / 32 - 1);
+    for (int kb = c0 / 32; kb <= kb_hi; ++kb) {
+      const int row0 = kb * 32 - c0;
+      f32x16 s;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = 0.f;
+      AI::tile_nreg(s, sK, row0, qreg.regs());
+      float bmax = -INFINITY;
+      const uint32_t kword = sBits[row0 >> 5];
+      const bool interior = (kb * 32 + 31 <= q0 || !a.causal) && __builtin_amdgcn_readfirstlane(kword) == 0xFFFFFFFFu;
+      if (interior) {  // (see attn_fwd_bf16_kernel)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bmax = fmaxf(bmax, s[r]);
+        bmax *= sc;
+      } else {
+        const uint32_t kbits = kword >> (4 * (lane >> 5));  // this half-wave's keys: bit (r&3) + 8*(r>>2)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = kb * 32 + xf_acc_row(r, lane);
+          const bool vis = (key <= q || !a.causal) && ((kbits >> ((r & 3) + 8 * (r >> 2))) & 1u);
+          s[r] = vis ? s[r] : -INFINITY;
+          bmax = fmaxf(bmax, s[r]);
+        }
+        bmax *= sc;  // (sc > 0; -inf stays -inf)
+      }
+      bmax = fmaxf(bmax, xf_half_swap(bmax));
+      const float mnew = fmaxf(m, bmax);
+      if (__all(mnew == -INFINITY)) continue;
+      const float msafe = (mnew == -INFINITY) ? 0.f : mnew;
+      const float alpha = xf_exp2(m - msafe);
+      float psum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = xf_exp2(fmaf(s[r], sc, -msafe));
+        psum += p;
+        s[r] = a.drop.on ? p * xf_keep_scale_rc(a.drop, rowkey, (uint32_t)(kb * 32 + xf_acc_row(r, lane)) * kDropColMul) : p;
+      }
+      lsum = lsum * alpha + psum;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[r] *= alpha;
+      m = mnew;
+      AI::tile_xb_tr(o, sV, 0, row0, s);
+    }
+    __syncthreads();  // every wave is done with the chunk (and, after the last one, with the images the scratch aliases)
+  }
+  const float ltot = lsum + xf_half_swap(lsum);
+  const float inv = ltot > 0.f ? 1.f / ltot : 0.f;
+  if (!active) return;
+  xf_store_tile_T_at<S16>(scratch + wid * 32 * 33, o, inv, a.ctx, tok0 * H + h * DH, H, q0, L);
+  if (lane < 32 && q < L)
+    a.lse[((int64_t)blk.by) * L + q] = ltot > 0.f ? (m + log2f(ltot)) * kLn2 : INFINITY;
+}
+
+template <bool S16>
+__global__ __launch_bounds__(256, 4) void attn_bwd_dq_stream_bf16_kernel(const AttnArgs a_in) {
+  AttnArgs a = a_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
+  XF_CHAIN_PRIO();
+  a.drop = xf_drop_resolve(a.drop);
+  using ST = Bf16Stream;
+  constexpr int CH = ST::CH;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int L = a.L, H = a.H;
+  const AttnBlock blk = attn_block(a);
+  if (!blk.valid) return;  // (whole workgroup: the grid is padded to a multiple of 8 sequences)
+  const int b = blk.by / a.A, h = blk.by % a.A;
+  const int qblk0 = blk.bx * 128;
+  const int nkeys = a.causal ? min(((L + 31) / 32) * 32, qblk0 + 128) : ((L + 31) / 32) * 32;
+  __bf16* sK = reinterpret_cast<__bf16*>(smem_raw);
+  __bf16* sV = sK + CH * DH;
+  float* scratch = reinterpret_cast<float*>(smem_raw);  // after the last chunk
+  uint32_t* sBits = reinterpret_cast<uint32_t*>(smem_raw + 2 * ST::kImg);  // key mask of the chunk, one bit per key
+
+  const int64_t tok0 = (int64_t)b * L;
+  const int lane = xf_lane(), wid = threadIdx.x >> 6;
+  const int q0 = qblk0 + wid * 32;
+  const bool active = q0 < L;
+  const int q = q0 + (lane & 31);
+  const bool qv = active && q < L;
+  RegRows<PrecBF16, DH> qreg, doreg;
+  qreg.load_at<S16>(a.qkv, (tok0 + q) * 3 * H + h * DH, qv);
+  doreg.load_at<S16>(a.d_ctx, (tok0 + q) * H + h * DH, qv);
+  float delta = 0.f;
+  if (qv) delta = dot16<S16>(a.ctx, a.d_ctx, (tok0 + q) * H + h * DH + 16 * (lane >> 5));
+  delta += xf_half_swap(delta);
+  const float lse2 = qv ? a.lse[(int64_t)blk.by * L + q] * kLog2e : INFINITY;
+  const float sc = 0.17677669529663687f * kLog2e;
+  const uint32_t rowkey = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * L + q));
+  f32x16 dq;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dq[r] = 0.f;
+  const int kb_end = !active ? -1 : a.causal ? min((q0 + 31) / 32, nkeys / 32 - 1) : nkeys / 32 - 1;
+  for (int c0 = 0; c0 < nkeys; c0 += CH) {
+    const int nr = min(CH, nkeys - c0);
+    stage2_rows_swz<S16>(sK, a.qkv, tok0 * 3 * H + H + h * DH, 3 * H, sV, a.qkv, tok0 * 3 * H + 2 * H + h * DH, 3 * H, c0,
+                         nr, L);
+    stage_key_bits(sBits, a.key_mask + tok0 + c0, nr, L - c0);
+    __syncthreads();
+    const int kb_hi = min(kb_end, (c0 + nr) / 32 - 1);
+    for (int kb = c0 / 32; kb <= kb_hi; ++kb) {
+      const int row0 = kb * 32 - c0;
+      f32x16 s, dp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+      AI::tile_nreg(s, sK, row0, qreg.regs());
+      AI::tile_nreg(dp, sV, row0, doreg.regs());
+      const uint32_t kword = sBits[row0 >> 5];
+      const bool interior = (kb * 32 + 31 <= q0 || !a.causal) && __builtin_amdgcn_readfirstlane(kword) == 0xFFFFFFFFu;
+      if (interior) {  // (see attn_fwd_bf16_kernel)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = xf_exp2(fmaf(s[r], sc, -lse2));
+          float dpv = dp[r];
+          if (a.drop.on) dpv *= xf_keep_scale_rc(a.drop, rowkey, (uint32_t)(kb * 32 + xf_acc_row(r, lane)) * kDropColMul);
+          s[r] = p * (dpv - delta);
+        }
+      } else {
+        const uint32_t kbits = kword >> (4 * (lane >> 5));
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = kb * 32 + xf_acc_row(r, lane);
+          const bool vis = (key <= q || !a.causal) && ((kbits >> ((r & 3) + 8 * (r >> 2))) & 1u);
+          const float p = vis ? xf_exp2(fmaf(s[r], sc, -lse2)) : 0.f;
+          float dpv = dp[r];
+          if (a.drop.on) dpv *= xf_keep_scale_rc(a.drop, rowkey, (uint32_t)key * kDropColMul);
+          s[r] = p * (dpv - delta);
+        }
+      }
+      AI::tile_xb_tr(dq, sK, 0, row0, s);
+    }
+    __syncthreads();  // every wave is done with the chunk (and, after the last one, with the images the scratch aliases)
+  }
+  if (!active) return;
+  xf_store_tile_T_at<S16>(scratch + wid * 32 * 33, dq, 0.17677669529663687f, a.d_qkv, tok0 * 3 * H + h * DH, 3 * H, q0,
+                          L);
+}
+
+// (three workgroups per CU, as the panel dK/dV kernel: at four -- 128 VGPRs -- the compiler spills 140 bytes per lane in the
+// tile loop; LDS would hold the fourth)
+template <bool S16>
+__global__ __launch_bounds__(256, 3) void attn_bwd_dkv_stream_bf16_kernel(const AttnArgs a_in) {
+  AttnArgs a = a_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
+  XF_CHAIN_PRIO();
+  a.drop = xf_drop_resolve(a.drop);
+  using ST = Bf16Stream;
+  constexpr int CH = ST::CH;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int L = a.L, H = a.H;
+  const AttnBlock blk = attn_block(a);
+  if (!blk.valid) return;  // (whole workgroup: the grid is padded to a multiple of 8 sequences)
+  const int b = blk.by / a.A, h = blk.by % a.A;
+  const int kblk0 = blk.bx * 128;
+  const int Lp = ((L + 31) / 32) * 32;
+  const int qs = a.causal ? kblk0 : 0;  // first query this block's keys are visible to
+  __bf16* sQ = reinterpret_cast<__bf16*>(smem_raw);  // queries [qs, Lp) stream through in chunks; image row = q - c0
+  __bf16* sDO = sQ + CH * DH;
+  float* scratch = reinterpret_cast<float*>(smem_raw);  // after the last chunk
+  float* sLse = reinterpret_cast<float*>(smem_raw + 2 * ST::kImg);  // [CH] log2-scaled lse
+  float* sDelta = sLse + CH;                                          // [CH]
+  uint32_t* sRowKey = reinterpret_cast<uint32_t*>(sDelta + CH);       // [CH] dropout row keys of the staged query rows
+
+  const int64_t tok0 = (int64_t)b * L;
+  const int64_t hoff = tok0 * H + h * DH;
+  const int lane = xf_lane(), wid = threadIdx.x >> 6;
+  const int k0 = kblk0 + wid * 32;
+  const bool active = k0 < L;
+  const int key = k0 + (lane & 31);
+  const bool kvis = active && key < L && a.key_mask[tok0 + (key < L ? key : 0)];
+  RegRows<PrecBF16, DH> kreg, vreg;
+  kreg.load_at<S16>(a.qkv, (tok0 + key) * 3 * H + H + h * DH, active && key < L);
+  vreg.load_at<S16>(a.qkv, (tok0 + key) * 3 * H + 2 * H + h * DH, active && key < L);
+  const float sc = 0.17677669529663687f * kLog2e;
+  f32x16 dk, dv;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { dk[r] = 0.f; dv[r] = 0.f; }
+  const bool all_kvis = __all(kvis);
+  const uint32_t colmix = (uint32_t)key * kDropColMul;
+  const int qb_lo = !active ? Lp / 32 : a.causal ? k0 / 32 : 0;
+  for (int c0 = qs; c0 < Lp; c0 += CH) {
+    const int nr = min(CH, Lp - c0);
+    stage2_rows_swz<S16>(sQ, a.qkv, tok0 * 3 * H + h * DH, 3 * H, sDO, a.d_ctx, hoff, H, c0, nr, L);
+    // delta[r] = rowsum(dO * O), lse[r]: loads of a batch of 4 pieces issued together (see stage2_rows_swz)
+    for (int p0 = threadIdx.x; p0 < nr * 8; p0 += (int)blockDim.x * 4) {
+      float4 x[4], y[4];
+      float ls[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int c = p0 + u * (int)blockDim.x, r = c >> 3, dd = (c & 7) * 4;
+        x[u] = y[u] = make_float4(0, 0, 0, 0);
+        ls[u] = INFINITY;
+        if (c < nr * 8 && c0 + r < L) {
+          x[u] = xf_ld4<S16>(a.ctx, hoff + (int64_t)(c0 + r) * H + dd);
+          y[u] = xf_ld4<S16>(a.d_ctx, hoff + (int64_t)(c0 + r) * H + dd);
+          if ((c & 7) == 0) ls[u] = a.lse[(int64_t)blk.by * L + c0 + r] * kLog2e;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int c = p0 + u * (int)blockDim.x, r = c >> 3;
+        float part = x[u].x * y[u].x + x[u].y * y[u].y + x[u].z * y[u].z + x[u].w * y[u].w;
+        part += __shfl_xor(part, 1, 64);
+        part += __shfl_xor(part, 2, 64);
+        part += __shfl_xor(part, 4, 64);
+        if (c < nr * 8 && (c & 7) == 0) {
+          sDelta[r] = part;
+          sLse[r] = ls[u];
+          sRowKey[r] = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * L + c0 + r));
+        }
+      }
+    }
+    __syncthreads();
+    const int qb_hi = (c0 + nr) / 32;
+    for (int qb = max(qb_lo, c0 / 32); qb < qb_hi; ++qb) {
+      const int row0 = qb * 32 - c0;
+      f32x16 s, dp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+      AI::tile_nreg(s, sQ, row0, kreg.regs());
+      AI::tile_nreg(dp, sDO, row0, vreg.regs());
+      const bool interior = all_kvis && (qb * 32 > k0 || !a.causal);  // every query row is after the wave's keys, every key valid
+      // the lane's 16 query rows are four runs of 4 consecutive rows: lse / delta come as 16-byte LDS reads
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int qi0 = row0 + 8 * g + 4 * (lane >> 5);
+        const float4 l4 = *reinterpret_cast<const float4*>(&sLse[qi0]);
+        const float4 d4 = *reinterpret_cast<const float4*>(&sDelta[qi0]);
+        const float ls[4] = {l4.x, l4.y, l4.z, l4.w}, dl[4] = {d4.x, d4.y, d4.z, d4.w};
+        uint32_t rk[4] = {0u, 0u, 0u, 0u};
+        if (a.drop.on) {
+          const uint4 k4 = *reinterpret_cast<const uint4*>(&sRowKey[qi0]);
+          rk[0] = k4.x; rk[1] = k4.y; rk[2] = k4.z; rk[3] = k4.w;
+        }
+        float pr[4];
+        if (interior) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) pr[u] = xf_exp2(fmaf(s[4 * g + u], sc, -ls[u]));
+        } else {
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            pr[u] = (kvis && (key <= qi0 + u + c0 || !a.causal)) ? xf_exp2(fmaf(s[4 * g + u], sc, -ls[u])) : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int r = 4 * g + u;
+          const float p = pr[u];
+          float keep = 1.f;
+          if (a.drop.on) keep = xf_keep_scale_rc(a.drop, rk[u], colmix);
+          s[r] = p * (dp[r] * keep - dl[u]);
+          dp[r] = p * keep;
+        }
+      }
+      AI::tile_xb_tr(dv, sDO, 0, row0, dp);
+      AI::tile_xb_tr(dk, sQ, 0, row0, s);
+    }
+    __syncthreads();  // every wave is done with the chunk (and, after the last one, with the images the scratch aliases)
+  }
+  if (!active) return;
+  float* sc_w = scratch + wid * 32 * 33;
+  xf_store_tile_T_at<S16>(sc_w, dk, 0.17677669529663687f, a.d_qkv, tok0 * 3 * H + H + h * DH, 3 * H, k0, L);
+  xf_store_tile_T_at<S16>(sc_w, dv, 1.f, a.d_qkv, tok0 * 3 * H + 2 * H + h * DH, 3 * H, k0, L);
+}
+
 // ---- fused backward: ONE workgroup per (batch, head) computes dQ, dK and dV -------------------------------------
 // The two-kernel form stages Q / dO / ctx / d_ctx (dK/dV kernel) and K / V / q / dO / ctx / d_ctx (dQ kernel) per
 // 128-row block and evaluates every probability twice; measured at B = 512, L = 200: 40 + 61 us of the 65 + 132 us
@@ -1748,11 +2076,15 @@ size_t dkv_smem(int L) {
 }
 constexpr size_t kLdsLimit = 160 * 1024;
 
+// stream_keys (XFMR_ATTN_STREAM_KEYS, the tests' and the benchmark's streaming-vs-panel switch; padded layout only): the
+// key-streaming two-kernel forms at any L, also where the one-workgroup or the panel forms would have run. With the bit
+// clear they run only where the panel does not fit LDS.
 template <bool S16>
-int launch_fwd_bf16(const AttnArgs& a, hipStream_t st) {
+int launch_fwd_bf16(const AttnArgs& a, hipStream_t st, bool stream_keys) {
+  const bool stream = stream_keys && !a.offs;
   static const int two_blocks = [] { const char* e = getenv("XFMR_ATTN_FWD_SPLIT"); return e ? atoi(e) : 0; }();
   if (a.offs && !(a.causal && a.L <= kSeqMaxL)) return XFMR_EUNSUPPORTED;  // packed rows: the one-workgroup forms only
-  if ((!two_blocks || a.offs) && a.causal && a.L <= kSeqMaxL) {  // the one-workgroup forms walk the causal triangle only
+  if (!stream && (!two_blocks || a.offs) && a.causal && a.L <= kSeqMaxL) {  // the one-workgroup forms walk the causal triangle only
     const size_t sf = bf16_smem_fwd_seq(a.L);
     if (hipFuncSetAttribute((const void*)attn_fwd_seq_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sf) != hipSuccess)
@@ -1764,7 +2096,15 @@ int launch_fwd_bf16(const AttnArgs& a, hipStream_t st) {
   }
   dim3 grid((unsigned)(((a.L + 127) / 128) * a.A * ((a.B + 7) / 8) * 8));  // see attn_block
   const size_t sm = bf16_smem_fwd(a.L);
-  if (sm > kLdsLimit) return XFMR_EUNSUPPORTED;
+  if (stream || sm > kLdsLimit) {  // the K/V panel does not fit: it passes through LDS in chunks
+    constexpr size_t ss = Bf16Stream::fwd_bytes();
+    if (hipFuncSetAttribute((const void*)attn_fwd_stream_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)ss) != hipSuccess)
+      return XFMR_EHIP;
+    hipLaunchKernelGGL((attn_fwd_stream_bf16_kernel<S16>), grid, dim3(256), ss, st, a);
+    XF_LAUNCH_CHECK();
+    return XFMR_OK;
+  }
   if (hipFuncSetAttribute((const void*)attn_fwd_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)sm) != hipSuccess)
     return XFMR_EHIP;
@@ -1773,7 +2113,8 @@ int launch_fwd_bf16(const AttnArgs& a, hipStream_t st) {
   return XFMR_OK;
 }
 template <bool S16>
-int launch_bwd_bf16(const AttnArgs& a, hipStream_t st) {
+int launch_bwd_bf16(const AttnArgs& a, hipStream_t st, bool stream_keys) {
+  const bool stream = stream_keys && !a.offs;  // (see launch_fwd_bf16)
   static const int two_kernels = [] { const char* e = getenv("XFMR_ATTN_BWD_SPLIT"); return e ? atoi(e) : 0; }();
   // the one-workgroup forms: round 1's four-wave lock-step form, or -- XFMR_ATTN_BWD_FORM=roles, read per call -- round 4's
   // "roles" (eight waves, two roles, one barrier). MEASURED, alternating runs on one box, batch 512: 113.9 / 112.1 us per
@@ -1785,7 +2126,7 @@ int launch_bwd_bf16(const AttnArgs& a, hipStream_t st) {
   if (a.offs && !(a.causal && a.L <= kSeqMaxL)) return XFMR_EUNSUPPORTED;  // packed rows: the one-workgroup forms only
   // 256 < L <= 512 (BASELINE config 5): the two-role form is the one-workgroup backward there (the lock-step form's schedule
   // table stops at eight tiles): Q, K, V, dO of 512 rows are 128 KB of LDS -- one workgroup of eight waves per CU
-  if ((!two_kernels || a.offs) && (roles || a.L > kFusedMaxL) && a.causal && a.L <= kSeqMaxL) {
+  if (!stream && (!two_kernels || a.offs) && (roles || a.L > kFusedMaxL) && a.causal && a.L <= kSeqMaxL) {
     const size_t sr = bf16_smem_roles(a.L);
     const dim3 grid((unsigned)(a.A * ((a.B + 7) / 8) * 8));
     if (a.L > kFusedMaxL) {
@@ -1803,7 +2144,7 @@ int launch_bwd_bf16(const AttnArgs& a, hipStream_t st) {
     return XFMR_OK;
   }
   const size_t sf = bf16_smem_fused(a.L);
-  if ((!two_kernels || a.offs) && a.causal && a.L <= kFusedMaxL && sf <= kLdsLimit) {
+  if (!stream && (!two_kernels || a.offs) && a.causal && a.L <= kFusedMaxL && sf <= kLdsLimit) {
     if (hipFuncSetAttribute((const void*)attn_bwd_fused_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sf) != hipSuccess)
       return XFMR_EHIP;
@@ -1814,7 +2155,19 @@ int launch_bwd_bf16(const AttnArgs& a, hipStream_t st) {
   }
   dim3 grid((unsigned)(((a.L + 127) / 128) * a.A * ((a.B + 7) / 8) * 8));  // see attn_block
   const size_t s1 = bf16_smem_fwd(a.L), s2 = bf16_smem_dkv(a.L);
-  if (s1 > kLdsLimit || s2 > kLdsLimit) return XFMR_EUNSUPPORTED;
+  if (stream || s1 > kLdsLimit || s2 > kLdsLimit) {  // a K/V or Q/dO panel does not fit: chunks through LDS
+    constexpr size_t ss1 = Bf16Stream::fwd_bytes(), ss2 = Bf16Stream::dkv_bytes();
+    if (hipFuncSetAttribute((const void*)attn_bwd_dq_stream_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)ss1) != hipSuccess ||
+        hipFuncSetAttribute((const void*)attn_bwd_dkv_stream_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)ss2) != hipSuccess)
+      return XFMR_EHIP;
+    hipLaunchKernelGGL((attn_bwd_dq_stream_bf16_kernel<S16>), grid, dim3(256), ss1, st, a);
+    XF_LAUNCH_CHECK();
+    hipLaunchKernelGGL((attn_bwd_dkv_stream_bf16_kernel<S16>), grid, dim3(256), ss2, st, a);
+    XF_LAUNCH_CHECK();
+    return XFMR_OK;
+  }
   if (hipFuncSetAttribute((const void*)attn_bwd_dq_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)s1) != hipSuccess ||
       hipFuncSetAttribute((const void*)attn_bwd_dkv_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1885,7 +2238,7 @@ int dispatch_fwd(const AttnArgs& a, int precision, bool s16, hipStream_t st, boo
   const int dh = a.H / a.A;
   if (a.offs && !(precision == XFMR_PREC_BF16 && dh == 32)) return XFMR_EUNSUPPORTED;  // packed rows: production kernels only
   if (precision == XFMR_PREC_BF16) {
-    if (dh == 32) return s16 ? launch_fwd_bf16<true>(a, st) : launch_fwd_bf16<false>(a, st);
+    if (dh == 32) return s16 ? launch_fwd_bf16<true>(a, st, stream_keys) : launch_fwd_bf16<false>(a, st, stream_keys);
     return s16 ? launch_fwd_generic<PrecBF16, 64, true>(a, st, stream_keys)
                : launch_fwd_generic<PrecBF16, 64, false>(a, st, stream_keys);
   }
@@ -1898,7 +2251,7 @@ int dispatch_bwd(const AttnArgs& a, int precision, bool s16, hipStream_t st, boo
   const int dh = a.H / a.A;
   if (a.offs && !(precision == XFMR_PREC_BF16 && dh == 32)) return XFMR_EUNSUPPORTED;
   if (precision == XFMR_PREC_BF16) {
-    if (dh == 32) return s16 ? launch_bwd_bf16<true>(a, st) : launch_bwd_bf16<false>(a, st);
+    if (dh == 32) return s16 ? launch_bwd_bf16<true>(a, st, stream_keys) : launch_bwd_bf16<false>(a, st, stream_keys);
     return s16 ? launch_bwd_generic<PrecBF16, 64, true>(a, st, stream_keys)
                : launch_bwd_generic<PrecBF16, 64, false>(a, st, stream_keys);
   }

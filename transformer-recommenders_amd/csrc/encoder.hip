@@ -308,8 +308,8 @@ const char* xfmr_strerror(int code) {
     case XFMR_EINVAL: return "invalid argument";
     case XFMR_EUNSUPPORTED:
       return "shape not supported by the gfx950 kernels (head size must be 32 or 64; the fused loss takes any d_model that is a "
-             "multiple of 32 up to 1024 in the bf16 policy and up to 512 in fp32; attention at head size 32 in the bf16 policy "
-             "takes L <= 1024 (packed rows: L <= 512, causal), the fp32 policy and head size 64 take any L)";
+             "multiple of 32 up to 1024 in the bf16 policy and up to 512 in fp32; attention takes any L in the padded layout, "
+             "packed rows: bf16 policy at head size 32, L <= 512, causal)";
     case XFMR_EWORKSPACE: return "workspace too small";
     case XFMR_EHIP: return "HIP launch failed";
     case XFMR_EALIGN: return "pointer or leading dimension not 16-byte aligned";

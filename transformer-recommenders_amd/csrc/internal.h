@@ -77,7 +77,9 @@ int xf_rowsum(float* dst, const float* src, int64_t rows, int64_t cols, hipStrea
 int xf_attn_fwd_ex(const void* qkv, const uint8_t* key_mask, void* ctx, float* lse, int32_t B, int32_t L, int32_t A,
                    int32_t H, float dropout_p, XfSeed seed, uint32_t site, int32_t precision, bool s16,
                    bool causal, hipStream_t st, const int32_t* seq_offsets = nullptr,  // packed rows: xfmr_encoder_cfg
-                   bool stream_keys = false);  // generic kernels: the key-streaming form at any L (XFMR_ATTN_STREAM_KEYS)
+                   bool stream_keys = false);  // the key-streaming form at any L (XFMR_ATTN_STREAM_KEYS): generic kernels, and
+                                               // bf16 at head size 32 without seq_offsets -- its streaming two-kernel
+                                               // form, bit-identical to the two-kernel panel form
 int xf_attn_bwd_ex(const void* qkv, const uint8_t* key_mask, const void* ctx, const float* lse, const void* d_ctx,
                    void* d_qkv, int32_t B, int32_t L, int32_t A, int32_t H, float dropout_p, XfSeed seed,
                    uint32_t site, int32_t precision, bool s16, bool causal, hipStream_t st,

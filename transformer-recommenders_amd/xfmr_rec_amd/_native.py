@@ -22,7 +22,7 @@ PRECISIONS = {"fp32": PREC_F32, "f32": PREC_F32, "bf16": PREC_BF16}
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RES = 0, 1, 2
 NEG_SHARED, NEG_CATALOG = 0, 1
 ATTN_CAUSAL, ATTN_BIDIRECTIONAL = 0, 1  # xfmr_attn_{fwd,bwd}_mode
-ATTN_STREAM_KEYS = 2  # OR-ed into the attn_mode above: the key-streaming form of the generic kernels at any L
+ATTN_STREAM_KEYS = 2  # OR-ed into the attn_mode above: the key-streaming form at any L (generic kernels; bf16 head size 32)
 # xfmr_encoder_cfg.flags
 ENC_BIDIRECTIONAL, ENC_LN_UNFUSED, ENC_FFN_UNFUSED, ENC_FFN_BWD_UNFUSED, ENC_DW_INLINE, ENC_DW_SIDE_ANY = 1, 2, 4, 8, 16, 32
 ENC_DW_UNPAIRED, ENC_REDUCE_HALF_EARLY = 64, 128

@@ -136,8 +136,9 @@ def colsum(a):
 
 
 def attn_fwd(qkv, key_mask, heads, *, dropout_p=0.0, seed=0, site=0, precision="bf16", causal=True, stream_keys=False):
-    """stream_keys: the key-streaming form of the generic kernels (fp32 policy, head size 64) even where the whole-panel
-    form fits LDS -- bit-identical results; the bf16 policy at head size 32 ignores it."""
+    """stream_keys: the key-streaming form even where the whole-panel form fits LDS. Generic kernels (fp32 policy, head
+    size 64): bit-identical results. bf16 policy at head size 32: the key-streaming two-kernel form, bit-identical to the
+    two-kernel panel form; against the one-workgroup forms (causal, L <= 512) equal within the bf16 tolerance only."""
     B, L, H3 = qkv.shape
     H = H3 // 3
     ctx, lse = _empty((B, L, H), qkv), _empty((B, heads, L), qkv)
@@ -154,6 +155,8 @@ def attn_fwd(qkv, key_mask, heads, *, dropout_p=0.0, seed=0, site=0, precision="
 
 def attn_bwd(qkv, key_mask, ctx, lse, d_ctx, heads, *, dropout_p=0.0, seed=0, site=0, precision="bf16", causal=True,
              stream_keys=False):
+    """stream_keys: as attn_fwd -- the key-streaming dQ and dK/dV kernels at any L. In the bf16 policy at head size 32 they
+    are bit-identical to the two-kernel panel form, and within the bf16 gradient tolerance of the one-workgroup forms."""
     B, L, H3 = qkv.shape
     d_qkv = torch.empty_like(qkv)
     lib = N.load()
