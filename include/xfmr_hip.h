@@ -216,7 +216,8 @@ typedef struct xfmr_encoder_cfg {
    * `packed_rows` = seq_offsets[batch] rows long), len_b <= seq_len. Every row-wise kernel (Linears, LayerNorms, FFN,
    * their backward, the weight gradients) then runs packed_rows rows instead of batch * seq_len; attention walks each
    * sequence's own length. Valid rows get the values of the padded layout bit for bit (dropout aside: its masks are keyed
-   * by the row index). bf16 policy, head size 32, causal, seq_len <= 256 only (XFMR_EUNSUPPORTED otherwise); workspaces
+   * by the row index). bf16 policy, head size 32, causal only (XFMR_EUNSUPPORTED otherwise), at any seq_len: attention
+   * runs its one-workgroup forms up to 512 and its key-streaming forms beyond; workspaces
    * are sized for batch * seq_len as before. xfmr_pack_rows builds the index tensors of this layout.               */
   const int32_t* seq_offsets; /* device, batch + 1 entries, ascending, seq_offsets[0] == 0                          */
   const int32_t* row_pos;     /* device, packed_rows entries: position of each packed row within its sequence

@@ -25,7 +25,8 @@ struct AttnArgs {
   int B, L, A, H;
   const int32_t* offs;  // packed rows (xfmr_encoder_cfg.seq_offsets): sequence b = rows [offs[b], offs[b + 1]) of qkv / ctx /
                         // key_mask / d_ctx / d_qkv, at most L of them; null: the padded layout, rows [b L, (b + 1) L). The
-                        // one-workgroup-per-(batch, head) kernels only. lse and the dropout row keys stay indexed by L.
+                        // one-workgroup-per-(batch, head) kernels and the bf16 head-size-32 key-streaming kernels only. lse
+                        // and the dropout row keys stay indexed by L.
   int causal;  // 1: key j is visible to query i only when j <= i (BertConfig.is_decoder=True, the reference's
                // setting, models.py:355); 0: every unpadded key is visible (is_decoder=False)
   XfDropout drop;
@@ -1063,6 +1064,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_bf16_kernel(const AttnArg
 // every wave runs the tiles of the chunk its (causal) range reaches -> barrier. A wave with nothing left (rows past L,
 // or past its causal end) still stages and waits at every barrier. After the last chunk the 4 x 32 x 33 fp32
 // output-transposition scratch aliases the chunk images. Results are bit-identical to the panel kernels.
+//   Packed rows (a.offs, as the one-workgroup kernels): the sequence of slot b starts at row offs[b] and has offs[b + 1] -
+// offs[b] rows; that length -- L below -- bounds every load, store and loop, so no row of the next sequence is touched. The
+// grid stays the padded layout's (128-row blocks from a.L): a workgroup whose block starts at or past its sequence's end
+// returns before the first barrier. a.L remains the stride of lse and of the dropout row key (slot * a.L + q).
 //   Chunk size: 256 rows, not 128. Every chunk costs two barriers and one exposed global-load latency (nothing is in
 //   flight while the waves wait for the images), so the fewer chunks the better; 128 rows would be 16 KiB of images,
 //   less than the 16.5 KiB scratch they have to hold anyway, while 256 rows is 32 KiB of images and still leaves the
@@ -1091,10 +1096,18 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_stream_bf16_kernel(const Attn
   using ST = Bf16Stream;
   constexpr int CH = ST::CH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int L = a.L, H = a.H;
+  const int H = a.H;
+  int L = a.L;  // this sequence's rows (packed layout: its own length); a.L stays the stride of lse and the row keys
   const AttnBlock blk = attn_block(a);
   if (!blk.valid) return;  // (whole workgroup: the grid is padded to a multiple of 8 sequences)
   const int b = blk.by / a.A, h = blk.by % a.A;
+  int64_t tok0 = (int64_t)b * a.L;
+  if (a.offs) {  // packed rows: the sequence starts at its offset and is as long as it is
+    const int o0 = a.offs[b];
+    L = a.offs[b + 1] - o0;
+    tok0 = o0;
+    if (blk.bx * 128 >= L) return;  // (whole workgroup, before any barrier) a block past the sequence's end, or an empty one
+  }
   const int qblk0 = blk.bx * 128;
   const int nkeys = a.causal ? min(((L + 31) / 32) * 32, qblk0 + 128) : ((L + 31) / 32) * 32;
   __bf16* sK = reinterpret_cast<__bf16*>(smem_raw);
@@ -1102,7 +1115,6 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_stream_bf16_kernel(const Attn
   float* scratch = reinterpret_cast<float*>(smem_raw);  // after the last chunk
   uint32_t* sBits = reinterpret_cast<uint32_t*>(smem_raw + 2 * ST::kImg);  // key mask of the chunk, one bit per key
 
-  const int64_t tok0 = (int64_t)b * L;
   const int lane = xf_lane(), wid = threadIdx.x >> 6;
   const int q0 = qblk0 + wid * 32;
   const bool active = q0 < L;  // (wave-uniform) inactive waves still stage and take part in every barrier
@@ -1114,7 +1126,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_stream_bf16_kernel(const Attn
   f32x16 o;
 #pragma unroll
   for (int r = 0; r < 16; ++r) o[r] = 0.f;
-  const uint32_t rowkey = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * L + q));
+  const uint32_t rowkey = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * a.L + q));
   const int kb_end = !active ? -1 : a.causal ? min((q0 + 31) / 32, nkeys / 32 - 1) : nkeys / 32 - 1;
   for (int c0 = 0; c0 < nkeys; c0 += CH) {
     const int nr = min(CH, nkeys - c0);
@@ -1172,7 +1184,7 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_stream_bf16_kernel(const Attn
   if (!active) return;
   xf_store_tile_T_at<S16>(scratch + wid * 32 * 33, o, inv, a.ctx, tok0 * H + h * DH, H, q0, L);
   if (lane < 32 && q < L)
-    a.lse[((int64_t)blk.by) * L + q] = ltot > 0.f ? (m + log2f(ltot)) * kLn2 : INFINITY;
+    a.lse[((int64_t)blk.by) * a.L + q] = ltot > 0.f ? (m + log2f(ltot)) * kLn2 : INFINITY;
 }
 
 template <bool S16>
@@ -1183,10 +1195,18 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_stream_bf16_kernel(const A
   using ST = Bf16Stream;
   constexpr int CH = ST::CH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int L = a.L, H = a.H;
+  const int H = a.H;
+  int L = a.L;  // this sequence's rows (packed layout: its own length); a.L stays the stride of lse and the row keys
   const AttnBlock blk = attn_block(a);
   if (!blk.valid) return;  // (whole workgroup: the grid is padded to a multiple of 8 sequences)
   const int b = blk.by / a.A, h = blk.by % a.A;
+  int64_t tok0 = (int64_t)b * a.L;
+  if (a.offs) {  // packed rows: the sequence starts at its offset and is as long as it is
+    const int o0 = a.offs[b];
+    L = a.offs[b + 1] - o0;
+    tok0 = o0;
+    if (blk.bx * 128 >= L) return;  // (whole workgroup, before any barrier) a block past the sequence's end, or an empty one
+  }
   const int qblk0 = blk.bx * 128;
   const int nkeys = a.causal ? min(((L + 31) / 32) * 32, qblk0 + 128) : ((L + 31) / 32) * 32;
   __bf16* sK = reinterpret_cast<__bf16*>(smem_raw);
@@ -1194,7 +1214,6 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_stream_bf16_kernel(const A
   float* scratch = reinterpret_cast<float*>(smem_raw);  // after the last chunk
   uint32_t* sBits = reinterpret_cast<uint32_t*>(smem_raw + 2 * ST::kImg);  // key mask of the chunk, one bit per key
 
-  const int64_t tok0 = (int64_t)b * L;
   const int lane = xf_lane(), wid = threadIdx.x >> 6;
   const int q0 = qblk0 + wid * 32;
   const bool active = q0 < L;
@@ -1206,9 +1225,9 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_stream_bf16_kernel(const A
   float delta = 0.f;
   if (qv) delta = dot16<S16>(a.ctx, a.d_ctx, (tok0 + q) * H + h * DH + 16 * (lane >> 5));
   delta += xf_half_swap(delta);
-  const float lse2 = qv ? a.lse[(int64_t)blk.by * L + q] * kLog2e : INFINITY;
+  const float lse2 = qv ? a.lse[(int64_t)blk.by * a.L + q] * kLog2e : INFINITY;
   const float sc = 0.17677669529663687f * kLog2e;
-  const uint32_t rowkey = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * L + q));
+  const uint32_t rowkey = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * a.L + q));
   f32x16 dq;
 #pragma unroll
   for (int r = 0; r < 16; ++r) dq[r] = 0.f;
@@ -1268,10 +1287,18 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_stream_bf16_kernel(const 
   using ST = Bf16Stream;
   constexpr int CH = ST::CH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int L = a.L, H = a.H;
+  const int H = a.H;
+  int L = a.L;  // this sequence's rows (packed layout: its own length); a.L stays the stride of lse and the row keys
   const AttnBlock blk = attn_block(a);
   if (!blk.valid) return;  // (whole workgroup: the grid is padded to a multiple of 8 sequences)
   const int b = blk.by / a.A, h = blk.by % a.A;
+  int64_t tok0 = (int64_t)b * a.L;
+  if (a.offs) {  // packed rows: the sequence starts at its offset and is as long as it is
+    const int o0 = a.offs[b];
+    L = a.offs[b + 1] - o0;
+    tok0 = o0;
+    if (blk.bx * 128 >= L) return;  // (whole workgroup, before any barrier) a block past the sequence's end, or an empty one
+  }
   const int kblk0 = blk.bx * 128;
   const int Lp = ((L + 31) / 32) * 32;
   const int qs = a.causal ? kblk0 : 0;  // first query this block's keys are visible to
@@ -1282,7 +1309,6 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_stream_bf16_kernel(const 
   float* sDelta = sLse + CH;                                          // [CH]
   uint32_t* sRowKey = reinterpret_cast<uint32_t*>(sDelta + CH);       // [CH] dropout row keys of the staged query rows
 
-  const int64_t tok0 = (int64_t)b * L;
   const int64_t hoff = tok0 * H + h * DH;
   const int lane = xf_lane(), wid = threadIdx.x >> 6;
   const int k0 = kblk0 + wid * 32;
@@ -1314,7 +1340,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_stream_bf16_kernel(const 
         if (c < nr * 8 && c0 + r < L) {
           x[u] = xf_ld4<S16>(a.ctx, hoff + (int64_t)(c0 + r) * H + dd);
           y[u] = xf_ld4<S16>(a.d_ctx, hoff + (int64_t)(c0 + r) * H + dd);
-          if ((c & 7) == 0) ls[u] = a.lse[(int64_t)blk.by * L + c0 + r] * kLog2e;
+          if ((c & 7) == 0) ls[u] = a.lse[(int64_t)blk.by * a.L + c0 + r] * kLog2e;
         }
       }
 #pragma unroll
@@ -1327,7 +1353,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_stream_bf16_kernel(const 
         if (c < nr * 8 && (c & 7) == 0) {
           sDelta[r] = part;
           sLse[r] = ls[u];
-          sRowKey[r] = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * L + c0 + r));
+          sRowKey[r] = xf_drop_rowkey(a.drop, (uint32_t)((int64_t)blk.by * a.L + c0 + r));
         }
       }
     }
@@ -2079,11 +2105,15 @@ constexpr size_t kLdsLimit = 160 * 1024;
 // stream_keys (XFMR_ATTN_STREAM_KEYS, the tests' and the benchmark's streaming-vs-panel switch; padded layout only): the
 // key-streaming two-kernel forms at any L, also where the one-workgroup or the panel forms would have run. With the bit
 // clear they run only where the panel does not fit LDS.
+//   Packed rows (a.offs; causal only): the one-workgroup forms up to kSeqMaxL rows per sequence, the key-streaming forms
+// beyond -- for EVERY sequence of the batch, the short ones too: they walk the same tiles in the same order as the padded
+// layout's two-kernel forms, so valid rows come out bit-identical to the padded run. The grid is the padded layout's
+// (blocks from a.L); blocks past a sequence's own end return at once.
 template <bool S16>
 int launch_fwd_bf16(const AttnArgs& a, hipStream_t st, bool stream_keys) {
-  const bool stream = stream_keys && !a.offs;
+  const bool stream = a.offs ? a.L > kSeqMaxL : stream_keys;
   static const int two_blocks = [] { const char* e = getenv("XFMR_ATTN_FWD_SPLIT"); return e ? atoi(e) : 0; }();
-  if (a.offs && !(a.causal && a.L <= kSeqMaxL)) return XFMR_EUNSUPPORTED;  // packed rows: the one-workgroup forms only
+  if (a.offs && !a.causal) return XFMR_EUNSUPPORTED;  // packed rows: the kernels that walk a.offs are causal only
   if (!stream && (!two_blocks || a.offs) && a.causal && a.L <= kSeqMaxL) {  // the one-workgroup forms walk the causal triangle only
     const size_t sf = bf16_smem_fwd_seq(a.L);
     if (hipFuncSetAttribute((const void*)attn_fwd_seq_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2114,7 +2144,7 @@ int launch_fwd_bf16(const AttnArgs& a, hipStream_t st, bool stream_keys) {
 }
 template <bool S16>
 int launch_bwd_bf16(const AttnArgs& a, hipStream_t st, bool stream_keys) {
-  const bool stream = stream_keys && !a.offs;  // (see launch_fwd_bf16)
+  const bool stream = a.offs ? a.L > kSeqMaxL : stream_keys;  // (see launch_fwd_bf16)
   static const int two_kernels = [] { const char* e = getenv("XFMR_ATTN_BWD_SPLIT"); return e ? atoi(e) : 0; }();
   // the one-workgroup forms: round 1's four-wave lock-step form, or -- XFMR_ATTN_BWD_FORM=roles, read per call -- round 4's
   // "roles" (eight waves, two roles, one barrier). MEASURED, alternating runs on one box, batch 512: 113.9 / 112.1 us per
@@ -2123,7 +2153,7 @@ int launch_bwd_bf16(const AttnArgs& a, hipStream_t st, bool stream_keys) {
   // pairs x ~2 800 issue cycles per (batch, head) against 28 x ~2 000) -- not the default. DESIGN.md section 4.
   const char* form = getenv("XFMR_ATTN_BWD_FORM");
   const bool roles = form && form[0] == 'r';
-  if (a.offs && !(a.causal && a.L <= kSeqMaxL)) return XFMR_EUNSUPPORTED;  // packed rows: the one-workgroup forms only
+  if (a.offs && !a.causal) return XFMR_EUNSUPPORTED;  // packed rows: the kernels that walk a.offs are causal only
   // 256 < L <= 512 (BASELINE config 5): the two-role form is the one-workgroup backward there (the lock-step form's schedule
   // table stops at eight tiles): Q, K, V, dO of 512 rows are 128 KB of LDS -- one workgroup of eight waves per CU
   if (!stream && (!two_kernels || a.offs) && (roles || a.L > kFusedMaxL) && a.causal && a.L <= kSeqMaxL) {

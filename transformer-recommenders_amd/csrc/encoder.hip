@@ -277,9 +277,9 @@ int check_cfg(const xfmr_encoder_cfg* c) {
   if (c->profile_kernel < XFMR_PROF_NONE || c->profile_kernel > XFMR_PROF_REDUCE) return XFMR_EINVAL;
   if (c->seq_offsets) {  // packed rows (ABI 3)
     if (!c->row_pos || c->packed_rows <= 0 || c->packed_rows > (int64_t)c->batch * c->seq_len) return XFMR_EINVAL;
-    // the kernels that walk a sequence by its offsets: the bf16 policy's one-workgroup attention forms (head size 32, causal,
-    // seq_len <= 512); everything else is row-wise and does not care
-    if (!mixed_storage(c) || c->hidden != c->heads * 32 || c->seq_len > 512 || (c->flags & XFMR_ENC_BIDIRECTIONAL))
+    // the kernels that walk a sequence by its offsets: the bf16 policy's head-size-32 causal attention (the one-workgroup forms
+    // up to 512 rows per sequence, the key-streaming forms beyond); everything else is row-wise and does not care
+    if (!mixed_storage(c) || c->hidden != c->heads * 32 || (c->flags & XFMR_ENC_BIDIRECTIONAL))
       return XFMR_EUNSUPPORTED;
   } else if (c->row_pos || c->packed_rows) {
     return XFMR_EINVAL;
@@ -309,7 +309,8 @@ const char* xfmr_strerror(int code) {
     case XFMR_EUNSUPPORTED:
       return "shape not supported by the gfx950 kernels (head size must be 32 or 64; the fused loss takes any d_model that is a "
              "multiple of 32 up to 1024 in the bf16 policy and up to 512 in fp32; attention takes any L in the padded layout, "
-             "packed rows: bf16 policy at head size 32, L <= 512, causal)";
+             "packed rows need the bf16 policy, head size 32 and causal, at any length: the one-workgroup forms run at L <= 512 "
+             "and the key-streaming forms beyond)";
     case XFMR_EWORKSPACE: return "workspace too small";
     case XFMR_EHIP: return "HIP launch failed";
     case XFMR_EALIGN: return "pointer or leading dimension not 16-byte aligned";

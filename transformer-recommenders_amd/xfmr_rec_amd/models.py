@@ -328,10 +328,13 @@ class RecommenderModel(torch.nn.Module):
 
     def supports_packed_rows(self, L: int) -> bool:
         """Whether the encoder can run the PACKED layout (xfmr_encoder_cfg.seq_offsets: the token axis holds each sequence's own
-        rows only, no padding rows) for sequences of up to L rows: bf16 policy, head size 32, causal, L <= 256."""
+        rows only, no padding rows) for sequences of up to L rows: bf16 policy, head size 32, causal, at any L (attention runs
+        its one-workgroup forms up to 512 rows per sequence and its key-streaming forms beyond). Every length range is
+        admitted because the packed training step was measured not slower than the padded one in it
+        (profiles/packed_long.md: widths 384 and 2048). ``XFMR_PACKED=0`` forces the padded layout."""
         c = self.config
         return (self.precision == "bf16" and c.hidden_size == 32 * c.num_attention_heads and bool(c.is_decoder)
-                and min(L, self.max_seq_length) <= 256 and self.flat.is_cuda and os.environ.get("XFMR_ACT_FP32", "0") in ("", "0")
+                and self.flat.is_cuda and os.environ.get("XFMR_ACT_FP32", "0") in ("", "0")
                 and os.environ.get("XFMR_PACKED", "1") != "0")
 
     def _cfg_kwargs(self, B: int, L: int, embed_event=None, packed=None) -> dict:
