@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs a_in) 
 //   fp32, 32       35 456 B             53 888 B               71 680 B
 //   fp32, 64       34 880 B             52 288 B               70 144 B
 //   bf16, 64       35 456 B             53 888 B               71 680 B
-// (<= 80 KiB: two workgroups per CU; the launchers check every instantiation against kLdsLimit.)
+// (<= 80 KiB, asserted for every instantiation: two workgroups per CU.)
 template <class P, int DHT>
 struct AttnStream {
   using elem = typename P::elem;
@@ -2067,7 +2067,7 @@ size_t bf16_smem_roles(int L) {  // Q, dO, K, V images; lse + delta + row keys; 
   return 4 * Lp * DH * 2 + 3 * Lp * 4 + (Lp / 32 + 2) * sizeof(uint32_t);
 }
 
-size_t bf16_smem_fused(int L) {  // Q + dO images, fp32 dQ accumulator, lse + delta + row keys, 4 dS images
+constexpr size_t bf16_smem_fused(int L) {  // Q + dO images, fp32 dQ accumulator, lse + delta + row keys, 4 dS images
   const size_t Lp = ((size_t)L + 31) / 32 * 32;
   return 2 * Lp * DH * 2 + Lp * DH * 4 + 3 * Lp * 4 + 4 * 32 * DH * 2;
 }
@@ -2102,193 +2102,175 @@ size_t dkv_smem(int L) {
 }
 constexpr size_t kLdsLimit = 160 * 1024;
 
-// stream_keys (XFMR_ATTN_STREAM_KEYS, the tests' and the benchmark's streaming-vs-panel switch; padded layout only): the
-// key-streaming two-kernel forms at any L, also where the one-workgroup or the panel forms would have run. With the bit
-// clear they run only where the panel does not fit LDS.
-//   Packed rows (a.offs; causal only): the one-workgroup forms up to kSeqMaxL rows per sequence, the key-streaming forms
-// beyond -- for EVERY sequence of the batch, the short ones too: they walk the same tiles in the same order as the padded
-// layout's two-kernel forms, so valid rows come out bit-identical to the padded run. The grid is the padded layout's
-// (blocks from a.L); blocks past a sequence's own end return at once.
-template <bool S16>
-int launch_fwd_bf16(const AttnArgs& a, hipStream_t st, bool stream_keys) {
-  const bool stream = a.offs ? a.L > kSeqMaxL : stream_keys;
-  static const int two_blocks = [] { const char* e = getenv("XFMR_ATTN_FWD_SPLIT"); return e ? atoi(e) : 0; }();
-  if (a.offs && !a.causal) return XFMR_EUNSUPPORTED;  // packed rows: the kernels that walk a.offs are causal only
-  if (!stream && (!two_blocks || a.offs) && a.causal && a.L <= kSeqMaxL) {  // the one-workgroup forms walk the causal triangle only
-    const size_t sf = bf16_smem_fwd_seq(a.L);
-    if (hipFuncSetAttribute((const void*)attn_fwd_seq_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sf) != hipSuccess)
-      return XFMR_EHIP;
-    hipLaunchKernelGGL((attn_fwd_seq_bf16_kernel<S16>), dim3((unsigned)(a.A * ((a.B + 7) / 8) * 8)), dim3(256), sf, st,
-                       a);
-    XF_LAUNCH_CHECK();
-    return XFMR_OK;
-  }
-  dim3 grid((unsigned)(((a.L + 127) / 128) * a.A * ((a.B + 7) / 8) * 8));  // see attn_block
-  const size_t sm = bf16_smem_fwd(a.L);
-  if (stream || sm > kLdsLimit) {  // the K/V panel does not fit: it passes through LDS in chunks
-    constexpr size_t ss = Bf16Stream::fwd_bytes();
-    if (hipFuncSetAttribute((const void*)attn_fwd_stream_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ss) != hipSuccess)
-      return XFMR_EHIP;
-    hipLaunchKernelGGL((attn_fwd_stream_bf16_kernel<S16>), grid, dim3(256), ss, st, a);
-    XF_LAUNCH_CHECK();
-    return XFMR_OK;
-  }
-  if (hipFuncSetAttribute((const void*)attn_fwd_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sm) != hipSuccess)
-    return XFMR_EHIP;
-  hipLaunchKernelGGL((attn_fwd_bf16_kernel<S16>), grid, dim3(256), sm, st, a);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+// ================================================================================================================
+// Host side: the plan of a call's kernels (attn_plan_fwd / attn_plan_bwd), the switches, one launch routine
+// ================================================================================================================
+enum AttnForm : int32_t {  // every kernel family of this file; forward | backward kernels of the form
+  kAttnNone = 0,       // the call is refused (AttnPlan::rc)
+  kAttnGenericPanel,   // generic, whole panel in LDS: attn_fwd_kernel | attn_bwd_dq_kernel, attn_bwd_dkv_kernel
+  kAttnGenericStream,  // generic, key streaming: attn_fwd_stream_kernel | attn_bwd_dq_stream_kernel, attn_bwd_dkv_stream_kernel
+  kAttnBf16Seq,        // bf16 head size 32 from here on. One workgroup per (batch, head): attn_fwd_seq_bf16_kernel | --
+  kAttnBf16Fused,      // -- | attn_bwd_fused_bf16_kernel (lock-step)
+  kAttnBf16Roles4,     // -- | attn_bwd_roles_bf16_kernel<4> (512 threads)
+  kAttnBf16Roles8,     // -- | attn_bwd_roles_bf16_kernel<8> (1024 threads)
+  kAttnBf16Panel,      // attn_fwd_bf16_kernel | attn_bwd_dq_bf16_kernel, attn_bwd_dkv_bf16_kernel
+  kAttnBf16Stream,     // attn_fwd_stream_bf16_kernel | attn_bwd_dq_stream_bf16_kernel, attn_bwd_dkv_stream_bf16_kernel
+};
+struct AttnKey {  // everything the choice of kernels depends on, besides the switches
+  int precision; bool s16;
+  int B, L, A, H;
+  bool causal, packed;  // packed: rows by seq_offsets (AttnArgs::offs)
+  bool stream_keys;     // XFMR_ATTN_STREAM_KEYS, the tests' and the benchmark's streaming-vs-panel switch
+};
+struct AttnSwitches { bool fwd_split, bwd_split, bwd_roles; };  // attn_switches()
+struct AttnPlan {
+  int rc;  // what the call returns when it is not launched (then form = kAttnNone, n = 0)
+  AttnForm form; bool bwd;
+  int n;  // kernels: 1, or 2 (dQ then dK/dV)
+  unsigned gx, gy, block;
+  size_t lds[2];  // dynamic LDS bytes of each kernel
+};
+
+// LDS bytes of a family's forward, dQ and dK/dV kernels: with the whole panel of L rows staged | key streaming (no L in it)
+struct AttnLds { size_t panel[3], stream[3]; };
+template <class P, int DHT>
+AttnLds generic_lds(int L) {
+  using ST = AttnStream<P, DHT>;
+  return {{fwd_smem<P, DHT>(L), dq_smem<P, DHT>(L), dkv_smem<P, DHT>(L)}, {ST::fwd_bytes(), ST::dq_bytes(), ST::dkv_bytes()}};
 }
-template <bool S16>
-int launch_bwd_bf16(const AttnArgs& a, hipStream_t st, bool stream_keys) {
-  const bool stream = a.offs ? a.L > kSeqMaxL : stream_keys;  // (see launch_fwd_bf16)
-  static const int two_kernels = [] { const char* e = getenv("XFMR_ATTN_BWD_SPLIT"); return e ? atoi(e) : 0; }();
-  // the one-workgroup forms: round 1's four-wave lock-step form, or -- XFMR_ATTN_BWD_FORM=roles, read per call -- round 4's
-  // "roles" (eight waves, two roles, one barrier). MEASURED, alternating runs on one box, batch 512: 113.9 / 112.1 us per
-  // layer for roles against 111.1 / 110.7 for lock-step (3.330 / 3.333 vs 3.315 / 3.302 ms per step): the barriers and
-  // the dQ read-modify-write it removes are paid back by evaluating every probability twice (the vector pipe: 28 tile
-  // pairs x ~2 800 issue cycles per (batch, head) against 28 x ~2 000) -- not the default. DESIGN.md section 4.
-  const char* form = getenv("XFMR_ATTN_BWD_FORM");
-  const bool roles = form && form[0] == 'r';
-  if (a.offs && !a.causal) return XFMR_EUNSUPPORTED;  // packed rows: the kernels that walk a.offs are causal only
-  // 256 < L <= 512 (BASELINE config 5): the two-role form is the one-workgroup backward there (the lock-step form's schedule
-  // table stops at eight tiles): Q, K, V, dO of 512 rows are 128 KB of LDS -- one workgroup of eight waves per CU
-  if (!stream && (!two_kernels || a.offs) && (roles || a.L > kFusedMaxL) && a.causal && a.L <= kSeqMaxL) {
-    const size_t sr = bf16_smem_roles(a.L);
-    const dim3 grid((unsigned)(a.A * ((a.B + 7) / 8) * 8));
-    if (a.L > kFusedMaxL) {
-      if (hipFuncSetAttribute((const void*)attn_bwd_roles_bf16_kernel<S16, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)sr) != hipSuccess)
-        return XFMR_EHIP;
-      hipLaunchKernelGGL((attn_bwd_roles_bf16_kernel<S16, 8>), grid, dim3(1024), sr, st, a);
-    } else {
-      if (hipFuncSetAttribute((const void*)attn_bwd_roles_bf16_kernel<S16, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)sr) != hipSuccess)
-        return XFMR_EHIP;
-      hipLaunchKernelGGL((attn_bwd_roles_bf16_kernel<S16, 4>), grid, dim3(512), sr, st, a);
-    }
-    XF_LAUNCH_CHECK();
-    return XFMR_OK;
+AttnLds attn_lds(const AttnKey& k, bool bf16h32) {
+  if (bf16h32) {  // forward and dQ stage the same K / V panel
+    const size_t kv = bf16_smem_fwd(k.L), ch = Bf16Stream::fwd_bytes();
+    return {{kv, kv, bf16_smem_dkv(k.L)}, {ch, ch, Bf16Stream::dkv_bytes()}};
   }
-  const size_t sf = bf16_smem_fused(a.L);
-  if (!stream && (!two_kernels || a.offs) && a.causal && a.L <= kFusedMaxL && sf <= kLdsLimit) {
-    if (hipFuncSetAttribute((const void*)attn_bwd_fused_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sf) != hipSuccess)
-      return XFMR_EHIP;
-    hipLaunchKernelGGL((attn_bwd_fused_bf16_kernel<S16>), dim3((unsigned)(a.A * ((a.B + 7) / 8) * 8)), dim3(256), sf,
-                       st, a);
-    XF_LAUNCH_CHECK();
-    return XFMR_OK;
-  }
-  dim3 grid((unsigned)(((a.L + 127) / 128) * a.A * ((a.B + 7) / 8) * 8));  // see attn_block
-  const size_t s1 = bf16_smem_fwd(a.L), s2 = bf16_smem_dkv(a.L);
-  if (stream || s1 > kLdsLimit || s2 > kLdsLimit) {  // a K/V or Q/dO panel does not fit: chunks through LDS
-    constexpr size_t ss1 = Bf16Stream::fwd_bytes(), ss2 = Bf16Stream::dkv_bytes();
-    if (hipFuncSetAttribute((const void*)attn_bwd_dq_stream_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ss1) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_bwd_dkv_stream_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ss2) != hipSuccess)
-      return XFMR_EHIP;
-    hipLaunchKernelGGL((attn_bwd_dq_stream_bf16_kernel<S16>), grid, dim3(256), ss1, st, a);
-    XF_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn_bwd_dkv_stream_bf16_kernel<S16>), grid, dim3(256), ss2, st, a);
-    XF_LAUNCH_CHECK();
-    return XFMR_OK;
-  }
-  if (hipFuncSetAttribute((const void*)attn_bwd_dq_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)s1) != hipSuccess ||
-      hipFuncSetAttribute((const void*)attn_bwd_dkv_bf16_kernel<S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)s2) != hipSuccess)
-    return XFMR_EHIP;
-  hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<S16>), grid, dim3(256), s1, st, a);
-  XF_LAUNCH_CHECK();
-  hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<S16>), grid, dim3(256), s2, st, a);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  if (k.precision == XFMR_PREC_BF16) return generic_lds<PrecBF16, 64>(k.L);
+  return k.H / k.A == 32 ? generic_lds<PrecF32, 32>(k.L) : generic_lds<PrecF32, 64>(k.L);
 }
 
-// The generic kernels: fp32 policy at head size 32, and both policies at head size 64 (operands fp32, or bf16 when S16).
-// Where the whole panel fits LDS the panel kernels run; beyond that -- or with stream_keys (XFMR_ATTN_STREAM_KEYS, the
-// tests' streaming-vs-panel comparison) -- the key-streaming forms, whose LDS use does not depend on L.
-template <class P, int DHT, bool S16>
-int launch_fwd_generic(const AttnArgs& a, hipStream_t st, bool stream_keys) {
-  dim3 grid((a.L + 127) / 128, a.B * a.A);
-  const size_t sm = fwd_smem<P, DHT>(a.L);
-  if (stream_keys || sm > kLdsLimit) {
-    using ST = AttnStream<P, DHT>;
-    static_assert(ST::fwd_bytes() <= kLdsLimit, "streaming forward LDS");
-    if (hipFuncSetAttribute((const void*)attn_fwd_stream_kernel<P, DHT, S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ST::fwd_bytes()) != hipSuccess)
-      return XFMR_EHIP;
-    hipLaunchKernelGGL((attn_fwd_stream_kernel<P, DHT, S16>), grid, dim3(256), ST::fwd_bytes(), st, a);
-    XF_LAUNCH_CHECK();
-    return XFMR_OK;
-  }
-  if (hipFuncSetAttribute((const void*)attn_fwd_kernel<P, DHT, S16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) !=
-      hipSuccess)
-    return XFMR_EHIP;
-  hipLaunchKernelGGL((attn_fwd_kernel<P, DHT, S16>), grid, dim3(256), sm, st, a);
-  XF_LAUNCH_CHECK();
+// ---- the plan: which kernels a call runs, as a pure function of its key and the switches (DESIGN.md section 4 has the
+// table; tests/test_attn_plan_host.py walks it through xf_attn_plan without a GPU). check_shape has passed: H / A is 32 or 64.
+AttnPlan attn_refuse(int rc) { return AttnPlan{rc, kAttnNone, false, 0, 0, 0, 0, {0, 0}}; }
+
+// precision x storage x head size -> family: the bf16 policy at head size 32 runs the production kernels (*bf16h32), the fp32
+// policy (fp32 storage only) and head size 64 the generic ones. Nonzero: the code the call returns instead.
+int attn_family(const AttnKey& k, bool* bf16h32) {
+  const bool bf16 = k.precision == XFMR_PREC_BF16;
+  *bf16h32 = bf16 && k.H / k.A == 32;
+  if (k.packed && !*bf16h32) return XFMR_EUNSUPPORTED;  // packed rows: production kernels only,
+  if (!bf16 && !(k.precision == XFMR_PREC_F32 && !k.s16)) return XFMR_EINVAL;
+  if (k.packed && !k.causal) return XFMR_EUNSUPPORTED;  // and of those only causal kernels walk the offsets
   return XFMR_OK;
 }
+// The key-streaming forms run where asked for, besides where a panel does not fit LDS (attn_tiled_plan). Padded layout:
+// stream_keys asks, at any L, also where the one-workgroup or the panel forms would have run. Packed rows: beyond the
+// one-workgroup forms' kSeqMaxL rows per sequence -- for EVERY sequence of the batch, the short ones too: they walk the same
+// tiles in the same order as the padded layout's two-kernel forms, so valid rows come out bit-identical to the padded run.
+bool attn_stream_asked(const AttnKey& k) { return k.packed ? k.L > kSeqMaxL : k.stream_keys; }
+// bf16 head size 32: one workgroup per (batch, head) walks the causal triangle of up to kSeqMaxL rows. split = the pass's
+// XFMR_ATTN_*_SPLIT switch (the 128-row-block forms instead); packed rows have no panel form and ignore it.
+bool attn_one_workgroup(const AttnKey& k, bool split) {
+  return !attn_stream_asked(k) && (!split || k.packed) && k.causal && k.L <= kSeqMaxL;
+}
+AttnPlan attn_one_workgroup_plan(const AttnKey& k, AttnForm form, bool bwd, unsigned block, size_t lds) {
+  return AttnPlan{XFMR_OK, form, bwd, 1, (unsigned)(k.A * ((k.B + 7) / 8) * 8), 1, block, {lds, 0}};  // see attn_seq_block
+}
+// One workgroup per 128-row block, of either family: the panel form while every panel of the pass fits LDS (the backward
+// takes the streaming pair when EITHER of its panels is over), else -- or when asked -- the K/V (Q/dO) panel passes through
+// LDS in chunks. Packed rows keep the padded layout's grid (blocks from k.L); blocks past a sequence's own end return at once.
+AttnPlan attn_tiled_plan(const AttnKey& k, bool bf16h32, bool bwd) {
+  const AttnLds l = attn_lds(k, bf16h32);
+  const int first = bwd ? 1 : 0, n = bwd ? 2 : 1;
+  bool stream = attn_stream_asked(k);
+  for (int i = 0; i < n; ++i) stream = stream || l.panel[first + i] > kLdsLimit;
+  const size_t* lds = stream ? l.stream : l.panel;
+  const int nblk = (k.L + 127) / 128;
+  AttnPlan p{XFMR_OK, kAttnNone, bwd, n, 0, 0, 256, {lds[first], bwd ? lds[2] : 0}};
+  if (bf16h32) {  // XCD-aware one-dimensional grid, the batch padded to eight sequences: see attn_block
+    p.form = stream ? kAttnBf16Stream : kAttnBf16Panel;
+    p.gx = (unsigned)(nblk * k.A * ((k.B + 7) / 8) * 8), p.gy = 1;
+  } else {
+    p.form = stream ? kAttnGenericStream : kAttnGenericPanel;
+    p.gx = nblk, p.gy = k.B * k.A;
+  }
+  return p;
+}
+
+AttnPlan attn_plan_fwd(const AttnKey& k, AttnSwitches sw) {
+  bool bf16h32;
+  if (int rc = attn_family(k, &bf16h32)) return attn_refuse(rc);
+  if (bf16h32 && attn_one_workgroup(k, sw.fwd_split))
+    return attn_one_workgroup_plan(k, kAttnBf16Seq, false, 256, bf16_smem_fwd_seq(k.L));
+  return attn_tiled_plan(k, bf16h32, false);
+}
+AttnPlan attn_plan_bwd(const AttnKey& k, AttnSwitches sw) {
+  bool bf16h32;
+  if (int rc = attn_family(k, &bf16h32)) return attn_refuse(rc);
+  if (bf16h32 && attn_one_workgroup(k, sw.bwd_split)) {
+    // kFusedMaxL < L <= kSeqMaxL (BASELINE config 5): the two-role form is the one-workgroup backward there (the lock-step
+    // form's schedule table stops at eight tiles): Q, K, V, dO of 512 rows are 128 KB of LDS -- one workgroup, eight waves
+    // per role, per CU
+    if (k.L > kFusedMaxL) return attn_one_workgroup_plan(k, kAttnBf16Roles8, true, 1024, bf16_smem_roles(k.L));
+    // up to kFusedMaxL: round 1's four-wave lock-step form, or -- XFMR_ATTN_BWD_FORM=roles -- round 4's "roles" (two roles,
+    // one barrier). MEASURED, alternating runs on one box, batch 512: 113.9 / 112.1 us per layer for roles against 111.1 /
+    // 110.7 for lock-step (3.330 / 3.333 vs 3.315 / 3.302 ms per step): the barriers and the dQ read-modify-write it
+    // removes are paid back by evaluating every probability twice (the vector pipe: 28 tile pairs x ~2 800 issue cycles
+    // per (batch, head) against 28 x ~2 000) -- not the default. DESIGN.md section 4.
+    if (sw.bwd_roles) return attn_one_workgroup_plan(k, kAttnBf16Roles4, true, 512, bf16_smem_roles(k.L));
+    // (no test against kLdsLimit: the lock-step form's LDS grows with L and is 76 800 B at kFusedMaxL, asserted below)
+    return attn_one_workgroup_plan(k, kAttnBf16Fused, true, 256, bf16_smem_fused(k.L));
+  }
+  return attn_tiled_plan(k, bf16h32, true);
+}
+static_assert(bf16_smem_fused(kFusedMaxL) == 76800 && bf16_smem_fused(kFusedMaxL) <= kLdsLimit, "lock-step backward LDS");
+
+// XFMR_ATTN_FWD_SPLIT / XFMR_ATTN_BWD_SPLIT (atoi, nonzero = on) are read ONCE per process: diagnostic switches that a
+// whole run is started under. XFMR_ATTN_BWD_FORM (a leading 'r' = roles) is read on EVERY call: the tests switch it
+// between two calls of one process to compare the two backward forms.
+AttnSwitches attn_switches() {
+  const auto on = [](const char* name) { const char* e = getenv(name); return (e ? atoi(e) : 0) != 0; };
+  static const bool fwd_split = on("XFMR_ATTN_FWD_SPLIT"), bwd_split = on("XFMR_ATTN_BWD_SPLIT");
+  const char* form = getenv("XFMR_ATTN_BWD_FORM");
+  return AttnSwitches{fwd_split, bwd_split, form && form[0] == 'r'};
+}
+
+// ---- the launch: (form, pass) x (policy, head size, storage) -> kernels, then set-attribute / launch / check in one place
+using AttnKernel = void (*)(const AttnArgs);
+struct AttnKernels { AttnKernel fwd, bwd[2]; };  // of a form: the forward kernel | the backward's one or two
 template <class P, int DHT, bool S16>
-int launch_bwd_generic(const AttnArgs& a, hipStream_t st, bool stream_keys) {
-  dim3 grid((a.L + 127) / 128, a.B * a.A);
-  const size_t s1 = dq_smem<P, DHT>(a.L), s2 = dkv_smem<P, DHT>(a.L);
-  if (stream_keys || s1 > kLdsLimit || s2 > kLdsLimit) {
-    using ST = AttnStream<P, DHT>;
-    static_assert(ST::dq_bytes() <= kLdsLimit && ST::dkv_bytes() <= kLdsLimit, "streaming backward LDS");
-    if (hipFuncSetAttribute((const void*)attn_bwd_dq_stream_kernel<P, DHT, S16>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ST::dq_bytes()) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_bwd_dkv_stream_kernel<P, DHT, S16>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ST::dkv_bytes()) != hipSuccess)
+AttnKernels generic_kernels(AttnForm f) {
+  if (f == kAttnGenericStream)
+    return {attn_fwd_stream_kernel<P, DHT, S16>, {attn_bwd_dq_stream_kernel<P, DHT, S16>, attn_bwd_dkv_stream_kernel<P, DHT, S16>}};
+  return {attn_fwd_kernel<P, DHT, S16>, {attn_bwd_dq_kernel<P, DHT, S16>, attn_bwd_dkv_kernel<P, DHT, S16>}};
+}
+template <bool S16>
+AttnKernels bf16_kernels(AttnForm f) {
+  switch (f) {
+    case kAttnBf16Seq: return {attn_fwd_seq_bf16_kernel<S16>, {}};
+    case kAttnBf16Fused: return {nullptr, {attn_bwd_fused_bf16_kernel<S16>}};
+    case kAttnBf16Roles4: return {nullptr, {attn_bwd_roles_bf16_kernel<S16, 4>}};
+    case kAttnBf16Roles8: return {nullptr, {attn_bwd_roles_bf16_kernel<S16, 8>}};
+    case kAttnBf16Stream:
+      return {attn_fwd_stream_bf16_kernel<S16>, {attn_bwd_dq_stream_bf16_kernel<S16>, attn_bwd_dkv_stream_bf16_kernel<S16>}};
+    default:  // kAttnBf16Panel
+      return {attn_fwd_bf16_kernel<S16>, {attn_bwd_dq_bf16_kernel<S16>, attn_bwd_dkv_bf16_kernel<S16>}};
+  }
+}
+int attn_launch(const AttnPlan& p, const AttnKey& key, const AttnArgs& a, hipStream_t st) {
+  if (p.rc != XFMR_OK) return p.rc;
+  AttnKernels ks;
+  if (p.form >= kAttnBf16Seq) ks = key.s16 ? bf16_kernels<true>(p.form) : bf16_kernels<false>(p.form);
+  else if (key.precision == XFMR_PREC_BF16)
+    ks = key.s16 ? generic_kernels<PrecBF16, 64, true>(p.form) : generic_kernels<PrecBF16, 64, false>(p.form);
+  else ks = key.H / key.A == 32 ? generic_kernels<PrecF32, 32, false>(p.form) : generic_kernels<PrecF32, 64, false>(p.form);
+  const AttnKernel* k = p.bwd ? ks.bwd : &ks.fwd;
+  for (int i = 0; i < p.n; ++i)
+    if (hipFuncSetAttribute((const void*)k[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds[i]) != hipSuccess)
       return XFMR_EHIP;
-    hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<P, DHT, S16>), grid, dim3(256), ST::dq_bytes(), st, a);
+  for (int i = 0; i < p.n; ++i) {
+    hipLaunchKernelGGL(k[i], dim3(p.gx, p.gy), dim3(p.block), p.lds[i], st, a);
     XF_LAUNCH_CHECK();
-    hipLaunchKernelGGL((attn_bwd_dkv_stream_kernel<P, DHT, S16>), grid, dim3(256), ST::dkv_bytes(), st, a);
-    XF_LAUNCH_CHECK();
-    return XFMR_OK;
   }
-  if (hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<P, DHT, S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)s1) != hipSuccess ||
-      hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<P, DHT, S16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)s2) != hipSuccess)
-    return XFMR_EHIP;
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<P, DHT, S16>), grid, dim3(256), s1, st, a);
-  XF_LAUNCH_CHECK();
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<P, DHT, S16>), grid, dim3(256), s2, st, a);
-  XF_LAUNCH_CHECK();
   return XFMR_OK;
-}
-// precision x storage x head size -> kernel family
-int dispatch_fwd(const AttnArgs& a, int precision, bool s16, hipStream_t st, bool stream_keys) {
-  const int dh = a.H / a.A;
-  if (a.offs && !(precision == XFMR_PREC_BF16 && dh == 32)) return XFMR_EUNSUPPORTED;  // packed rows: production kernels only
-  if (precision == XFMR_PREC_BF16) {
-    if (dh == 32) return s16 ? launch_fwd_bf16<true>(a, st, stream_keys) : launch_fwd_bf16<false>(a, st, stream_keys);
-    return s16 ? launch_fwd_generic<PrecBF16, 64, true>(a, st, stream_keys)
-               : launch_fwd_generic<PrecBF16, 64, false>(a, st, stream_keys);
-  }
-  if (precision == XFMR_PREC_F32 && !s16)
-    return dh == 32 ? launch_fwd_generic<PrecF32, 32, false>(a, st, stream_keys)
-                    : launch_fwd_generic<PrecF32, 64, false>(a, st, stream_keys);
-  return XFMR_EINVAL;
-}
-int dispatch_bwd(const AttnArgs& a, int precision, bool s16, hipStream_t st, bool stream_keys) {
-  const int dh = a.H / a.A;
-  if (a.offs && !(precision == XFMR_PREC_BF16 && dh == 32)) return XFMR_EUNSUPPORTED;
-  if (precision == XFMR_PREC_BF16) {
-    if (dh == 32) return s16 ? launch_bwd_bf16<true>(a, st, stream_keys) : launch_bwd_bf16<false>(a, st, stream_keys);
-    return s16 ? launch_bwd_generic<PrecBF16, 64, true>(a, st, stream_keys)
-               : launch_bwd_generic<PrecBF16, 64, false>(a, st, stream_keys);
-  }
-  if (precision == XFMR_PREC_F32 && !s16)
-    return dh == 32 ? launch_bwd_generic<PrecF32, 32, false>(a, st, stream_keys)
-                    : launch_bwd_generic<PrecF32, 64, false>(a, st, stream_keys);
-  return XFMR_EINVAL;
 }
 
 int check_shape(int B, int L, int A, int H) {
@@ -2301,6 +2283,22 @@ int check_shape(int B, int L, int A, int H) {
 
 extern "C" {
 
+int xf_attn_plan(int32_t bwd, int32_t precision, int32_t s16, int32_t B, int32_t L, int32_t A, int32_t H, int32_t causal,
+                 int32_t packed, int32_t stream_keys, int32_t switches, int32_t out[8]) {
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (int rc = check_shape(B, L, A, H)) return rc;
+  const AttnKey k{precision, s16 != 0, B, L, A, H, causal != 0, packed != 0, stream_keys != 0};
+  const AttnSwitches sw{(switches & 1) != 0, (switches & 2) != 0, (switches & 4) != 0};
+  const AttnPlan p = bwd ? attn_plan_bwd(k, sw) : attn_plan_fwd(k, sw);
+  const int32_t fields[7] = {p.form, p.n, (int32_t)p.gx, (int32_t)p.gy, (int32_t)p.block, (int32_t)p.lds[0], (int32_t)p.lds[1]};
+  for (int i = 0; i < 7; ++i) out[i] = fields[i];
+  return p.rc;
+}
+int xf_attn_switches() {
+  const AttnSwitches sw = attn_switches();
+  return (int)sw.fwd_split | (int)sw.bwd_split << 1 | (int)sw.bwd_roles << 2;
+}
+
 int xf_attn_fwd_ex(const void* qkv, const uint8_t* key_mask, void* ctx, float* lse, int32_t B, int32_t L, int32_t A,
                    int32_t H, float dropout_p, XfSeed seed, uint32_t site, int32_t precision, bool s16,
                    bool causal, hipStream_t st, const int32_t* seq_offsets, bool stream_keys) {
@@ -2311,7 +2309,8 @@ int xf_attn_fwd_ex(const void* qkv, const uint8_t* key_mask, void* ctx, float* l
   a.qkv = (const float*)qkv; a.key_mask = key_mask; a.ctx = (float*)ctx; a.lse = lse; a.B = B; a.L = L; a.A = A;
   a.H = H; a.causal = causal; a.offs = seq_offsets;
   a.drop = xf_make_dropout(dropout_p, seed, site);
-  return dispatch_fwd(a, precision, s16, st, stream_keys);
+  const AttnKey k{precision, s16, B, L, A, H, causal, seq_offsets != nullptr, stream_keys};
+  return attn_launch(attn_plan_fwd(k, attn_switches()), k, a, st);
 }
 
 int xfmr_attn_fwd(const float* qkv, const uint8_t* key_mask, float* ctx, float* lse, int32_t B, int32_t L,
@@ -2341,7 +2340,8 @@ int xf_attn_bwd_ex(const void* qkv, const uint8_t* key_mask, const void* ctx, co
   a.lse = const_cast<float*>(lse); a.d_ctx = (const float*)d_ctx; a.d_qkv = (float*)d_qkv;
   a.B = B; a.L = L; a.A = A; a.H = H; a.causal = causal; a.offs = seq_offsets;
   a.drop = xf_make_dropout(dropout_p, seed, site);
-  return dispatch_bwd(a, precision, s16, st, stream_keys);
+  const AttnKey k{precision, s16, B, L, A, H, causal, seq_offsets != nullptr, stream_keys};
+  return attn_launch(attn_plan_bwd(k, attn_switches()), k, a, st);
 }
 
 int xfmr_attn_bwd(const float* qkv, const uint8_t* key_mask, const float* ctx, const float* lse,

@@ -127,6 +127,14 @@ int xf_embed_param_grads_packed(const float* d_pre, float* d_pos, float* d_type,
 // fuse_ffn, rederive, fuse_ffn_bwd, dw_buffers_per_layer, dw_side, group_dw, lin_copy, half_layer, then zeros. Returns
 // check_cfg's code; reads the cfg's pointers only for being null or not.
 int xf_encoder_plan(const xfmr_encoder_cfg* cfg, int32_t out[16]);
+// attention.hip: the kernels xf_attn_fwd_ex (bwd = 0) / xf_attn_bwd_ex (bwd = 1) would launch for these arguments (AttnPlan), as
+// integers: form (AttnForm), kernels, grid x, grid y, block, dynamic LDS bytes of the first and of the second kernel, then
+// zero. packed = seq_offsets given; switches = the bits of xf_attn_switches, which the real entries read from the
+// environment (1: XFMR_ATTN_FWD_SPLIT, 2: XFMR_ATTN_BWD_SPLIT, 4: XFMR_ATTN_BWD_FORM=roles). Returns the code the call would
+// return for its shape, precision and layout (check_shape first); touches no device.
+int xf_attn_plan(int32_t bwd, int32_t precision, int32_t s16, int32_t B, int32_t L, int32_t A, int32_t H, int32_t causal,
+                 int32_t packed, int32_t stream_keys, int32_t switches, int32_t out[8]);
+int xf_attn_switches();
 int xf_layernorm_bwd_impl(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                           float* dx, void* d_lin, bool lin16, float* d_gamma, float* d_beta, float* d_bias,
                           int64_t rows, int32_t H, XfDropout drop_out, XfDropout drop_lin, void* partials,
