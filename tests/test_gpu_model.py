@@ -740,7 +740,11 @@ def test_loss_api_errors_mirror_reference(X):
                                          ((2, 20), 1024, 70)])
 def test_fused_loss_positions_form_vs_oracle(X, prec, T_shape, H, V):
     """All seven heads + statistics + d_tok from ONE launch sequence, on ragged positions, vs the oracle that
-    materialises the (Np, 1+N, H) candidates like models.py:408-416. Several tiles and splits are exercised."""
+    materialises the (Np, 1+N, H) candidates like models.py:408-416. Several tiles and splits are exercised.
+
+    No `table_bf16` is passed, so in bf16 this runs the GENERIC loss_main_kernel, not the LDS-DMA production path: that one
+    is held to fp64 by tests/test_gpu_loss_dma_forms.py. The inputs here are random, hence the flips allowance and the 0.25
+    hinge limit below."""
     from oracle import losses as OL
     from xfmr_rec_amd import _native as N
     from xfmr_rec_amd import ops

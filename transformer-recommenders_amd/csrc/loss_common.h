@@ -109,6 +109,9 @@ __device__ __forceinline__ void loss_epilogue_t(f32x16& s, RowState& st, f32x16 
       }
     }
     bmax = fmaxf(bmax, xf_half_swap(bmax));
+    // InfoNCE gradient pass: the running maximum moves in WHOLE powers of two (see the weight below), so the first
+    // sub-block lifts the start value scale * pos to an integer as well
+    if (head == XFMR_LOSS_INFONCE) bmax = ceilf(bmax);
     if (__any(bmax > m)) {
       const float alpha = xf_exp2(m - bmax);
       l *= alpha;
@@ -149,7 +152,17 @@ __device__ __forceinline__ void loss_epilogue_t(f32x16& s, RowState& st, f32x16 
       cnt_d += md;
       if (want_lse) {
         // counted logits are <= m by construction; the clamp keeps an uncounted large logit from inf * 0
-        const float e = xf_exp2(fminf(sv * sc2 - m, 0.f)) * md;
+        float e;
+        if (head == XFMR_LOSS_INFONCE && !mask_fn) {
+          // The weight goes into the dQ product as bf16. Taken as 2^(x - m) its rounding would depend on the running
+          // maximum, i.e. on where the column split started, and two launch plans would differ by 2^-9 per weight. As
+          // 2^frac(x) scaled by the exact power of two 2^(floor(x) - m), m an integer, every plan rounds the same
+          // significand: plans agree to fp32 summation order (tests/test_gpu_loss_dma_forms.py).
+          const float x = sv * sc2, xi = floorf(x);
+          e = ldexpf(xf_exp2(x - xi), (int)fmaxf(fminf(xi - m, 0.f), -200.f)) * md;
+        } else {
+          e = xf_exp2(fminf(sv * sc2 - m, 0.f)) * md;
+        }
         l += e;
         if (head == XFMR_LOSS_INFONCE) w = e;
       }

@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
     float smax = pos_dot;
     if (qvalid)
       for (int s = 0; s < a.pin_nsplit; ++s) smax = fmaxf(smax, a.pin_part[((int64_t)s * a.T + qi) * REC + R_SMAX]);
-    st.m = smax * sc2;
+    st.m = ceilf(smax * sc2);  // (a whole power of two, as the online form keeps it: loss_epilogue_t)
   }
   const RowConst kc{pos_dot, cpos, pos_dot * (1.f - a.margin), sc2, rq, a.margin, pos_item, head,
                     a.mask_fn != 0, catalog, head <= XFMR_LOSS_CONTRASTIVE};

@@ -456,12 +456,14 @@ def dense_loss(query, cand, target=None, *, target_position="first", train_head,
 
 def sampled_loss_lists(query, pos_items, neg_items, table, rnorm, *, train_head, all_heads=False,
                        mask_false_negatives=True, mode=N.NEG_SHARED, scale=1.0, margin=0.5, precision="bf16",
-                       need_grad=True, table_bf16=None, num_hard_negatives=0):
-    """List form (compacted queries): returns (losses[7], stats[16], d_query or None)."""
+                       need_grad=True, table_bf16=None, num_hard_negatives=0, nsplit=0, nsplit_grad=0):
+    """List form (compacted queries): returns (losses[7], stats[16], d_query or None). `nsplit` / `nsplit_grad`: as in
+    sampled_loss (0 = the library's plan)."""
     Np, H = query.shape
     Nn = 0 if neg_items is None else neg_items.numel()
     lib = N.load()
-    cfg = _loss_cfg(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives)
+    cfg = _loss_cfg(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives,
+                    flags=_plan_flags(nsplit, nsplit_grad))
     n_rows = table.shape[0]
     losses, stats = _empty((2 * N.NUM_LOSSES,), query), _empty((N.NUM_STATS,), query)
     d_q = torch.empty_like(query) if need_grad else None
