@@ -1,5 +1,5 @@
-"""Every form of the LDS-DMA bf16 loss kernels (csrc/loss_dma.inc, the four loss_dma_h*.hip launchers, run_loss and
-loss_combine_kernel of csrc/loss.hip) against fp64 references, on inputs whose dot logits are EXACT in the kernels
+"""Every form of the LDS-DMA bf16 loss kernels (csrc/loss_dma.inc with its launcher xfl_launch_form<H>, loss_plan, run_loss
+and loss_combine_kernel of csrc/loss.hip) against fp64 references, on inputs whose dot logits are EXACT in the kernels
 (tests/loss_cases.py; preconditions proven on the CPU by test_loss_cases_host.py).
 
 With exact logits no mask and no hinge indicator can flip, so nothing here gets a "flips" allowance or a hinge
@@ -11,7 +11,8 @@ at the plain bf16 gradient limit (the one bf16 step left is the rounding of the 
 bit-identical, and the generic kernels (bf16 without the table copy, fp32) meet the same limits on the same inputs,
 which shows that the inputs, not the kernel family, earn them.
 
-How a call reaches a kernel form (run_loss -> xf_launch_loss_dma_<H> -> loss_main_dma_kernel<H, HEAD_CODE, QIMG>):
+How a call reaches a kernel form (loss_plan -> run_loss -> xfl_launch_form<H> -> loss_main_dma_kernel<H, HEAD_CODE, QIMG>;
+tests/test_loss_plan_host.py asks the plan for the codes named here):
   * all_heads = True: gradient pass of the train head + logging pass (code -2 when the train head is InfoNCE, whose value
     then comes from the gradient records; -1 otherwise); all_heads = False: gradient pass only; AlignmentLoss has no
     gradient pass: logging pass -1, its gradient in loss_combine_kernel; all_heads = 2 without a gradient: logging only.

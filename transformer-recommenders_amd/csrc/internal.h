@@ -135,6 +135,19 @@ int xf_encoder_plan(const xfmr_encoder_cfg* cfg, int32_t out[16]);
 int xf_attn_plan(int32_t bwd, int32_t precision, int32_t s16, int32_t B, int32_t L, int32_t A, int32_t H, int32_t causal,
                  int32_t packed, int32_t stream_keys, int32_t switches, int32_t out[8]);
 int xf_attn_switches();
+// loss.hip: what xfmr_sampled_loss[_prepared, _lists] would launch for this key (LossPlan), as integers. The key: T positions (or
+// list rows), H, n_rows, the xfmr_loss_cfg fields, whether d_tok and table_bf16 are given, the device's compute units, and
+// `switches`, the bits of xf_loss_switches, which the real entries read from the environment (bit 0: XFMR_LOSS_Q_FP32,
+// bit 1: XFMR_LOSS_LOGM256 not off, bits 2-32: XFMR_LOSS_NSPLIT, bits 33-63: XFMR_LOSS_NSPLIT_GRAD; 0 = unset or <= 0).
+// out: family (0 generic bf16, 1 generic fp32, 2 LDS-DMA), hard-negative prologue, qprep launch, number of passes; two
+// passes of 11 -- role (0 gradient or a generic call's only kernel, 1 logging), HEAD_* code (generic: template width), ALL
+// (generic), grid x, y, z, nsplit, record buffer (0 part, 1 part2), query image, in-kernel finish, pin_part --; the combine
+// kernel's need_grad, nsplit, nsplit_loss, values' buffer, lse_from_grad, skip_train_head, values-only variant, blocks;
+// then zeros. Returns the code the call would return for the key (all zeros then); touches no device.
+int xf_loss_plan(int64_t T, int32_t H, int64_t n_rows, int32_t train_head, int32_t all_heads, int32_t mask_false_negatives,
+                 int32_t mode, int32_t precision, int32_t num_hard_negatives, uint32_t flags, int32_t has_d_tok,
+                 int32_t has_table_bf16, int32_t cus, uint64_t switches, int32_t out[40]);
+uint64_t xf_loss_switches();
 int xf_layernorm_bwd_impl(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                           float* dx, void* d_lin, bool lin16, float* d_gamma, float* d_beta, float* d_bias,
                           int64_t rows, int32_t H, XfDropout drop_out, XfDropout drop_lin, void* partials,

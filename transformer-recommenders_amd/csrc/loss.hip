@@ -15,6 +15,9 @@
 //   * the negatives axis is split across workgroups (grid.y) to fill 256 CUs; a combine kernel merges the
 //     split partials per query, finishes the seven row losses and the gradient row, and a final
 //     single-workgroup kernel reduces them deterministically.
+#include <stdlib.h>
+#include <string.h>
+
 #include "internal.h"
 #include "loss_common.h"
 
@@ -154,14 +157,13 @@ __global__ __launch_bounds__(PREP) void distinct_write_kernel(const int* hist, i
 // That is how every d_model the reference can be configured with (models.py:22-48: any hidden_size) reaches this kernel:
 // the width is rounded up to the next instantiation (64, 128, 256, 384, 512, 768, 1024; the fp32 policy up to 512: its
 // tile image is 4 bytes per element, and at 512 the dQ parts are 64 columns wide so that both images fit 160 KB).
-template <class P, int H>
-constexpr int loss_main_hparts() { return H <= 256 ? 1 : (sizeof(typename P::elem) == 4 && H >= 512) ? H / 64 : H / 128; }
+constexpr int loss_main_hparts(bool f32, int H) { return H <= 256 ? 1 : (f32 && H >= 512) ? H / 64 : H / 128; }
 template <class P, int H, bool ALL>
 __global__ __launch_bounds__(256, (H <= 128 ? 2 : 1)) void loss_main_kernel(LossArgs a) {
   using elem = typename P::elem;
   constexpr int LDE = xf_ld<P>(H);
   constexpr int NPASS = 2 * (H / 64);  // staging passes: 32 rows x 64 columns per pass per workgroup
-  constexpr int HP = loss_main_hparts<P, H>(), HW = H / HP, NO = HW / 32;
+  constexpr int HP = loss_main_hparts(sizeof(elem) == 4, H), HW = H / HP, NO = HW / 32;
   const int Hr = a.H;
   const int hpart = HP > 1 ? (int)blockIdx.z : 0;
   // With every head evaluated the epilogue needs the registers: the wave's query rows then live in LDS
@@ -812,20 +814,45 @@ __global__ void loss_final_kernel(const double* tot, const int* counts, int mode
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------
-struct Plan {
-  int nsplit;
-  size_t off_part2, off_negrc, off_tot;
-  size_t off_dump, off_tau, off_qinfo; int64_t dump_ld;  // num_hard_negatives only
-  size_t off_hist, off_dcnt, off_negmul; int ndblocks;    // distinct-item compaction
-  size_t off_counts, off_blockcnt, off_neg, off_qrow, off_qpos, off_part, off_partO, off_block, total;
-  size_t off_qimg, off_qaux;  // bf16 image of the query rows + {|q|^2, q . e_pos} per query (loss_qprep_kernel)
-  int nblocks;
-};
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-// `ns_override` (xfmr_loss_cfg.flags, XFMR_LOSS_NSPLIT(n)): a column-split count forced by the caller (parity tests walk
-// several plans in one process); 0 = the plan's own choice below.
-Plan make_plan(int64_t T, int H, int64_t n_rows, bool hard = false, int ns_override = 0) {
-  Plan p;
+// The four environment switches of the loss, read here and nowhere else. Once per process: XFMR_LOSS_NSPLIT and
+// XFMR_LOSS_NSPLIT_GRAD (tuning experiments: the column-split counts below; atoi, <= 0: none) and XFMR_LOSS_LOGM256 (a
+// leading '0': the general logging epilogue at H = 256, loss_dma_form). On every call: XFMR_LOSS_Q_FP32 (set, not empty and
+// not "0": every launch reads the fp32 query rows, none the bf16 image).
+struct LossSwitches { int nsplit, nsplit_grad; bool logm256, q_fp32; };
+LossSwitches loss_switches() {
+  static const LossSwitches once = [] {
+    const char* n = getenv("XFMR_LOSS_NSPLIT");
+    const char* g = getenv("XFMR_LOSS_NSPLIT_GRAD");
+    const char* m = getenv("XFMR_LOSS_LOGM256");
+    return LossSwitches{n ? atoi(n) : 0, g ? atoi(g) : 0, !(m && *m == '0'), false};
+  }();
+  LossSwitches s = once;
+  const char* q = getenv("XFMR_LOSS_Q_FP32");
+  s.q_fp32 = q && q[0] && !(q[0] == '0' && !q[1]);
+  return s;
+}
+// ... as the bits xf_loss_switches returns and xf_loss_plan takes (internal.h); a count <= 0 means "none" and travels as 0
+uint64_t switch_bits(const LossSwitches& s) {
+  return (uint64_t)s.q_fp32 | (uint64_t)s.logm256 << 1 | (uint64_t)(s.nsplit > 0 ? s.nsplit : 0) << 2 |
+         (uint64_t)(s.nsplit_grad > 0 ? s.nsplit_grad : 0) << 33;
+}
+LossSwitches switches_of(uint64_t b) {
+  return LossSwitches{(int)(b >> 2 & 0x7fffffffu), (int)(b >> 33), (b >> 1 & 1) != 0, (b & 1) != 0};
+}
+// compute units of the current device, asked once per process; 256 (MI355X) when no device answers
+int loss_cu_count() {
+  static const int cus = [] {
+    int dev = 0, cu = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
+    return cu > 0 ? cu : 256;
+  }();
+  return cus;
+}
+
+// The column-split count the workspace is carved for, which is the logging pass's (and the generic kernels') own.
+// ns_env: XFMR_LOSS_NSPLIT. ns_override (xfmr_loss_cfg.flags, XFMR_LOSS_NSPLIT(n)): a count forced by the caller (parity
+// tests walk several plans in one process); 0 = the choice below.
+int loss_nsplit(int64_t T, int64_t n_rows, int ns_env, int ns_override) {
   const int64_t qblocks = (T + QB - 1) / QB;
   const int64_t cols = T > n_rows ? T : n_rows;
   const int64_t tiles = (cols + BN - 1) / BN;
@@ -837,17 +864,34 @@ Plan make_plan(int64_t T, int H, int64_t n_rows, bool hard = false, int ns_overr
   // fewer than 32 blocks (the reference's default model: 8) keep the finer split.
   if (qblocks >= 32 && qblocks < 64 && ns > 8) ns = 8;
   if (ns < 2) ns = 2;  // measured at 800 query blocks (B = 512): 2 splits 95.5k seq/s, 1 split 94.1k
-  // >= 512 query blocks: the gradient pass runs ONE split there (run_loss), so this count is the logging pass's alone. At
+  // >= 512 query blocks: the gradient pass runs ONE split there (loss_plan), so this count is the logging pass's alone. At
   // three workgroups per CU (768 slots) 800 blocks x 2 splits are 2.08 rounds -- the third round nearly empty; finer
   // pieces fill it: isolated 456 us (2 splits), 427 (3), 422 (4), 414 (5), 425 (6), 428 (8); 525 with one. In the step the
   // pass is hidden underneath the backward either way (3.32-3.36 ms for 2 ... 6 splits).
   if (ns < 4 && qblocks >= 512) ns = 4;
-  static const int ns_env = [] { const char* e = getenv("XFMR_LOSS_NSPLIT"); return e ? atoi(e) : 0; }();  // tuning experiments
   if (ns_env > 0) ns = ns_env;
   if (ns_override > 0) ns = ns_override;
   if (ns > tiles) ns = tiles;
   if (ns < 1) ns = 1;
-  p.nsplit = (int)ns;
+  return (int)ns;
+}
+
+// The workspace carve. It depends only on what xfmr_sampled_loss_prepare knows.
+struct Plan {
+  int nsplit;
+  size_t off_part2, off_negrc, off_tot;
+  size_t off_dump, off_tau, off_qinfo; int64_t dump_ld;  // num_hard_negatives only
+  size_t off_hist, off_dcnt, off_negmul; int ndblocks;    // distinct-item compaction
+  size_t off_counts, off_blockcnt, off_neg, off_qrow, off_qpos, off_part, off_partO, off_block, total;
+  size_t off_qimg, off_qaux;  // bf16 image of the query rows + {|q|^2, q . e_pos} per query (loss_qprep_kernel)
+  int nblocks;
+};
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+Plan make_plan(int64_t T, int H, int64_t n_rows, bool hard, int nsplit) {
+  Plan p;
+  const int64_t cols = T > n_rows ? T : n_rows;
+  const size_t ns = (size_t)nsplit;
+  p.nsplit = nsplit;
   p.nblocks = (int)((T + kCombineRows - 1) / kCombineRows);
   size_t o = 0;
   p.off_counts = o; o += 256;
@@ -860,9 +904,9 @@ Plan make_plan(int64_t T, int H, int64_t n_rows, bool hard = false, int ns_overr
   p.off_dcnt = o; o += up256((size_t)p.ndblocks * 4);
   p.off_qrow = o; o += up256((size_t)T * 4);
   p.off_qpos = o; o += up256((size_t)T * 4);
-  p.off_part = o; o += up256((size_t)ns * T * REC * 4);
-  p.off_part2 = o; o += up256((size_t)ns * T * REC * 4);
-  p.off_partO = o; o += up256((size_t)ns * T * H * 4);
+  p.off_part = o; o += up256(ns * T * REC * 4);
+  p.off_part2 = o; o += up256(ns * T * REC * 4);
+  p.off_partO = o; o += up256(ns * T * H * 4);
   p.off_block = o; o += up256((size_t)p.nblocks * BP * 8);
   p.off_tot = o; o += 256;
   p.off_qimg = o; o += up256((size_t)T * H * 2);
@@ -877,29 +921,191 @@ Plan make_plan(int64_t T, int H, int64_t n_rows, bool hard = false, int ns_overr
   p.total = o;
   return p;
 }
-
-template <class P, int H>
-void launch_main(const LossArgs& a, bool all, dim3 grid, hipStream_t st) {
-  grid.z = (a.need_grad && !a.dump) ? loss_main_hparts<P, H>() : 1;  // dQ column parts (values-only launches: one)
-  if (all) hipLaunchKernelGGL((loss_main_kernel<P, H, true>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((loss_main_kernel<P, H, false>), grid, dim3(256), 0, st, a);
+// ... of a call: `rows` positions (or list rows); cfg null = the defaults (no hard negatives, no override)
+Plan loss_carve(const xfmr_loss_cfg* cfg, int64_t rows, int H, int64_t n_rows) {
+  const int ns_override = cfg ? (int)XFMR_LOSS_NSPLIT_OF(cfg->flags) : 0;
+  return make_plan(rows, H, n_rows, cfg && cfg->num_hard_negatives > 0,
+                   loss_nsplit(rows, n_rows, loss_switches().nsplit, ns_override));
 }
-// H: the rows' real width (any multiple of 32) -> the next instantiated template width (see loss_main_kernel)
+
+// ---- the plan: which main passes a call runs, in which forms, and how the combine kernel is wired ---------------------
+// One pure function of the call's key: no environment, no device, no pointer beyond given-or-not. run_loss executes what it
+// says; xf_loss_plan (internal.h) shows it to the tests. Every field is an int32: the entry copies the struct out.
+enum { kLossGenericBf16 = 0, kLossGenericF32, kLossDma };  // LossPlan::family: loss_main_kernel<P> / loss_main_dma_kernel
+enum { kPassGrad = 0, kPassLog };  // LossPass::role: kPassGrad = the gradient pass, or a generic call's ONLY main kernel
+struct LossKey {
+  int64_t T, n_rows;
+  int H, train_head, all_heads, mask_fn, mode, precision, num_hard;  // xfmr_loss_cfg's
+  uint32_t flags;
+  bool d_tok, table_bf16;  // given or null
+  int cus;
+  LossSwitches sw;
+};
+struct LossPass {
+  int32_t role;
+  int32_t code;        // DMA: the HEAD_* code (loss_dma_form); generic: the template width
+  int32_t all;         // generic: ALL (every head evaluated)
+  int32_t gx, gy, gz;  // query blocks, column splits, dQ column parts
+  int32_t nsplit;      // the split count its records are written with (= gy)
+  int32_t buf;         // ... and where: 0 = part, 1 = part2
+  int32_t image;       // stages its query rows from the bf16 image (DMA, more than one split)
+  int32_t finish;      // finishes its rows in the kernel (LossArgs::d_tok set)
+  int32_t pinned;      // LossArgs::pin_part set: the row maxima of the logging pass before it
+};
+struct LossPlan {
+  int32_t family, hard /* dump + select prologue */, qprep /* loss_qprep_kernel before the first `image` pass */, npass;
+  LossPass pass[2];
+  // CombineArgs: need_grad, the split counts of the gradient's and of the values' records, the values' buffer (0 = part:
+  // the gradient's), lse_from_grad, skip_train_head; then the kernel variant and its blocks (kValueRows / kCombineRows)
+  int32_t need_grad, nsplit, nsplit_loss, loss_buf, lse_from_grad, skip_train_head, values_only, blocks;
+};
+constexpr int kLossPlanInts = sizeof(LossPlan) / sizeof(int32_t);
+
+// what check_loss_args and the plan refuse of the key alone
+bool loss_key_ok(int64_t rows, int64_t n_rows, int train_head, int num_hard) {
+  return rows > 0 && n_rows > 0 && rows <= (1 << 30) && n_rows <= (1 << 30) && train_head >= 0 &&
+         train_head < XFMR_NUM_LOSSES && num_hard >= 0;
+}
+// H: the rows' real width (any multiple of 32) -> the next instantiated template width (see loss_main_kernel); 0: none
+constexpr int loss_main_width(bool f32, int H) {
+  if (H <= 0 || (H & 31)) return 0;
+  for (int w : {64, 128, 256, 384, 512})
+    if (H <= w) return w;
+  if (f32) return 0;  // (the fp32 tile image of 64 x 768 does not fit LDS)
+  return H <= 768 ? 768 : H <= 1024 ? 1024 : 0;
+}
+
+// Returns the code the call returns for its key (lp all zero unless XFMR_OK).
+int loss_plan(const LossKey& k, LossPlan& lp) {
+  lp = LossPlan{};
+  if (!loss_key_ok(k.T, k.n_rows, k.train_head, k.num_hard)) return XFMR_EINVAL;
+  const bool f32 = k.precision == XFMR_PREC_F32;
+  if (!f32 && k.precision != XFMR_PREC_BF16) return XFMR_EINVAL;
+  const int H = k.H, head = k.train_head;
+  const int qblocks = (int)((k.T + QB - 1) / QB);
+  const int ns = loss_nsplit(k.T, k.n_rows, k.sw.nsplit, (int)XFMR_LOSS_NSPLIT_OF(k.flags));
+  const bool hard = k.num_hard > 0;
+  // widths the LDS-DMA kernel is instantiated for; its gather addresses rows by a 32-bit byte offset from the table base
+  const bool dma_width = (H == 64 || H == 128 || H == 256 || H == 384) && (uint64_t)k.n_rows * (uint64_t)H * 2 < (1ull << 32);
+  bool finish = false;
+  if (hard || f32 || !k.table_bf16 || !dma_width) {
+    // The generic kernel, one launch with every split writing `part`. top-k hard negatives (losses.py:295-330) take it in
+    // both precisions: (1) the same kernel dumps its logits (bit-identical to what the loss pass will see), (2) per-row
+    // thresholds by radix select, (3) the loss pass with every counted negative weighted by its top-k weight.
+    const int W = loss_main_width(f32, H);
+    if (!W) return XFMR_EUNSUPPORTED;
+    lp.family = f32 ? kLossGenericF32 : kLossGenericBf16;
+    lp.hard = hard;
+    const int parts = k.d_tok ? loss_main_hparts(f32, W) : 1;  // dQ column parts (values-only launches: one)
+    lp.pass[lp.npass++] = LossPass{kPassGrad, W, k.all_heads != 0, qblocks, ns, parts, ns, 0, 0, 0, 0};
+    lp.nsplit = lp.nsplit_loss = ns;
+  } else {
+    // bf16 production path (never with hard negatives: LossArgs::tau, which only they set, is null in every DMA launch):
+    // the gradient pass of the train head (skipped for AlignmentLoss, whose gradient has no negative term) and, when every
+    // head is wanted or no gradient is, the values-only logging pass.
+    lp.family = kLossDma;
+    const bool mask_fn = k.mask_fn != 0;
+    const bool grad_pass = k.d_tok && head != XFMR_LOSS_ALIGNMENT;
+    const bool log_pass = k.all_heads != 0 || !grad_pass;
+    // unmasked InfoNCE with the logging pass in the same call: logging first, then the gradient pass with the row
+    // maximum pinned from the logging records (lean epilogue, see HEAD_INFONCE_PINNED)
+    const bool pinned = grad_pass && k.all_heads == 1 && head == XFMR_LOSS_INFONCE && !mask_fn;
+    const int gcode = loss_dma_form(H, head, mask_fn, k.mode, pinned, k.sw.logm256);
+    const int parts = loss_dma_hparts(H, gcode);
+    const bool col_parts = parts > 1;  // they keep the split form (no in-kernel finish)
+    // Gradient pass with ONE column split when the query blocks alone fill the chip (>= two workgroups per CU): the kernel
+    // then finishes its rows itself (LossArgs::d_tok) -- no (split, T, H) partial dQ written and re-read (105 + 105 MB at the
+    // benchmark shape), no gradient work in the combine kernel. Measured at 800 query blocks: the pass itself takes the
+    // same time with 1, 2 or 3 splits (387 us). XFMR_LOSS_NSPLIT_GRAD overrides (experiments).
+    int ns_grad = ns;
+    // (round 4: from 257 blocks on. n splits of b blocks take ceil(n b / 512) rounds of 1/n of the columns each: with more than
+    //  256 blocks two splits are two rounds of half a walk -- one split's time -- plus the partial dQ and the combine launch.
+    //  Measured on MovieLens-like batches of 512 in the packed layout, ~390 blocks: 2.00-2.01 against 2.03 ms per step.)
+    if (qblocks >= 512 || (H <= 128 && qblocks > 256)) ns_grad = 1;  // (H > 128: one workgroup per CU, planned by rounds below)
+    const int ns_grad_env = k.sw.nsplit_grad;
+    const int ns_grad_flag = (int)XFMR_LOSS_NSPLIT_GRAD_OF(k.flags);  // (tests: several plans in one process)
+    if (ns_grad_env > 0) ns_grad = ns_grad_env;
+    if (ns_grad_flag > 0) ns_grad = ns_grad_flag;
+    if (ns_grad < 1) ns_grad = 1;
+    if (ns_grad > ns) ns_grad = ns;  // (the workspace is carved for ns)
+    // H > 128 below 512 query blocks: these gradient kernels run ONE workgroup per CU (loss_dma.inc), all of them equally
+    // long, so the pass takes ceil(blocks * n / CUs) rounds of 1 / n of the columns each. The fewest splits among the best
+    // such n: config 5 (256 blocks on 256 CUs) runs 1 split -- one full round, the rows finished in the kernel, no 134 MB
+    // of partial dQ written and re-read (6.62 -> 6.51 ms/step); config 4 (100 blocks) 5 splits instead of 10 (two rounds
+    // of 250: 3.06 -> 2.99; 3 splits = 1.17 rounds measured 3.30).
+    if (H > 128 && qblocks < 512 && ns_grad_env <= 0 && ns_grad_flag <= 0) {
+      int best = ns;
+      double best_cost = 1e30;
+      for (int n = 1; n <= ns; ++n) {
+        // (+ 0.01 per split: every split writes and the combine kernel re-reads a (queries x H) fp32 partial dQ -- at 8 query
+        //  blocks (the reference's default model: 32 x 32 tokens, H = 384) 8 splits measured 0.303 ms per step against 0.313
+        //  for 16 and 0.306 for 4; configs 4 / 5 keep their 5 / 1)
+        const double cost = (double)(((int64_t)qblocks * n + k.cus - 1) / k.cus) / n + 0.01 * n;
+        if (cost < best_cost - 1e-9) { best_cost = cost; best = n; }
+      }
+      ns_grad = best;
+    }
+    if (col_parts) {  // the carve's count; overrides still apply
+      ns_grad = ns;
+      if (ns_grad_env > 0) ns_grad = ns_grad_env < ns ? ns_grad_env : ns;
+      if (ns_grad_flag > 0) ns_grad = ns_grad_flag < ns ? ns_grad_flag : ns;
+    }
+    finish = grad_pass && ns_grad == 1 && !col_parts;
+    // The logging pass without the InfoNCE log-sum-exp (-2) when the train head is InfoNCE and its value comes from
+    // elsewhere: from the gradient pass of THIS call, whose records the combine kernel then reads it from (lse_from_grad),
+    // or -- all_heads == 2 -- from the gradient pass of the same step, the caller having it already.
+    const bool lse_elsewhere = head == XFMR_LOSS_INFONCE && (grad_pass || k.all_heads == 2);
+    const int lcode = loss_dma_form(H, lse_elsewhere ? -2 : -1, mask_fn, k.mode, false, k.sw.logm256);
+    // Query rows as bf16, converted once per call: a launch with n > 1 column splits would read and round every fp32 query
+    // row n times (and gather and multiply its positive's row n times); it stages them from the image instead, which
+    // loss_qprep_kernel writes in front of the first such launch. A launch with one split reads the fp32 rows itself --
+    // once. XFMR_LOSS_Q_FP32=1 keeps every launch on the fp32 rows: the results are the same bit for bit
+    // (tests/test_gpu_loss_bf16_rows.py).
+    auto add = [&](int role, int code, int gz, int n, int buf, bool fin) {
+      const bool image = !k.sw.q_fp32 && n > 1;
+      lp.qprep |= image;
+      lp.pass[lp.npass++] = LossPass{role, code, 0, qblocks, n, gz, n, buf, image, fin, role == kPassGrad && pinned};
+    };
+    // (a logging pass beside a gradient pass writes part2: the values come from there, the gradient from part)
+    if (log_pass && pinned) add(kPassLog, lcode, 1, ns, 1, false);
+    if (grad_pass) add(kPassGrad, gcode, parts, ns_grad, 0, finish);
+    if (log_pass && !pinned) add(kPassLog, lcode, 1, ns, grad_pass, false);
+    lp.nsplit = grad_pass ? ns_grad : ns;
+    lp.loss_buf = grad_pass && log_pass;
+    lp.nsplit_loss = lp.loss_buf ? ns : lp.nsplit;
+    lp.lse_from_grad = lp.loss_buf && lse_elsewhere;
+  }
+  lp.need_grad = k.d_tok && !finish;  // finish: the gradient pass wrote d_tok itself
+  lp.skip_train_head = k.all_heads == 2 && !k.d_tok;
+  lp.values_only = !lp.need_grad;  // one lane per row
+  const int rows = lp.values_only ? kValueRows : kCombineRows;
+  lp.blocks = (int)((k.T + rows - 1) / rows);
+  return XFMR_OK;
+}
+
+template <class P, int W>
+void launch_main(const LossArgs& a, bool all, dim3 grid, hipStream_t st) {
+  if (all) hipLaunchKernelGGL((loss_main_kernel<P, W, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((loss_main_kernel<P, W, false>), grid, dim3(256), 0, st, a);
+}
 template <class P>
-int launch_main_h(const LossArgs& a, int H, bool all, dim3 grid, hipStream_t st) {
-  if (H <= 0 || (H & 31)) return XFMR_EUNSUPPORTED;
-  constexpr bool f32 = sizeof(typename P::elem) == 4;
-  if (H <= 64) launch_main<P, 64>(a, all, grid, st);
-  else if (H <= 128) launch_main<P, 128>(a, all, grid, st);
-  else if (H <= 256) launch_main<P, 256>(a, all, grid, st);
-  else if (H <= 384) launch_main<P, 384>(a, all, grid, st);
-  else if (H <= 512) launch_main<P, 512>(a, all, grid, st);
-  else if (f32) return XFMR_EUNSUPPORTED;  // (the fp32 tile image of 64 x 768 does not fit LDS)
-  else if (H <= 768) launch_main<PrecBF16, 768>(a, all, grid, st);
-  else if (H <= 1024) launch_main<PrecBF16, 1024>(a, all, grid, st);
-  else return XFMR_EUNSUPPORTED;
+int launch_main_w(const LossArgs& a, int W, bool all, dim3 grid, hipStream_t st) {
+  switch (W) {
+    case 64: launch_main<P, 64>(a, all, grid, st); break;
+    case 128: launch_main<P, 128>(a, all, grid, st); break;
+    case 256: launch_main<P, 256>(a, all, grid, st); break;
+    case 384: launch_main<P, 384>(a, all, grid, st); break;
+    case 512: launch_main<P, 512>(a, all, grid, st); break;
+    case 768: launch_main<PrecBF16, 768>(a, all, grid, st); break;  // (bf16 only: loss_main_width)
+    case 1024: launch_main<PrecBF16, 1024>(a, all, grid, st); break;
+    default: return XFMR_EUNSUPPORTED;
+  }
   XF_LAUNCH_CHECK();
   return XFMR_OK;
+}
+// W: loss_main_width's
+int launch_generic(const LossArgs& a, int family, int W, bool all, dim3 grid, hipStream_t st) {
+  return family == kLossGenericF32 ? launch_main_w<PrecF32>(a, W, all, grid, st) : launch_main_w<PrecBF16>(a, W, all, grid, st);
 }
 
 int launch_qprep_h(const LossArgs& a, __bf16* qimg, float2* qaux, int H, dim3 grid, hipStream_t st) {
@@ -912,12 +1118,12 @@ int launch_qprep_h(const LossArgs& a, __bf16* qimg, float2* qaux, int H, dim3 gr
   }
 }
 
-int launch_dma_h(const LossArgs& a, const void* tbf, int H, int head, dim3 grid, hipStream_t st) {
+int launch_dma_h(const LossArgs& a, const void* tbf, int H, int code, dim3 grid, hipStream_t st) {
   switch (H) {
-    case 64: return xf_launch_loss_dma_64(a, tbf, head, grid, st);
-    case 128: return xf_launch_loss_dma_128(a, tbf, head, grid, st);
-    case 256: return xf_launch_loss_dma_256(a, tbf, head, grid, st);
-    case 384: return xf_launch_loss_dma_384(a, tbf, head, grid, st);
+    case 64: return xf_launch_loss_dma_64(a, tbf, code, grid, st);
+    case 128: return xf_launch_loss_dma_128(a, tbf, code, grid, st);
+    case 256: return xf_launch_loss_dma_256(a, tbf, code, grid, st);
+    case 384: return xf_launch_loss_dma_384(a, tbf, code, grid, st);
     default: return XFMR_EUNSUPPORTED;
   }
 }
@@ -936,66 +1142,55 @@ int xf_loss_finalize(const double* blockpart, int nblocks, int rows_per_block, c
   return XFMR_OK;
 }
 
+uint64_t xf_loss_switches() { return switch_bits(loss_switches()); }
+int xf_loss_plan(int64_t T, int32_t H, int64_t n_rows, int32_t train_head, int32_t all_heads, int32_t mask_false_negatives,
+                 int32_t mode, int32_t precision, int32_t num_hard_negatives, uint32_t flags, int32_t has_d_tok,
+                 int32_t has_table_bf16, int32_t cus, uint64_t switches, int32_t out[40]) {
+  static_assert(kLossPlanInts <= 40, "xf_loss_plan's array");
+  LossPlan lp;
+  const int rc = loss_plan(LossKey{T, n_rows, H, train_head, all_heads, mask_false_negatives, mode, precision,
+                                   num_hard_negatives, flags, has_d_tok != 0, has_table_bf16 != 0, cus,
+                                   switches_of(switches)}, lp);
+  memset(out, 0, 40 * sizeof(int32_t));
+  memcpy(out, &lp, sizeof(lp));
+  return rc;
+}
+
 size_t xfmr_sampled_loss_workspace(int64_t positions, int32_t H, int64_t n_rows) {
   if (positions <= 0 || H <= 0) return 0;
-  return make_plan(positions, H, n_rows).total;
+  return loss_carve(nullptr, positions, H, n_rows).total;
 }
 size_t xfmr_sampled_loss_workspace_cfg(const xfmr_loss_cfg* cfg, int64_t positions, int32_t H, int64_t n_rows) {
   if (!cfg || positions <= 0 || H <= 0) return 0;
-  return make_plan(positions, H, n_rows, cfg->num_hard_negatives > 0, (int)XFMR_LOSS_NSPLIT_OF(cfg->flags)).total;
+  return loss_carve(cfg, positions, H, n_rows).total;
 }
 
+// p: loss_carve of the same (cfg, T, H, n_rows), filled by the prepare step; the caller checked the workspace against p.total
 static int run_loss(const xfmr_loss_cfg* cfg, const float* tok, const float* table, const float* table_rnorm,
-                    const void* table_bf16, int64_t n_rows, int T, int32_t H, float* losses, float* stats, float* d_tok, unsigned char* ws,
-                    size_t ws_bytes, const Plan& p, hipStream_t st) {
+                    const void* table_bf16, int64_t n_rows, int T, int32_t H, float* losses, float* stats, float* d_tok,
+                    unsigned char* ws, const Plan& p, hipStream_t st) {
+  LossPlan lp;
+  if (int rc = loss_plan(LossKey{T, n_rows, H, cfg->train_head, cfg->all_heads, cfg->mask_false_negatives, cfg->mode,
+                                 cfg->precision, cfg->num_hard_negatives, cfg->flags, d_tok != nullptr,
+                                 table_bf16 != nullptr, loss_cu_count(), loss_switches()}, lp))
+    return rc;
   int* counts = (int*)(ws + p.off_counts);
   int* neg_item = (int*)(ws + p.off_neg);
   int* qrow = (int*)(ws + p.off_qrow);
   int* qpos = (int*)(ws + p.off_qpos);
+  float* const part[2] = {(float*)(ws + p.off_part), (float*)(ws + p.off_part2)};
   LossArgs a{};
   a.tok = tok; a.table = table; a.rnorm = table_rnorm; a.n_rows = n_rows; a.counts = counts;
   a.neg_item = cfg->mode == XFMR_NEG_SHARED ? neg_item : nullptr;
   a.neg_rc = (const float*)(ws + p.off_negrc);
   a.neg_mult = cfg->mode == XFMR_NEG_SHARED ? (const float*)(ws + p.off_negmul) : nullptr;
-  a.qrow = qrow; a.qpos = qpos; a.part = (float*)(ws + p.off_part); a.partO = (float*)(ws + p.off_partO);
+  a.qrow = qrow; a.qpos = qpos; a.part = part[0]; a.partO = (float*)(ws + p.off_partO);
   a.T = T; a.H = H; a.nsplit = p.nsplit; a.train_head = cfg->train_head; a.mask_fn = cfg->mask_false_negatives;
   a.mode = cfg->mode; a.need_grad = d_tok != nullptr; a.scale = cfg->scale; a.margin = cfg->margin;
-  dim3 grid((unsigned)((T + QB - 1) / QB), p.nsplit);
-  // Gradient pass of the bf16 production path with ONE column split when the query blocks alone fill the chip (>= two
-  // workgroups per CU): the kernel then finishes its rows itself (LossArgs::d_tok) -- no (split, T, H) partial dQ written
-  // and re-read (105 + 105 MB at the benchmark shape), no gradient work in the combine kernel. Measured at 800 query
-  // blocks: the pass itself takes the same time with 1, 2 or 3 splits (387 us). XFMR_LOSS_NSPLIT_GRAD overrides (experiments).
-  int ns_grad = p.nsplit;
-  // (round 4: from 257 blocks on. n splits of b blocks take ceil(n b / 512) rounds of 1/n of the columns each: with more than
-  //  256 blocks two splits are two rounds of half a walk -- one split's time -- plus the partial dQ and the combine launch.
-  //  Measured on MovieLens-like batches of 512 in the packed layout, ~390 blocks: 2.00-2.01 against 2.03 ms per step.)
-  if (grid.x >= 512 || (H <= 128 && grid.x > 256)) ns_grad = 1;  // (H > 128: one workgroup per CU, planned by rounds below)
-  static const int ns_grad_env = [] { const char* e = getenv("XFMR_LOSS_NSPLIT_GRAD"); return e ? atoi(e) : 0; }();
-  if (ns_grad_env > 0) ns_grad = ns_grad_env;
-  const int ns_grad_flag = (int)XFMR_LOSS_NSPLIT_GRAD_OF(cfg->flags);  // (tests: several plans in one process)
-  if (ns_grad_flag > 0) ns_grad = ns_grad_flag;
-  if (ns_grad < 1) ns_grad = 1;
-  if (ns_grad > p.nsplit) ns_grad = p.nsplit;  // (the workspace is carved for p.nsplit)
-  int ns_part = p.nsplit;  // split count the records in a.part (and partO) are written with
-  bool fused_finish = false;
-  int rc;
-  // measurement events (xfmr_loss_cfg): profile_grad around the gradient pass -- or around the call's single main kernel
-  // when it runs the generic kernel --, profile_log around the values-only logging pass of the bf16 production path
-  hipEvent_t ev0 = (hipEvent_t)cfg->profile_grad[0], ev1 = (hipEvent_t)cfg->profile_grad[1];
-  hipEvent_t lev0 = (hipEvent_t)cfg->profile_log[0], lev1 = (hipEvent_t)cfg->profile_log[1];
-  const float* part_loss = nullptr;  // records the loss VALUES are read from (null: the same as the gradient's)
-  bool lse_from_grad = false;        // InfoNCE value from the gradient pass's records (logging pass ran without it)
-  const bool hard = cfg->num_hard_negatives > 0;
-  if (hard) {
-    // top-k hard negatives (losses.py:295-330), generic kernel for both precisions: (1) the same kernel dumps its
-    // logits (bit-identical to what the loss pass will see), (2) per-row thresholds by radix select, (3) the loss
-    // pass with every counted negative weighted by its top-k weight.
+  if (lp.hard) {  // logits dump + per-row thresholds (loss_plan)
     LossArgs d = a;
     d.dump = (float*)(ws + p.off_dump); d.dump_ld = p.dump_ld; d.qinfo = (float2*)(ws + p.off_qinfo); d.need_grad = 0;
-    if (cfg->precision == XFMR_PREC_BF16) rc = launch_main_h<PrecBF16>(d, H, false, grid, st);
-    else if (cfg->precision == XFMR_PREC_F32) rc = launch_main_h<PrecF32>(d, H, false, grid, st);
-    else rc = XFMR_EINVAL;
-    if (rc) return rc;
+    if (int rc = launch_generic(d, lp.family, lp.pass[0].code, false, dim3(lp.pass[0].gx, lp.pass[0].gy), st)) return rc;
     SelectArgs s{};
     s.dump = d.dump; s.dump_ld = p.dump_ld; s.qinfo = d.qinfo; s.counts = counts; s.neg_item = neg_item;
     s.neg_rc = a.neg_rc; s.neg_mult = a.neg_mult; s.rnorm = table_rnorm; s.qpos = qpos; s.tau = (float4*)(ws + p.off_tau);
@@ -1004,151 +1199,47 @@ static int run_loss(const xfmr_loss_cfg* cfg, const float* tok, const float* tab
     XF_LAUNCH_CHECK();
     a.tau = (const float4*)(ws + p.off_tau);
   }
-  // widths the LDS-DMA kernel is instantiated for; its gather addresses rows by a 32-bit byte offset from the table base
-  const bool dma_width = (H == 64 || H == 128 || H == 256 || H == 384) && (uint64_t)n_rows * (uint64_t)H * 2 < (1ull << 32);
-  if (!hard && cfg->precision == XFMR_PREC_BF16 && table_bf16 && dma_width) {
-    // bf16 production path: the gradient pass of the train head (skipped for AlignmentLoss, whose gradient has
-    // no negative term) and, when every head is wanted or no gradient is, the values-only logging pass.
-    const bool all = cfg->all_heads != 0;
-    const bool grad_pass = a.need_grad && cfg->train_head != XFMR_LOSS_ALIGNMENT;
-    // unmasked InfoNCE with the logging pass in the same call: logging first, then the gradient pass with the row
-    // maximum pinned from the logging records (lean epilogue, see HEAD_INFONCE_PINNED)
-    const bool pinned = grad_pass && cfg->all_heads == 1 && cfg->train_head == XFMR_LOSS_INFONCE &&
-                        !cfg->mask_false_negatives;
-    // the online-maximum InfoNCE at H > 128 runs as dQ column parts (loss_dma.inc): it keeps the split form
-    const bool col_parts = (H > 128 && cfg->train_head == XFMR_LOSS_INFONCE && !cfg->mask_false_negatives && !pinned) ||
-                           (H == 256 && grad_pass && !pinned && xf_loss_dma_256_hparts(a, cfg->train_head) > 1);
-    // H > 128 below 512 query blocks: these gradient kernels run ONE workgroup per CU (loss_dma.inc), all of them equally
-    // long, so the pass takes ceil(blocks * n / CUs) rounds of 1 / n of the columns each. The fewest splits among the best
-    // such n: config 5 (256 blocks on 256 CUs) runs 1 split -- one full round, the rows finished in the kernel, no 134 MB
-    // of partial dQ written and re-read (6.62 -> 6.51 ms/step); config 4 (100 blocks) 5 splits instead of 10 (two rounds
-    // of 250: 3.06 -> 2.99; 3 splits = 1.17 rounds measured 3.30).
-    if (H > 128 && grid.x < 512 && ns_grad_env <= 0 && ns_grad_flag <= 0) {
-      static const int cus = [] {
-        int dev = 0, cu = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-        return cu > 0 ? cu : 256;
-      }();
-      int best = p.nsplit;
-      double best_cost = 1e30;
-      for (int n = 1; n <= p.nsplit; ++n) {
-        // (+ 0.01 per split: every split writes and the combine kernel re-reads a (queries x H) fp32 partial dQ -- at 8 query
-        //  blocks (the reference's default model: 32 x 32 tokens, H = 384) 8 splits measured 0.303 ms per step against 0.313
-        //  for 16 and 0.306 for 4; configs 4 / 5 keep their 5 / 1)
-        const double cost = (double)(((int64_t)grid.x * n + cus - 1) / cus) / n + 0.01 * n;
-        if (cost < best_cost - 1e-9) { best_cost = cost; best = n; }
-      }
-      ns_grad = best;
-    }
-    if (!grad_pass || col_parts) {  // column parts keep the split form (no in-kernel finish); overrides still apply
-      ns_grad = p.nsplit;
-      if (col_parts && ns_grad_env > 0) ns_grad = ns_grad_env < p.nsplit ? ns_grad_env : p.nsplit;
-      if (col_parts && ns_grad_flag > 0) ns_grad = ns_grad_flag < p.nsplit ? ns_grad_flag : p.nsplit;
-    }
-    dim3 ggrid(grid.x, (unsigned)ns_grad);
-    if (grad_pass) {
-      a.nsplit = ns_part = ns_grad;
-      if (ns_grad == 1 && !col_parts) { a.d_tok = d_tok; fused_finish = true; }
-    }
-    // Query rows as bf16, converted once per call: a launch with n > 1 column splits would read and round every fp32 query
-    // row n times (and gather and multiply its positive's row n times); it stages them from the image instead, which
-    // loss_qprep_kernel writes in front of the first such launch. A launch with one split reads the fp32 rows itself --
-    // once. XFMR_LOSS_Q_FP32=1 (read per call) keeps every launch on the fp32 rows: the results are the same bit for bit
-    // (tests/test_gpu_loss_bf16_rows.py).
-    const char* q_env = getenv("XFMR_LOSS_Q_FP32");
-    const bool q_fp32 = q_env && q_env[0] && !(q_env[0] == '0' && !q_env[1]);
-    bool img_ready = false;
-    auto with_image = [&](LossArgs& l) -> int {
-      if (q_fp32 || l.nsplit <= 1) return XFMR_OK;
-      if (p.off_qimg + (size_t)T * H * 2 > ws_bytes || p.off_qaux + (size_t)T * sizeof(float2) > ws_bytes)
-        return XFMR_EWORKSPACE;  // (the image lives in the caller's workspace: no allocation inside the step)
-      __bf16* qimg = (__bf16*)(ws + p.off_qimg);
-      float2* qaux = (float2*)(ws + p.off_qaux);
+  bool img_ready = false;
+  for (int i = 0; i < lp.npass; ++i) {
+    const LossPass& ps = lp.pass[i];
+    LossArgs l = a;
+    l.nsplit = ps.nsplit; l.part = part[ps.buf];
+    if (ps.role == kPassLog) l.need_grad = 0;
+    if (ps.finish) l.d_tok = d_tok;
+    if (ps.pinned) { l.pin_part = part[lp.loss_buf]; l.pin_nsplit = lp.nsplit_loss; }  // (the logging pass's records)
+    if (ps.image) {
+      // The image lives in the caller's workspace (no allocation inside the step) and fits it: the carve ends behind
+      // off_qimg + T H 2 and off_qaux + T sizeof(float2), and every entry refused workspace_bytes < p.total before this.
+      l.qimg = (__bf16*)(ws + p.off_qimg); l.qaux = (float2*)(ws + p.off_qaux);
       if (!img_ready) {
-        if (int e = launch_qprep_h(a, qimg, qaux, H, grid, st)) return e;
+        if (int rc = launch_qprep_h(a, (__bf16*)(ws + p.off_qimg), (float2*)(ws + p.off_qaux), H, dim3(ps.gx), st)) return rc;
         img_ready = true;
       }
-      l.qimg = qimg; l.qaux = qaux;
-      return XFMR_OK;
-    };
-    if (pinned) {
-      LossArgs b = a;
-      b.nsplit = p.nsplit; b.d_tok = nullptr;
-      b.part = (float*)(ws + p.off_part2);
-      b.need_grad = 0;
-      if ((rc = with_image(b))) return rc;
-      if (lev0 && hipEventRecord(lev0, st) != hipSuccess) return XFMR_EHIP;
-      rc = launch_dma_h(b, table_bf16, H, -2, grid, st);  // (the InfoNCE value comes from the gradient records)
-      if (rc) return rc;
-      if (lev1 && hipEventRecord(lev1, st) != hipSuccess) return XFMR_EHIP;
-      part_loss = b.part;
-      lse_from_grad = true;
-      a.pin_part = b.part;
-      a.pin_nsplit = p.nsplit;
-      if ((rc = with_image(a))) return rc;
-      if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return XFMR_EHIP;
-      rc = launch_dma_h(a, table_bf16, H, cfg->train_head, ggrid, st);
-      if (rc) return rc;
-      if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return XFMR_EHIP;
-    } else {
-    if (grad_pass) {
-      if ((rc = with_image(a))) return rc;
-      if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return XFMR_EHIP;
-      rc = launch_dma_h(a, table_bf16, H, cfg->train_head, ggrid, st);
-      if (rc) return rc;
-      if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return XFMR_EHIP;
     }
-    if (all || !grad_pass) {
-      LossArgs b = a;
-      b.nsplit = p.nsplit; b.d_tok = nullptr;
-      if (grad_pass) b.part = (float*)(ws + p.off_part2);
-      b.need_grad = 0;
-      // all_heads == 2: the train head's value is not wanted from this call (the caller has it from the gradient
-      // pass of the same step): for InfoNCE that drops the log-sum-exp from the per-logit work
-      // ... and likewise when the gradient pass of THIS call is the InfoNCE one: the combine kernel then takes the
-      // head's value from the gradient pass's records
-      const bool lse_elsewhere = cfg->train_head == XFMR_LOSS_INFONCE && (grad_pass || cfg->all_heads == 2);
-      lse_from_grad = lse_elsewhere && grad_pass;
-      const int code = lse_elsewhere ? -2 : -1;
-      if ((rc = with_image(b))) return rc;
-      if (lev0 && hipEventRecord(lev0, st) != hipSuccess) return XFMR_EHIP;
-      rc = launch_dma_h(b, table_bf16, H, code, grid, st);
-      if (rc) return rc;
-      if (lev1 && hipEventRecord(lev1, st) != hipSuccess) return XFMR_EHIP;
-      if (grad_pass) part_loss = b.part;
-    }
-    }
-  } else {
-    if (ev0 && hipEventRecord(ev0, st) != hipSuccess) return XFMR_EHIP;
-    if (cfg->precision == XFMR_PREC_BF16) rc = launch_main_h<PrecBF16>(a, H, cfg->all_heads != 0, grid, st);
-    else if (cfg->precision == XFMR_PREC_F32) rc = launch_main_h<PrecF32>(a, H, cfg->all_heads != 0, grid, st);
-    else rc = XFMR_EINVAL;
-    if (rc) return rc;
-    if (ev1 && hipEventRecord(ev1, st) != hipSuccess) return XFMR_EHIP;
+    // measurement events (xfmr_loss_cfg): profile_grad around the gradient pass -- or around the call's single main kernel
+    // when it runs the generic kernel --, profile_log around the values-only logging pass of the bf16 production path
+    void* const* ev = ps.role == kPassGrad ? cfg->profile_grad : cfg->profile_log;
+    if (ev[0] && hipEventRecord((hipEvent_t)ev[0], st) != hipSuccess) return XFMR_EHIP;
+    const dim3 grid(ps.gx, ps.gy, ps.gz);
+    if (int rc = lp.family == kLossDma ? launch_dma_h(l, table_bf16, H, ps.code, grid, st)
+                                       : launch_generic(l, lp.family, ps.code, ps.all != 0, grid, st))
+      return rc;
+    if (ev[1] && hipEventRecord((hipEvent_t)ev[1], st) != hipSuccess) return XFMR_EHIP;
   }
 
   CombineArgs c{};
   c.tok = tok; c.table = table; c.rnorm = table_rnorm; c.counts = counts; c.qrow = qrow; c.qpos = qpos;
-  c.part = a.part; c.part_loss = part_loss ? part_loss : a.part; c.partO = a.partO; c.d_tok = d_tok; c.blockpart = (double*)(ws + p.off_block);
+  c.part = part[0]; c.part_loss = part[lp.loss_buf]; c.partO = a.partO; c.d_tok = d_tok; c.blockpart = (double*)(ws + p.off_block);
   c.T = T; c.H = H; c.train_head = cfg->train_head;
-  // split counts of the two record sets: `part` (and partO) were written by the launch that used a.nsplit; part_loss,
-  // when it is another buffer, by a logging pass with p.nsplit
-  c.nsplit = ns_part; c.nsplit_loss = part_loss ? p.nsplit : ns_part;
-  c.need_grad = (d_tok != nullptr && !fused_finish) ? 1 : 0;  // fused_finish: the gradient pass wrote d_tok itself
+  c.nsplit = lp.nsplit; c.nsplit_loss = lp.nsplit_loss; c.need_grad = lp.need_grad;
   c.mode = cfg->mode; c.n_rows = n_rows; c.scale = cfg->scale; c.margin = cfg->margin;
   c.k_hard = cfg->num_hard_negatives;
-  c.skip_train_head = (cfg->all_heads == 2 && d_tok == nullptr) ? 1 : 0;
-  c.lse_from_grad = lse_from_grad ? 1 : 0;
-  if (!c.need_grad) {  // values only: one lane per row
-    const int nb = (T + kValueRows - 1) / kValueRows;
-    hipLaunchKernelGGL(loss_combine_kernel<true>, dim3(nb), dim3(256), 0, st, c);
-    XF_LAUNCH_CHECK();
-    return xf_loss_finalize(c.blockpart, nb, kValueRows, counts, cfg->mode, n_rows, cfg->padded_positions > 0 ? cfg->padded_positions : (int64_t)T, losses, stats,
-                            (double*)(ws + p.off_tot), st);
-  }
-  hipLaunchKernelGGL(loss_combine_kernel<false>, dim3(p.nblocks), dim3(256), 0, st, c);
+  c.skip_train_head = lp.skip_train_head; c.lse_from_grad = lp.lse_from_grad;
+  if (lp.values_only) hipLaunchKernelGGL(loss_combine_kernel<true>, dim3(lp.blocks), dim3(256), 0, st, c);
+  else hipLaunchKernelGGL(loss_combine_kernel<false>, dim3(lp.blocks), dim3(256), 0, st, c);
   XF_LAUNCH_CHECK();
-  return xf_loss_finalize(c.blockpart, p.nblocks, kCombineRows, counts, cfg->mode, n_rows, cfg->padded_positions > 0 ? cfg->padded_positions : (int64_t)T, losses, stats,
+  return xf_loss_finalize(c.blockpart, lp.blocks, lp.values_only ? kValueRows : kCombineRows, counts, cfg->mode, n_rows,
+                          cfg->padded_positions > 0 ? cfg->padded_positions : (int64_t)T, losses, stats,
                           (double*)(ws + p.off_tot), st);
 }
 
@@ -1168,8 +1259,7 @@ static int launch_distinct(unsigned char* ws, const Plan& p, int64_t n_rows, con
 static int check_loss_args(const xfmr_loss_cfg* cfg, const float* tok, const float* table, const float* rnorm,
                            float* losses, float* stats, void* workspace, float* d_tok, int64_t rows, int64_t n_rows) {
   if (!cfg || !tok || !table || !rnorm || !losses || !stats || !workspace) return XFMR_EINVAL;
-  if (rows <= 0 || n_rows <= 0 || rows > (1 << 30) || n_rows > (1 << 30)) return XFMR_EINVAL;
-  if (cfg->train_head < 0 || cfg->train_head >= XFMR_NUM_LOSSES || cfg->num_hard_negatives < 0) return XFMR_EINVAL;
+  if (!loss_key_ok(rows, n_rows, cfg->train_head, cfg->num_hard_negatives)) return XFMR_EINVAL;
   if (!xf_aligned16(tok) || !xf_aligned16(table) || !xf_aligned16(workspace) || (d_tok && !xf_aligned16(d_tok)))
     return XFMR_EALIGN;
   return XFMR_OK;
@@ -1185,7 +1275,7 @@ int xfmr_sampled_loss_prepare(const xfmr_loss_cfg* cfg, const uint8_t* key_mask,
     return XFMR_EINVAL;
   if (cfg->mode == XFMR_NEG_SHARED && !neg_idx) return XFMR_EINVAL;
   if (!xf_aligned16(workspace)) return XFMR_EALIGN;
-  const Plan p = make_plan(positions, H, n_rows, cfg->num_hard_negatives > 0, (int)XFMR_LOSS_NSPLIT_OF(cfg->flags));
+  const Plan p = loss_carve(cfg, positions, H, n_rows);
   if (workspace_bytes < p.total) return XFMR_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
@@ -1216,14 +1306,14 @@ int xfmr_sampled_loss_prepared(const xfmr_loss_cfg* cfg, const float* tok, const
     return rc;
   if (!key_mask || !pos_idx) return XFMR_EINVAL;
   if (cfg->mode == XFMR_NEG_SHARED && !neg_idx) return XFMR_EINVAL;
-  const Plan p = make_plan(positions, H, n_rows, cfg->num_hard_negatives > 0, (int)XFMR_LOSS_NSPLIT_OF(cfg->flags));
+  const Plan p = loss_carve(cfg, positions, H, n_rows);
   if (workspace_bytes < p.total) return XFMR_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const bool zeroed = (cfg->flags & XFMR_LOSS_DTOK_ZEROED) != 0;  // the caller zeroed d_tok itself
   if (d_tok && !zeroed && xf_zero_async(d_tok, (size_t)positions * H * sizeof(float), st) != hipSuccess) return XFMR_EHIP;
   if (table_bf16 && !xf_aligned16(table_bf16)) return XFMR_EALIGN;
   return run_loss(cfg, tok, table, table_rnorm, table_bf16, n_rows, (int)positions, H, losses, stats, d_tok,
-                  (unsigned char*)workspace, workspace_bytes, p, st);
+                  (unsigned char*)workspace, p, st);
 }
 
 int xfmr_sampled_loss(const xfmr_loss_cfg* cfg, const float* tok, const uint8_t* key_mask, const int64_t* pos_idx,
@@ -1242,13 +1332,13 @@ int xfmr_sampled_loss(const xfmr_loss_cfg* cfg, const float* tok, const uint8_t*
 size_t xfmr_sampled_loss_lists_workspace(int64_t n_query, int64_t n_neg, int32_t H, int64_t n_rows) {
   const int64_t rows = n_query > n_neg ? n_query : n_neg;
   if (rows <= 0 || H <= 0) return 0;
-  return make_plan(rows, H, n_rows).total;
+  return loss_carve(nullptr, rows, H, n_rows).total;
 }
 size_t xfmr_sampled_loss_lists_workspace_cfg(const xfmr_loss_cfg* cfg, int64_t n_query, int64_t n_neg, int32_t H,
                                              int64_t n_rows) {
   const int64_t rows = n_query > n_neg ? n_query : n_neg;
   if (!cfg || rows <= 0 || H <= 0) return 0;
-  return make_plan(rows, H, n_rows, cfg->num_hard_negatives > 0, (int)XFMR_LOSS_NSPLIT_OF(cfg->flags)).total;
+  return loss_carve(cfg, rows, H, n_rows).total;
 }
 
 int xfmr_sampled_loss_lists(const xfmr_loss_cfg* cfg, const float* query, const int64_t* pos_items,
@@ -1260,7 +1350,7 @@ int xfmr_sampled_loss_lists(const xfmr_loss_cfg* cfg, const float* query, const 
     return rc;
   if (!pos_items || n_query <= 0) return XFMR_EINVAL;
   if (cfg->mode == XFMR_NEG_SHARED && (!neg_items || n_neg <= 0)) return XFMR_EINVAL;
-  const Plan p = make_plan(rows, H, n_rows, cfg->num_hard_negatives > 0, (int)XFMR_LOSS_NSPLIT_OF(cfg->flags));
+  const Plan p = loss_carve(cfg, rows, H, n_rows);
   if (workspace_bytes < p.total) return XFMR_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
@@ -1276,7 +1366,7 @@ int xfmr_sampled_loss_lists(const xfmr_loss_cfg* cfg, const float* query, const 
     if (int rc = launch_distinct(ws, p, n_rows, table_rnorm, st)) return rc;
   }
   if (table_bf16 && !xf_aligned16(table_bf16)) return XFMR_EALIGN;
-  return run_loss(cfg, query, table, table_rnorm, table_bf16, n_rows, T, H, losses, stats, d_query, ws, workspace_bytes, p, st);
+  return run_loss(cfg, query, table, table_rnorm, table_bf16, n_rows, T, H, losses, stats, d_query, ws, p, st);
 }
 
 int xfmr_table_prepare(const float* table, float* table_rnorm, void* table_bf16, int64_t n_rows, int32_t H,

@@ -555,18 +555,57 @@ __device__ __forceinline__ void write_partial(const RowState& st, float* rec, bo
   }
 }
 
+// ---- the forms of the LDS-DMA main kernel (loss_dma.inc), written once: the kernel template and the host plan
+// (loss.hip: loss_plan) both call these ------------------------------------------------------------------------------
+// XFL_H256_LEAN_HALVES (experiment build): the LEAN masked gradient epilogues at H = 256 as two dQ column halves too -- their
+// epilogues are cheap since round 3, so recomputing the scores per half may cost less than the second wave per SIMD gives.
+#ifndef XFL_H256_LEAN_HALVES
+#define XFL_H256_LEAN_HALVES 0
+#endif
+constexpr bool loss_dma_lean_masked(int code) {
+  return code == HEAD_CCL_MASKED || code == HEAD_CONTR_MASKED || code == HEAD_BPR_MASKED || code == HEAD_INFONCE_MASKED;
+}
+// HEAD_* code of one pass. head: XFMR_LOSS_* = gradient pass of that head; -1 = logging pass (all heads + statistics,
+// values only); -2 = the logging pass without the InfoNCE log-sum-exp. pinned: the logging pass of the same call ran
+// first and its records pin the row maximum (HEAD_INFONCE_PINNED). logm256: XFMR_LOSS_LOGM256 (loss_switches).
+constexpr int loss_dma_form(int H, int head, bool mask_fn, int mode, bool pinned, bool logm256) {
+  const bool lean = mask_fn && mode == XFMR_NEG_SHARED;  // masking on + in-batch negatives: the reference's training form
+  // Logging pass: the lean form takes the fast epilogue (loss_epilogue_logging_masked), the full-catalogue softmax without
+  // masking (BASELINE config 4) its unmasked form; everything else the general one. H = 384 runs one wave per SIMD whatever
+  // the registers, and there the fast epilogue measured 26 % SLOWER than the general one (2.21 against 1.75 ms at BASELINE
+  // config 5 -- round 2, at H = 256, when its values-only kernels ran one wave too; they now run two): H <= 256 only.
+  // XFMR_LOSS_LOGM256=0 keeps the general epilogue at H = 256: A/B.
+  const bool fast_log = H <= 128 || (H == 256 && logm256);
+  switch (head) {
+    case -1: return (fast_log && lean) ? HEAD_LOG_MASKED_LSE : -1;
+    case -2:
+      return (fast_log && lean) ? HEAD_LOG_MASKED
+             : (fast_log && !mask_fn && mode == XFMR_NEG_CATALOG) ? HEAD_LOG_UNMASKED_CATALOG : -2;
+    case XFMR_LOSS_ALIGNMENT_CONTRASTIVE: return lean ? HEAD_CCL_MASKED : head;   // the lean cosine epilogue
+    case XFMR_LOSS_CONTRASTIVE: return lean ? HEAD_CONTR_MASKED : head;
+    case XFMR_LOSS_INFONCE: return mask_fn ? HEAD_INFONCE_MASKED : pinned ? HEAD_INFONCE_PINNED : head;
+    case XFMR_LOSS_PAIRWISE_LOGISTIC: return lean ? HEAD_BPR_MASKED : head;       // BPR: the lean epilogue
+    default: return head;
+  }
+}
+// dQ column parts (grid.z; the kernel indexes blockIdx.z with it) of the pass with this code: the online-maximum InfoNCE
+// at H > 128 runs as parts of 128 columns (loss_dma.inc). More than one part keeps the split form: no in-kernel finish.
+constexpr int loss_dma_hparts(int H, int code) {
+  return (H > 128 && code == (int)XFMR_LOSS_INFONCE) ? H / 128
+         : (XFL_H256_LEAN_HALVES && H == 256 && loss_dma_lean_masked(code)) ? 2 : 1;
+}
+
 }  // namespace xfl
 using namespace xfl;
 
-// launchers of the LDS-DMA main kernel, one translation unit per hidden size (compile time)
-// head: XFMR_LOSS_* = gradient pass of that head; -1 = logging pass (all heads + statistics, values only)
-// ... and of loss_qprep_kernel (a.qimg / a.qaux are the OUTPUTS there); grid.x = query blocks of QB
+// Launchers of the LDS-DMA main kernel (loss_dma.inc: xfl_launch_form) and of loss_qprep_kernel (a.qimg / a.qaux are the
+// OUTPUTS there; grid.x = query blocks of QB), one translation unit per hidden size (compile time; Makefile flags).
+// code: loss_dma_form's; grid.z: loss_dma_hparts'. A code the width is not built with: XFMR_EINVAL.
 int xf_launch_loss_qprep_64(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st);
 int xf_launch_loss_qprep_128(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st);
 int xf_launch_loss_qprep_256(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st);
 int xf_launch_loss_qprep_384(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 grid, hipStream_t st);
-int xf_launch_loss_dma_64(const LossArgs& a, const void* table_bf16, int head, dim3 grid, hipStream_t st);
-int xf_launch_loss_dma_128(const LossArgs& a, const void* table_bf16, int head, dim3 grid, hipStream_t st);
-int xf_launch_loss_dma_256(const LossArgs& a, const void* table_bf16, int head, dim3 grid, hipStream_t st);
-int xf_loss_dma_256_hparts(const LossArgs& a, int head);  // dQ column parts of the H = 256 gradient pass (loss_dma_h256.hip)
-int xf_launch_loss_dma_384(const LossArgs& a, const void* table_bf16, int head, dim3 grid, hipStream_t st);
+int xf_launch_loss_dma_64(const LossArgs& a, const void* table_bf16, int code, dim3 grid, hipStream_t st);
+int xf_launch_loss_dma_128(const LossArgs& a, const void* table_bf16, int code, dim3 grid, hipStream_t st);
+int xf_launch_loss_dma_256(const LossArgs& a, const void* table_bf16, int code, dim3 grid, hipStream_t st);
+int xf_launch_loss_dma_384(const LossArgs& a, const void* table_bf16, int code, dim3 grid, hipStream_t st);

@@ -1,4 +1,4 @@
-// loss_main_dma_kernel: the bf16 production path of the fused sampled loss (included by loss.hip).
+// loss_main_dma_kernel: the bf16 production path of the fused sampled loss (included by the per-width loss_dma_h*.hip).
 //
 // Same math and partial-record format as loss_main_kernel; what differs is how a tile of 64 negatives
 // reaches the matrix cores:
@@ -31,21 +31,7 @@
 // H = 384 (the reference's default d_model: the all-MiniLM item table, models.py:80-91): two tile buffers are 96 KiB, so
 // one workgroup per CU and one wave per SIMD whatever the registers; the online-maximum InfoNCE runs as three dQ column
 // parts of 128 (64 accumulator registers beside the 96 of Q).
-// XFL_H256_LEAN_HALVES (experiment build): the LEAN masked gradient epilogues at H = 256 as two dQ column halves too -- their
-// epilogues are cheap since round 3, so recomputing the scores per half may cost less than the second wave per SIMD gives.
-#ifndef XFL_H256_LEAN_HALVES
-#define XFL_H256_LEAN_HALVES 0
-#endif
-template <int HEAD_CODE>
-constexpr bool loss_dma_lean_masked() {
-  return HEAD_CODE == HEAD_CCL_MASKED || HEAD_CODE == HEAD_CONTR_MASKED || HEAD_CODE == HEAD_BPR_MASKED ||
-         HEAD_CODE == HEAD_INFONCE_MASKED;
-}
-template <int H, int HEAD_CODE>
-constexpr int loss_dma_hparts() {
-  return (H > 128 && HEAD_CODE == (int)XFMR_LOSS_INFONCE) ? H / 128
-         : (XFL_H256_LEAN_HALVES && H == 256 && loss_dma_lean_masked<HEAD_CODE>()) ? 2 : 1;
-}
+// (The parts rule itself, loss_dma_hparts, and the experiment build XFL_H256_LEAN_HALVES: loss_common.h.)
 // Waves per SIMD of the masked logging kernels at H <= 128. This pass is bound by vector-instruction ISSUE: a plain fp32
 // wave64 instruction holds the SIMD 4 cycles (scripts/probe/valu_rates.hip; a transcendental 8), and two resident waves
 // cannot keep the pipe full once each spends time waiting -- a third one can (profiles/r02_loss_passes_pmc.md: 47 %
@@ -76,7 +62,7 @@ constexpr int loss_dma_waves() {
          : (H <= 128 && HEAD_CODE == HEAD_INFONCE_MASKED) ? XFL_GRAD_WAVES
          // values-only passes keep no dQ accumulators: two waves per SIMD up to H = 256 (two
          // 64 KB tile-buffer pairs + side data = 152 KB of LDS per CU)
-         : (H <= 128 || (H <= 256 && (HEAD_CODE < 0 || loss_dma_hparts<H, HEAD_CODE>() > 1))) ? 2 : 1;
+         : (H <= 128 || (H <= 256 && (HEAD_CODE < 0 || loss_dma_hparts(H, HEAD_CODE) > 1))) ? 2 : 1;
 }
 // (Balanced spans -- one workgroup per resident slot, each walking an equal contiguous run of the (query block, tile)
 // units, at most two query prologues each, no partly filled last round -- were built and measured for the logging
@@ -215,7 +201,7 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
   }
   const RowConst kc{pos_dot, cpos, pos_dot * (1.f - a.margin), sc2, rq, a.margin, pos_item, head,
                     a.mask_fn != 0, catalog, head <= XFMR_LOSS_CONTRASTIVE};
-  constexpr int HP = loss_dma_hparts<H, HEAD_CODE>();  // dQ column parts (grid.z)
+  constexpr int HP = loss_dma_hparts(H, HEAD_CODE);  // dQ column parts (grid.z)
   constexpr int NO = GRAD ? H / 32 / HP : 1;     // no gradient accumulators in the values-only pass
   const int hpart = HP > 1 ? (int)blockIdx.z : 0;
   f32x16 o[NO];
@@ -470,8 +456,43 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
   }
 }
 
+// ---- the launcher: every (H, code) that is built, and nothing else -----------------------------------------------------
+// The logging passes -1 / -2, the six general gradient heads, the five lean gradient codes; up to H = 256 the three fast
+// logging epilogues (loss_dma_form never asks for them beyond).
+constexpr bool loss_dma_built(int H, int code) {
+  if (code <= HEAD_LOG_MASKED) return code >= HEAD_LOG_UNMASKED_CATALOG && H <= 256;
+  return code != (int)XFMR_LOSS_ALIGNMENT && code <= HEAD_CONTR_MASKED;  // (AlignmentLoss has no gradient pass)
+}
 template <int H, int HEAD_CODE>
-void xfl_launch_dma(const LossArgs& a, const __bf16* tbf, dim3 grid, dim3 block, hipStream_t st) {
-  if (a.qimg != nullptr) hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, true>), grid, block, 0, st, a, tbf);
-  else hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, false>), grid, block, 0, st, a, tbf);
+int xfl_launch_code(const LossArgs& a, const __bf16* tbf, dim3 grid, hipStream_t st) {
+  if constexpr (loss_dma_built(H, HEAD_CODE)) {
+    if (a.qimg != nullptr) hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, true>), grid, dim3(256), 0, st, a, tbf);
+    else hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, false>), grid, dim3(256), 0, st, a, tbf);
+    XF_LAUNCH_CHECK();
+    return XFMR_OK;
+  }
+  return XFMR_EINVAL;
+}
+// code: loss_dma_form's; grid: (query blocks, column splits, loss_dma_hparts(H, code))
+template <int H>
+int xfl_launch_form(const LossArgs& a, const __bf16* tbf, int code, dim3 grid, hipStream_t st) {
+  switch (code) {
+    case -1: return xfl_launch_code<H, -1>(a, tbf, grid, st);
+    case -2: return xfl_launch_code<H, -2>(a, tbf, grid, st);
+    case HEAD_LOG_MASKED: return xfl_launch_code<H, HEAD_LOG_MASKED>(a, tbf, grid, st);
+    case HEAD_LOG_MASKED_LSE: return xfl_launch_code<H, HEAD_LOG_MASKED_LSE>(a, tbf, grid, st);
+    case HEAD_LOG_UNMASKED_CATALOG: return xfl_launch_code<H, HEAD_LOG_UNMASKED_CATALOG>(a, tbf, grid, st);
+    case XFMR_LOSS_ALIGNMENT_CONTRASTIVE: return xfl_launch_code<H, XFMR_LOSS_ALIGNMENT_CONTRASTIVE>(a, tbf, grid, st);
+    case XFMR_LOSS_CONTRASTIVE: return xfl_launch_code<H, XFMR_LOSS_CONTRASTIVE>(a, tbf, grid, st);
+    case XFMR_LOSS_INFONCE: return xfl_launch_code<H, XFMR_LOSS_INFONCE>(a, tbf, grid, st);
+    case XFMR_LOSS_NCE: return xfl_launch_code<H, XFMR_LOSS_NCE>(a, tbf, grid, st);
+    case XFMR_LOSS_PAIRWISE_HINGE: return xfl_launch_code<H, XFMR_LOSS_PAIRWISE_HINGE>(a, tbf, grid, st);
+    case XFMR_LOSS_PAIRWISE_LOGISTIC: return xfl_launch_code<H, XFMR_LOSS_PAIRWISE_LOGISTIC>(a, tbf, grid, st);
+    case HEAD_INFONCE_MASKED: return xfl_launch_code<H, HEAD_INFONCE_MASKED>(a, tbf, grid, st);
+    case HEAD_INFONCE_PINNED: return xfl_launch_code<H, HEAD_INFONCE_PINNED>(a, tbf, grid, st);
+    case HEAD_BPR_MASKED: return xfl_launch_code<H, HEAD_BPR_MASKED>(a, tbf, grid, st);
+    case HEAD_CCL_MASKED: return xfl_launch_code<H, HEAD_CCL_MASKED>(a, tbf, grid, st);
+    case HEAD_CONTR_MASKED: return xfl_launch_code<H, HEAD_CONTR_MASKED>(a, tbf, grid, st);
+    default: return XFMR_EINVAL;
+  }
 }
