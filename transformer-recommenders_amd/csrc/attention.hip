@@ -11,6 +11,8 @@
 // the whole K/V (or Q/dO) panel of that head that the causal mask can reach is staged once into LDS
 // (while it fits 160 KiB), so there is a single barrier per kernel; longer sequences run the key-streaming forms
 // (of the generic and of the production kernels), which pass the panel through LDS in fixed-size chunks.
+#include <type_traits>
+
 #include "internal.h"
 
 namespace {
@@ -1531,6 +1533,9 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_seq_bf16_kernel(const AttnArg
       if (__all(mnew == -INFINITY)) continue;
       const float msafe = (mnew == -INFINITY) ? 0.f : mnew;
       const float alpha = xf_exp2(m - msafe);
+      // (a.drop.on is tested per score: one basic block each. Testing it once around a second 16-score loop was built and
+      // measured -- 455 -> 391 instructions per tile, but 94 -> 121 VGPRs, 99 at best, and so four waves per SIMD for five:
+      // 39.3 / 37.5 us per launch against 37.6. Not kept; profiles/attn_straightline.md.)
       float psum = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -1672,11 +1677,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused_bf16_kernel(const AttnA
   };
   // a wave walks at most two key tiles (up to 8 tiles): the operands of BOTH are fetched up front -- a fetch at the
   // switch would stall the wave, and with it the whole lock-step, for a global round trip
-  struct TileOps { RegRows<PrecBF16, DH> k, v; bf16x8 kb[2]; };
+  // (the key's mask byte comes with them: no load from global memory is left between the barrier below and the last step)
+  struct TileOps { RegRows<PrecBF16, DH> k, v; bf16x8 kb[2]; uint8_t kmask; };
   auto fetch_tile = [&](int kt, TileOps& o) {  // K / V row operands, K in the dQ product's B layout
     const int k0 = kt * 32, ky = k0 + (lane & 31);
     o.k.template load_at<S16>(a.qkv, (tok0 + ky) * 3 * H + H + h * DH, ky < L);
     o.v.template load_at<S16>(a.qkv, (tok0 + ky) * 3 * H + 2 * H + h * DH, ky < L);
+    o.kmask = a.key_mask[tok0 + (ky < L ? ky : 0)];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -1690,23 +1697,39 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused_bf16_kernel(const AttnA
         o.kb[s][j] = (__bf16)v;
       }
   };
+  TileOps cur, nxt;
   auto enter_tile = [&](int kt) {
     cur_kt = kt;
     key = kt * 32 + (lane & 31);
     kin = key < L;
-    kvis = kin && a.key_mask[tok0 + (kin ? key : 0)];
+    kvis = kin && cur.kmask;  // (the caller has made `cur` this tile's operands)
     all_kvis = __all(kvis);
     colmix = (uint32_t)key * kDropColMul;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dk[r] = 0.f; dv[r] = 0.f; }
   };
   const int steps = kBwdSteps[nt - 1];
-  TileOps cur, nxt;
+  // the wave's row of the schedule, read once into scalar registers (byte i of sched_a = step i, of sched_b = step 4 + i,
+  // sched_8 = step 8): a byte of the table is a load from global memory, and one per step sat in front of every step's
+  // first MFMA
+  uint32_t sched_a = 0u, sched_b = 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    sched_a |= (uint32_t)kBwdSched[nt - 1][wid][i] << (8 * i);
+    sched_b |= (uint32_t)kBwdSched[nt - 1][wid][4 + i] << (8 * i);
+  }
+  sched_a = __builtin_amdgcn_readfirstlane(sched_a);
+  sched_b = __builtin_amdgcn_readfirstlane(sched_b);
+  const uint32_t sched_8 = __builtin_amdgcn_readfirstlane((uint32_t)kBwdSched[nt - 1][wid][8]);
+  auto sched_code = [&](int i) -> int {
+    const uint32_t word = i >= 8 ? sched_8 : i >= 4 ? sched_b : sched_a;
+    return (int)((word >> (8 * (i & 3))) & 255u);
+  };
   {
-    const int code0 = kBwdSched[nt - 1][wid][0];
+    const int code0 = sched_code(0);
     int kt_a = code0 == 255 ? -1 : (code0 >> 4), kt_b = -1;
     for (int sidx = 1; sidx < steps; ++sidx) {
-      const int cd = kBwdSched[nt - 1][wid][sidx];
+      const int cd = sched_code(sidx);
       if (cd != 255 && (cd >> 4) != kt_a && kt_b < 0) kt_b = cd >> 4;
     }
     if (kt_a >= 0) fetch_tile(kt_a, cur);
@@ -1715,7 +1738,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused_bf16_kernel(const AttnA
   }
   __syncthreads();
   for (int step = 0; step < steps; ++step) {
-    const int code = kBwdSched[nt - 1][wid][step];  // (wave-uniform)
+    const int code = sched_code(step);  // (wave-uniform)
     if (code != 255) {
       const int kt = code >> 4, qb = code & 15;
       if (kt != cur_kt) {
@@ -1730,40 +1753,55 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_fused_bf16_kernel(const AttnA
       AI::tile_nreg(s, sQ, row0, cur.k.regs());
       AI::tile_nreg(dp, sDO, row0, cur.v.regs());
       const bool interior = all_kvis && qb > kt;  // every query row is after the wave's keys, every key valid
+      // The tile's 16 scores in one straight line: dropout and `interior` are wave-uniform RUN-TIME values, and tested
+      // per group / per element they cut the epilogue into ~45 basic blocks a step. They are compile-time here and
+      // the tile branches once, to one of four instances of the same arithmetic.
+      auto epilogue = [&](auto drop_c, auto interior_c) {
+        constexpr bool kDrop = decltype(drop_c)::value, kInterior = decltype(interior_c)::value;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int qi0 = row0 + 8 * g + 4 * hh;
-        const float4 l4 = *reinterpret_cast<const float4*>(&sLse[qi0]);
-        const float4 d4 = *reinterpret_cast<const float4*>(&sDelta[qi0]);
-        const float ls[4] = {l4.x, l4.y, l4.z, l4.w}, dl[4] = {d4.x, d4.y, d4.z, d4.w};
-        uint32_t rk[4] = {0u, 0u, 0u, 0u};
-        if (a.drop.on) {
-          const uint4 k4 = *reinterpret_cast<const uint4*>(&sRowKey[qi0]);
-          rk[0] = k4.x; rk[1] = k4.y; rk[2] = k4.z; rk[3] = k4.w;
+        for (int g = 0; g < 4; ++g) {
+          const int qi0 = row0 + 8 * g + 4 * hh;
+          const float4 l4 = *reinterpret_cast<const float4*>(&sLse[qi0]);
+          const float4 d4 = *reinterpret_cast<const float4*>(&sDelta[qi0]);
+          const float ls[4] = {l4.x, l4.y, l4.z, l4.w}, dl[4] = {d4.x, d4.y, d4.z, d4.w};
+          uint32_t rk[4] = {0u, 0u, 0u, 0u};
+          if (kDrop) {
+            const uint4 k4 = *reinterpret_cast<const uint4*>(&sRowKey[qi0]);
+            rk[0] = k4.x; rk[1] = k4.y; rk[2] = k4.z; rk[3] = k4.w;
+          }
+          float pr[4];
+          if (kInterior) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) pr[u] = xf_exp2(fmaf(s[4 * g + u], sc, -ls[u]));
+          } else {  // (the exponential of every lane, then the select: `kvis &&` in front of it was a branch per score)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const float e = xf_exp2(fmaf(s[4 * g + u], sc, -ls[u]));
+              pr[u] = (kvis & (key <= qi0 + u)) ? e : 0.f;
+            }
+          }
+          float4 ds4;
+          float* dsv = &ds4.x;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int r = 4 * g + u;
+            const float p = pr[u];
+            float keep = 1.f;
+            if (kDrop) keep = xf_keep_scale_rc(a.drop, rk[u], colmix);
+            s[r] = p * (dp[r] * keep - dl[u]);  // dS
+            dp[r] = p * keep;                   // P.D
+            dsv[u] = s[r];
+          }
+          // dS^T image: row = key (this lane), columns = the tile's queries 8g + 4hh .. + 3
+          *reinterpret_cast<uint2*>(sDSw + AI::off(lane & 31, g) + 4 * hh) = xf_f32x4_to_bf16(ds4);
         }
-        float pr[4];
-        if (interior) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) pr[u] = xf_exp2(fmaf(s[4 * g + u], sc, -ls[u]));
-        } else {
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            pr[u] = (kvis && key <= qi0 + u) ? xf_exp2(fmaf(s[4 * g + u], sc, -ls[u])) : 0.f;
-        }
-        float4 ds4;
-        float* dsv = &ds4.x;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int r = 4 * g + u;
-          const float p = pr[u];
-          float keep = 1.f;
-          if (a.drop.on) keep = xf_keep_scale_rc(a.drop, rk[u], colmix);
-          s[r] = p * (dp[r] * keep - dl[u]);  // dS
-          dp[r] = p * keep;                   // P.D
-          dsv[u] = s[r];
-        }
-        // dS^T image: row = key (this lane), columns = the tile's queries 8g + 4hh .. + 3
-        *reinterpret_cast<uint2*>(sDSw + AI::off(lane & 31, g) + 4 * hh) = xf_f32x4_to_bf16(ds4);
+      };
+      using T = std::true_type;
+      using F = std::false_type;
+      if (a.drop.on) {
+        if (interior) epilogue(T{}, T{}); else epilogue(T{}, F{});
+      } else {
+        if (interior) epilogue(F{}, T{}); else epilogue(F{}, F{});
       }
       AI::tile_xb_tr(dv, sDO, 0, row0, dp);
       AI::tile_xb_tr(dk, sQ, 0, row0, s);
