@@ -1,9 +1,9 @@
 """Inputs on which the loss kernels' dot logits are EXACT, and their fp64 references (plain module, shared by
-test_loss_cases_host.py and test_gpu_loss_dma_forms.py).
+test_loss_cases_host.py, test_gpu_loss_dma_forms.py, loss_hard_cases.py and test_gpu_loss_hard_negatives.py).
 
 Every query entry is a multiple of 2^-6 in [-2, 2] and every table entry a multiple of 2^-7 in [-0.25, 0.25]: both are
-bf16 numbers (staging rounds nothing), every product is a multiple of 2^-13 of size <= 2^-1, and a sum of H <= 384 of
-them is an integer below 2^21 in units of 2^-13 -- it fits the 24-bit significand of fp32 at every step, in any order.
+bf16 numbers (staging rounds nothing), every product is a multiple of 2^-13 of size <= 2^-1, and a sum of H <= 1024 of
+them is an integer of at most 2^22 in units of 2^-13 -- it fits the 24-bit significand of fp32 at every step, in any order.
 The kernels' dot logits are therefore the fp64 values bit for bit, and every decision taken on a dot logit (the
 false-negative mask `l < pos`, the hinge indicator up to the fp32 rounding of (1 - margin) pos) is the reference's. What
 stays inexact is the cosine normalisation, the epilogue arithmetic and the bf16 rounding of the gradient weights.
@@ -32,8 +32,10 @@ import torch
 from oracle import lean
 from oracle import losses as OL
 
-WIDTHS = (64, 128, 256, 384)
-SEEDS = {64: 11, 128: 12, 256: 13, 384: 14}  # one case per width (chosen on the CPU: test_loss_cases_host.py)
+WIDTHS = (64, 128, 256, 384)  # the widths of the LDS-DMA kernels (and of the generic kernel's narrow instantiations)
+# The generic kernel's widest instantiations only: 512 = the widest fp32 width (direct staging), 1024 = bf16 only
+GENERIC_WIDTHS = (512, 1024)
+SEEDS = {64: 11, 128: 12, 256: 13, 384: 14, 512: 15, 1024: 16}  # one case per width (chosen on the CPU: test_loss_cases_host.py)
 MARGINS = (0.5, 0.3)  # every margin the GPU matrix uses
 T, V, CLUSTERS = 320, 200, 6  # T = 4 sequences of 80 slots
 Q_GRID, E_GRID = 2.0 ** -6, 2.0 ** -7

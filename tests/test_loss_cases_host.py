@@ -1,6 +1,6 @@
 """Preconditions of tests/loss_cases.py, on the CPU: what makes the tight limits of test_gpu_loss_dma_forms.py meaningful.
 
-For every (width, seed, margin) the GPU matrix uses:
+For every (width, seed, margin) the GPU matrices use (loss_cases.WIDTHS and the generic-only GENERIC_WIDTHS):
   (a) queries and table lie on their grids and are bf16 numbers;
   (b) fp32 logits in two summation orders equal the fp64 logits exactly;
   (c) the guard band dropped at most 5 % of the query rows (and three 128-query blocks are left);
@@ -17,7 +17,7 @@ from oracle import lean
 from oracle import losses as OL
 
 
-@pytest.mark.parametrize("H", LC.WIDTHS)
+@pytest.mark.parametrize("H", LC.WIDTHS + LC.GENERIC_WIDTHS)
 def test_inputs_lie_on_their_grids_and_are_bf16_numbers(H):
     c = LC.inputs(H)
     for t, grid, bound in ((c.tok, LC.Q_GRID, 2.0), (c.table, LC.E_GRID, 0.25)):
@@ -30,7 +30,7 @@ def test_inputs_lie_on_their_grids_and_are_bf16_numbers(H):
     assert float(worst) < 2 ** 24
 
 
-@pytest.mark.parametrize("H", LC.WIDTHS)
+@pytest.mark.parametrize("H", LC.WIDTHS + LC.GENERIC_WIDTHS)
 def test_fp32_logits_equal_fp64_in_two_summation_orders(H):
     c = LC.inputs(H)
     want = c.tok.double() @ c.table.double().T
@@ -42,7 +42,7 @@ def test_fp32_logits_equal_fp64_in_two_summation_orders(H):
     assert torch.equal(blocked.double(), want) and torch.equal(backwards.double(), want)
 
 
-@pytest.mark.parametrize("H", LC.WIDTHS)
+@pytest.mark.parametrize("H", LC.WIDTHS + LC.GENERIC_WIDTHS)
 def test_shape_reaches_the_blocks_tiles_and_edges_it_is_meant_to(H):
     c = LC.inputs(H)
     nq, negs = int(c.qsel.sum()), c.neg[c.mask]
@@ -57,7 +57,7 @@ def test_shape_reaches_the_blocks_tiles_and_edges_it_is_meant_to(H):
 
 
 @pytest.mark.parametrize("margin", LC.MARGINS)
-@pytest.mark.parametrize("H", LC.WIDTHS)
+@pytest.mark.parametrize("H", LC.WIDTHS + LC.GENERIC_WIDTHS)
 def test_guard_band_is_narrow_and_masks_and_margins_are_active(H, margin):
     a = LC.activity(H, margin)
     assert a["dropped"] <= 0.05, a

@@ -243,6 +243,10 @@ __global__ __launch_bounds__(256, (H <= 128 ? 2 : 1)) void loss_main_kernel(Loss
   if (kc.hard) {
     const float4 th = a.tau[qvalid ? qi : 0];
     kc.tau_d = th.x; kc.rho_d = th.y; kc.tau_c = th.z; kc.rho_c = th.w;
+    // A wave none of whose rows is cut (k >= 1 + N, or fewer counted negatives than k: tau = -inf, rho = 1) takes the plain
+    // epilogue. The HARD instantiation weights by 1 there, but the compiler contracts its products differently: with the
+    // restriction off the call then gives the bits of num_hard_negatives = 0 (tests/test_gpu_loss_hard_negatives.py).
+    kc.hard = __any(th.x != -INFINITY || th.z != -INFINITY);
   }
   const bool dump = a.dump != nullptr;
   if (dump && split == 0 && lane < 32 && qvalid) a.qinfo[qi] = make_float2(pos_dot, rq);
