@@ -967,14 +967,28 @@ class Trainer:
         return cls(module, **reference_trainer_options(cfg), **kwargs)
 
     def _check_val(self, val) -> None:
-        if val is not None and self.world_size > 1:
-            raise ValueError("validation inside a data-parallel run (world_size > 1) is not supported: a sharded validation "
-                             "set has never run on more than one GPU")
+        """The validation set's world is the trainer's: its ``world_size`` (1 for anything that does not say) equals this
+        trainer's, and under ``world_size > 1`` its ``rank`` is this process's rank in ``process_group``."""
+        if val is None:
+            return
+        import torch.distributed as dist
+
+        val_world = getattr(val, "world_size", 1)
+        if val_world != self.world_size:
+            raise ValueError(f"the validation set is sharded over world_size = {val_world!r}, this trainer runs world_size = "
+                             f"{self.world_size}: build it with DeviceEvalSet.from_rows(..., rank=, world_size=, "
+                             "process_group=) of this run")
+        if self.world_size > 1:
+            rank = dist.get_rank(self.process_group) if dist.is_available() and dist.is_initialized() else 0
+            if getattr(val, "rank", None) != rank:
+                raise ValueError(f"the validation set holds the shard of rank {getattr(val, 'rank', None)!r}, this process is "
+                                 f"rank {rank} of world_size = {self.world_size}")
 
     def validate(self, val, stage: str = "val", cutoffs=None) -> dict:
         """One validation pass over ``val`` (a :class:`~xfmr_rec_amd.evalset.DeviceEvalSet`) outside ``fit``: the dict of
         ``DeviceEvalSet.evaluate``, also handed to ``module.log_dict``. ``cutoffs``: the rank path, with the
-        ``<metric>@<K>`` keys (``DeviceEvalSet.evaluate(stage, cutoffs=...)``)."""
+        ``<metric>@<K>`` keys (``DeviceEvalSet.evaluate(stage, cutoffs=...)``). Under ``world_size > 1`` ``val`` is this
+        rank's sharded set, the call is collective (every rank makes it) and every rank gets the same dict."""
         self._check_val(val)
         metrics = val.evaluate(stage) if cutoffs is None else val.evaluate(stage, cutoffs=cutoffs)
         self.module.log_dict(metrics)
@@ -1107,6 +1121,14 @@ class Trainer:
         ``best_model_path``, ``stopped_early`` and ``val_elapsed`` (seconds in validation passes: a host clock from a
         stream sync in front of the pass to its read-back).
 
+        Under ``world_size > 1`` ``val`` is this rank's SHARDED set (``DeviceEvalSet.from_rows(..., rank=, world_size=,
+        process_group=)`` of this run; anything else is a ``ValueError``). Every rank runs the pass on its own rows and
+        its one exchange; the metrics are over all global rows and the same bits on every rank, so the best tracker,
+        the early-stopping rule, ``val_history``, ``best_score``, ``best_step`` and ``stopped_early`` are the same
+        everywhere and all ranks leave the loop after the same batch -- no decision is broadcast, and no rank is left
+        waiting in a gradient all-reduce. ``checkpoint_dir / "best"`` is written by rank 0 only, a barrier follows, and
+        ``best_model_path`` is set on every rank.
+
         ``val_cutoffs`` (e.g. ``(5, 10, 20, 500)``): every pass takes the rank path (``DeviceEvalSet.evaluate(stage,
         cutoffs=val_cutoffs)``): the metrics at every cutoff under ``<stage>/<metric>@<K>`` next to the plain keys (those
         of ``config.top_k``), all of them in ``val_history``. ``monitor["name"]`` may then be ``'<stage>/<metric>@<K>'`` for
@@ -1142,7 +1164,8 @@ class Trainer:
         sync; once it is spent the loop ends, ``stopped_on_time`` is True and ``save_last`` applies. A limit <= 0 still
         runs one batch. This deviates from Lightning, whose ``Timer`` carries the elapsed time across a resume: there, a
         run stopped on time and resumed with the same limit stops after one batch; here the resumed call has the whole
-        budget again. None of the four is supported under ``world_size > 1``."""
+        budget again. None of the four is supported under ``world_size > 1`` (validation, early stopping and the best
+        model are: above; full-state checkpoints and a host-clock limit inside a data-parallel loop are not)."""
         from . import checkpoint as CK
         from .data import SEQ_BATCH_KEYS, DeviceSeqLoader, PinnedBatchRing
 
@@ -1268,7 +1291,12 @@ class Trainer:
                 self.best_score, self.best_step = tracker.best, batches_done
                 if checkpoint_dir is not None:
                     path = pathlib.Path(checkpoint_dir) / "best"
-                    self.module.save(path)
+                    if self.world_size == 1:
+                        self.module.save(path)
+                    else:  # replicas hold the same weights: rank 0 writes, nobody goes on before the directory is whole
+                        if val.rank == 0:
+                            self.module.save(path)
+                        torch.distributed.barrier(self.process_group)
                     self.best_model_path = str(path)
             stop = stopper.update(value) if stopper is not None else False
             # the "auto" probe compares STEPS: whatever a pass (and its checkpoint) took leaves the open window
