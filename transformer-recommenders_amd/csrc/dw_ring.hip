@@ -35,16 +35,11 @@ namespace {
 // system, not at the ring depth or the LDS port. (Also measured: even / odd 16-token steps on separate accumulators -- four
 // independent MFMA chains per wave instead of two -- 36.7 against 36.7 us on a 102-workgroup launch: the SQ counters' 45 %
 // "issue stalled" of this kernel, profiles/r04_step_pmc.md, is not the accumulate chain.)
-#ifndef XF_DWR_RT
-#define XF_DWR_RT 64
-#endif
+// (XF_DWR_RT, XF_DWR_NST and the tile width are in internal.h: the plan of the launch, gemm.hip gemm_plan, needs them too)
 constexpr int RT = XF_DWR_RT;  // tokens per stage
-#ifndef XF_DWR_NST
-#define XF_DWR_NST 4
-#endif
 constexpr int NST = XF_DWR_NST;  // ring stages
 constexpr int IPW = RT / 16;   // gather instructions per wave and stage
-constexpr int TW = 128;   // tile width in features, both ways
+constexpr int TW = kDwRingTile;   // tile width in features, both ways
 using Img = SwzImg<TW>;
 constexpr int IMG_ELEMS = RT * TW;  // one stage image: [RT][128] bf16
 
@@ -199,87 +194,74 @@ __global__ __launch_bounds__(512, (RT * NST <= 128) ? 4 : 2) void dw_ring_kernel
   }
 }
 
+// This kernel's slab plan (gemm.hip dw_ring_plan). The generic plan (~1024 workgroups of 128 x 64 tiles, three per CU) cuts the
+// tokens into 62-115 slabs per weight at the benchmark shape and 25-50 at small batches; this kernel runs ONE workgroup per CU
+// on 128 x 128 tiles, and a slab costs it a ring fill, a 64 KB tile store and later a row of the reduction launch: ~3 000
+// tokens per slab, but at least 64 workgroups per weight (128 x 128 tiles x slabs), never more slabs than the generic plan (the
+// slab room is carved for that). MEASURED (round 4, scripts/probe/dwr_plan_sweep.sh, one box, two rounds, ms per step against
+// the generic plan): batch 128 1.166-1.170 against 1.210; batch 32 0.656-0.670 against 0.690-0.692; MovieLens-like packed batches
+// of 512 (~50 k tokens) 1.94-1.95 against 1.96-1.97; batch 512 dense 3.20-3.22 against 3.19-3.22 (there the plan changes little:
+// 34 / 34 / 64 / 34 slabs instead of 62 / 62 / 115 / 80). 4 096 tokens per slab or fewer than 64 workgroups per weight lose at
+// batch 512 (3.30-3.38 / 3.24-3.25): its four launches per layer run one after the other on the side stream and need the
+// chip's width each.
+constexpr int kSmem = 2 * NST * IMG_ELEMS * (int)sizeof(__bf16);  // 128 KB: what this build of the kernel needs, whatever the plan says
+
 }  // namespace
 
 extern "C" {
 
-// Whether the ring kernel takes these weight-gradient GEMMs (bf16 operands in HBM, 128-wide tiles both ways, operands
-// within the 32-bit byte offsets of the gather); XFMR_DW_RING=0 keeps the generic kernel (A/B runs).
+// Whether the ring kernel takes these weight-gradient GEMMs: pointers in order, and every item's plan of the ring family
 bool xf_dw_ring_takes(const XfDwItem* items, int n, int64_t M, int32_t precision, uint32_t s16) {
-  static const bool on = [] { const char* e = getenv("XFMR_DW_RING"); return !(e && *e == '0'); }();
-  constexpr uint32_t SAB = XF_S16_A | XF_S16_B;
-  if (!on || !items || n < 1 || n > 4 || precision != XFMR_PREC_BF16 || (s16 & SAB) != SAB || M <= 0) return false;
+  if (!items || n < 1 || n > 4) return false;
   for (int i = 0; i < n; ++i) {
     const XfDwItem& t = items[i];
-    if (!t.dy || !t.x || !t.slabs || !t.splits || t.N <= 0 || t.K <= 0 || (t.N % TW) || (t.K % TW)) return false;
-    if (!xf_aligned16(t.dy) || !xf_aligned16(t.x) || !xf_aligned16(t.slabs)) return false;
-    const int64_t widest = t.N > t.K ? t.N : t.K;
-    if ((uint64_t)M * (uint64_t)widest * 2u >= (1ull << 32)) return false;
+    if (!t.dy || !t.x || !t.slabs || !t.splits || !xf_aligned16(t.dy) || !xf_aligned16(t.x) || !xf_aligned16(t.slabs)) return false;
+    if (gemm_plan(GemmKey{kGemmDwGroup, M, t.N, t.K, precision, s16, n, 0}, gemm_switches_once()).family != kGemmRing) return false;
   }
   return true;
 }
 
-// The ring kernel's own slab plan. The generic plan (xf_dw_split_plan: ~1024 workgroups of 128 x 64 tiles, three per CU) cuts
-// the tokens into 62-115 slabs per weight at the benchmark shape and 25-50 at small batches; this kernel runs ONE workgroup
-// per CU on 128 x 128 tiles, and a slab costs it a ring fill, a 64 KB tile store and later a row of the reduction launch:
-// ~3 000 tokens per slab, but at least 64 workgroups per weight (128 x 128 tiles x slabs), never more slabs than the generic plan
-// (the slab room is carved for that: xfmr_linear_bwd_dw_workspace). MEASURED (round 4, scripts/probe/dwr_plan_sweep.sh, one
-// box, two rounds, ms per step against the generic plan): batch 128 1.166-1.170 against 1.210; batch 32 0.656-0.670 against
-// 0.690-0.692; MovieLens-like packed batches of 512 (~50 k tokens) 1.94-1.95 against 1.96-1.97; batch 512 dense 3.20-3.22 against
-// 3.19-3.22 (there the plan changes little: 34 / 34 / 64 / 34 slabs instead of 62 / 62 / 115 / 80). 4 096 tokens per slab or
-// fewer than 64 workgroups per weight lose at batch 512 (3.30-3.38 / 3.24-3.25): its four launches per layer run one after the
-// other on the side stream and need the chip's width each.
-static int dw_ring_plan(int64_t M, int N, int K, int* k_chunk) {
-  static const int tokens = [] { const char* e = getenv("XFMR_DWR_TOKENS"); const int v = e ? atoi(e) : 3072; return v < 128 ? 128 : v; }();
-  // (a function of the weight alone -- not of how many weights share the launch -- so that the grouped in-line launch and the
-  //  four side-stream launches of a layer write the same slabs, bit for bit: tests/test_gpu_fullsize.py)
-  static const int min_wg = [] { const char* e = getenv("XFMR_DWR_MINWG"); const int v = e ? atoi(e) : 64; return v < 1 ? 1 : v; }();
-  const int launch_tiles = (N / TW) * (K / TW);
-  int generic_chunk;
-  const int generic = xf_dw_split_plan(M, N, K, &generic_chunk);
-  int64_t want = (M + tokens - 1) / tokens;
-  const int64_t lo = (min_wg + launch_tiles - 1) / launch_tiles;
-  if (want < lo) want = lo;
-  if (want > generic) want = generic;
-  if (want < 1) want = 1;
-  int64_t chunk = (M + want - 1) / want;
-  chunk = ((chunk + 127) / 128) * 128;
-  if (chunk < generic_chunk) chunk = generic_chunk;  // (never finer than the generic plan: its slab count is the room's bound)
-  *k_chunk = (int)chunk;
-  return (int)((M + chunk - 1) / chunk);
-}
-
-int xf_dw_ring_launch(const XfDwItem* items, int n, int64_t M, hipStream_t st) {
+// The launch of items whose plans are of the ring family: slabs and each item's share of the grid are the plan's
+int xf_dw_ring_launch_plans(const XfDwItem* items, const GemmPlan* plans, int n, int64_t M, hipStream_t st) {
   DwRingArgs p{};
   p.T = M;
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
     const XfDwItem& t = items[i];
-    int k_chunk;
-    const int splits = dw_ring_plan(M, t.N, t.K, &k_chunk);
     DwRingItem& d = p.it[i];
     d.dy = reinterpret_cast<const __bf16*>(t.dy); d.x = reinterpret_cast<const __bf16*>(t.x);
-    d.slabs = t.slabs; d.bias_part = t.bias_part; d.N = t.N; d.K = t.K; d.k_chunk = k_chunk; d.splits = splits;
+    d.slabs = t.slabs; d.bias_part = t.bias_part; d.N = t.N; d.K = t.K; d.k_chunk = plans[i].k_chunk; d.splits = plans[i].splits;
     p.start[i] = (int)total;
-    total += (int64_t)((splits + 7) / 8) * 8 * (t.N / TW) * (t.K / TW);
+    total += plans[i].grid;
     if (total > 0x7fffffffll) return XFMR_EUNSUPPORTED;
-    *t.splits = splits;
+    *t.splits = plans[i].splits;
   }
   for (int i = n; i <= 4; ++i) p.start[i] = (int)total;
-  constexpr size_t smem = (size_t)2 * NST * IMG_ELEMS * sizeof(__bf16);  // 128 KB
   {  // the dynamic-LDS limit is a per-device attribute of the function: set once per device of this process
     static bool attr_set[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return XFMR_EHIP;
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-      if (hipFuncSetAttribute((const void*)dw_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+      if (hipFuncSetAttribute((const void*)dw_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem) != hipSuccess)
         return XFMR_EHIP;
       if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
   }
-  hipLaunchKernelGGL(dw_ring_kernel, dim3((unsigned)total), dim3(512), smem, st, p);
+  hipLaunchKernelGGL(dw_ring_kernel, dim3((unsigned)total), dim3(512), (size_t)kSmem, st, p);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
+}
+// ... of items known to be the ring's (scripts/probe: XFMR_DW_RING is not consulted), planned here
+int xf_dw_ring_launch(const XfDwItem* items, int n, int64_t M, hipStream_t st) {
+  if (!items || n < 1 || n > 4) return XFMR_EINVAL;
+  GemmSwitches sw = gemm_switches_once();
+  sw.dw_ring = 1;
+  GemmPlan plans[4];
+  for (int i = 0; i < n; ++i) {
+    plans[i] = gemm_plan(GemmKey{kGemmDwGroup, M, items[i].N, items[i].K, XFMR_PREC_BF16, XF_S16_A | XF_S16_B, n, 0}, sw);
+    if (plans[i].family != kGemmRing) return XFMR_EUNSUPPORTED;  // (another family's geometry must not reach this kernel)
+  }
+  return xf_dw_ring_launch_plans(items, plans, n, M, st);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 // the parallelism); the operands are L2 / Infinity-Cache resident between the kernels of one step.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -89,7 +90,7 @@ struct GemmArgs {
   int k_chunk;            // split-K: split z handles [z*k_chunk, min(K,(z+1)*k_chunk)); 0 = whole K
   int nt_n, nt_m, nt_z;   // tiles along N, M and the number of K splits (the launch is one-dimensional: see tile_of)
   // Two-region row map of the whole-row (N == 128) kernels: M-tiles [0, nt_full) are BM rows tall, tiles [nt_full, nt_m)
-  // `short_rows` (< BM) -- see xf_plan_row_tiles. nt_full == 0: every tile BM rows (the plain map).
+  // `short_rows` (< BM) -- see row_tiles. nt_full == 0: every tile BM rows (the plain map).
   int nt_full, short_rows;
   const float* bias;      // [N] or null
   const float* R;         // residual / residual-grad [M,ldc] or null
@@ -344,22 +345,23 @@ static int xf_num_cus() {
   }();
   return n;
 }
-static void xf_plan_row_tiles(GemmArgs& g, int BM) {
-  g.nt_full = 0; g.short_rows = 0;
-  g.nt_m = (int)((g.M + BM - 1) / BM);
+// The M-tiles of a whole-row kernel for M rows on `cus` compute units (GemmArgs nt_m, nt_full, short_rows). Pure.
+struct RowTiles { int nt_m, nt_full, short_rows; };
+static RowTiles row_tiles(int64_t M, int BM, int64_t cus, bool short_on) {
+  RowTiles t{(int)((M + BM - 1) / BM), 0, 0};
   // MEASURED AND NOT KEPT AS THE DEFAULT (round 3, batch 512, alternating runs on one box): 3.297 / 3.312 / 3.290 ms per step
   // with the short tiles against 3.278 / 3.288 / 3.279 with the plain map; per kernel 103.3 vs 101.0 us (fused FFN forward),
   // 126.4 vs 127.0 (backward), 62.6 vs 61.1, 43.6 vs 43.5 (the two LayerNorm-fused GEMMs). A lone short tile costs about what
   // a lone full tile costs -- its time is the latency chain of staging, K loop and epilogue, not its rows -- so dealing the
   // tail over all CUs moves it around without shortening it. XFMR_ROW_TILES_SHORT=1 turns the map on (experiments).
-  static const bool on = [] { const char* e = getenv("XFMR_ROW_TILES_SHORT"); return e && *e && *e != '0'; }();
-  const int64_t cus = xf_num_cus();
-  const int64_t per_cu = g.M / (BM * cus), rem = g.M - per_cu * BM * cus;
-  if (!on || per_cu < 1 || rem <= 0 || rem > 32 * cus) return;
+  if (!short_on || cus < 1) return t;
+  const int64_t per_cu = M / (BM * cus), rem = M - per_cu * BM * cus;
+  if (per_cu < 1 || rem <= 0 || rem > 32 * cus) return t;
   const int64_t each = (((rem + cus - 1) / cus) + 15) / 16 * 16;  // rows per short tile: a multiple of 16
-  g.nt_full = (int)(per_cu * cus);
-  g.short_rows = (int)each;
-  g.nt_m = g.nt_full + (int)((rem + each - 1) / each);
+  t.nt_full = (int)(per_cu * cus);
+  t.short_rows = (int)each;
+  t.nt_m = t.nt_full + (int)((rem + each - 1) / each);
+  return t;
 }
 
 // Epilogue of a 64 x 128 tile that spans whole output rows (N == 128), computed by 2 x 2 waves (wave = 32 rows x 64
@@ -858,6 +860,13 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g_in, const int bid) {
     }
   }
 }
+// Tile and slice depth per call: gemm_plan. These GEMMs are skinny (K <= 1024): bound by the CU's memory-instruction
+// throughput and by how many workgroups are co-resident, not by the matrix core. Many small workgroups
+// win -- 64 x 64 tiles with 64-deep slices for the forward / dX GEMMs (64 x 128 once N >= 256): measured 1.874 vs 1.888 ms/step
+// against 32-deep (whole-K 128-deep slices: 2.026); 128-deep slices only pay for the split-K dW GEMMs, on 128 x 64 tiles:
+// twice the workgroups of 128 x 128 at half the LDS and registers each -- the split-K GEMMs are a latency chain of a dozen K
+// slices per workgroup and want co-resident workgroups (measured +1.4 ... 2 % of the step at batch 512 / 128 against
+// 128 x 128; 64 x 64 no better).
 template <class P, int BM, int BN, int BK, bool TA, bool TB, int EPI, uint32_t S>
 __global__ __launch_bounds__(256, (epi_res_ln(EPI) || EPI == EPI_DX_LNBWD) ? XF_LN_EPI_MIN_WAVES : 1) void gemm_kernel(const GemmArgs g_in) {
   gemm_body<P, BM, BN, BK, TA, TB, EPI, S>(g_in, (int)blockIdx.x);
@@ -1490,121 +1499,104 @@ __global__ __launch_bounds__(256) void multi_rowsum_kernel(MultiSegs m) {
   if (rg == 0 && col < sg.cols) sg.dst[col] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
 }
 
-// Tuning override for experiments: XFMR_GEMM_TILE="bm,bn,bk" (64|128, 64|128, 32|128) forces the tile.
-struct TileOverride { int bm, bn, bk; };
-static TileOverride tile_override() {
-  static TileOverride o = [] {
-    TileOverride t{0, 0, 0};
-    if (const char* e = getenv("XFMR_GEMM_TILE")) sscanf(e, "%d,%d,%d", &t.bm, &t.bn, &t.bk);
-    return t;
-  }();
-  return o;
+// ================================================================================================================
+// Host side: the switches, the plan of a call (gemm_plan), one launch routine per kernel family, the entry points
+// ================================================================================================================
+constexpr uint32_t SAB = XF_S16_A | XF_S16_B, SABC = SAB | XF_S16_C, SABCP = SABC | XF_S16_P;
+// ---- the gemm_kernel instantiations: (operation, policy, storage mask, tile, slice depth) -> kernel. The lists bound the set:
+// S16 names the masks an operation is ever launched with besides 0 (all fp32); a combination outside them has no kernel.
+using GemmKernel = void (*)(const GemmArgs);
+template <class P, bool TA, bool TB, int EPI, uint32_t S>
+GemmKernel tile_kernel_of(int bm, int bn, int bk) {
+  // the one slice depth beside 32: 128 for the bf16 split-K dW GEMMs, 64 for the other bf16 GEMMs, none for fp32
+  constexpr int DEEP = P::kId != XFMR_PREC_BF16 ? 32 : EPI == EPI_SPLITK ? 128 : 64;
+  const bool deep = bk == DEEP;
+  if (bm == 64 && bn == 128) return deep ? gemm_kernel<P, 64, 128, DEEP, TA, TB, EPI, S> : gemm_kernel<P, 64, 128, 32, TA, TB, EPI, S>;
+  if (bm == 128 && bn == 64) return deep ? gemm_kernel<P, 128, 64, DEEP, TA, TB, EPI, S> : gemm_kernel<P, 128, 64, 32, TA, TB, EPI, S>;
+  if (bm == 64) return deep ? gemm_kernel<P, 64, 64, DEEP, TA, TB, EPI, S> : gemm_kernel<P, 64, 64, 32, TA, TB, EPI, S>;
+  return deep ? gemm_kernel<P, 128, 128, DEEP, TA, TB, EPI, S> : gemm_kernel<P, 128, 128, 32, TA, TB, EPI, S>;
+}
+template <bool TA, bool TB, int EPI, uint32_t... S16>
+GemmKernel tile_kernel_in(int precision, uint32_t s16, int bm, int bn, int bk) {
+  if (precision == XFMR_PREC_F32) return s16 ? nullptr : tile_kernel_of<PrecF32, TA, TB, EPI, 0>(bm, bn, bk);
+  if (precision != XFMR_PREC_BF16) return nullptr;
+  if (s16 == 0) return tile_kernel_of<PrecBF16, TA, TB, EPI, 0>(bm, bn, bk);
+  GemmKernel k = nullptr;
+  (void)((s16 == S16 ? (k = tile_kernel_of<PrecBF16, TA, TB, EPI, S16>(bm, bn, bk), true) : false) || ...);
+  return k;
+}
+GemmKernel tile_kernel(GemmOp op, int precision, uint32_t s16, int bm, int bn, int bk) {
+  switch (op) {
+    case kGemmFwdBias:
+      return tile_kernel_in<false, false, EPI_STORE, XF_S16_C, (XF_S16_C | XF_S16_B), SABC>(precision, s16, bm, bn, bk);
+    case kGemmFwdGelu:
+      return tile_kernel_in<false, false, EPI_GELU, XF_S16_C, (XF_S16_C | XF_S16_B), SABC>(precision, s16, bm, bn, bk);
+    case kGemmFwdDropRes: return tile_kernel_in<false, false, EPI_DROP_RES, XF_S16_A, SAB>(precision, s16, bm, bn, bk);
+    case kGemmLnFwd: return tile_kernel_in<false, false, EPI_DROP_RES_LN, XF_S16_A, SAB>(precision, s16, bm, bn, bk);
+    // (the re-derived forms exist for the storage the encoder runs them with: bf16 A and B operands -- the plan checks)
+    case kGemmLnFwdRe: return tile_kernel_of<PrecBF16, false, false, EPI_DROP_RES_LN_RE, SAB>(bm, bn, bk);
+    case kGemmLnFwdReDrop: return tile_kernel_of<PrecBF16, false, false, EPI_DROP_RES_LN_RED, SAB>(bm, bn, bk);
+    case kGemmDx:
+      return tile_kernel_in<false, true, EPI_STORE, XF_S16_A, (XF_S16_A | XF_S16_C), SAB, SABC>(precision, s16, bm, bn, bk);
+    case kGemmDxGelu:
+      return tile_kernel_in<false, true, EPI_GELU_GRAD, (XF_S16_A | XF_S16_C | XF_S16_P), SABCP>(precision, s16, bm, bn, bk);
+    case kGemmDxLnBwd: return tile_kernel_in<false, true, EPI_DX_LNBWD, XF_S16_A, SAB>(precision, s16, bm, bn, bk);
+    case kGemmDw: case kGemmDwDeferred: case kGemmDwGroup:
+      return tile_kernel_in<true, true, EPI_SPLITK, XF_S16_A, SAB>(precision, s16, bm, bn, bk);
+    default: return nullptr;
+  }
 }
 
-template <class P, int BK, bool TA, bool TB, int EPI, uint32_t S>
-int launch_gemm_bk(const GemmArgs& g, int splits, hipStream_t st) {
-  // These GEMMs are skinny (K <= 1024): bound by the CU's memory-instruction throughput and by how many workgroups
-  // are co-resident, not by the matrix core. Many small workgroups win -- 64x64 tiles with
-  // 64-deep slices for the forward / dX GEMMs (64x128 once N >= 256), 128-deep slices only for the split-K dW GEMMs.
-  int bm = 64, bn = (g.N >= 256 && EPI != EPI_GELU_GRAD) ? 128 : 64;
-  if (epi_res_ln(EPI) || EPI == EPI_DX_LNBWD) bn = 128;  // whole rows (N == 128, checked by the caller)
-  if (EPI == EPI_SPLITK && g.M > 64 && g.N > 64) {
-    // 128 x 64: twice the workgroups of 128 x 128 at half the LDS and registers each -- the split-K GEMMs are a
-    // latency chain of a dozen K slices per workgroup and want co-resident workgroups (measured +1.4 ... 2 % of the
-    // step at batch 512 / 128 against 128 x 128; 64 x 64 no better). XFMR_DW_TILE="bm,bn" for experiments.
-    bm = 128; bn = 64;
-    static const TileOverride dw = [] {
-      TileOverride o{0, 0, 0};
-      if (const char* e = getenv("XFMR_DW_TILE")) sscanf(e, "%d,%d", &o.bm, &o.bn);
-      return o;
-    }();
-    if (dw.bm) { bm = dw.bm; bn = dw.bn; }
-  }
-  const TileOverride ov = tile_override();
-  if (ov.bm && !epi_res_ln(EPI) && EPI != EPI_DX_LNBWD) { bm = ov.bm; bn = ov.bn; }
-  dim3 block(256);
-  static const int pad_lds = [] { const char* e = getenv("XFMR_GEMM_PAD_LDS"); return e ? atoi(e) : 0; }();
-  GemmArgs ga = g;
-  ga.nt_n = (int)((g.N + bn - 1) / bn);
-  ga.nt_m = (int)((g.M + bm - 1) / bm);
-  if (epi_res_ln(EPI) || EPI == EPI_DX_LNBWD) xf_plan_row_tiles(ga, bm);  // (whole-row tiles: bm = 64, one N-tile)
-  ga.nt_z = splits;
-  // one-dimensional launch, padded so that every XCD gets whole groups (see tile_of)
-  const int64_t groups = splits > 1 ? (splits + 7) / 8 : (ga.nt_m + 7) / 8;
-  const int64_t per = splits > 1 ? (int64_t)ga.nt_n * ga.nt_m : ga.nt_n;
-  if (groups * per * 8 > 0x7fffffffll) return XFMR_EUNSUPPORTED;
-  dim3 grid((unsigned)(groups * per * 8));
-  if (bm == 64 && bn == 128) hipLaunchKernelGGL((gemm_kernel<P, 64, 128, BK, TA, TB, EPI, S>), grid, block, pad_lds, st, ga);
-  else if (bm == 128 && bn == 64) hipLaunchKernelGGL((gemm_kernel<P, 128, 64, BK, TA, TB, EPI, S>), grid, block, pad_lds, st, ga);
-  else if (bm == 64) hipLaunchKernelGGL((gemm_kernel<P, 64, 64, BK, TA, TB, EPI, S>), grid, block, pad_lds, st, ga);
-  else hipLaunchKernelGGL((gemm_kernel<P, 128, 128, BK, TA, TB, EPI, S>), grid, block, pad_lds, st, ga);
+}  // namespace
+
+#include "gemm_plan.inc"
+
+namespace {
+
+// What an entry returns before it launches, in the order of its checks: the key's early ones, its pointers' alignment, a
+// check of its own that sits between (the residual operand, the workspace), the key's other ones
+int plan_rc(const GemmPlan& p, bool aligned, int between = XFMR_OK) {
+  return p.rc_shape ? p.rc_shape : !aligned ? XFMR_EALIGN : between ? between : p.rc;
+}
+
+void set_tiles(GemmArgs& g, const GemmPlan& p) {
+  g.nt_n = p.nt_n; g.nt_m = p.nt_m; g.nt_z = p.nt_z; g.nt_full = p.nt_full; g.short_rows = p.short_rows;
+}
+// ---- the launch of gemm_kernel: the plan's instantiation, tile counts, storage mask, grid and LDS
+int launch_tile(const GemmPlan& p, GemmArgs g, hipStream_t st) {
+  set_tiles(g, p);
+  g.s16 = p.s16;
+  hipLaunchKernelGGL((GemmKernel)p.kernel, dim3((unsigned)p.grid), dim3((unsigned)p.block), (size_t)p.lds, st, g);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
 }
-
-template <class P, bool TA, bool TB, int EPI, uint32_t S>
-int launch_gemm(const GemmArgs& g, int splits, hipStream_t st) {
-  // deep (128) K slices only pay for the split-K dW GEMMs (see launch_gemm_bk); bf16 only.
-  const int kspan = g.k_chunk > 0 ? g.k_chunk : g.K;
-  const TileOverride ov = tile_override();
-  if constexpr (P::kId == XFMR_PREC_BF16 && EPI == EPI_SPLITK) {
-    if (kspan % 128 == 0 && ov.bk != 32) return launch_gemm_bk<P, 128, TA, TB, EPI, S>(g, splits, st);
+// The split-K weight-gradient GEMM of one Linear over M tokens: dw[N,K] = dy^T[N,M] * x[M,K]. A' = dy^T (dy stored [M][N]),
+// B'[K rows][M] = x^T, C = the slabs [splits][N][K]; bias_part: [splits][N] column sums of dy, or null.
+GemmArgs dw_args(const XfDwItem& t, int64_t M, const GemmPlan& p) {
+  GemmArgs g{};
+  g.A = t.dy; g.B = t.x; g.C = t.slabs; g.lda = t.N; g.ldb = t.K; g.ldc = t.K;
+  g.M = t.N; g.N = t.K; g.K = (int)M; g.k_chunk = p.k_chunk;
+  g.s16 = p.s16; g.bias_part = t.bias_part;
+  g.drop = xf_make_dropout(0.f, 0, 0);
+  set_tiles(g, p);
+  return g;
+}
+// ---- the launch of gemm_group_kernel: every item's plan is of family kGemmGroup, i.e. on the kernel's one tile
+int launch_group(const XfDwItem* items, const GemmPlan* plans, int n, int64_t M, hipStream_t st) {
+  GemmGroup p{};
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    p.g[i] = dw_args(items[i], M, plans[i]);
+    p.start[i] = (int)total;
+    total += plans[i].grid;
+    if (total > 0x7fffffffll) return XFMR_EUNSUPPORTED;
+    *items[i].splits = plans[i].splits;
   }
-  if constexpr (P::kId == XFMR_PREC_BF16 && EPI != EPI_SPLITK) {
-    // 64-deep slices for the forward / dX GEMMs: measured 1.874 vs 1.888 ms/step against 32-deep (whole-K 128-deep
-    // slices: 2.026). XFMR_GEMM_TILE="bm,bn,32" forces 32.
-    if (ov.bk != 32 && kspan % 64 == 0) return launch_gemm_bk<P, 64, TA, TB, EPI, S>(g, splits, st);
-  }
-  return launch_gemm_bk<P, 32, TA, TB, EPI, S>(g, splits, st);
-}
-
-// S16 lists the storage masks this (TA, TB, EPI) combination is ever launched with besides 0 (all fp32).
-template <bool TA, bool TB, int EPI, uint32_t... S16>
-int dispatch_gemm(const GemmArgs& g, int splits, int precision, hipStream_t st) {
-  if (precision == XFMR_PREC_F32) return g.s16 ? XFMR_EINVAL : launch_gemm<PrecF32, TA, TB, EPI, 0>(g, splits, st);
-  if (precision != XFMR_PREC_BF16) return XFMR_EINVAL;
-  if (g.s16 == 0) return launch_gemm<PrecBF16, TA, TB, EPI, 0>(g, splits, st);
-  int rc = XFMR_EINVAL;
-  (void)((g.s16 == S16 ? (rc = launch_gemm<PrecBF16, TA, TB, EPI, S16>(g, splits, st), true) : false) || ...);
-  return rc;
-}
-
-int dw_split_plan(int64_t M, int N, int K, int* k_chunk) {
-  // reduction dimension = M (tokens): <= 128 deterministic slabs
-  int64_t tiles = ((N + 63) / 64) * ((K + 63) / 64);
-  // <= 128 slabs: the 128 x 128 / 384 x 128 weights have few output tiles and need the splits for parallelism
-  // (64 -> 128: +0.9 % of the step at batch 512; 256 no better). XFMR_DW_MAXSPLIT for experiments (<= 256).
-  static const int max_split = [] {
-    const char* e = getenv("XFMR_DW_MAXSPLIT");
-    const int v = e ? atoi(e) : 128;
-    return v < 1 ? 1 : (v > 256 ? 256 : v);
-  }();
-  int64_t want = (1024 + tiles - 1) / tiles;
-  if (want > max_split) want = max_split;
-  if (want < 1) want = 1;
-  int64_t chunk = (M + want - 1) / want;
-  chunk = ((chunk + 127) / 128) * 128;  // multiple of the deep K slice
-  // at least two deep slices per slab once there are tokens for it: at batch 32 (6400 tokens) 50 one-slice slabs per
-  // weight made the slab traffic (write + reduction) the larger part of the weight gradients -- 25 slabs: 0.760 against
-  // 0.847 ms/step; batch 128 and up already have >= 256 tokens per slab (round 3, one box)
-  if (M >= 4096 && chunk < 256) chunk = 256;
-  if (chunk < 64) chunk = 64;
-  *k_chunk = (int)chunk;
-  return (int)((M + chunk - 1) / chunk);
-}
-// The most slabs dw_split_plan gives for ANY token count <= M. The plan is not monotone in M (4 095 tokens: 32 slabs of
-// 128; 4 096: 16 of 256), and the packed layout (xfmr_encoder_cfg.seq_offsets) carves its slab buffers for batch x seq_len
-// tokens and then launches with the real row count -- round 4: a 128 x 32 batch of 2 750 real rows wrote 22 slabs into room
-// for 16. chunk >= max(128, M / want)  =>  slabs <= min(ceil(M / 128), want).
-int dw_split_bound(int64_t M, int N, int K) {
-  int k_chunk;
-  const int64_t tiles = ((N + 63) / 64) * ((K + 63) / 64);
-  int64_t want = (1024 + tiles - 1) / tiles;
-  if (want > 256) want = 256;
-  const int64_t by_rows = (M + 127) / 128;
-  const int64_t bound = by_rows < want ? by_rows : want;
-  const int plan = dw_split_plan(M, N, K, &k_chunk);
-  return bound > plan ? (int)bound : plan;
+  for (int i = n; i <= 4; ++i) p.start[i] = (int)total;
+  hipLaunchKernelGGL((gemm_group_kernel<PrecBF16, 128, 64, 128, true, true, EPI_SPLITK, SAB>), dim3((unsigned)total),
+                     dim3((unsigned)plans[0].block), (size_t)plans[0].lds, st, p);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
 }
 
 // residual operand of the EPI_DROP_RES_LN family: `residual` (loaded) or `res` (re-derived) -- exactly one
@@ -1623,35 +1615,29 @@ int linear_ln_fwd(const void* x, const float* w, const float* bias, float* pre, 
                   const float* residual, const XfLnResidual* res, float dropout_p, XfSeed seed, uint32_t site,
                   const float* gamma, const float* beta, float eps, float* y, void* y16, float* mean, float* rstd,
                   int32_t precision, uint32_t s16, hipStream_t st) {
-  if (!x || !w || !pre || !gamma || !beta || (!y && !y16) || !mean || !rstd || M <= 0 || K <= 0) return XFMR_EINVAL;
-  if (N != 128 || (K & 7)) return XFMR_EUNSUPPORTED;  // the tile spans one whole 128-column row
-  if (precision != XFMR_PREC_BF16) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(x) || !xf_aligned16(w) || !xf_aligned16(pre) || (y && !xf_aligned16(y))) return XFMR_EALIGN;
+  if (!x || !w || !pre || !gamma || !beta || (!y && !y16) || !mean || !rstd) return XFMR_EINVAL;
+  const GemmKey k{!res ? kGemmLnFwd : res->dropout_p > 0.f ? kGemmLnFwdReDrop : kGemmLnFwdRe, M, N, K, precision, s16, 1, xf_num_cus()};
+  const GemmPlan p = gemm_plan(k, gemm_switches_once());
   GemmArgs g{};
   g.A = x; g.B = w; g.C = pre; g.lda = K; g.ldb = K; g.ldc = N; g.M = M; g.N = N; g.K = K; g.k_chunk = 0;
-  g.bias = bias; g.s16 = s16 & (XF_S16_A | XF_S16_B);
-  if (const int rc = set_ln_residual(g, residual, res, seed)) return rc;
+  g.bias = bias;
+  const int res_rc = set_ln_residual(g, residual, res, seed);
+  if (const int rc = plan_rc(p, xf_aligned16(x) && xf_aligned16(w) && xf_aligned16(pre) && xf_aligned16(y), res_rc)) return rc;
   g.drop = xf_make_dropout(dropout_p, seed, site);
   g.ln_gamma = gamma; g.ln_beta = beta; g.ln_eps = eps; g.Y = y; g.Y16 = y16; g.ln_mean = mean; g.ln_rstd = rstd;
-  if (!res) return dispatch_gemm<false, false, EPI_DROP_RES_LN, XF_S16_A, (XF_S16_A | XF_S16_B)>(g, 1, precision, st);
-  // (the re-derived forms exist for the storage the encoder runs them with: bf16 A and B operands)
-  if (g.s16 != (XF_S16_A | XF_S16_B)) return XFMR_EUNSUPPORTED;
-  if (g.rp_drop.on) return launch_gemm<PrecBF16, false, false, EPI_DROP_RES_LN_RED, (XF_S16_A | XF_S16_B)>(g, 1, st);
-  return launch_gemm<PrecBF16, false, false, EPI_DROP_RES_LN_RE, (XF_S16_A | XF_S16_B)>(g, 1, st);
+  return launch_tile(p, g, st);
 }
 
 int ffn_fwd_fused(const void* x16, const void* w1_16, const float* b1, const void* w2_16, const float* b2, void* u16,
                   void* g16, float* pre, int64_t M, int32_t H, int32_t I, const float* residual, const XfLnResidual* res,
                   float dropout_p, XfSeed seed, uint32_t site, const float* gamma, const float* beta, float eps, float* y,
                   void* y16, float* mean, float* rstd, hipStream_t st) {
-  if (!x16 || !w1_16 || !b1 || !w2_16 || !pre || !gamma || !beta || (!y && !y16) || !mean || !rstd || M <= 0)
-    return XFMR_EINVAL;
-  if (H != 128 || I <= 0 || (I % 128) || I > 1024) return XFMR_EUNSUPPORTED;  // (b1 is staged in 4 KB of LDS)
-  if (res && res->dropout_p > 0.f) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(x16) || !xf_aligned16(w1_16) || !xf_aligned16(w2_16) || !xf_aligned16(pre) ||
-      (y && !xf_aligned16(y)) || (u16 && !xf_aligned16(u16)) || (g16 && !xf_aligned16(g16)) || (y16 && !xf_aligned16(y16)) || !xf_aligned16(b1) ||
-      (b2 && !xf_aligned16(b2)) || !xf_aligned16(gamma) || !xf_aligned16(beta))
-    return XFMR_EALIGN;
+  if (!x16 || !w1_16 || !b1 || !w2_16 || !pre || !gamma || !beta || (!y && !y16) || !mean || !rstd) return XFMR_EINVAL;
+  GemmPlan p = gemm_plan(GemmKey{res ? kGemmFfnFwdRe : kGemmFfnFwd, M, H, I, XFMR_PREC_BF16, 0, 1, xf_num_cus()}, gemm_switches());
+  if (!p.rc_shape && res && res->dropout_p > 0.f) p.rc_shape = XFMR_EUNSUPPORTED;  // (no dropout on this kernel's residual)
+  const bool aligned = xf_aligned16(x16) && xf_aligned16(w1_16) && xf_aligned16(w2_16) && xf_aligned16(pre) && xf_aligned16(y) &&
+                       xf_aligned16(u16) && xf_aligned16(g16) && xf_aligned16(y16) && xf_aligned16(b1) && xf_aligned16(b2) &&
+                       xf_aligned16(gamma) && xf_aligned16(beta);  // (a null pointer is aligned)
   FfnFwdArgs f{};
   f.X = (const __bf16*)x16; f.W1 = (const __bf16*)w1_16; f.b1 = b1; f.W2 = (const __bf16*)w2_16; f.U = (__bf16*)u16; f.G = (__bf16*)g16;
   f.I = I;
@@ -1660,22 +1646,14 @@ int ffn_fwd_fused(const void* x16, const void* w1_16, const float* b1, const voi
 #endif
   GemmArgs& g = f.e;
   g.C = pre; g.ldc = H; g.M = M; g.N = H; g.K = I; g.bias = b2;
-  if (const int rc = set_ln_residual(g, residual, res, seed)) return rc;
+  const int res_rc = set_ln_residual(g, residual, res, seed);
+  if (const int rc = plan_rc(p, aligned, res_rc)) return rc;
   g.drop = xf_make_dropout(dropout_p, seed, site);
   g.ln_gamma = gamma; g.ln_beta = beta; g.ln_eps = eps; g.Y = y; g.Y16 = y16; g.ln_mean = mean; g.ln_rstd = rstd;
-  g.nt_n = 1; g.nt_z = 1;
-  xf_plan_row_tiles(g, 64);
-  const int64_t groups = (g.nt_m + 7) / 8;
-  if (groups * 8 > 0x7fffffffll) return XFMR_EUNSUPPORTED;
-  // XFMR_FFN_CHUNK=128 (tiling only -- what the kernel stores does not depend on it; read per call so that one test process
-  // can cover both): the wider chunk, two workgroups per CU -- measured slower
-  const char* ce = getenv("XFMR_FFN_CHUNK");
-  const int chunk = ce ? atoi(ce) : 64;
-  const dim3 grid((unsigned)(groups * 8));
-  if (chunk == 64 && res) hipLaunchKernelGGL((ffn_fwd_fused_kernel<64, true>), grid, dim3(256), 0, st, f);
-  else if (chunk == 64) hipLaunchKernelGGL((ffn_fwd_fused_kernel<64, false>), grid, dim3(256), 0, st, f);
-  else if (res) hipLaunchKernelGGL((ffn_fwd_fused_kernel<128, true>), grid, dim3(256), 0, st, f);
-  else hipLaunchKernelGGL((ffn_fwd_fused_kernel<128, false>), grid, dim3(256), 0, st, f);
+  set_tiles(g, p);
+  const auto kernel = p.ffn_chunk == 64 ? (res ? ffn_fwd_fused_kernel<64, true> : ffn_fwd_fused_kernel<64, false>)
+                                        : (res ? ffn_fwd_fused_kernel<128, true> : ffn_fwd_fused_kernel<128, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3((unsigned)p.block), 0, st, f);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
 }
@@ -1685,49 +1663,51 @@ int ffn_fwd_fused(const void* x16, const void* w1_16, const float* b1, const voi
 
 extern "C" {
 
-int xf_dw_split_plan(int64_t M, int32_t N, int32_t K, int* k_chunk) { return dw_split_plan(M, N, K, k_chunk); }
+int xf_gemm_plan(int32_t op, int64_t M, int32_t N, int32_t K, int32_t precision, uint32_t s16, int32_t items, int32_t cus,
+                 const int32_t sw[16], int32_t out[24]) {
+  static_assert(sizeof(GemmSwitches) == 16 * sizeof(int32_t), "xf_gemm_switches writes the struct as sixteen integers");
+  GemmSwitches s;
+  memcpy(&s, sw, sizeof s);
+  const GemmPlan p = gemm_plan(GemmKey{(GemmOp)op, M, N, K, precision, s16, items, cus}, s);
+  const int32_t fields[20] = {p.family, p.epi, p.precision, (int32_t)p.s16, p.bm, p.bn, p.bk, p.splits, p.k_chunk, p.nt_n, p.nt_m,
+                              p.nt_z, p.nt_full, p.short_rows, p.grid, p.block, p.lds, p.ffn_chunk, p.ffn_ring, p.records};
+  for (int i = 0; i < 24; ++i) out[i] = (i < 20 && p.rc == XFMR_OK) ? fields[i] : 0;
+  return p.rc;
+}
+void xf_gemm_switches(int32_t sw[16]) {
+  const GemmSwitches s = gemm_switches();
+  memcpy(sw, &s, sizeof s);
+}
+
+// thin readers of the plan: the generic slab plan of one weight gradient over M tokens; the M-tiles (= LayerNorm partial
+// records) of the whole-row kernels for M rows on this device
+int xf_dw_split_plan(int64_t M, int32_t N, int32_t K, int* k_chunk) {
+  return dw_split_plan(M, N, K, gemm_switches_once().dw_maxsplit, k_chunk);
+}
+int xf_ln_row_tiles(int64_t M) {
+  return gemm_plan(GemmKey{kGemmDxLnBwd, M, 8, 128, XFMR_PREC_BF16, 0, 1, xf_num_cus()}, gemm_switches_once()).records;
+}
 
 // internal (norm.hip): dst[c] = sum over all rows
 int xf_rowsum(float* dst, const float* src, int64_t rows, int64_t cols, hipStream_t st) {
   return launch_rowsum(dst, src, rows, cols, rows, st);
 }
 
-// M-tiles (= LayerNorm partial records) of the whole-row kernels for M rows: the two-region row map's count
-int xf_ln_row_tiles(int64_t M) {
-  GemmArgs g{};
-  g.M = M;
-  xf_plan_row_tiles(g, 64);
-  return g.nt_m;
-}
-
 int xf_linear_fwd_ex(const void* x, const float* w, const float* bias, void* y, int64_t M, int32_t N, int32_t K,
                      int32_t epilogue, const float* residual, void* aux_out, float dropout_p, XfSeed seed,
                      uint32_t site, int32_t precision, uint32_t s16, hipStream_t st) {
-  if (!x || !w || !y || M <= 0 || N <= 0 || K <= 0) return XFMR_EINVAL;
-  if ((K & 3) || (N & 3)) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(x) || !xf_aligned16(w) || !xf_aligned16(y)) return XFMR_EALIGN;
-  if ((s16 & ~XF_AUX_GELU_GRAD) && precision != XFMR_PREC_BF16) return XFMR_EINVAL;
-  if ((s16 & (XF_S16_A | XF_S16_B | XF_S16_C | XF_S16_P)) && ((K & 7) || (N & 7))) return XFMR_EUNSUPPORTED;  // 16-byte bf16 pieces
+  if (!x || !w || !y) return XFMR_EINVAL;
+  const bool gelu = epilogue == XFMR_EPI_BIAS_GELU, res = epilogue == XFMR_EPI_BIAS_DROP_RES;
+  const GemmKey k{gelu ? kGemmFwdGelu : res ? kGemmFwdDropRes : kGemmFwdBias, M, N, K, precision, s16, 1, 0};
+  const GemmPlan p = gemm_plan(k, gemm_switches_once());
+  if (const int rc = plan_rc(p, xf_aligned16(x) && xf_aligned16(w) && xf_aligned16(y))) return rc;
+  if ((epilogue != XFMR_EPI_BIAS && !gelu && !res) || (gelu && !aux_out) || (res && !residual)) return XFMR_EINVAL;
   GemmArgs g{};
   g.A = x; g.B = w; g.C = y; g.lda = K; g.ldb = K; g.ldc = N; g.M = M; g.N = N; g.K = K; g.k_chunk = 0;
-  g.bias = bias; g.R = residual; g.C2 = aux_out; g.P = nullptr; g.s16 = s16 & (XF_S16_A | XF_S16_B | XF_S16_C);
+  g.bias = bias; g.R = epilogue == XFMR_EPI_BIAS ? nullptr : residual; g.C2 = aux_out; g.P = nullptr;
   g.aux_grad = (s16 & XF_AUX_GELU_GRAD) != 0;
   g.drop = xf_make_dropout(dropout_p, seed, site);
-  switch (epilogue) {
-    case XFMR_EPI_BIAS:
-      g.R = nullptr;
-      return dispatch_gemm<false, false, EPI_STORE, XF_S16_C, (XF_S16_C | XF_S16_B),
-                           (XF_S16_A | XF_S16_B | XF_S16_C)>(g, 1, precision, st);
-    case XFMR_EPI_BIAS_GELU:
-      if (!aux_out) return XFMR_EINVAL;
-      return dispatch_gemm<false, false, EPI_GELU, XF_S16_C, (XF_S16_C | XF_S16_B),
-                           (XF_S16_A | XF_S16_B | XF_S16_C)>(g, 1, precision, st);
-    case XFMR_EPI_BIAS_DROP_RES:
-      if (!residual) return XFMR_EINVAL;
-      return dispatch_gemm<false, false, EPI_DROP_RES, XF_S16_A, (XF_S16_A | XF_S16_B)>(g, 1, precision, st);
-    default:
-      return XFMR_EINVAL;
-  }
+  return launch_tile(p, g, st);
 }
 
 int xf_linear_ln_fwd_ex(const void* x, const float* w, const float* bias, float* pre, int64_t M, int32_t N, int32_t K,
@@ -1776,13 +1756,13 @@ int xf_ffn_bwd_dx_fused_ex(const void* dy16, const void* w2_16, const void* u16,
                            const float* ln_rstd, const float* ln_gamma, float dropout_p, XfSeed seed, uint32_t site,
                            float* dx, void* d_lin16, float* partials, int* blocks_out, hipStream_t st) {
   if (!dy16 || !w2_16 || !u16 || !w1_16 || !di16 || !ln_x || !ln_mean || !ln_rstd || !ln_gamma || !dx || !partials ||
-      !blocks_out || M <= 0)
+      !blocks_out)
     return XFMR_EINVAL;
-  if (H != 128 || I <= 0 || (I % 64)) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(dy16) || !xf_aligned16(w2_16) || !xf_aligned16(u16) || !xf_aligned16(w1_16) || !xf_aligned16(di16) ||
-      !xf_aligned16(dx) || !xf_aligned16(ln_x) || (residual_grad && !xf_aligned16(residual_grad)) ||
-      (d_lin16 && !xf_aligned16(d_lin16)) || !xf_aligned16(ln_gamma))
-    return XFMR_EALIGN;
+  const GemmPlan p = gemm_plan(GemmKey{kGemmFfnBwd, M, H, I, XFMR_PREC_BF16, 0, 1, xf_num_cus()}, gemm_switches());
+  if (const int rc = plan_rc(p, xf_aligned16(dy16) && xf_aligned16(w2_16) && xf_aligned16(u16) && xf_aligned16(w1_16) &&
+                                    xf_aligned16(di16) && xf_aligned16(dx) && xf_aligned16(ln_x) && xf_aligned16(residual_grad) &&
+                                    xf_aligned16(d_lin16) && xf_aligned16(ln_gamma)))
+    return rc;
   FfnBwdArgs f{};
   f.DY = (const __bf16*)dy16; f.W2 = (const __bf16*)w2_16; f.U = (const __bf16*)u16; f.W1 = (const __bf16*)w1_16;
   f.DI = (__bf16*)di16; f.I = I;
@@ -1792,17 +1772,11 @@ int xf_ffn_bwd_dx_fused_ex(const void* dy16, const void* w2_16, const void* u16,
   g.drop2 = xf_make_dropout(0.f, 0, 0);
   g.ln_gamma = ln_gamma; g.lnb_x = ln_x; g.lnb_mean = ln_mean; g.lnb_rstd = ln_rstd; g.D16 = d_lin16;
   g.lnb_partials = partials;
-  g.nt_n = 1; g.nt_z = 1;
-  xf_plan_row_tiles(g, 64);
-  *blocks_out = g.nt_m;
-  const int64_t groups = (g.nt_m + 7) / 8;
-  if (groups * 8 > 0x7fffffffll) return XFMR_EUNSUPPORTED;
-  // XFMR_FFN_REG_STAGE=1 (read per call: tests, A/B timing inside one library): the register-staged weight chunks
-  const char* const reg_stage = getenv("XFMR_FFN_REG_STAGE");
-  if (reg_stage && *reg_stage && *reg_stage != '0')
-    hipLaunchKernelGGL(ffn_bwd_dx_fused_kernel<false>, dim3((unsigned)(groups * 8)), dim3(256), 0, st, f);
-  else
-    hipLaunchKernelGGL(ffn_bwd_dx_fused_kernel<true>, dim3((unsigned)(groups * 8)), dim3(256), 0, st, f);
+  set_tiles(g, p);
+  *blocks_out = p.records;
+  const dim3 grid((unsigned)p.grid), block((unsigned)p.block);
+  if (p.ffn_ring) hipLaunchKernelGGL(ffn_bwd_dx_fused_kernel<true>, grid, block, 0, st, f);
+  else hipLaunchKernelGGL(ffn_bwd_dx_fused_kernel<false>, grid, block, 0, st, f);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
 }
@@ -1810,23 +1784,17 @@ int xf_ffn_bwd_dx_fused_ex(const void* dy16, const void* w2_16, const void* u16,
 int xf_linear_bwd_dx_ex(const void* dy, const float* w, void* dx, int64_t M, int32_t N, int32_t K,
                         const float* residual_grad, const void* gelu_pre, int32_t precision, uint32_t s16,
                         hipStream_t st) {
-  if (!dy || !w || !dx || M <= 0 || N <= 0 || K <= 0) return XFMR_EINVAL;
-  if ((K & 3) || (N & 3)) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(dy) || !xf_aligned16(w) || !xf_aligned16(dx)) return XFMR_EALIGN;
-  if ((s16 & ~XF_AUX_GELU_GRAD) && precision != XFMR_PREC_BF16) return XFMR_EINVAL;
-  if ((s16 & (XF_S16_A | XF_S16_B | XF_S16_C | XF_S16_P)) && ((K & 7) || (N & 7))) return XFMR_EUNSUPPORTED;  // 16-byte bf16 pieces
+  if (!dy || !w || !dx) return XFMR_EINVAL;
+  const GemmKey k{gelu_pre ? kGemmDxGelu : kGemmDx, M, N, K, precision, s16, 1, 0};
+  const GemmPlan p = gemm_plan(k, gemm_switches_once());
+  if (const int rc = plan_rc(p, xf_aligned16(dy) && xf_aligned16(w) && xf_aligned16(dx))) return rc;
   // dx[M,K] = dy[M,N] * w[N,K]: contraction over N; B' [K rows][N] = w^T -> w is stored [N][K] = K-major
   GemmArgs g{};
   g.A = dy; g.B = w; g.C = dx; g.lda = N; g.ldb = K; g.ldc = K; g.M = M; g.N = K; g.K = N; g.k_chunk = 0;
   g.bias = nullptr; g.R = residual_grad; g.P = gelu_pre; g.C2 = nullptr;
-  g.s16 = s16 & (XF_S16_A | XF_S16_B | XF_S16_C | XF_S16_P);
   g.aux_grad = (s16 & XF_AUX_GELU_GRAD) != 0;
   g.drop = xf_make_dropout(0.f, 0, 0);
-  if (gelu_pre)
-    return dispatch_gemm<false, true, EPI_GELU_GRAD, (XF_S16_A | XF_S16_C | XF_S16_P),
-                         (XF_S16_A | XF_S16_B | XF_S16_C | XF_S16_P)>(g, 1, precision, st);
-  return dispatch_gemm<false, true, EPI_STORE, XF_S16_A, (XF_S16_A | XF_S16_C), (XF_S16_A | XF_S16_B),
-                       (XF_S16_A | XF_S16_B | XF_S16_C)>(g, 1, precision, st);
+  return launch_tile(p, g, st);
 }
 
 int xf_linear_bwd_dx_lnbwd_ex(const void* dy, const float* w, int64_t M, int32_t N, int32_t K,
@@ -1834,20 +1802,19 @@ int xf_linear_bwd_dx_lnbwd_ex(const void* dy, const float* w, int64_t M, int32_t
                               const float* ln_gamma, float dropout_p, XfSeed seed, uint32_t site, float* dx,
                               void* d_lin16, float* partials, int* blocks_out, int32_t precision, uint32_t s16,
                               hipStream_t st, float out_dropout_p, uint32_t out_site) {
-  if (!dy || !w || !dx || !ln_x || !ln_mean || !ln_rstd || !ln_gamma || !partials || !blocks_out || M <= 0 || N <= 0)
-    return XFMR_EINVAL;
-  if (K != 128 || (N & 7)) return XFMR_EUNSUPPORTED;  // output rows = whole 128-wide LayerNorm rows
-  if (precision != XFMR_PREC_BF16) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(dy) || !xf_aligned16(w) || !xf_aligned16(dx) || !xf_aligned16(ln_x)) return XFMR_EALIGN;
+  if (!dy || !w || !dx || !ln_x || !ln_mean || !ln_rstd || !ln_gamma || !partials || !blocks_out) return XFMR_EINVAL;
+  const GemmKey k{kGemmDxLnBwd, M, N, K, precision, s16, 1, xf_num_cus()};
+  const GemmPlan p = gemm_plan(k, gemm_switches_once());
+  if (const int rc = plan_rc(p, xf_aligned16(dy) && xf_aligned16(w) && xf_aligned16(dx) && xf_aligned16(ln_x))) return rc;
   GemmArgs g{};
   g.A = dy; g.B = w; g.C = dx; g.lda = N; g.ldb = K; g.ldc = K; g.M = M; g.N = K; g.K = N; g.k_chunk = 0;
-  g.R = residual_grad; g.s16 = s16 & (XF_S16_A | XF_S16_B);
+  g.R = residual_grad;
   g.drop = xf_make_dropout(dropout_p, seed, site);
   g.ln_gamma = ln_gamma; g.lnb_x = ln_x; g.lnb_mean = ln_mean; g.lnb_rstd = ln_rstd; g.D16 = d_lin16;
   g.lnb_partials = partials;
   g.drop2 = xf_make_dropout(out_dropout_p, seed, out_site);
-  *blocks_out = xf_ln_row_tiles(M);  // (the launch plans the same row map: launch_gemm_bk)
-  return dispatch_gemm<false, true, EPI_DX_LNBWD, XF_S16_A, (XF_S16_A | XF_S16_B)>(g, 1, precision, st);
+  *blocks_out = p.records;  // the records of the row map this launch runs
+  return launch_tile(p, g, st);
 }
 
 int xfmr_linear_bwd_dx(const float* dy, const float* w, float* dx, int64_t M, int32_t N, int32_t K,
@@ -1858,105 +1825,58 @@ int xfmr_linear_bwd_dx(const float* dy, const float* w, float* dx, int64_t M, in
 size_t xfmr_linear_bwd_dw_workspace(int64_t M, int32_t N, int32_t K) {  // enough for every token count <= M
   return (size_t)dw_split_bound(M, N, K) * (size_t)N * (size_t)K * sizeof(float);
 }
+size_t xf_linear_bwd_dw_slab_bytes(int64_t M, int32_t N, int32_t K) { return xfmr_linear_bwd_dw_workspace(M, N, K); }
 
 int xf_linear_bwd_dw_ex(const void* dy, const void* x, float* dw, int64_t M, int32_t N, int32_t K, int32_t precision,
                         void* workspace, size_t workspace_bytes, uint32_t s16, hipStream_t st) {
-  if (!dy || !x || !dw || !workspace || M <= 0 || N <= 0 || K <= 0) return XFMR_EINVAL;
-  if ((K & 3) || (N & 3)) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(dy) || !xf_aligned16(x) || !xf_aligned16(workspace)) return XFMR_EALIGN;
-  if (workspace_bytes < xfmr_linear_bwd_dw_workspace(M, N, K)) return XFMR_EWORKSPACE;
-  if ((s16 & ~XF_AUX_GELU_GRAD) && precision != XFMR_PREC_BF16) return XFMR_EINVAL;
-  if ((s16 & (XF_S16_A | XF_S16_B | XF_S16_C | XF_S16_P)) && ((K & 7) || (N & 7))) return XFMR_EUNSUPPORTED;  // 16-byte bf16 pieces
-  // dw[N,K] = dy^T[N,M] * x[M,K]: contraction over M. A' = dy^T (dy stored [M][N]), B'[K rows][M] = x^T.
-  int k_chunk;
-  int splits = dw_split_plan(M, N, K, &k_chunk);
-  GemmArgs g{};
-  g.A = dy; g.B = x; g.C = workspace; g.lda = N; g.ldb = K; g.ldc = K;
-  g.M = N; g.N = K; g.K = (int)M; g.k_chunk = k_chunk;
-  g.bias = nullptr; g.R = nullptr; g.P = nullptr; g.C2 = nullptr; g.s16 = s16 & (XF_S16_A | XF_S16_B);
-  g.drop = xf_make_dropout(0.f, 0, 0);
-  int rc = dispatch_gemm<true, true, EPI_SPLITK, XF_S16_A, (XF_S16_A | XF_S16_B)>(g, splits, precision, st);
-  if (rc) return rc;
-  const int64_t n = (int64_t)N * K;
-  return launch_rowsum(dw, (const float*)workspace, splits, n, splits, st);
+  if (!dy || !x || !dw || !workspace) return XFMR_EINVAL;
+  const GemmKey k{kGemmDw, M, N, K, precision, s16, 1, 0};
+  const GemmPlan p = gemm_plan(k, gemm_switches_once());
+  const int room = (!p.rc_shape && workspace_bytes < xfmr_linear_bwd_dw_workspace(M, N, K)) ? XFMR_EWORKSPACE : XFMR_OK;
+  if (const int rc = plan_rc(p, xf_aligned16(dy) && xf_aligned16(x) && xf_aligned16(workspace), room)) return rc;
+  const XfDwItem one{dy, x, N, K, (float*)workspace, nullptr, nullptr};
+  if (const int rc = launch_tile(p, dw_args(one, M, p), st)) return rc;
+  return launch_rowsum(dw, (const float*)workspace, p.splits, (int64_t)N * K, p.splits, st);
 }
-
-size_t xf_linear_bwd_dw_slab_bytes(int64_t M, int32_t N, int32_t K) { return xfmr_linear_bwd_dw_workspace(M, N, K); }
 
 int xf_linear_bwd_dw_deferred(const void* dy, const void* x, int64_t M, int32_t N, int32_t K, int32_t precision,
                               uint32_t s16, float* slabs, float* bias_part, int* splits_out, hipStream_t st) {
-  if (!dy || !x || !slabs || !splits_out || M <= 0 || N <= 0 || K <= 0) return XFMR_EINVAL;
-  if ((K & 3) || (N & 3)) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(dy) || !xf_aligned16(x) || !xf_aligned16(slabs)) return XFMR_EALIGN;
-  if ((s16 & ~XF_AUX_GELU_GRAD) && precision != XFMR_PREC_BF16) return XFMR_EINVAL;
-  if ((s16 & (XF_S16_A | XF_S16_B | XF_S16_C | XF_S16_P)) && ((K & 7) || (N & 7))) return XFMR_EUNSUPPORTED;  // 16-byte bf16 pieces
-  // XFMR_EXP_SKIP_DW=1 (experiments only: upper bound of what a faster dW GEMM can give the step; gradients are garbage)
-  static const bool skip_ring = [] { const char* e = getenv("XFMR_EXP_SKIP_DW"); return e && *e == '1'; }();
-  {
-    const XfDwItem one{dy, x, N, K, slabs, bias_part, splits_out};
-    if (!skip_ring && xf_dw_ring_takes(&one, 1, M, precision, s16)) return xf_dw_ring_launch(&one, 1, M, st);  // dw_ring.hip
-  }
-  int k_chunk;
-  const int splits = dw_split_plan(M, N, K, &k_chunk);
-  GemmArgs g{};
-  g.A = dy; g.B = x; g.C = slabs; g.lda = N; g.ldb = K; g.ldc = K;
-  g.M = N; g.N = K; g.K = (int)M; g.k_chunk = k_chunk;
-  g.s16 = s16 & (XF_S16_A | XF_S16_B); g.bias_part = bias_part;
-  g.drop = xf_make_dropout(0.f, 0, 0);
-  *splits_out = splits;
-  // XFMR_EXP_SKIP_DW=1 (experiments only: upper bound of what a faster dW GEMM can give the step; gradients are garbage)
-  static const bool skip = [] { const char* e = getenv("XFMR_EXP_SKIP_DW"); return e && *e == '1'; }();
-  if (skip) return XFMR_OK;
-  return dispatch_gemm<true, true, EPI_SPLITK, XF_S16_A, (XF_S16_A | XF_S16_B)>(g, splits, precision, st);
+  if (!dy || !x || !slabs || !splits_out) return XFMR_EINVAL;
+  const GemmKey k{kGemmDwDeferred, M, N, K, precision, s16, 1, 0};
+  const GemmPlan p = gemm_plan(k, gemm_switches_once());
+  if (const int rc = plan_rc(p, xf_aligned16(dy) && xf_aligned16(x) && xf_aligned16(slabs))) return rc;
+  const XfDwItem one{dy, x, N, K, slabs, bias_part, splits_out};
+  if (p.family == kGemmRing) return xf_dw_ring_launch_plans(&one, &p, 1, M, st);  // dw_ring.hip
+  *splits_out = p.splits;
+  if (p.family == kGemmNone) return XFMR_OK;  // XFMR_EXP_SKIP_DW
+  return launch_tile(p, dw_args(one, M, p), st);
 }
 
-// internal (encoder.hip): the split-K weight-gradient GEMMs of up to FOUR Linears over the same M tokens in ONE launch
-// (gemm_group_kernel); anything but the bf16 production form falls back to one launch each. Results are those of
-// xf_linear_bwd_dw_deferred bit for bit (same tiles, same splits, same order inside each).
+// internal (encoder.hip): the split-K weight-gradient GEMMs of up to FOUR Linears over the same M tokens in ONE launch -- the
+// ring kernel when it takes every item, else gemm_group_kernel when every item is groupable, else one launch each. Results
+// are those of xf_linear_bwd_dw_deferred bit for bit (the same plan per item: same tiles, same slabs, same order inside each).
 int xf_linear_bwd_dw_group(const XfDwItem* items, int n, int64_t M, int32_t precision, uint32_t s16, hipStream_t st) {
-  constexpr uint32_t SAB = XF_S16_A | XF_S16_B;
   if (!items || n < 1 || n > 4) return XFMR_EINVAL;
-  if (xf_dw_ring_takes(items, n, M, precision, s16)) return xf_dw_ring_launch(items, n, M, st);  // dw_ring.hip
-  static const bool env_tiles = getenv("XFMR_DW_TILE") || getenv("XFMR_GEMM_TILE");
-  bool groupable = n > 1 && precision == XFMR_PREC_BF16 && (s16 & SAB) == SAB && !env_tiles && M > 0;
-  for (int i = 0; i < n && groupable; ++i) {
-    const XfDwItem& t = items[i];
-    groupable = t.dy && t.x && t.slabs && t.splits && t.N > 64 && t.K > 64 && !((t.N | t.K) & 7) && xf_aligned16(t.dy) &&
-                xf_aligned16(t.x) && xf_aligned16(t.slabs);
-  }
-  if (!groupable) {
+  GemmPlan p[4];
+  const auto all_of = [&](const GemmSwitches& sw, int family) {  // plans every item; true: pointers in order, all of `family`
+    bool all = true;
     for (int i = 0; i < n; ++i) {
       const XfDwItem& t = items[i];
-      const int rc = xf_linear_bwd_dw_deferred(t.dy, t.x, M, t.N, t.K, precision, s16, t.slabs, t.bias_part, t.splits, st);
-      if (rc != XFMR_OK) return rc;
+      p[i] = gemm_plan(GemmKey{kGemmDwGroup, M, t.N, t.K, precision, s16, n, 0}, sw);
+      all = all && p[i].family == family && t.dy && t.x && t.slabs && t.splits && xf_aligned16(t.dy) && xf_aligned16(t.x) &&
+            xf_aligned16(t.slabs);
     }
-    return XFMR_OK;
-  }
-  GemmGroup p{};
-  int64_t total = 0;
+    return all;
+  };
+  GemmSwitches sw = gemm_switches_once();
+  if (all_of(sw, kGemmRing)) return xf_dw_ring_launch_plans(items, p, n, M, st);  // dw_ring.hip
+  sw.dw_ring = 0;  // (the ring takes a launch whole or not at all)
+  if (all_of(sw, kGemmGroup)) return launch_group(items, p, n, M, st);
   for (int i = 0; i < n; ++i) {
     const XfDwItem& t = items[i];
-    int k_chunk;
-    const int splits = dw_split_plan(M, t.N, t.K, &k_chunk);
-    GemmArgs& g = p.g[i];
-    g.A = t.dy; g.B = t.x; g.C = t.slabs; g.lda = t.N; g.ldb = t.K; g.ldc = t.K;
-    g.M = t.N; g.N = t.K; g.K = (int)M; g.k_chunk = k_chunk;
-    g.s16 = SAB; g.bias_part = t.bias_part;
-    g.drop = xf_make_dropout(0.f, 0, 0);
-    g.nt_n = (t.K + 63) / 64;    // 128 x 64 tiles (launch_gemm_bk)
-    g.nt_m = (t.N + 127) / 128;
-    g.nt_z = splits;
-    const int64_t groups = splits > 1 ? (splits + 7) / 8 : (g.nt_m + 7) / 8;
-    const int64_t per = splits > 1 ? (int64_t)g.nt_n * g.nt_m : g.nt_n;
-    p.start[i] = (int)total;
-    total += groups * per * 8;
-    if (total > 0x7fffffffll) return XFMR_EUNSUPPORTED;
-    *t.splits = splits;
+    const int rc = xf_linear_bwd_dw_deferred(t.dy, t.x, M, t.N, t.K, precision, s16, t.slabs, t.bias_part, t.splits, st);
+    if (rc != XFMR_OK) return rc;
   }
-  for (int i = n; i <= 4; ++i) p.start[i] = (int)total;
-  hipLaunchKernelGGL((gemm_group_kernel<PrecBF16, 128, 64, 128, true, true, EPI_SPLITK, SAB>), dim3((unsigned)total),
-                     dim3(256), 0, st, p);
-  XF_LAUNCH_CHECK();
   return XFMR_OK;
 }
 

@@ -15,7 +15,79 @@ enum : uint32_t {
   XF_AUX_GELU_GRAD = 0x100u,
 };
 
+// ---- gemm.hip: the plan of one call of the GEMM family (linear forward / dX / dW, the LayerNorm-fused and the fused FFN
+// kernels): which kernel runs, with which tile, slabs, grid and LDS, as ONE pure function of the call's key and the
+// environment switches (tests/test_gemm_plan_host.py walks the table without a GPU).
+enum GemmOp : int32_t {
+  kGemmFwdBias = 0, kGemmFwdGelu, kGemmFwdDropRes,  // xf_linear_fwd_ex by epilogue
+  kGemmLnFwd, kGemmLnFwdRe, kGemmLnFwdReDrop,       // xf_linear_ln_fwd_ex / _re: residual loaded | re-derived | re-derived + dropout
+  kGemmDx, kGemmDxGelu, kGemmDxLnBwd,               // xf_linear_bwd_dx_ex (gelu_pre null | given), xf_linear_bwd_dx_lnbwd_ex
+  kGemmDw, kGemmDwDeferred, kGemmDwGroup,           // xf_linear_bwd_dw_ex | _deferred | one item of _group
+  kGemmFfnFwd, kGemmFfnFwdRe, kGemmFfnBwd,          // xf_ffn_fwd_fused_ex | _re, xf_ffn_bwd_dx_fused_ex (N = H, K = I)
+  kGemmOps
+};
+enum GemmFamily : int32_t {
+  kGemmNone = 0,  // nothing is launched: the call is refused (GemmPlan::rc), or XFMR_EXP_SKIP_DW
+  kGemmTile,      // gemm_kernel
+  kGemmGroup,     // gemm_group_kernel: this item's share of the launch
+  kGemmRing,      // dw_ring.hip dw_ring_kernel: this item's share of the launch
+  kGemmFfnFwdKernel, kGemmFfnBwdKernel,  // ffn_fwd_fused_kernel, ffn_bwd_dx_fused_kernel
+};
+struct GemmKey {  // in the entry points' own terms: M rows (tokens), N output and K input features of the Linear
+  GemmOp op;
+  int64_t M; int32_t N, K;
+  int32_t precision; uint32_t s16;  // the mask as the caller passes it
+  int32_t items;                    // kGemmDwGroup: weights in the launch (1 ... 4)
+  int32_t cus;                      // compute units of the device (the whole-row kernels' row map): the plan touches no device
+};
+// The environment, read in one place (gemm_switches). All but the last two once per process; XFMR_FFN_CHUNK and
+// XFMR_FFN_REG_STAGE on every call (the tests flip them inside one process).
+struct GemmSwitches {
+  int32_t tile_bm, tile_bn, tile_bk, tile_set;  // XFMR_GEMM_TILE="bm,bn,bk" (64|128, 64|128, 32|128); set at all
+  int32_t dw_bm, dw_bn, dw_tile_set;            // XFMR_DW_TILE="bm,bn": the 128 x 64 split-K tile
+  int32_t pad_lds;                              // XFMR_GEMM_PAD_LDS: dynamic LDS bytes of the tile kernel (occupancy experiments)
+  int32_t dw_maxsplit;                          // XFMR_DW_MAXSPLIT: 1 ... 256, default 128
+  int32_t row_tiles_short;                      // XFMR_ROW_TILES_SHORT: the two-region row map (measured, not the default)
+  int32_t skip_dw;                              // XFMR_EXP_SKIP_DW=1: the deferred dW launches nothing (gradients are garbage)
+  int32_t dw_ring;                              // XFMR_DW_RING: off only on '0'
+  int32_t dwr_tokens, dwr_minwg;                // XFMR_DWR_TOKENS >= 128 (3072), XFMR_DWR_MINWG >= 1 (64): the ring's slab plan
+  int32_t ffn_chunk;                            // XFMR_FFN_CHUNK: 64, anything else = 128
+  int32_t ffn_reg_stage;                        // XFMR_FFN_REG_STAGE: register-staged weight chunks in the fused FFN backward
+};
+struct GemmPlan {
+  int32_t rc_shape;  // the code of the checks an entry makes BEFORE it looks at its pointers' alignment
+  int32_t rc;        // what the call returns for this key when its pointers are in order
+  int32_t family, epi, precision; uint32_t s16;  // kernel family, epilogue id, policy and storage mask instantiated
+  int32_t bm, bn, bk;
+  int32_t splits, k_chunk;                        // weight gradients: slabs and tokens per slab
+  int32_t nt_n, nt_m, nt_z, nt_full, short_rows;  // GemmArgs' tile counts and row map
+  int32_t grid, block, lds;                       // grid x (group / ring: this item's workgroups), threads, dynamic LDS bytes
+  int32_t ffn_chunk, ffn_ring;                    // fused FFN: forward chunk width | backward LDS-DMA ring (0: register-staged)
+  int32_t records;                                // LayerNorm partial records written (*blocks_out)
+  const void* kernel;                             // kGemmTile: the gemm_kernel instantiation (gemm.hip tile_kernel)
+};
+GemmPlan gemm_plan(const GemmKey& k, const GemmSwitches& sw);
+const GemmSwitches& gemm_switches_once();  // the once-per-process switches (the two per-call ones at their defaults)
+GemmSwitches gemm_switches();              // ... with the two per-call ones as the environment has them now
+// dw_ring.hip's geometry, which the plan needs: stage depth and ring length are compile-time switches for A/B builds
+// (scripts/build_variant.sh; the measurements are with the kernel)
+#ifndef XF_DWR_RT
+#define XF_DWR_RT 64
+#endif
+#ifndef XF_DWR_NST
+#define XF_DWR_NST 4
+#endif
+constexpr int kDwRingTile = 128;                  // tile width in features, both ways
+constexpr uint64_t kDwRingOffsetLimit = 1ull << 32;  // the gather's byte offsets into an operand are 32-bit
+constexpr int kDwRingLds = 2 * XF_DWR_NST * XF_DWR_RT * kDwRingTile * 2;  // dy and x images of every stage, bf16: 128 KB
+
 extern "C" {
+// The plan and the switches as integers. out: family, epi, precision, s16, bm, bn, bk, splits, k_chunk, nt_n, nt_m, nt_z,
+// nt_full, short_rows, grid, block, lds, ffn_chunk, ffn_ring, records, then zeros (all zeros when refused); sw: the fields
+// of GemmSwitches in their order. Returns GemmPlan::rc; touches no device.
+int xf_gemm_plan(int32_t op, int64_t M, int32_t N, int32_t K, int32_t precision, uint32_t s16, int32_t items, int32_t cus,
+                 const int32_t sw[16], int32_t out[24]);
+void xf_gemm_switches(int32_t sw[16]);
 int xf_linear_fwd_ex(const void* x, const float* w, const float* bias, void* y, int64_t M, int32_t N, int32_t K,
                      int32_t epilogue, const float* residual, void* aux_out, float dropout_p, XfSeed seed,
                      uint32_t site, int32_t precision, uint32_t s16, hipStream_t st);
@@ -69,7 +141,8 @@ int xf_linear_bwd_dw_group(const XfDwItem* items, int n, int64_t M, int32_t prec
 int xf_dw_split_plan(int64_t M, int32_t N, int32_t K, int* k_chunk);
 // dw_ring.hip: the LDS-DMA ring form of the same GEMMs (same plan, same slab layout) for the shapes it takes
 bool xf_dw_ring_takes(const XfDwItem* items, int n, int64_t M, int32_t precision, uint32_t s16);
-int xf_dw_ring_launch(const XfDwItem* items, int n, int64_t M, hipStream_t st);
+int xf_dw_ring_launch(const XfDwItem* items, int n, int64_t M, hipStream_t st);  // plans for itself (the probes)
+int xf_dw_ring_launch_plans(const XfDwItem* items, const GemmPlan* plans, int n, int64_t M, hipStream_t st);
 // dst[c] = sum_r src[r * ld + c], r < rows, c < cols, for every segment, in one launch (deterministic order)
 struct XfReduceSeg { const float* src; float* dst; int rows; int cols; int ld; int pad; };
 int xf_multi_rowsum(const XfReduceSeg* segs, int nseg, hipStream_t st);
@@ -88,9 +161,6 @@ int xf_attn_bwd_ex(const void* qkv, const uint8_t* key_mask, const void* ctx, co
 // losses[14], stats[16]; counts = device {n_valid, n_query}; tot = 24 doubles of scratch
 int xf_loss_finalize(const double* blockpart, int nblocks, int rows_per_block, const int* counts, int mode,
                      int64_t n_rows, int64_t positions, float* losses, float* stats, double* tot, hipStream_t st);
-// d_lin (optional): the gradient of the Linear output feeding this LayerNorm (dropout-scaled dx), bf16 if lin16
-// d_gamma == d_beta == d_bias == nullptr defers the reduction of `partials` ([blocks][3][H], blocks returned in
-// *blocks_out) to the caller (xf_multi_rowsum)
 // Linear (+ bias, dropout, residual) with the LayerNorm that follows it applied in the GEMM epilogue (N == 128, bf16
 // policy): pre = the LayerNorm input (saved for the backward), y / y16 = the output, mean / rstd per row.
 int xf_linear_ln_fwd_ex(const void* x, const float* w, const float* bias, float* pre, int64_t M, int32_t N, int32_t K,
@@ -101,14 +171,14 @@ int xf_linear_ln_fwd_ex(const void* x, const float* w, const float* bias, float*
 // output is the gradient of a LayerNorm output applies that LayerNorm's backward in its epilogue. d_lin16 (bf16,
 // optional) = the dropout-scaled copy; partials[*blocks_out][3][128] = d gamma / d beta / d bias partial records.
 // out_dropout_p / out_site: dropout that was applied to the LayerNorm OUTPUT (the embedding LayerNorm).
-// number of 64-row M-tiles (one LayerNorm partial record each) the whole-row kernels run for M rows: >= (M + 63) / 64
-// (short last-round tiles: gemm.hip xf_plan_row_tiles)
-int xf_ln_row_tiles(int64_t M);
 int xf_linear_bwd_dx_lnbwd_ex(const void* dy, const float* w, int64_t M, int32_t N, int32_t K,
                               const float* residual_grad, const float* ln_x, const float* ln_mean, const float* ln_rstd,
                               const float* ln_gamma, float dropout_p, XfSeed seed, uint32_t site, float* dx,
                               void* d_lin16, float* partials, int* blocks_out, int32_t precision, uint32_t s16,
                               hipStream_t st, float out_dropout_p = 0.f, uint32_t out_site = 0);
+// number of 64-row M-tiles (one LayerNorm partial record each) the whole-row kernels run for M rows: >= (M + 63) / 64
+// (GemmPlan::records on this device; short last-round tiles: gemm.hip row_tiles)
+int xf_ln_row_tiles(int64_t M);
 // LayerNorm forward variants that also write a bf16 copy of the output (the operand of the GEMMs that consume it;
 // the fp32 output stays the residual stream). y16 / out16 may be null.
 int xf_layernorm_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y16, float* mean,
@@ -148,6 +218,9 @@ int xf_loss_plan(int64_t T, int32_t H, int64_t n_rows, int32_t train_head, int32
                  int32_t mode, int32_t precision, int32_t num_hard_negatives, uint32_t flags, int32_t has_d_tok,
                  int32_t has_table_bf16, int32_t cus, uint64_t switches, int32_t out[40]);
 uint64_t xf_loss_switches();
+// d_lin (optional): the gradient of the Linear output feeding this LayerNorm (dropout-scaled dx), bf16 if lin16
+// d_gamma == d_beta == d_bias == nullptr defers the reduction of `partials` ([blocks][3][H], blocks returned in
+// *blocks_out) to the caller (xf_multi_rowsum)
 int xf_layernorm_bwd_impl(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                           float* dx, void* d_lin, bool lin16, float* d_gamma, float* d_beta, float* d_bias,
                           int64_t rows, int32_t H, XfDropout drop_out, XfDropout drop_lin, void* partials,
