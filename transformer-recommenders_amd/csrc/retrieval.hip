@@ -3,19 +3,14 @@
 // The reference validates one user at a time: encode(history) -> LanceDB IVF_HNSW_PQ search over the item embeddings
 // with the history prefiltered out -> top_k ids -> seven torchmetrics retrieval metrics on a synthesised score vector
 // (xfmr_rec/trainer.py:186-211, 266-325; index.py:214-255; metrics.py:17-79). Here a batch of users is scored EXACTLY
-// against the whole table (the ANN's limit of full probing):
-//   topk_kernel     one workgroup per query: scores for every item (16 lanes per item, 16-byte pieces), the query's
-//                   history and the padding row masked out, the k-th largest score by a 4-pass radix select, ordered
-//                   compaction (ties: lower item index first), bitonic sort of the k survivors, best first
-//   topk_tiled_kernel + topk_merge_kernel  the same search for many queries at once (MFMA score tiles, streaming
-//                   top-k, no per-(query, item) workspace): see the comment above topk_tiled_kernel
-//   metrics_kernel  one thread per query: nDCG, MAP, AUROC, precision, recall, hit rate, MRR at k from the ranked
-//                   list and the user's target set, with torchmetrics' definitions for a strictly decreasing score
-//                   vector over [recommendations | missing targets] (metrics.py:66-79)
-//   metrics_sum_kernel + metrics_sum_final_kernel  the same per-row values and, in the same call, their fp64 sums over
-//                   the rows that count (xfmr_retrieval_metrics_sum: nothing of a validation pass is summed on the host)
-//   rank_prep_kernel + rank_tile_kernel + rank_finish_kernel  every target's exact rank over the whole catalogue
-//                   (xfmr_target_ranks), and rank_metrics_sum_kernel: the seven metrics at several cutoffs from those ranks
+// against the whole table (the ANN's limit of full probing): a scan for one query (xfmr_topk), score tiles on the matrix
+// cores for a user set (xfmr_topk_tiled), or every target's exact rank with no list at all (xfmr_target_ranks); the seven
+// metrics come from a ranked list or from the ranks. Each section below describes its kernels.
+// The contract between the paths: a target's rank is its place in the tiled list, the score the rank pre-pass reports is
+// the list's score bit for bit, and the rank metrics are the list metrics bit for bit. It holds because each piece is
+// written ONCE: the order (tt_better), the eligibility test (tt_finite), the score formula (rk_score), the query norm
+// (rk_query_sqnorm), the 32 x 32 score tile (tile_* and its scalar mirror rk_chain_dot), the sort (tt_sort) and the
+// metrics arithmetic (ms_*).
 // metric: cosine (reference default, index.py:47), dot, or l2; score = 1 - distance as index.py:248-251 appends it.
 #include "common.h"
 
@@ -23,7 +18,175 @@ namespace {
 
 constexpr int TOPK_MAX = 1024;
 constexpr int TOPK_MAX_H = 1024;
+constexpr int TT_Q = 32;   // queries per workgroup of a tile kernel (one 32-row MFMA tile)
+constexpr int TT_N = 128;  // items per tile (4 waves x 32)
+constexpr int TT_IDX_NONE = 0x7fffffff;  // "no item" in every (score, index) list; as a rank, XFMR_RANK_NONE
+static_assert(TT_IDX_NONE == XFMR_RANK_NONE, "a dead target's item and its rank are the same sentinel");
 
+// ---- shared pieces ------------------------------------------------------------------------------------------------
+// best first: score descending, then item index ascending (a total order over distinct items)
+__device__ __forceinline__ bool tt_better(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
+
+// the scores the tiled search can return and the rank path counts: neither infinity nor NaN
+__device__ __forceinline__ bool tt_finite(float s) { return s > -INFINITY && s < INFINITY; }
+
+// 1 - distance; rq = 1 / |q|, qq = |q|^2, rn = 1 / |e| (cosine), ee = |e|^2 (l2)
+__device__ __forceinline__ float rk_score(int metric, float dot, float rq, float qq, float rn, float ee) {
+  if (metric == XFMR_METRIC_COSINE) return dot * rq * rn;  // 1 - (1 - cos)
+  if (metric == XFMR_METRIC_DOT) return dot;                // 1 - (1 - dot)
+  return 1.f - (qq - 2.f * dot + ee);                       // 1 - |q - e|^2
+}
+
+__device__ __forceinline__ float rk_inv_norm(float qq) { return 1.f / fmaxf(sqrtf(qq), 1e-8f); }
+
+// |q|^2 by 8 threads per query (part = the thread's place among them); every thread of the aligned group gets the value
+__device__ __forceinline__ float rk_query_sqnorm(const float* qr, int H, int part) {
+  float qq = 0.f;
+  for (int h = 4 * part; h < H; h += 32) {
+    const float4 v = *reinterpret_cast<const float4*>(qr + h);
+    qq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, qq))));
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) qq += __shfl_xor(qq, o, 64);
+  return qq;
+}
+
+// Best-first bitonic sort of LISTS lists of len entries each (len a power of two) in LDS, by all 256 threads; ends on a
+// barrier. One list: no index division.
+template <int LISTS>
+__device__ __forceinline__ void tt_sort(float* S, int* I, int len) {
+  const int half = len >> 1;
+  for (int size = 2; size <= len; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int x = threadIdx.x; x < LISTS * half; x += 256) {
+        const int i = LISTS == 1 ? 0 : x / half, p = LISTS == 1 ? x : x % half;
+        const int e = 2 * p - (p & (stride - 1)), f = e + stride;
+        const bool up = (e & size) == 0;  // "up" blocks hold the better element first
+        float* s = S + i * len;
+        int* ix = I + i * len;
+        const float se = s[e], sf = s[f];
+        const int ie = ix[e], jf = ix[f];
+        if (tt_better(sf, jf, se, ie) == up) { s[e] = sf; s[f] = se; ix[e] = jf; ix[f] = ie; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// number of entries of the best-first list (s, ix)[0..n) that are better than (v, iv)
+__device__ __forceinline__ int tt_count_better(const float* s, const int* ix, int n, float v, int iv) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (tt_better(s[mid], ix[mid], v, iv)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// item `it` in the sorted list ex[lo..hi)
+__device__ __forceinline__ bool tt_excluded(const int64_t* ex, int64_t lo, int64_t hi, int it) {
+  const int64_t end = hi;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (ex[mid] < it) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < end && ex[lo] == it;
+}
+
+// ---- the 32 x 32 score tile of the tiled search and the rank path ---------------------------------------------------
+// A workgroup owns TT_Q queries and one slice of the catalogue; wave w scores the 32 items t0 + 32 w + (lane & 31) of
+// every TT_N-item tile against the 32 queries with v_mfma_f32_32x32x2_f32 -- exact f32, bit for bit a k-ordered fmaf
+// chain. Operands come straight from global memory, not through LDS: the 32 query rows are shared by the four waves (L1
+// hits), every item row is read by one wave once per query tile, and the f32 MFMA rate (64 FLOP/clk/SIMD) needs only
+// 16 B/clk per CU of item rows.
+struct ScoreArgs {  // what a score and a slice need: the head of both tile kernels' arguments
+  const float* q; const float* table; const float* rnorm; const float* sqnorm; int n_rows; int n_query;
+  const int64_t* excl; const int64_t* excl_off;  // CSR of excluded items per query, each row SORTED (may be null)
+  int H, metric, splits;
+  int64_t slice;  // items per slice, a multiple of TT_N
+};
+
+// Query prologue: thread group tid >> 3 gets |q|^2 of query q0 + (tid >> 3); rows past n_query give 0
+__device__ __forceinline__ float tile_query_sqnorm(const ScoreArgs& a, int q0) {
+  const int i = threadIdx.x >> 3;
+  const bool real = q0 + i < a.n_query;
+  const float qq = rk_query_sqnorm(a.q + (int64_t)(real ? q0 + i : 0) * a.H, a.H, threadIdx.x & 7);
+  return real ? qq : 0.f;
+}
+
+// the lane's query row (accumulator row block; rows past n_query read the last query and are masked by the epilogues)
+__device__ __forceinline__ const float* tile_query_ptr(const ScoreArgs& a, int q0, int lane) {
+  return a.q + (int64_t)min(q0 + (lane & 31), a.n_query - 1) * a.H + 4 * (lane >> 5);
+}
+
+// the lane's item (accumulator column) of the tile at t0: row 0 (padding) and rows past the slice are not ok and read row 0
+struct TileCol { bool ok; int j; const float* e; };
+__device__ __forceinline__ TileCol tile_col(const ScoreArgs& a, int64_t t0, int64_t hi, int w, int lane) {
+  const int64_t j64 = t0 + 32 * w + (lane & 31);
+  const bool ok = j64 >= 1 && j64 < hi;
+  const int j = ok ? (int)j64 : 0;
+  return {ok, j, a.table + (int64_t)j * a.H + 4 * (lane >> 5)};
+}
+
+// k-step order, tile and mirror alike: chunk c = 0, 8, ... takes four MFMAs, one per float4 component; in each, lane
+// half 0 supplies dim c + component and lane half 1 dim c + 4 + component (zeros past H), and k = 0 is added before
+// k = 1. So a dot product is the fmaf chain over dims c + {0, 4, 1, 5, 2, 6, 3, 7}. Change both or neither.
+__device__ __forceinline__ f32x16 tile_dots(const float* qa, const float* eb, int H, int h2) {
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll 4
+  for (int c = 0; c < H; c += 8, qa += 8, eb += 8) {  // (bumped pointers: the lane half's offset stays folded in them)
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
+    if (c + 4 * h2 < H) {
+      x = *reinterpret_cast<const float4*>(qa);
+      y = *reinterpret_cast<const float4*>(eb);
+    }
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, y.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, y.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, y.w, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// the scalar mirror: one (query, item) dot product in that order
+__device__ __forceinline__ float rk_chain_dot(const float* sQ, const float* e, int H) {
+  float acc = 0.f;
+  for (int c = 0; c < H; c += 8) {
+    const float4 x0 = *reinterpret_cast<const float4*>(sQ + c), y0 = *reinterpret_cast<const float4*>(e + c);
+    float4 x1 = make_float4(0.f, 0.f, 0.f, 0.f), y1 = x1;
+    if (c + 4 < H) {
+      x1 = *reinterpret_cast<const float4*>(sQ + c + 4);
+      y1 = *reinterpret_cast<const float4*>(e + c + 4);
+    }
+    acc = fmaf(x0.x, y0.x, acc); acc = fmaf(x1.x, y1.x, acc);
+    acc = fmaf(x0.y, y0.y, acc); acc = fmaf(x1.y, y1.y, acc);
+    acc = fmaf(x0.z, y0.z, acc); acc = fmaf(x1.z, y1.z, acc);
+    acc = fmaf(x0.w, y0.w, acc); acc = fmaf(x1.w, y1.w, acc);
+  }
+  return acc;
+}
+
+// an item's own term of the score, fetched when ok
+struct ItemTerm { float rn, ee; };
+__device__ __forceinline__ ItemTerm rk_item_term(const ScoreArgs& a, int it, bool ok) {
+  ItemTerm t = {0.f, 0.f};
+  if (ok) {
+    if (a.metric == XFMR_METRIC_COSINE) t.rn = a.rnorm[it];
+    else if (a.metric == XFMR_METRIC_L2) t.ee = a.sqnorm[it];
+  }
+  return t;
+}
+
+// ---- scan top-k (xfmr_topk) -------------------------------------------------------------------------------------------
+// One workgroup per query: scores for every item (16 lanes per item, 16-byte pieces) into an n_query x n_rows
+// workspace, the query's history and the padding row masked out, the k-th largest score by a 4-pass radix select,
+// ordered compaction (ties: lower item index first), tt_sort of the k survivors. The right kernel for ONE query (a
+// single query would fill one row of a 32-row MFMA tile) and the wrong one for a user set (6 040 users x a 6 MB table =
+// 36 GB of table reads). Its scores differ from the tile's in summation order only.
 struct TopkArgs {
   const float* q; const float* table; const float* rnorm; int64_t n_rows;
   const int64_t* excl; const int64_t* excl_off;  // CSR of excluded item indices per query (may be null)
@@ -36,6 +199,10 @@ __device__ __forceinline__ unsigned key_of(float f) {
   const unsigned b = __float_as_uint(f);
   return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
+
+// The scan admits a +inf score and rejects only -inf (its own mask) and NaN, where tt_finite rejects all three: that is
+// this entry's behaviour since its first version and stays.
+__device__ __forceinline__ bool scan_admits(float s) { return s > -INFINITY; }
 
 __global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
   __shared__ __attribute__((aligned(16))) float sQ[TOPK_MAX_H];
@@ -58,7 +225,7 @@ __global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
   if (lane == 0) sh[w] = __float_as_int(qq);
   __syncthreads();
   qq = __int_as_float(sh[0]) + __int_as_float(sh[1]) + __int_as_float(sh[2]) + __int_as_float(sh[3]);
-  const float rq = 1.f / fmaxf(sqrtf(qq), 1e-8f);
+  const float rq = rk_inv_norm(qq);
   __syncthreads();
   // ---- scores ------------------------------------------------------------------------------------------------
   {
@@ -78,11 +245,8 @@ __global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
         ee += __shfl_xor(ee, o, 64);
       }
       if (j == 0) {
-        float s;
-        if (a.metric == XFMR_METRIC_COSINE) s = dot * rq * a.rnorm[it];  // 1 - (1 - cos)
-        else if (a.metric == XFMR_METRIC_DOT) s = dot;                   // 1 - (1 - dot)
-        else s = 1.f - (qq - 2.f * dot + ee);                            // 1 - |q - e|^2
-        sc[it] = it == 0 ? -INFINITY : s;                                // row 0 is the padding item
+        const float rn = a.metric == XFMR_METRIC_COSINE ? a.rnorm[it] : 0.f;
+        sc[it] = it == 0 ? -INFINITY : rk_score(a.metric, dot, rq, qq, rn, ee);  // row 0 is the padding item
       }
     }
   }
@@ -94,12 +258,12 @@ __global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
     }
   }
   __syncthreads();
-  // ---- k-th largest finite score: 4-pass radix select ------------------------------------------------------------
+  // ---- k-th largest admitted score: 4-pass radix select -----------------------------------------------------------
   if (tid == 0) sh[3] = 0;
   __syncthreads();
   {
     int n = 0;
-    for (int64_t it = tid; it < V; it += 256) n += sc[it] > -INFINITY ? 1 : 0;
+    for (int64_t it = tid; it < V; it += 256) n += scan_admits(sc[it]) ? 1 : 0;
     if (n) atomicAdd(&sh[3], n);
   }
   __syncthreads();
@@ -116,7 +280,7 @@ __global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
       const int shift = 8 * p;
       for (int64_t it = tid; it < V; it += 256) {
         const float v = sc[it];
-        if (!(v > -INFINITY)) continue;
+        if (!scan_admits(v)) continue;
         const unsigned key = key_of(v);
         if (p == 3 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(key >> shift) & 255u], 1u);
       }
@@ -145,7 +309,7 @@ __global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
     float v = -INFINITY;
     if (it < V) {
       v = sc[it];
-      if (v > -INFINITY) {
+      if (scan_admits(v)) {
         if (avail <= a.k) gt = true;
         else {
           const unsigned key = key_of(v);
@@ -176,264 +340,51 @@ __global__ __launch_bounds__(256) void topk_kernel(TopkArgs a) {
     }
     __syncthreads();
   }
-  // ---- bitonic sort, best first (score descending, then item index ascending) -------------------------------------
+  // ---- the survivors, best first ------------------------------------------------------------------------------------
   int np2 = 1;
   while (np2 < k) np2 <<= 1;
-  for (int i = k + tid; i < np2; i += 256) { sScore[i] = -INFINITY; sIdx[i] = 0x7fffffff; }
+  for (int i = k + tid; i < np2; i += 256) { sScore[i] = -INFINITY; sIdx[i] = TT_IDX_NONE; }
   __syncthreads();
-  for (int size = 2; size <= np2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < np2; i += 256) {
-        const int j = i ^ stride;
-        if (j > i) {
-          const bool up = (i & size) == 0;  // "up" blocks hold the better elements first
-          const float si = sScore[i], sj = sScore[j];
-          const int ii = sIdx[i], ij = sIdx[j];
-          const bool i_better = si > sj || (si == sj && ii < ij);
-          if (i_better != up) { sScore[i] = sj; sScore[j] = si; sIdx[i] = ij; sIdx[j] = ii; }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  tt_sort<1>(sScore, sIdx, np2);
   for (int i = tid; i < a.k; i += 256) {
     a.out_idx[qi * a.k + i] = i < k ? (int64_t)sIdx[i] : -1;  // fewer than k candidates: padded like metrics.py:61-64
     a.out_score[qi * a.k + i] = i < k ? sScore[i] : -INFINITY;
   }
 }
 
-// One query's seven metrics: rec (B,k) ranked item indices (-1 = padding), targets CSR; v = ndcg, map, auroc, precision,
-// recall, hit, mrr. Returns false (v all zero) when the user has no target (the reference returns {} for it,
-// metrics.py:58-59). metrics_kernel and metrics_sum_kernel both call it: their per-row values are the same bits.
-__device__ __forceinline__ bool metrics_row(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off, int64_t b, int k,
-                                            int top_k, float v[7]) {
-  const int64_t* t = tgt + tgt_off[b];
-  const int nt_raw = (int)(tgt_off[b + 1] - tgt_off[b]);
-  for (int i = 0; i < 7; ++i) v[i] = 0.f;
-  // distinct targets (target_ids = set(target_ids), metrics.py:66)
-  int nt = 0;
-  for (int i = 0; i < nt_raw; ++i) {
-    bool dup = false;
-    for (int j = 0; j < i; ++j) dup |= t[j] == t[i];
-    nt += dup ? 0 : 1;
-  }
-  if (nt == 0) return false;
-  const int64_t* r = rec + b * k;
-  // the list torchmetrics sees: max(len(rec), top_k) slots of recommendations (padding never matches a target), then
-  // the missing targets. Every metric below only looks at the first top_k slots (+ the number of targets).
-  const int K = top_k;
-  float dcg = 0.f, ap_sum = 0.f, rr = 0.f;
-  int hits = 0, pairs = 0, neg_seen = 0;
-  for (int i = 0; i < K; ++i) {
-    bool rel = false;
-    if (i < k && r[i] >= 0) {
-      for (int j = 0; j < nt_raw; ++j) rel |= t[j] == r[i];
-    }
-    if (rel) {
-      ++hits;
-      dcg += 1.f / log2f((float)i + 2.f);
-      ap_sum += (float)hits / (float)(i + 1);
-      if (rr == 0.f) rr = 1.f / (float)(i + 1);
-    } else {
-      ++neg_seen;
-      pairs += hits;  // each earlier positive outranks this negative
-    }
-  }
-  float idcg = 0.f;
-  for (int i = 0; i < (nt < K ? nt : K); ++i) idcg += 1.f / log2f((float)i + 2.f);
-  v[0] = idcg > 0.f ? dcg / idcg : 0.f;
-  v[1] = hits > 0 ? ap_sum / (float)hits : 0.f;
-  v[2] = (hits > 0 && neg_seen > 0) ? (float)pairs / ((float)hits * (float)neg_seen) : 0.f;
-  v[3] = (float)hits / (float)K;
-  v[4] = (float)hits / (float)nt;
-  v[5] = hits > 0 ? 1.f : 0.f;
-  v[6] = rr;
-  return true;
-}
-
-// one thread per query: out (B,7), valid[b] = 0 when the user has no target
-__global__ void metrics_kernel(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off, int B, int k, int top_k,
-                               float* out, uint8_t* valid) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  float v[7];
-  valid[b] = metrics_row(rec, tgt, tgt_off, b, k, top_k, v);
-  float* o = out + (int64_t)b * 7;
-  for (int i = 0; i < 7; ++i) o[i] = v[i];
-}
-
-// ---- the metrics and their sums in one call (xfmr_retrieval_metrics_sum) ---------------------------------------------
-// metrics_sum_kernel: 256-row workgroups, one row per lane. The seven values and the count of the rows that are valid and
-// used go to fp64 (lanes past n_query and rows left out: exact zeros), are added across the wave by xor shuffles (a fixed
-// tree), across the four waves through LDS in a fixed order, and leave as ONE 8-double record per workgroup.
-// metrics_sum_final_kernel: one workgroup adds the records in index order (lane t takes records t, t + 256, ...) and
-// finishes with the same tree. No atomics, no dependence on which workgroup finishes first: the same input gives the same
-// eight doubles on every launch.
-constexpr int MS_ROWS = 256;
-constexpr int MS_VALS = 8;  // XFMR_NUM_RM sums + the number of rows
-
-__device__ __forceinline__ void ms_block_sum(double acc[MS_VALS], double (*sP)[MS_VALS], double* dst) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-#pragma unroll
-  for (int i = 0; i < MS_VALS; ++i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[i] += __shfl_xor(acc[i], o, 64);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < MS_VALS; ++i) sP[w][i] = acc[i];
-  }
-  __syncthreads();
-  if (tid < MS_VALS) dst[tid] = (sP[0][tid] + sP[1][tid]) + (sP[2][tid] + sP[3][tid]);
-}
-
-__global__ __launch_bounds__(MS_ROWS) void metrics_sum_kernel(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off,
-                                                              const uint8_t* use, int64_t B, int k, int top_k, float* out,
-                                                              uint8_t* valid, double* partial) {
-  __shared__ double sP[MS_ROWS / 64][MS_VALS];
-  const int64_t b = (int64_t)blockIdx.x * MS_ROWS + threadIdx.x;
-  double acc[MS_VALS];
-#pragma unroll
-  for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
-  if (b < B) {
-    float v[7];
-    const bool ok = metrics_row(rec, tgt, tgt_off, b, k, top_k, v);
-    if (out) {
-      for (int i = 0; i < 7; ++i) out[b * 7 + i] = v[i];
-    }
-    if (valid) valid[b] = ok;
-    if (ok && (!use || use[b])) {
-#pragma unroll
-      for (int i = 0; i < 7; ++i) acc[i] = (double)v[i];
-      acc[7] = 1.0;
-    }
-  }
-  ms_block_sum(acc, sP, partial + (int64_t)blockIdx.x * MS_VALS);
-}
-
-__global__ __launch_bounds__(MS_ROWS) void metrics_sum_final_kernel(const double* partial, int64_t n_partial, double* sums) {
-  __shared__ double sP[MS_ROWS / 64][MS_VALS];
-  double acc[MS_VALS];
-#pragma unroll
-  for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
-  for (int64_t p = threadIdx.x; p < n_partial; p += MS_ROWS) {
-#pragma unroll
-    for (int i = 0; i < MS_VALS; ++i) acc[i] += partial[p * MS_VALS + i];
-  }
-  ms_block_sum(acc, sP, sums);
-}
-
-
-// ---- tiled top-k: score tiles on the matrix cores and a streaming top-k (xfmr_topk_tiled) --------------------------
-// topk_kernel above is one workgroup per query: every query re-reads the whole table through VALU dot products and
-// keeps an n_query x n_rows score workspace. That is the right kernel for ONE query (a single query spread over a whole
-// workgroup; here it would fill one row of a 32-row MFMA tile) and the wrong one for a whole user set (6 040 users x a
-// 6 MB table = 36 GB of table reads). topk_tiled_kernel instead:
-//   - a workgroup owns TT_Q = 32 queries and one slice of the catalogue; its four waves score 32 x 32 blocks of
-//     (query, item) with v_mfma_f32_32x32x2_f32 -- exact f32, bit for bit a k-ordered fmaf chain, so the scores differ
-//     from topk_kernel's only in summation order. 32 queries rather than 64 because each query's candidate list and
-//     running top-k (double-buffered) live in LDS: 96 KB at k = 128. Operands are read straight from global memory,
-//     not staged through LDS: the 32 query rows are shared by the four waves (L1 hits), every item row is read by one
-//     wave once per query tile, and the f32 MFMA rate (64 FLOP/clk/SIMD) needs only 16 B/clk per CU of item rows.
-//   - the epilogue applies topk_kernel's formulas, masks row 0, rows past the slice and non-finite scores, and keeps a
-//     per-query threshold (the current k-th best, ties broken by the lower item index). Only scores that beat it are
-//     checked against the query's SORTED exclusion list (binary search) and appended to an LDS candidate list; when a
-//     list fills, or at the end of the slice, the candidates are sorted and merged into the running top-k. A tile
-//     whose candidates overflowed a list is re-offered after the merge (against the new threshold).
-//   - grid = (query tiles, slices), slices chosen so that the grid covers the chip; topk_merge_kernel then merges each
-//     query's per-slice lists into the final sorted k. Scratch: n_query x slices x k (score, index) pairs, no
-//     per-(query, item) workspace. No float atomics: the candidate order inside a list depends on LDS atomics, the
-//     result does not (every list is sorted by (score desc, index asc), a total order), so runs are bit-identical.
-constexpr int TT_Q = 32;         // queries per workgroup (one 32-row MFMA tile)
-constexpr int TT_N = 128;        // items per tile (4 waves x 32)
-constexpr int TT_C = 128;        // candidate list per query (a power of two: bitonic sort)
+// ---- tiled top-k: score tiles and a streaming top-k (xfmr_topk_tiled) ------------------------------------------------
+// topk_tiled_kernel: per score tile, the epilogue masks row 0, rows past the slice and scores that are not tt_finite,
+// and keeps a per-query threshold (the current k-th best). Only scores that beat it are checked against the query's
+// exclusion list (binary search) and appended to an LDS candidate list; when a list fills, or at the end of the slice,
+// the candidates are sorted and merged into the running top-k. A tile whose candidates overflowed a list is re-offered
+// after the merge (against the new threshold). 32 queries per workgroup rather than 64 because each query's candidate
+// list and running top-k (double-buffered) live in LDS: 96 KB at k = 128.
+// grid = (query tiles, slices), slices chosen so that the grid covers the chip (tiled_plan); topk_merge_kernel then
+// merges each query's per-slice lists into the final sorted k. Scratch: n_query x slices x k (score, index) pairs, no
+// per-(query, item) workspace. No float atomics: the candidate order inside a list depends on LDS atomics, the result
+// does not (every list is sorted by tt_better), so runs are bit-identical.
+constexpr int TT_C = 128;        // candidate list per query (a power of two: tt_sort)
 constexpr int TT_KMAX = 128;
 constexpr int TT_MAX_SPLITS = 16;
 constexpr int TT_TARGET_WG = 512;  // 256 CUs x 2 resident workgroups
-constexpr int TT_IDX_NONE = 0x7fffffff;
 
-struct TiledPlan { int splits; int64_t slice; };
-
-static TiledPlan tiled_plan(int64_t n_query, int64_t n_rows) {
-  const int64_t qtiles = (n_query + TT_Q - 1) / TT_Q;
-  const int64_t itiles = (n_rows + TT_N - 1) / TT_N;
-  int64_t s = (TT_TARGET_WG + qtiles - 1) / qtiles;
-  if (s > TT_MAX_SPLITS) s = TT_MAX_SPLITS;
-  if (s > itiles) s = itiles;
-  if (s < 1) s = 1;
-  TiledPlan p;
-  p.slice = ((itiles + s - 1) / s) * TT_N;
-  p.splits = (int)((n_rows + p.slice - 1) / p.slice);
-  return p;
-}
-
-static int tiled_kp(int k) {
-  int kp = 1;
-  while (kp < k) kp <<= 1;
-  return kp;
-}
-
-static size_t tiled_lds_bytes(int kp) {
-  return (size_t)TT_Q * TT_C * 8 + (size_t)2 * TT_Q * kp * 8;
-}
-
-struct TiledArgs {
-  const float* q; const float* table; const float* rnorm; const float* sqnorm; int n_rows; int n_query;
-  const int64_t* excl; const int64_t* excl_off;
+struct TiledArgs : ScoreArgs {
   float* ws_score; int* ws_idx;  // [n_query][splits][k]
-  int H, k, kp, metric, splits;
-  int64_t slice;  // items per slice, a multiple of TT_N
+  int k, kp;
 };
 
-__device__ __forceinline__ bool tt_better(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
-
-// number of entries of the best-first list (s, ix)[0..n) that are better than (v, iv)
-__device__ __forceinline__ int tt_count_better(const float* s, const int* ix, int n, float v, int iv) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (tt_better(s[mid], ix[mid], v, iv)) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// item `it` in the sorted list ex[lo..hi)
-__device__ __forceinline__ bool tt_excluded(const int64_t* ex, int64_t lo, int64_t hi, int it) {
-  const int64_t end = hi;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ex[mid] < it) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < end && ex[lo] == it;
-}
-
 // Sorts every query's candidates and merges them into its running list (buffer `cur` -> 1 - cur); new thresholds.
-// Called by all threads of the workgroup; returns the new buffer index.
-__device__ int tt_merge(const TiledArgs& a, float* cS, int* cI, float* lS, int* lI, int cur, int* cnt, float* thrS,
-                        int* thrI, int* flag) {
-  const int tid = threadIdx.x, kp = a.kp;
+// Called by all threads of the workgroup; returns the new buffer index. k and kp by value: a reference to the kernel's
+// arguments would escape wherever the merge is not inlined, and the tile loop's global loads would become flat ones.
+__device__ int tt_merge(int k, int kp, float* cS, int* cI, float* lS, int* lI, int cur, int* cnt, float* thrS, int* thrI,
+                        int* flag) {
+  const int tid = threadIdx.x;
   for (int x = tid; x < TT_Q * TT_C; x += 256) {
     const int i = x / TT_C, e = x % TT_C;
     if (e >= min(cnt[i], TT_C)) { cS[x] = -INFINITY; cI[x] = TT_IDX_NONE; }
   }
   __syncthreads();
-  for (int size = 2; size <= TT_C; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int x = tid; x < TT_Q * TT_C / 2; x += 256) {
-        const int i = x / (TT_C / 2), p = x % (TT_C / 2);
-        const int e = 2 * p - (p & (stride - 1)), f = e + stride;
-        const bool up = (e & size) == 0;  // "up" blocks hold the better element first
-        float* s = cS + i * TT_C;
-        int* ix = cI + i * TT_C;
-        const float se = s[e], sf = s[f];
-        const int ie = ix[e], jf = ix[f];
-        if (tt_better(sf, jf, se, ie) == up) { s[e] = sf; s[f] = se; ix[e] = jf; ix[f] = ie; }
-      }
-      __syncthreads();
-    }
-  }
+  tt_sort<TT_Q>(cS, cI, TT_C);
   // merge path: rank of an entry = its place in its own list + the entries of the other list that are better
   const int nxt = 1 - cur;
   for (int x = tid; x < TT_Q * (kp + TT_C); x += 256) {
@@ -449,8 +400,8 @@ __device__ int tt_merge(const TiledArgs& a, float* cS, int* cI, float* lS, int* 
   }
   __syncthreads();
   if (tid < TT_Q) {
-    thrS[tid] = lS[(nxt * TT_Q + tid) * kp + a.k - 1];
-    thrI[tid] = lI[(nxt * TT_Q + tid) * kp + a.k - 1];
+    thrS[tid] = lS[(nxt * TT_Q + tid) * kp + k - 1];
+    thrI[tid] = lI[(nxt * TT_Q + tid) * kp + k - 1];
     cnt[tid] = 0;
   }
   if (tid == 0) *flag = 0;
@@ -467,77 +418,38 @@ __global__ __launch_bounds__(256) void topk_tiled_kernel(TiledArgs a) {
   float* lS = reinterpret_cast<float*>(cI + TT_Q * TT_C);
   int* lI = reinterpret_cast<int*>(lS + 2 * TT_Q * a.kp);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int H = a.H;
   const int q0 = blockIdx.x * TT_Q;
   const int split = blockIdx.y;
   const int64_t lo = split * a.slice;
   const int64_t hi = lo + a.slice < a.n_rows ? lo + a.slice : a.n_rows;
-  // ---- query norms: 8 threads per query ------------------------------------------------------------------------
-  {
-    const int i = tid >> 3, part = tid & 7;
-    float qq = 0.f;
-    if (q0 + i < a.n_query) {
-      const float* qr = a.q + (int64_t)(q0 + i) * H;
-      for (int h = 4 * part; h < H; h += 32) {
-        const float4 v = *reinterpret_cast<const float4*>(qr + h);
-        qq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, qq))));
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) qq += __shfl_xor(qq, o, 64);
-    if (part == 0) {
-      sQQ[i] = qq;
-      sRQ[i] = 1.f / fmaxf(sqrtf(qq), 1e-8f);
-      thrS[i] = -INFINITY;
-      thrI[i] = TT_IDX_NONE;
-      cnt[i] = 0;
-    }
+  const float qq = tile_query_sqnorm(a, q0);
+  if ((tid & 7) == 0) {
+    const int i = tid >> 3;
+    sQQ[i] = qq;
+    sRQ[i] = rk_inv_norm(qq);
+    thrS[i] = -INFINITY;
+    thrI[i] = TT_IDX_NONE;
+    cnt[i] = 0;
   }
   for (int x = tid; x < TT_Q * a.kp; x += 256) { lS[x] = -INFINITY; lI[x] = TT_IDX_NONE; }
   if (tid == 0) flag = 0;
   __syncthreads();
   int cur = 0;
-  const int h2 = lane >> 5;
-  const float* qa = a.q + (int64_t)min(q0 + (lane & 31), a.n_query - 1) * H + 4 * h2;
+  const float* qa = tile_query_ptr(a, q0, lane);
   for (int64_t t0 = lo; t0 < hi; t0 += TT_N) {
-    const int64_t j64 = t0 + 32 * w + (lane & 31);  // this lane's item (accumulator column)
-    const bool jok = j64 >= 1 && j64 < hi;
-    const int j = jok ? (int)j64 : 0;
-    const float* eb = a.table + (int64_t)j * H + 4 * h2;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // k-step order: dims 8c + 4h2 + {0..3} -- lane half h2 supplies k = h2 of each MFMA, both operands alike
-#pragma unroll 4
-    for (int c = 0; c < H; c += 8) {
-      float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
-      if (c + 4 * h2 < H) {
-        x = *reinterpret_cast<const float4*>(qa + c);
-        y = *reinterpret_cast<const float4*>(eb + c);
-      }
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, y.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, y.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, y.w, acc, 0, 0, 0);
-    }
+    const TileCol col = tile_col(a, t0, hi, w, lane);
+    const int j = col.j;
+    const f32x16 acc = tile_dots(qa, col.e, a.H, lane >> 5);
     // ---- epilogue: scores, masks, threshold, candidates ------------------------------------------------------------
-    float rn = 0.f, ee = 0.f;
-    if (jok) {
-      if (a.metric == XFMR_METRIC_COSINE) rn = a.rnorm[j];
-      else if (a.metric == XFMR_METRIC_L2) ee = a.sqnorm[j];
-    }
+    const ItemTerm term = rk_item_term(a, j, col.ok);
     float sc[16];
     unsigned pending = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int i = xf_acc_row(r, lane);
-      const float dot = acc[r];
-      float s;
-      if (a.metric == XFMR_METRIC_COSINE) s = dot * sRQ[i] * rn;
-      else if (a.metric == XFMR_METRIC_DOT) s = dot;
-      else s = 1.f - (sQQ[i] - 2.f * dot + ee);
+      const float s = rk_score(a.metric, acc[r], sRQ[i], sQQ[i], term.rn, term.ee);
       sc[r] = s;
-      if (jok && q0 + i < a.n_query && s > -INFINITY && s < INFINITY) pending |= 1u << r;
+      if (col.ok && q0 + i < a.n_query && tt_finite(s)) pending |= 1u << r;
     }
     while (true) {
 #pragma unroll
@@ -556,10 +468,10 @@ __global__ __launch_bounds__(256) void topk_tiled_kernel(TiledArgs a) {
       __syncthreads();
       if (!flag) break;
       __syncthreads();
-      cur = tt_merge(a, cS, cI, lS, lI, cur, cnt, thrS, thrI, &flag);
+      cur = tt_merge(a.k, a.kp, cS, cI, lS, lI, cur, cnt, thrS, thrI, &flag);
     }
   }
-  cur = tt_merge(a, cS, cI, lS, lI, cur, cnt, thrS, thrI, &flag);
+  cur = tt_merge(a.k, a.kp, cS, cI, lS, lI, cur, cnt, thrS, thrI, &flag);
   for (int x = tid; x < TT_Q * a.k; x += 256) {
     const int i = x / a.k, e = x % a.k;
     if (q0 + i >= a.n_query) continue;
@@ -569,7 +481,7 @@ __global__ __launch_bounds__(256) void topk_tiled_kernel(TiledArgs a) {
   }
 }
 
-// one workgroup per query: the query's splits x k (score, index) pairs -> bitonic sort -> the best k
+// one workgroup per query: the query's splits x k (score, index) pairs -> tt_sort -> the best k
 constexpr int TT_MERGE_MAX = TT_MAX_SPLITS * TT_KMAX;
 __global__ __launch_bounds__(256) void topk_merge_kernel(const float* ws_score, const int* ws_idx, int splits, int k,
                                                          int64_t* out_idx, float* out_score) {
@@ -585,18 +497,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* ws_score, 
     else { sS[x] = -INFINITY; sI[x] = TT_IDX_NONE; }
   }
   __syncthreads();
-  for (int size = 2; size <= np2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int p = tid; p < np2 / 2; p += 256) {
-        const int e = 2 * p - (p & (stride - 1)), f = e + stride;
-        const bool up = (e & size) == 0;
-        const float se = sS[e], sf = sS[f];
-        const int ie = sI[e], jf = sI[f];
-        if (tt_better(sf, jf, se, ie) == up) { sS[e] = sf; sS[f] = se; sI[e] = jf; sI[f] = ie; }
-      }
-      __syncthreads();
-    }
-  }
+  tt_sort<1>(sS, sI, np2);
   for (int e = tid; e < k; e += 256) {
     const bool real = sI[e] != TT_IDX_NONE;  // (only finite scores ever enter a list)
     out_idx[qi * k + e] = real ? (int64_t)sI[e] : -1;
@@ -618,36 +519,32 @@ __global__ __launch_bounds__(256) void table_sqnorm_kernel(const float* table, f
   if (lane == 0) out[row] = s;
 }
 
-// ---- full-catalogue target ranks (xfmr_target_ranks) and the metrics written from ranks (xfmr_rank_metrics_sum) ------
+// ---- full-catalogue target ranks (xfmr_target_ranks) -------------------------------------------------------------------
 // Every one of the seven metrics is a function of the ranks of a row's distinct targets among the eligible items and of
 // the number of distinct targets: no ranked list is needed, so no cutoff limit either. An item is ELIGIBLE for a query
-// when it is in [1, n_rows), not in the query's exclusion list and its score is finite (what topk_tiled_kernel can
+// when it is in [1, n_rows), not in the query's exclusion list and its score is tt_finite (what topk_tiled_kernel can
 // return); rank(t) = 1 + the eligible items that are tt_better than t. Three launches:
-//   rank_prep_kernel    one workgroup per query. The scores of the query's targets by the k-ordered fmaf chain that
-//                       the f32 MFMA equals bit for bit (dims 8c + {0,4,1,5,2,6,3,7}) and topk_tiled_kernel's formulas;
-//                       the best-first order of the targets (a count per entry, ties between repeats by entry order;
-//                       targets that are not eligible go last and are "dead"); and a histogram of the query's distinct,
-//                       in-range excluded items with a finite score, binned by how many live targets beat them.
-//   rank_tile_kernel    topk_tiled_kernel's grid and MFMA loop. The epilogue masks row 0, rows past the slice and
-//                       non-finite scores and bins every remaining (query, item) by b = the live targets of the query that
-//                       beat the item (one comparison against the worst target: most items end there; else a binary
-//                       search over the sorted targets in LDS) with an integer LDS atomic. No exclusion lookup: excluded
-//                       items are counted in here and taken out by the prep histogram. RK_T live targets per pass; a
-//                       tile whose rows have more passes over its slice again for the next RK_T.
+//   rank_prep_kernel    one workgroup per query. The scores of the query's targets (rk_item_score); the best-first
+//                       order of the targets (a count per entry, ties between repeats by entry order; targets that
+//                       are not eligible go last and are "dead"); and a histogram of the query's distinct, in-range
+//                       excluded items with a finite score, binned by how many live targets beat them.
+//   rank_tile_kernel    topk_tiled_kernel's grid and score tile. The epilogue bins every unmasked (query, item) by b =
+//                       the live targets of the query that beat the item (one comparison against the worst target:
+//                       most items end there; else a binary search over the sorted targets in LDS) with an integer
+//                       LDS atomic. No exclusion lookup: excluded items are counted in here and taken out by the prep
+//                       histogram. RK_T live targets per pass; a tile whose rows have more passes over its slice
+//                       again for the next RK_T.
 //   rank_finish_kernel  per query: slices added in index order and prefix-summed over b within each pass, the excluded
 //                       items prefix-summed over the whole list. The m-th best live target t_m is beaten by exactly the
 //                       counted items of its pass with b <= m, less itself and less the excluded ones with b <= m:
 //                       rank = (sum_{b <= m} hist[b]) - 1 - (sum_{b <= m} exb[b]) + 1.
 // Integer counts only: two calls give the same bits.
 constexpr int RK_T = 128;
-constexpr int RK_NONE = 0x7fffffff;
-constexpr int RK_WS_ARRAYS = 6;  // per-entry arrays ahead of the per-query and per-slice ones
 
-struct RankArgs {
-  const float* q; const float* table; const float* rnorm; const float* sqnorm; int n_rows; int n_query;
-  const int64_t* excl; const int64_t* excl_off; const int64_t* tgt; const int64_t* tgt_off;
-  // workspace, indexed by CSR entry relative to tgt_off[0]
-  float* tS; int* tI;  // entry order: score and item (-inf, RK_NONE: dead)
+struct RankArgs : ScoreArgs {
+  const int64_t* tgt; const int64_t* tgt_off;
+  // workspace (RankWs), indexed by CSR entry relative to tgt_off[0]
+  float* tS; int* tI;  // entry order: score and item (-inf, TT_IDX_NONE: dead)
   float* sS; int* sI;  // each query's entries best first
   int* pos;            // an entry's place in that order
   int* exb;            // per place: excluded items in bin b; after the finish, the ranks by place
@@ -655,53 +552,12 @@ struct RankArgs {
   int* hist;           // [splits][n_targets]
   int* out_rank; float* out_tscore;
   int64_t n_targets;
-  int H, metric, splits;
-  int64_t slice;
 };
 
-__device__ __forceinline__ float rk_score(int metric, float dot, float rq, float qq, float rn, float ee) {
-  if (metric == XFMR_METRIC_COSINE) return dot * rq * rn;
-  if (metric == XFMR_METRIC_DOT) return dot;
-  return 1.f - (qq - 2.f * dot + ee);
-}
-
-// |q|^2 as topk_tiled_kernel's 8 threads per query compute it; every thread of an aligned group of 8 gets the value
-__device__ __forceinline__ float rk_query_sqnorm(const float* qr, int H, int part) {
-  float qq = 0.f;
-  for (int h = 4 * part; h < H; h += 32) {
-    const float4 v = *reinterpret_cast<const float4*>(qr + h);
-    qq = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, qq))));
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) qq += __shfl_xor(qq, o, 64);
-  return qq;
-}
-
-// one (query, item) dot product in the k-step order of the 32x32x2 MFMA loop: lane half 0 supplies dims 8c + {0..3},
-// lane half 1 dims 8c + 4 + {0..3} (zeros past H), one MFMA per component
-__device__ __forceinline__ float rk_chain_dot(const float* sQ, const float* e, int H) {
-  float acc = 0.f;
-  for (int c = 0; c < H; c += 8) {
-    const float4 x0 = *reinterpret_cast<const float4*>(sQ + c), y0 = *reinterpret_cast<const float4*>(e + c);
-    float4 x1 = make_float4(0.f, 0.f, 0.f, 0.f), y1 = x1;
-    if (c + 4 < H) {
-      x1 = *reinterpret_cast<const float4*>(sQ + c + 4);
-      y1 = *reinterpret_cast<const float4*>(e + c + 4);
-    }
-    acc = fmaf(x0.x, y0.x, acc); acc = fmaf(x1.x, y1.x, acc);
-    acc = fmaf(x0.y, y0.y, acc); acc = fmaf(x1.y, y1.y, acc);
-    acc = fmaf(x0.z, y0.z, acc); acc = fmaf(x1.z, y1.z, acc);
-    acc = fmaf(x0.w, y0.w, acc); acc = fmaf(x1.w, y1.w, acc);
-  }
-  return acc;
-}
-
-__device__ __forceinline__ float rk_item_score(const RankArgs& a, const float* sQ, float rq, float qq, int it) {
-  const float dot = rk_chain_dot(sQ, a.table + (int64_t)it * a.H, a.H);
-  float rn = 0.f, ee = 0.f;
-  if (a.metric == XFMR_METRIC_COSINE) rn = a.rnorm[it];
-  else if (a.metric == XFMR_METRIC_L2) ee = a.sqnorm[it];
-  return rk_score(a.metric, dot, rq, qq, rn, ee);
+// the tile's score of (query in sQ, item it), bit for bit
+__device__ __forceinline__ float rk_item_score(const ScoreArgs& a, const float* sQ, float rq, float qq, int it) {
+  const ItemTerm t = rk_item_term(a, it, true);
+  return rk_score(a.metric, rk_chain_dot(sQ, a.table + (int64_t)it * a.H, a.H), rq, qq, t.rn, t.ee);
 }
 
 __global__ __launch_bounds__(256) void rank_prep_kernel(RankArgs a) {
@@ -712,7 +568,7 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(RankArgs a) {
   const float* qr = a.q + (int64_t)qi * H;
   for (int h = tid; h < H; h += 256) sQ[h] = qr[h];
   const float qq = rk_query_sqnorm(qr, H, tid & 7);
-  const float rq = 1.f / fmaxf(sqrtf(qq), 1e-8f);
+  const float rq = rk_inv_norm(qq);
   const int64_t base = a.tgt_off[0];
   const int64_t e0 = a.tgt_off[qi] - base, e1 = a.tgt_off[qi + 1] - base;
   const int64_t x0 = a.excl ? a.excl_off[qi] : 0, x1 = a.excl ? a.excl_off[qi + 1] : 0;
@@ -723,10 +579,10 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(RankArgs a) {
   for (int64_t e = e0 + tid; e < e1; e += 256) {
     const int64_t t = a.tgt[base + e];
     float s = -INFINITY;
-    int it = RK_NONE;
+    int it = TT_IDX_NONE;
     if (t >= 1 && t < a.n_rows && !(a.excl && tt_excluded(a.excl, x0, x1, (int)t))) {
       const float v = rk_item_score(a, sQ, rq, qq, (int)t);
-      if (v > -INFINITY && v < INFINITY) { s = v; it = (int)t; ++live; }
+      if (tt_finite(v)) { s = v; it = (int)t; ++live; }
     }
     a.tS[e] = s;
     a.tI[e] = it;
@@ -758,7 +614,7 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(RankArgs a) {
       const int64_t it = a.excl[x];
       if (it < 1 || it >= a.n_rows || (x > x0 && a.excl[x - 1] == it)) continue;
       const float v = rk_item_score(a, sQ, rq, qq, (int)it);
-      if (!(v > -INFINITY && v < INFINITY)) continue;
+      if (!tt_finite(v)) continue;
       const int b = tt_count_better(a.sS + e0, a.sI + e0, nl, v, (int)it);
       if (b < nl) atomicAdd(&a.exb[e0 + b], 1);
     }
@@ -772,27 +628,23 @@ __global__ __launch_bounds__(256) void rank_tile_kernel(RankArgs a) {
   __shared__ float tS[TT_Q * RK_T];
   __shared__ int tI[TT_Q * RK_T], hist[TT_Q * RK_T];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int H = a.H;
   const int q0 = blockIdx.x * TT_Q;
   const int split = blockIdx.y;
   const int64_t lo = split * a.slice;
   const int64_t hi = lo + a.slice < a.n_rows ? lo + a.slice : a.n_rows;
-  {
-    const int i = tid >> 3, part = tid & 7;
+  const float qq = tile_query_sqnorm(a, q0);
+  if ((tid & 7) == 0) {
+    const int i = tid >> 3;
     const bool real = q0 + i < a.n_query;
-    const float qq = rk_query_sqnorm(a.q + (int64_t)(real ? q0 + i : 0) * H, H, part);
-    if (part == 0) {
-      sQQ[i] = real ? qq : 0.f;
-      sRQ[i] = 1.f / fmaxf(sqrtf(real ? qq : 0.f), 1e-8f);
-      sLive[i] = real ? a.nlive[q0 + i] : 0;
-      sE0[i] = real ? a.tgt_off[q0 + i] - a.tgt_off[0] : 0;
-    }
+    sQQ[i] = qq;
+    sRQ[i] = rk_inv_norm(qq);
+    sLive[i] = real ? a.nlive[q0 + i] : 0;
+    sE0[i] = real ? a.tgt_off[q0 + i] - a.tgt_off[0] : 0;
   }
   __syncthreads();
   int maxlive = 0;
   for (int i = 0; i < TT_Q; ++i) maxlive = max(maxlive, sLive[i]);
-  const int h2 = lane >> 5;
-  const float* qa = a.q + (int64_t)min(q0 + (lane & 31), a.n_query - 1) * H + 4 * h2;
+  const float* qa = tile_query_ptr(a, q0, lane);
   for (int c0 = 0; c0 < maxlive; c0 += RK_T) {
     for (int x = tid; x < TT_Q * RK_T; x += 256) {
       const int i = x / RK_T, m = x % RK_T;
@@ -802,38 +654,18 @@ __global__ __launch_bounds__(256) void rank_tile_kernel(RankArgs a) {
     if (tid < TT_Q) sN[tid] = min(max(sLive[tid] - c0, 0), RK_T);
     __syncthreads();
     for (int64_t t0 = lo; t0 < hi; t0 += TT_N) {
-      const int64_t j64 = t0 + 32 * w + (lane & 31);  // this lane's item (accumulator column)
-      const bool jok = j64 >= 1 && j64 < hi;
-      const int j = jok ? (int)j64 : 0;
-      const float* eb = a.table + (int64_t)j * H + 4 * h2;
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      // topk_tiled_kernel's k-step order
-#pragma unroll 4
-      for (int c = 0; c < H; c += 8) {
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
-        if (c + 4 * h2 < H) {
-          x = *reinterpret_cast<const float4*>(qa + c);
-          y = *reinterpret_cast<const float4*>(eb + c);
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, y.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, y.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, y.w, acc, 0, 0, 0);
-      }
-      float rn = 0.f, ee = 0.f;
-      if (jok) {
-        if (a.metric == XFMR_METRIC_COSINE) rn = a.rnorm[j];
-        else if (a.metric == XFMR_METRIC_L2) ee = a.sqnorm[j];
-      }
-      if (jok) {
+      const TileCol col = tile_col(a, t0, hi, w, lane);
+      const int j = col.j;
+      const f32x16 acc = tile_dots(qa, col.e, a.H, lane >> 5);
+      // ---- epilogue: scores, masks, bins ----------------------------------------------------------------------------
+      const ItemTerm term = rk_item_term(a, j, col.ok);
+      if (col.ok) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int i = xf_acc_row(r, lane);
           const int n = sN[i];  // (0 for the rows past n_query)
-          const float s = rk_score(a.metric, acc[r], sRQ[i], sQQ[i], rn, ee);
-          if (n == 0 || !(s > -INFINITY && s < INFINITY)) continue;
+          const float s = rk_score(a.metric, acc[r], sRQ[i], sQQ[i], term.rn, term.ee);
+          if (n == 0 || !tt_finite(s)) continue;
           const float* ts = tS + i * RK_T;
           const int* ti = tI + i * RK_T;
           if (tt_better(ts[n - 1], ti[n - 1], s, j)) continue;  // behind every target of this pass: no bin
@@ -887,14 +719,167 @@ __global__ __launch_bounds__(256) void rank_finish_kernel(RankArgs a) {
     __syncthreads();
   }
   for (int64_t e = e0 + tid; e < e1; e += 256)
-    a.out_rank[base + e] = a.tI[e] != RK_NONE ? a.exb[e0 + a.pos[e]] : RK_NONE;
+    a.out_rank[base + e] = a.tI[e] != TT_IDX_NONE ? a.exb[e0 + a.pos[e]] : TT_IDX_NONE;
 }
 
-// ---- the seven metrics at up to 8 cutoffs from the ranks (xfmr_rank_metrics_sum) ---------------------------------
-// One thread per row, metrics_sum_kernel's layout and reduction. The hits of a row at cutoff K are its distinct targets
-// with rank <= K in ascending rank (distinct eligible items have distinct ranks and the repeats of one target share a
-// rank: picking the next larger rank each time skips repeats); they are walked ONCE, every cutoff that still reaches the
-// rank takes the hit with metrics_row's float expressions in metrics_row's order, so the per-row values are its bits.
+// ---- the seven metrics: from a ranked list, or from the ranks ---------------------------------------------------------
+// v = ndcg, map, auroc, precision, recall, hit, mrr with torchmetrics' definitions for a strictly decreasing score
+// vector over [recommendations | missing targets] (metrics.py:66-79). The list torchmetrics sees: max(len(rec), top_k)
+// slots of recommendations (padding never matches a target), then the missing targets; every metric only looks at the
+// first K = top_k slots (+ the number of targets). Both walks below feed the SAME float expressions in the same order
+// (ms_gain, ms_idcg, ms_values), so their per-row values are the same bits.
+constexpr int MS_ROWS = 256;
+constexpr int MS_VALS = 8;  // XFMR_NUM_RM sums + the number of rows
+
+// distinct targets (target_ids = set(target_ids), metrics.py:66), eligible or not
+__device__ __forceinline__ int ms_distinct(const int64_t* t, int n) {
+  int nt = 0;
+  for (int i = 0; i < n; ++i) {
+    bool dup = false;
+    for (int j = 0; j < i; ++j) dup |= t[j] == t[i];
+    nt += dup ? 0 : 1;
+  }
+  return nt;
+}
+
+__device__ __forceinline__ float ms_gain(int slot) { return 1.f / log2f((float)slot + 2.f); }  // slot = rank - 1
+
+__device__ __forceinline__ float ms_idcg(int nt, int K) {
+  float idcg = 0.f;
+  for (int i = 0; i < (nt < K ? nt : K); ++i) idcg += ms_gain(i);
+  return idcg;
+}
+
+// one hit at rank r (1 = best) joins a cutoff's running sums
+__device__ __forceinline__ void ms_hit(int r, int& hits, float& dcg, float& ap_sum, float& rr) {
+  ++hits;
+  dcg += ms_gain(r - 1);
+  ap_sum += (float)hits / (float)r;
+  if (rr == 0.f) rr = 1.f / (float)r;
+}
+
+// pairs = (hit, non-hit behind it) among the K slots, neg_seen = the non-hits among them
+__device__ __forceinline__ void ms_values(float dcg, float ap_sum, float rr, int hits, int64_t pairs, int64_t neg_seen,
+                                          int nt, int K, float v[7]) {
+  const float idcg = ms_idcg(nt, K);
+  v[0] = idcg > 0.f ? dcg / idcg : 0.f;
+  v[1] = hits > 0 ? ap_sum / (float)hits : 0.f;
+  v[2] = (hits > 0 && neg_seen > 0) ? (float)pairs / ((float)hits * (float)neg_seen) : 0.f;
+  v[3] = (float)hits / (float)K;
+  v[4] = (float)hits / (float)nt;
+  v[5] = hits > 0 ? 1.f : 0.f;
+  v[6] = rr;
+}
+
+// One query's seven metrics from its list: rec (B,k) ranked item indices (-1 = padding), targets CSR. Returns false
+// (v all zero) when the user has no target (the reference returns {} for it, metrics.py:58-59).
+__device__ __forceinline__ bool metrics_row(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off, int64_t b, int k,
+                                            int top_k, float v[7]) {
+  const int64_t* t = tgt + tgt_off[b];
+  const int nt_raw = (int)(tgt_off[b + 1] - tgt_off[b]);
+  for (int i = 0; i < 7; ++i) v[i] = 0.f;
+  const int nt = ms_distinct(t, nt_raw);
+  if (nt == 0) return false;
+  const int64_t* r = rec + b * k;
+  const int K = top_k;
+  float dcg = 0.f, ap_sum = 0.f, rr = 0.f;
+  int hits = 0, pairs = 0, neg_seen = 0;
+  for (int i = 0; i < K; ++i) {
+    bool rel = false;
+    if (i < k && r[i] >= 0) {
+      for (int j = 0; j < nt_raw; ++j) rel |= t[j] == r[i];
+    }
+    if (rel) ms_hit(i + 1, hits, dcg, ap_sum, rr);
+    else {
+      ++neg_seen;
+      pairs += hits;  // each earlier positive outranks this negative
+    }
+  }
+  ms_values(dcg, ap_sum, rr, hits, pairs, neg_seen, nt, K, v);
+  return true;
+}
+
+// one thread per query: out (B,7), valid[b] = 0 when the user has no target
+__global__ void metrics_kernel(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off, int B, int k, int top_k,
+                               float* out, uint8_t* valid) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float v[7];
+  valid[b] = metrics_row(rec, tgt, tgt_off, b, k, top_k, v);
+  float* o = out + (int64_t)b * 7;
+  for (int i = 0; i < 7; ++i) o[i] = v[i];
+}
+
+// ---- the metrics and their sums in one call (xfmr_retrieval_metrics_sum, xfmr_rank_metrics_sum) ----------------------
+// 256-row workgroups, one row per lane. The seven values and the count of the rows that are valid and used go to fp64
+// (lanes past n_query and rows left out: exact zeros), are added across the wave by xor shuffles (a fixed tree), across
+// the four waves through LDS in a fixed order, and leave as ONE 8-double record per workgroup and cutoff.
+// metrics_final_kernel: workgroup ci adds cutoff ci's records in index order (lane t takes records t, t + 256, ...) and
+// finishes with the same tree. No atomics, no dependence on which workgroup finishes first: the same input gives the
+// same doubles on every launch.
+__device__ __forceinline__ void ms_block_sum(double acc[MS_VALS], double (*sP)[MS_VALS], double* dst) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+  for (int i = 0; i < MS_VALS; ++i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc[i] += __shfl_xor(acc[i], o, 64);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < MS_VALS; ++i) sP[w][i] = acc[i];
+  }
+  __syncthreads();
+  if (tid < MS_VALS) dst[tid] = (sP[0][tid] + sP[1][tid]) + (sP[2][tid] + sP[3][tid]);
+}
+
+// a row's record: its values and a one when it counts, exact zeros otherwise
+__device__ __forceinline__ void ms_record(const float v[7], bool counts, double acc[MS_VALS]) {
+#pragma unroll
+  for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
+  if (counts) {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) acc[i] = (double)v[i];
+    acc[7] = 1.0;
+  }
+}
+
+__global__ __launch_bounds__(MS_ROWS) void metrics_sum_kernel(const int64_t* rec, const int64_t* tgt, const int64_t* tgt_off,
+                                                              const uint8_t* use, int64_t B, int k, int top_k, float* out,
+                                                              uint8_t* valid, double* partial) {
+  __shared__ double sP[MS_ROWS / 64][MS_VALS];
+  const int64_t b = (int64_t)blockIdx.x * MS_ROWS + threadIdx.x;
+  float v[7];
+  bool counts = false;
+  if (b < B) {
+    const bool ok = metrics_row(rec, tgt, tgt_off, b, k, top_k, v);
+    if (out) {
+      for (int i = 0; i < 7; ++i) out[b * 7 + i] = v[i];
+    }
+    if (valid) valid[b] = ok;
+    counts = ok && (!use || use[b]);
+  }
+  double acc[MS_VALS];
+  ms_record(v, counts, acc);
+  ms_block_sum(acc, sP, partial + (int64_t)blockIdx.x * MS_VALS);
+}
+
+__global__ __launch_bounds__(MS_ROWS) void metrics_final_kernel(const double* partial, int64_t n_partial, int n_cut,
+                                                                double* sums) {
+  __shared__ double sP[MS_ROWS / 64][MS_VALS];
+  const int ci = blockIdx.x;
+  double acc[MS_VALS];
+#pragma unroll
+  for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
+  for (int64_t p = threadIdx.x; p < n_partial; p += MS_ROWS) {
+#pragma unroll
+    for (int i = 0; i < MS_VALS; ++i) acc[i] += partial[(p * n_cut + ci) * MS_VALS + i];
+  }
+  ms_block_sum(acc, sP, sums + (int64_t)ci * MS_VALS);
+}
+
+// From the ranks, at up to 8 cutoffs. The hits of a row at cutoff K are its distinct targets with rank <= K in
+// ascending rank (distinct eligible items have distinct ranks and the repeats of one target share a rank: picking the
+// next larger rank each time skips repeats); they are walked ONCE, every cutoff that still reaches the rank takes the hit.
 constexpr int RK_MAX_CUTOFFS = 8;
 struct RankCutoffs { int k[RK_MAX_CUTOFFS]; int n; };
 
@@ -913,31 +898,23 @@ __global__ __launch_bounds__(MS_ROWS) void rank_metrics_sum_kernel(const int* ra
   if (b < B) {
     const int64_t e0 = tgt_off[b];
     const int n = (int)(tgt_off[b + 1] - e0);
-    const int64_t* t = tgt + e0;
     const int* rk = ranks + e0;
-    for (int i = 0; i < n; ++i) {  // distinct targets, eligible or not (target_ids = set(target_ids), metrics.py:66)
-      bool dup = false;
-      for (int j = 0; j < i; ++j) dup |= t[j] == t[i];
-      nt += dup ? 0 : 1;
-    }
+    nt = ms_distinct(tgt + e0, n);
     int kmax = 0;
 #pragma unroll
     for (int ci = 0; ci < RK_MAX_CUTOFFS; ++ci) kmax = ci < c.n ? max(kmax, c.k[ci]) : kmax;
     int prev = 0;
     while (nt > 0) {
-      int r = RK_NONE;
+      int r = TT_IDX_NONE;
       for (int i = 0; i < n; ++i) {
         const int x = rk[i];
         if (x > prev && x < r) r = x;
       }
-      if (r == RK_NONE || r > kmax) break;
+      if (r == TT_IDX_NONE || r > kmax) break;
 #pragma unroll
       for (int ci = 0; ci < RK_MAX_CUTOFFS; ++ci) {
         if (ci < c.n && r <= c.k[ci]) {
-          ++hits[ci];
-          dcg[ci] += 1.f / log2f((float)(r - 1) + 2.f);
-          ap_sum[ci] += (float)hits[ci] / (float)r;
-          if (rr[ci] == 0.f) rr[ci] = 1.f / (float)r;
+          ms_hit(r, hits[ci], dcg[ci], ap_sum[ci], rr[ci]);
           rank_sum[ci] += r;
         }
       }
@@ -949,54 +926,97 @@ __global__ __launch_bounds__(MS_ROWS) void rank_metrics_sum_kernel(const int* ra
 #pragma unroll
   for (int ci = 0; ci < RK_MAX_CUTOFFS; ++ci) {
     if (ci >= c.n) break;
-    double acc[MS_VALS];
-#pragma unroll
-    for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
+    float v[7];
     if (b < B) {
-      float v[7];
       for (int i = 0; i < 7; ++i) v[i] = 0.f;
       if (nt > 0) {
         const int K = c.k[ci], h = hits[ci];
-        const int64_t neg_seen = (int64_t)K - h;
         // each hit outranks the non-hits behind it among the K slots: (K - r_j) - (h - 1 - j), summed over the hits
         const int64_t pairs = (int64_t)h * K - rank_sum[ci] - (int64_t)h * (h - 1) / 2;
-        float idcg = 0.f;
-        for (int i = 0; i < (nt < K ? nt : K); ++i) idcg += 1.f / log2f((float)i + 2.f);
-        v[0] = idcg > 0.f ? dcg[ci] / idcg : 0.f;
-        v[1] = h > 0 ? ap_sum[ci] / (float)h : 0.f;
-        v[2] = (h > 0 && neg_seen > 0) ? (float)pairs / ((float)h * (float)neg_seen) : 0.f;
-        v[3] = (float)h / (float)K;
-        v[4] = (float)h / (float)nt;
-        v[5] = h > 0 ? 1.f : 0.f;
-        v[6] = rr[ci];
+        ms_values(dcg[ci], ap_sum[ci], rr[ci], h, pairs, (int64_t)K - h, nt, K, v);
       }
       if (out) {
         for (int i = 0; i < 7; ++i) out[(b * c.n + ci) * 7 + i] = v[i];
       }
-      if (used) {
-#pragma unroll
-        for (int i = 0; i < 7; ++i) acc[i] = (double)v[i];
-        acc[7] = 1.0;
-      }
     }
+    double acc[MS_VALS];
+    ms_record(v, used, acc);
     if (ci) __syncthreads();  // (the previous cutoff's sP reads)
     ms_block_sum(acc, sP, partial + ((int64_t)blockIdx.x * c.n + ci) * MS_VALS);
   }
 }
 
-// workgroup ci adds cutoff ci's records in index order, as metrics_sum_final_kernel
-__global__ __launch_bounds__(MS_ROWS) void rank_metrics_final_kernel(const double* partial, int64_t n_partial, int n_cut,
-                                                                     double* sums) {
-  __shared__ double sP[MS_ROWS / 64][MS_VALS];
-  const int ci = blockIdx.x;
-  double acc[MS_VALS];
-#pragma unroll
-  for (int i = 0; i < MS_VALS; ++i) acc[i] = 0.0;
-  for (int64_t p = threadIdx.x; p < n_partial; p += MS_ROWS) {
-#pragma unroll
-    for (int i = 0; i < MS_VALS; ++i) acc[i] += partial[(p * n_cut + ci) * MS_VALS + i];
-  }
-  ms_block_sum(acc, sP, sums + (int64_t)ci * MS_VALS);
+// ---- host: one plan, one layout, one set of checks ------------------------------------------------------------------
+struct TiledPlan {
+  int splits; int64_t slice;  // catalogue slices and the items in each (a multiple of TT_N)
+  unsigned qtiles;            // query tiles
+  dim3 grid() const { return dim3(qtiles, (unsigned)splits); }
+};
+
+static TiledPlan tiled_plan(int64_t n_query, int64_t n_rows) {
+  const int64_t qtiles = (n_query + TT_Q - 1) / TT_Q;
+  const int64_t itiles = (n_rows + TT_N - 1) / TT_N;
+  int64_t s = (TT_TARGET_WG + qtiles - 1) / qtiles;
+  if (s > TT_MAX_SPLITS) s = TT_MAX_SPLITS;
+  if (s > itiles) s = itiles;
+  if (s < 1) s = 1;
+  TiledPlan p;
+  p.slice = ((itiles + s - 1) / s) * TT_N;
+  p.splits = (int)((n_rows + p.slice - 1) / p.slice);
+  p.qtiles = (unsigned)qtiles;
+  return p;
+}
+
+static int tiled_kp(int k) {
+  int kp = 1;
+  while (kp < k) kp <<= 1;
+  return kp;
+}
+
+static size_t tiled_lds_bytes(int kp) {
+  return (size_t)TT_Q * TT_C * 8 + (size_t)2 * TT_Q * kp * 8;
+}
+
+// the rank workspace, in ints: six per-entry arrays, the per-query live counts, one histogram per slice
+struct RankWs { size_t tS, tI, sS, sI, pos, exb, nlive, hist, end; };
+static RankWs rank_ws(int64_t n_query, int64_t n_targets, int splits) {
+  const size_t t = (size_t)n_targets, q = (size_t)n_query;
+  return {0, t, 2 * t, 3 * t, 4 * t, 5 * t, 6 * t, 6 * t + q, 6 * t + q + (size_t)splits * t};
+}
+
+static int64_t ms_partials(int64_t n_query) { return (n_query + MS_ROWS - 1) / MS_ROWS; }
+
+// The search entries' common refusals, in their common precedence: EINVAL (pointers, sizes, the exclusion pair, the
+// metric, the norm array the metric needs) < EUNSUPPORTED < EALIGN; the workspace size is the caller's, last.
+// scan = xfmr_topk: always needs table_rnorm, does not test the query's alignment, puts no bound on n_query.
+// own_valid / own_supported: the entry's own pointers and sizes (outputs, k or the targets).
+static int search_check(const float* query, const float* table, const float* rnorm, const float* sqnorm, int64_t n_rows,
+                        int64_t n_query, int32_t H, const int64_t* excl, const int64_t* excl_off, int32_t metric,
+                        const void* workspace, bool scan, bool own_valid, bool own_supported) {
+  if (!query || !table || !workspace || !own_valid) return XFMR_EINVAL;
+  if (n_rows <= 0 || n_query <= 0 || H <= 0) return XFMR_EINVAL;
+  if ((excl == nullptr) != (excl_off == nullptr)) return XFMR_EINVAL;
+  if (metric < XFMR_METRIC_COSINE || metric > XFMR_METRIC_L2) return XFMR_EINVAL;
+  if ((scan || metric == XFMR_METRIC_COSINE) && !rnorm) return XFMR_EINVAL;
+  if (!scan && metric == XFMR_METRIC_L2 && !sqnorm) return XFMR_EINVAL;
+  if ((H & 3) || H > TOPK_MAX_H || n_rows >= (1ll << 31) || (!scan && n_query >= (1ll << 31)) || !own_supported)
+    return XFMR_EUNSUPPORTED;
+  if ((!scan && !xf_aligned16(query)) || !xf_aligned16(table) || !xf_aligned16(workspace)) return XFMR_EALIGN;
+  return XFMR_OK;
+}
+
+static void fill_score_args(ScoreArgs& a, const float* query, const float* table, const float* rnorm, const float* sqnorm,
+                            int64_t n_rows, int64_t n_query, int32_t H, const int64_t* excl, const int64_t* excl_off,
+                            int32_t metric, const TiledPlan& p) {
+  a.q = query; a.table = table; a.rnorm = rnorm; a.sqnorm = sqnorm; a.n_rows = (int)n_rows; a.n_query = (int)n_query;
+  a.excl = excl; a.excl_off = excl_off; a.H = H; a.metric = metric; a.splits = p.splits; a.slice = p.slice;
+}
+
+// the two sum entries' second launch: cutoff ci's records -> sums[ci]
+static int launch_metrics_final(const double* partial, int64_t n_partial, int n_cut, double* sums, hipStream_t stream) {
+  hipLaunchKernelGGL(metrics_final_kernel, dim3((unsigned)n_cut), dim3(MS_ROWS), 0, stream, partial, n_partial, n_cut, sums);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
 }
 
 }  // namespace
@@ -1011,12 +1031,9 @@ size_t xfmr_topk_workspace(int64_t n_query, int64_t n_rows) {
 int xfmr_topk(const float* query, const float* table, const float* table_rnorm, int64_t n_rows, int64_t n_query,
               int32_t H, const int64_t* exclude, const int64_t* exclude_offsets, int32_t k, int32_t metric,
               int64_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!query || !table || !table_rnorm || !out_idx || !out_score || !workspace) return XFMR_EINVAL;
-  if (n_rows <= 0 || n_query <= 0 || H <= 0 || k <= 0) return XFMR_EINVAL;
-  if ((exclude == nullptr) != (exclude_offsets == nullptr)) return XFMR_EINVAL;
-  if (metric < XFMR_METRIC_COSINE || metric > XFMR_METRIC_L2) return XFMR_EINVAL;
-  if ((H & 3) || H > TOPK_MAX_H || k > TOPK_MAX || n_rows >= (1ll << 31)) return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(table) || !xf_aligned16(workspace)) return XFMR_EALIGN;
+  const int rc = search_check(query, table, table_rnorm, nullptr, n_rows, n_query, H, exclude, exclude_offsets, metric,
+                              workspace, true, out_idx && out_score && k > 0, k <= TOPK_MAX);
+  if (rc != XFMR_OK) return rc;
   if (workspace_bytes < xfmr_topk_workspace(n_query, n_rows)) return XFMR_EWORKSPACE;
   TopkArgs a{};
   a.q = query; a.table = table; a.rnorm = table_rnorm; a.n_rows = n_rows; a.excl = exclude; a.excl_off = exclude_offsets;
@@ -1036,11 +1053,7 @@ int xfmr_retrieval_metrics(const int64_t* rec_idx, const int64_t* targets, const
   return XFMR_OK;
 }
 
-
-size_t xfmr_retrieval_metrics_sum_workspace(int64_t n_query) {
-  if (n_query <= 0) return 0;
-  return (size_t)((n_query + MS_ROWS - 1) / MS_ROWS) * MS_VALS * sizeof(double);
-}
+size_t xfmr_retrieval_metrics_sum_workspace(int64_t n_query) { return xfmr_rank_metrics_sum_workspace(n_query, 1); }
 
 int xfmr_retrieval_metrics_sum(const int64_t* rec_idx, const int64_t* targets, const int64_t* target_offsets,
                                const uint8_t* use, int64_t n_query, int32_t k, int32_t top_k, double* sums, float* out,
@@ -1049,21 +1062,17 @@ int xfmr_retrieval_metrics_sum(const int64_t* rec_idx, const int64_t* targets, c
     return XFMR_EINVAL;
   if (n_query >= (1ll << 31)) return XFMR_EUNSUPPORTED;  // (xfmr_retrieval_metrics takes an int32 row count)
   if (workspace_bytes < xfmr_retrieval_metrics_sum_workspace(n_query)) return XFMR_EWORKSPACE;
-  const int64_t n_partial = (n_query + MS_ROWS - 1) / MS_ROWS;
+  const int64_t n_partial = ms_partials(n_query);
   double* partial = (double*)workspace;
   hipLaunchKernelGGL(metrics_sum_kernel, dim3((unsigned)n_partial), dim3(MS_ROWS), 0, (hipStream_t)stream, rec_idx, targets,
                      target_offsets, use, n_query, k, top_k, out, valid, partial);
   XF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(metrics_sum_final_kernel, dim3(1), dim3(MS_ROWS), 0, (hipStream_t)stream, (const double*)partial,
-                     n_partial, sums);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  return launch_metrics_final(partial, n_partial, 1, sums, (hipStream_t)stream);
 }
 
 size_t xfmr_topk_tiled_workspace(int64_t n_query, int64_t n_rows, int32_t k) {
   if (n_query <= 0 || n_rows <= 0 || k <= 0) return 0;
-  const TiledPlan p = tiled_plan(n_query, n_rows);
-  const size_t n = (size_t)n_query * (size_t)p.splits * (size_t)k;
+  const size_t n = (size_t)n_query * (size_t)tiled_plan(n_query, n_rows).splits * (size_t)k;
   return n * sizeof(float) + n * sizeof(int);
 }
 
@@ -1071,29 +1080,20 @@ int xfmr_topk_tiled(const float* query, const float* table, const float* table_r
                     int64_t n_rows, int64_t n_query, int32_t H, const int64_t* exclude, const int64_t* exclude_offsets,
                     int32_t k, int32_t metric, int64_t* out_idx, float* out_score, void* workspace,
                     size_t workspace_bytes, void* stream) {
-  if (!query || !table || !out_idx || !out_score || !workspace) return XFMR_EINVAL;
-  if (n_rows <= 0 || n_query <= 0 || H <= 0 || k <= 0) return XFMR_EINVAL;
-  if ((exclude == nullptr) != (exclude_offsets == nullptr)) return XFMR_EINVAL;
-  if (metric < XFMR_METRIC_COSINE || metric > XFMR_METRIC_L2) return XFMR_EINVAL;
-  if (metric == XFMR_METRIC_COSINE && !table_rnorm) return XFMR_EINVAL;
-  if (metric == XFMR_METRIC_L2 && !table_sqnorm) return XFMR_EINVAL;
-  if ((H & 3) || H > TOPK_MAX_H || k > TT_KMAX || n_rows >= (1ll << 31) || n_query >= (1ll << 31))
-    return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(query) || !xf_aligned16(table) || !xf_aligned16(workspace)) return XFMR_EALIGN;
+  const int rc = search_check(query, table, table_rnorm, table_sqnorm, n_rows, n_query, H, exclude, exclude_offsets, metric,
+                              workspace, false, out_idx && out_score && k > 0, k <= TT_KMAX);
+  if (rc != XFMR_OK) return rc;
   if (workspace_bytes < xfmr_topk_tiled_workspace(n_query, n_rows, k)) return XFMR_EWORKSPACE;
   const TiledPlan p = tiled_plan(n_query, n_rows);
-  const size_t n = (size_t)n_query * (size_t)p.splits * (size_t)k;
   TiledArgs a{};
-  a.q = query; a.table = table; a.rnorm = table_rnorm; a.sqnorm = table_sqnorm; a.n_rows = (int)n_rows;
-  a.n_query = (int)n_query; a.excl = exclude; a.excl_off = exclude_offsets;
-  a.ws_score = (float*)workspace; a.ws_idx = (int*)((float*)workspace + n);
-  a.H = H; a.k = k; a.kp = tiled_kp(k); a.metric = metric; a.splits = p.splits; a.slice = p.slice;
+  fill_score_args(a, query, table, table_rnorm, table_sqnorm, n_rows, n_query, H, exclude, exclude_offsets, metric, p);
+  a.ws_score = (float*)workspace; a.ws_idx = (int*)(a.ws_score + (size_t)n_query * (size_t)p.splits * (size_t)k);
+  a.k = k; a.kp = tiled_kp(k);
   const size_t lds = tiled_lds_bytes(a.kp);
   if (hipFuncSetAttribute((const void*)topk_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
       hipSuccess)
     return XFMR_EHIP;
-  const unsigned qtiles = (unsigned)((n_query + TT_Q - 1) / TT_Q);
-  hipLaunchKernelGGL(topk_tiled_kernel, dim3(qtiles, (unsigned)p.splits), dim3(256), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(topk_tiled_kernel, p.grid(), dim3(256), lds, (hipStream_t)stream, a);
   XF_LAUNCH_CHECK();
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)n_query), dim3(256), 0, (hipStream_t)stream, a.ws_score,
                      a.ws_idx, p.splits, k, out_idx, out_score);
@@ -1103,38 +1103,30 @@ int xfmr_topk_tiled(const float* query, const float* table, const float* table_r
 
 size_t xfmr_target_ranks_workspace(int64_t n_query, int64_t n_rows, int64_t n_targets) {
   if (n_query <= 0 || n_rows <= 0 || n_targets < 0) return 0;
-  const TiledPlan p = tiled_plan(n_query, n_rows);
-  return ((size_t)(RK_WS_ARRAYS + p.splits) * (size_t)n_targets + (size_t)n_query) * sizeof(int);
+  return rank_ws(n_query, n_targets, tiled_plan(n_query, n_rows).splits).end * sizeof(int);
 }
 
 int xfmr_target_ranks(const float* query, const float* table, const float* table_rnorm, const float* table_sqnorm,
                       int64_t n_rows, int64_t n_query, int32_t H, const int64_t* exclude, const int64_t* exclude_offsets,
                       const int64_t* targets, const int64_t* target_offsets, int64_t n_targets, int32_t metric,
                       int32_t* out_rank, float* out_target_score, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!query || !table || !targets || !target_offsets || !out_rank || !workspace) return XFMR_EINVAL;
-  if (n_rows <= 0 || n_query <= 0 || H <= 0 || n_targets < 0) return XFMR_EINVAL;
-  if ((exclude == nullptr) != (exclude_offsets == nullptr)) return XFMR_EINVAL;
-  if (metric < XFMR_METRIC_COSINE || metric > XFMR_METRIC_L2) return XFMR_EINVAL;
-  if (metric == XFMR_METRIC_COSINE && !table_rnorm) return XFMR_EINVAL;
-  if (metric == XFMR_METRIC_L2 && !table_sqnorm) return XFMR_EINVAL;
-  if ((H & 3) || H > TOPK_MAX_H || n_rows >= (1ll << 31) || n_query >= (1ll << 31) || n_targets >= (1ll << 31))
-    return XFMR_EUNSUPPORTED;
-  if (!xf_aligned16(query) || !xf_aligned16(table) || !xf_aligned16(workspace)) return XFMR_EALIGN;
+  const int rc = search_check(query, table, table_rnorm, table_sqnorm, n_rows, n_query, H, exclude, exclude_offsets, metric,
+                              workspace, false, targets && target_offsets && out_rank && n_targets >= 0,
+                              n_targets < (1ll << 31));
+  if (rc != XFMR_OK) return rc;
   if (workspace_bytes < xfmr_target_ranks_workspace(n_query, n_rows, n_targets)) return XFMR_EWORKSPACE;
   const TiledPlan p = tiled_plan(n_query, n_rows);
+  const RankWs ws = rank_ws(n_query, n_targets, p.splits);
   RankArgs a{};
-  a.q = query; a.table = table; a.rnorm = table_rnorm; a.sqnorm = table_sqnorm; a.n_rows = (int)n_rows;
-  a.n_query = (int)n_query; a.excl = exclude; a.excl_off = exclude_offsets; a.tgt = targets; a.tgt_off = target_offsets;
+  fill_score_args(a, query, table, table_rnorm, table_sqnorm, n_rows, n_query, H, exclude, exclude_offsets, metric, p);
+  a.tgt = targets; a.tgt_off = target_offsets;
   int* w = (int*)workspace;
-  a.tS = (float*)w; a.tI = w + n_targets; a.sS = (float*)(w + 2 * n_targets); a.sI = w + 3 * n_targets;
-  a.pos = w + 4 * n_targets; a.exb = w + 5 * n_targets; a.nlive = w + RK_WS_ARRAYS * n_targets;
-  a.hist = a.nlive + n_query;
+  a.tS = (float*)(w + ws.tS); a.tI = w + ws.tI; a.sS = (float*)(w + ws.sS); a.sI = w + ws.sI;
+  a.pos = w + ws.pos; a.exb = w + ws.exb; a.nlive = w + ws.nlive; a.hist = w + ws.hist;
   a.out_rank = out_rank; a.out_tscore = out_target_score; a.n_targets = n_targets;
-  a.H = H; a.metric = metric; a.splits = p.splits; a.slice = p.slice;
-  const unsigned qtiles = (unsigned)((n_query + TT_Q - 1) / TT_Q);
   hipLaunchKernelGGL(rank_prep_kernel, dim3((unsigned)n_query), dim3(256), 0, (hipStream_t)stream, a);
   XF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rank_tile_kernel, dim3(qtiles, (unsigned)p.splits), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(rank_tile_kernel, p.grid(), dim3(256), 0, (hipStream_t)stream, a);
   XF_LAUNCH_CHECK();
   hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)n_query), dim3(256), 0, (hipStream_t)stream, a);
   XF_LAUNCH_CHECK();
@@ -1143,7 +1135,7 @@ int xfmr_target_ranks(const float* query, const float* table, const float* table
 
 size_t xfmr_rank_metrics_sum_workspace(int64_t n_query, int32_t n_cutoffs) {
   if (n_query <= 0 || n_cutoffs <= 0) return 0;
-  return (size_t)((n_query + MS_ROWS - 1) / MS_ROWS) * (size_t)n_cutoffs * MS_VALS * sizeof(double);
+  return (size_t)ms_partials(n_query) * (size_t)n_cutoffs * MS_VALS * sizeof(double);
 }
 
 int xfmr_rank_metrics_sum(const int32_t* ranks, const int64_t* targets, const int64_t* target_offsets, const uint8_t* use,
@@ -1159,15 +1151,12 @@ int xfmr_rank_metrics_sum(const int32_t* ranks, const int64_t* targets, const in
   }
   if (n_query >= (1ll << 31)) return XFMR_EUNSUPPORTED;
   if (workspace_bytes < xfmr_rank_metrics_sum_workspace(n_query, n_cutoffs)) return XFMR_EWORKSPACE;
-  const int64_t n_partial = (n_query + MS_ROWS - 1) / MS_ROWS;
+  const int64_t n_partial = ms_partials(n_query);
   double* partial = (double*)workspace;
   hipLaunchKernelGGL(rank_metrics_sum_kernel, dim3((unsigned)n_partial), dim3(MS_ROWS), 0, (hipStream_t)stream, ranks,
                      targets, target_offsets, use, n_query, c, out, valid, partial);
   XF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rank_metrics_final_kernel, dim3((unsigned)n_cutoffs), dim3(MS_ROWS), 0, (hipStream_t)stream,
-                     (const double*)partial, n_partial, n_cutoffs, sums);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  return launch_metrics_final(partial, n_partial, n_cutoffs, sums, (hipStream_t)stream);
 }
 
 int xfmr_table_sqnorm(const float* table, float* table_sqnorm, int64_t n_rows, int32_t H, void* stream) {

@@ -23,22 +23,47 @@ METRIC_NAMES = (  # metrics.py:7-15, in the order of XFMR_RM_*
 )
 
 
+def _flat_csr(rows):
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in rows], out=off[1:])
+    flat = np.concatenate(rows) if off[-1] else np.zeros(1, dtype=np.int64)  # (one placeholder element: never read)
+    return flat, off
+
+
 def _csr(lists, device):
-    lens = np.asarray([len(x) for x in lists], dtype=np.int64)
-    off = np.zeros(len(lists) + 1, dtype=np.int64)
-    np.cumsum(lens, out=off[1:])
-    flat = np.concatenate([np.asarray(x, dtype=np.int64) for x in lists]) if off[-1] else np.zeros(1, dtype=np.int64)
-    return torch.from_numpy(flat).to(device), torch.from_numpy(off).to(device)
+    return tuple(torch.from_numpy(x).to(device) for x in _flat_csr([np.asarray(x, dtype=np.int64) for x in lists]))
 
 
 def sorted_exclusion_csr(lists):
     """Host side of xfmr_topk_tiled's exclusions: each query's list sorted ascending with duplicates removed, as one
     flat int64 array + (B + 1) int64 offsets (numpy). The kernel binary-searches each list."""
-    rows = [np.unique(np.asarray(x, dtype=np.int64).reshape(-1)) for x in lists]
-    off = np.zeros(len(rows) + 1, dtype=np.int64)
-    np.cumsum([r.size for r in rows], out=off[1:])
-    flat = np.concatenate(rows) if off[-1] else np.zeros(1, dtype=np.int64)
+    return _flat_csr([np.unique(np.asarray(x, dtype=np.int64).reshape(-1)) for x in lists])
+
+
+def _queries(embedding):
+    """(B,H) or (H,) -> (contiguous float32 (B,H), B, H, device)."""
+    q = embedding.reshape(-1, embedding.shape[-1]).contiguous().to(torch.float32)
+    return q, q.shape[0], q.shape[1], q.device
+
+
+def _check_csr(name, csr, B, rows="queries", int64=True):
+    flat, off = csr
+    if off.numel() != B + 1:
+        raise ValueError(f"{name} offsets have {off.numel()} entries for {B} {rows}")
+    if int64 and (flat.dtype != torch.int64 or off.dtype != torch.int64):
+        raise ValueError(f"{name} must be int64 tensors")
     return flat, off
+
+
+def _use_mask(use, B):
+    if use is None:
+        return None
+    if use.numel() != B:
+        raise ValueError(f"use has {use.numel()} entries for {B} rows")
+    use = use.view(torch.uint8) if use.dtype == torch.bool else use
+    if use.dtype != torch.uint8:
+        raise ValueError(f"use must be uint8 or bool, got {use.dtype}")
+    return use
 
 
 class ExactItemIndex:
@@ -61,12 +86,15 @@ class ExactItemIndex:
             self._sqnorm = ops.table_sqnorm(self.table)
         return self._sqnorm
 
+    def _norms(self):
+        """(rnorm, sqnorm) as the tile kernels take them: only the array the metric reads."""
+        return (self.rnorm if self.metric == METRICS["cosine"] else None,
+                self.sqnorm if self.metric == METRICS["l2"] else None)
+
     def search(self, embedding: torch.Tensor, exclude_item_idx=None, top_k: int = 20):
         """embedding (B,H) or (H,); exclude_item_idx: per-query lists of item indices (the users' histories).
         Returns (item_idx (B,top_k) int64, -1 padded; score (B,top_k) = 1 - distance), best first."""
-        q = embedding.reshape(-1, embedding.shape[-1]).contiguous().to(torch.float32)
-        B, H = q.shape
-        dev = q.device
+        q, B, H, dev = _queries(embedding)
         idx = torch.empty((B, top_k), dtype=torch.int64, device=dev)
         score = torch.empty((B, top_k), dtype=torch.float32, device=dev)
         ex, exo = (None, None) if exclude_item_idx is None else _csr(exclude_item_idx, dev)
@@ -84,9 +112,7 @@ class ExactItemIndex:
         """:meth:`search` for a batch of users through xfmr_topk_tiled: score tiles on the matrix cores and a streaming
         top-k, no (B, n_items) workspace. Same results as :meth:`search` up to the summation order of the scores (so up
         to near-tied scores at the k-th place). top_k <= 128."""
-        q = embedding.reshape(-1, embedding.shape[-1]).contiguous().to(torch.float32)
-        B, H = q.shape
-        dev = q.device
+        q, B, H, dev = _queries(embedding)
         idx = torch.empty((B, top_k), dtype=torch.int64, device=dev)
         score = torch.empty((B, top_k), dtype=torch.float32, device=dev)
         if B == 0:
@@ -95,11 +121,9 @@ class ExactItemIndex:
         if exclude_item_idx is not None:
             if len(exclude_item_idx) != B:
                 raise ValueError(f"exclude_item_idx has {len(exclude_item_idx)} lists for {B} queries")
-            flat, off = sorted_exclusion_csr(exclude_item_idx)
-            ex, exo = torch.from_numpy(flat).to(dev), torch.from_numpy(off).to(dev)
+            ex, exo = (torch.from_numpy(x).to(dev) for x in sorted_exclusion_csr(exclude_item_idx))
         n_rows = self.table.shape[0]
-        rnorm = self.rnorm if self.metric == METRICS["cosine"] else None
-        sqnorm = self.sqnorm if self.metric == METRICS["l2"] else None
+        rnorm, sqnorm = self._norms()
         lib = N.load()
         nbytes = lib.xfmr_topk_tiled_workspace(B, n_rows, top_k)
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
@@ -121,21 +145,9 @@ class ExactItemIndex:
         entries the offsets cover (default: all of ``flat``; sizes the workspace); ``out``: an int32 tensor parallel to
         ``flat`` to write into (entries outside the offsets are left alone). ``return_scores=True`` also returns the
         targets' scores (float32, -inf where there is no rank): the bits :meth:`search_batch` reports for the item."""
-        q = embedding.reshape(-1, embedding.shape[-1]).contiguous().to(torch.float32)
-        B, H = q.shape
-        dev = q.device
-        tg, tgo = targets_csr
-        if tgo.numel() != B + 1:
-            raise ValueError(f"targets_csr offsets have {tgo.numel()} entries for {B} queries")
-        if tg.dtype != torch.int64 or tgo.dtype != torch.int64:
-            raise ValueError("targets_csr must be int64 tensors")
-        ex = exo = None
-        if exclude_csr is not None:
-            ex, exo = exclude_csr
-            if exo.numel() != B + 1:
-                raise ValueError(f"exclude_csr offsets have {exo.numel()} entries for {B} queries")
-            if ex.dtype != torch.int64 or exo.dtype != torch.int64:
-                raise ValueError("exclude_csr must be int64 tensors")
+        q, B, H, dev = _queries(embedding)
+        tg, tgo = _check_csr("targets_csr", targets_csr, B)
+        ex, exo = (None, None) if exclude_csr is None else _check_csr("exclude_csr", exclude_csr, B)
         if out is None:
             out = torch.full((tg.numel(),), N.RANK_NONE, dtype=torch.int32, device=dev)
         elif out.dtype != torch.int32 or out.numel() != tg.numel():
@@ -145,8 +157,7 @@ class ExactItemIndex:
             return (out, score) if return_scores else out
         nt = int(tg.numel() if n_targets is None else n_targets)
         n_rows = self.table.shape[0]
-        rnorm = self.rnorm if self.metric == METRICS["cosine"] else None
-        sqnorm = self.sqnorm if self.metric == METRICS["l2"] else None
+        rnorm, sqnorm = self._norms()
         lib = N.load()
         nbytes = lib.xfmr_target_ranks_workspace(B, n_rows, nt)
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
@@ -192,12 +203,7 @@ def rank_metrics_sum(ranks: torch.Tensor, targets_csr, cutoffs, use: torch.Tenso
         raise ValueError(f"ranks must be int32 with one entry per target ({tg.numel()}); got {ranks.dtype}, {ranks.numel()}")
     if B < 1:
         raise ValueError("targets_csr has no row")
-    if use is not None:
-        if use.numel() != B:
-            raise ValueError(f"use has {use.numel()} entries for {B} rows")
-        use = use.view(torch.uint8) if use.dtype == torch.bool else use
-        if use.dtype != torch.uint8:
-            raise ValueError(f"use must be uint8 or bool, got {use.dtype}")
+    use = _use_mask(use, B)
     nc = len(cut)
     sums = torch.empty((nc, 8), dtype=torch.float64, device=dev)
     vals = torch.empty((B, nc, len(METRIC_NAMES)), dtype=torch.float32, device=dev) if per_row else None
@@ -245,15 +251,8 @@ def retrieval_metrics_sum(rec_idx: torch.Tensor, targets_csr, use: torch.Tensor 
     row. ``per_row=True`` returns ``(sums, values (B,7), valid (B,) bool)``: the bits of :func:`retrieval_metrics`."""
     B, k = rec_idx.shape
     dev = rec_idx.device
-    tg, tgo = targets_csr
-    if tgo.numel() != B + 1:
-        raise ValueError(f"targets_csr offsets have {tgo.numel()} entries for {B} rows")
-    if use is not None:
-        if use.numel() != B:
-            raise ValueError(f"use has {use.numel()} entries for {B} rows")
-        use = use.view(torch.uint8) if use.dtype == torch.bool else use
-        if use.dtype != torch.uint8:
-            raise ValueError(f"use must be uint8 or bool, got {use.dtype}")
+    tg, tgo = _check_csr("targets_csr", targets_csr, B, rows="rows", int64=False)
+    use = _use_mask(use, B)
     sums = torch.empty((8,), dtype=torch.float64, device=dev)
     out = torch.empty((B, len(METRIC_NAMES)), dtype=torch.float32, device=dev) if per_row else None
     valid = torch.empty((B,), dtype=torch.uint8, device=dev) if per_row else None
