@@ -342,6 +342,23 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
 int xfmr_encoder_bwd(const xfmr_encoder_cfg* cfg, const float* params, float* grads, float* d_tok,
                      const uint8_t* key_mask, void* acts, size_t acts_bytes, void* stream);
 
+/* The forward-only pass (evaluation, prediction, serving): tok and key_mask are exactly what xfmr_encoder_fwd writes for the
+ * same cfg -- the same kernel forms in the same order, on instantiations that store nothing a backward would read -- bit for
+ * bit, in the padded (B, L, H) layout or the packed one. Nothing can follow it with xfmr_encoder_bwd.
+ * cfg: checked as xfmr_encoder_fwd checks it (packed-rows rules included); hidden_dropout or attn_dropout != 0 is
+ * XFMR_EINVAL (this entry is eval). embed_event and the profile_* events of XFMR_PROF_ATTN_FWD / XFMR_PROF_FFN_FWD are
+ * honoured; context, grads_half_event and step_device are ignored. The call creates no HIP object.
+ * `workspace`: xfmr_encoder_infer_workspace_bytes(cfg) bytes (0: the cfg is refused), scratch of this call only: the
+ * embedding LayerNorm's output, one qkv / ctx / lse, two sets of LayerNorm outputs that alternate by layer, the bf16
+ * parameter copy, and one [T][I] / [T][H] buffer where the FFN / a LayerNorm runs as launches of its own. Sized by the
+ * rows actually run (packed_rows in the packed layout) and independent of `layers` but for the parameter copy; no
+ * gradient buffer, no per-layer block. In the padded layout the size never shrinks as batch or seq_len grow: a
+ * workspace sized for the largest batch serves every smaller one. Too small: XFMR_EWORKSPACE before anything is launched. */
+size_t xfmr_encoder_infer_workspace_bytes(const xfmr_encoder_cfg* cfg);
+int xfmr_encoder_infer(const xfmr_encoder_cfg* cfg, const float* params, const int64_t* item_idx, const float* table,
+                       int64_t n_rows, float* tok, uint8_t* key_mask, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* Pooling over the token axis: sentence-transformers Pooling(pooling_mode) as wired at xfmr_rec/models.py:143-145
  * for the modes ModelConfig.pooling_mode allows (models.py:47): mean = sum_t tok*m / max(sum_t m, 1e-9);
  * max = max_t (m ? tok : -1e9); cls = tok[:,0]; lasttoken = the last token with m != 0 (zero if none).

@@ -1,0 +1,284 @@
+"""The forward-only encoder pass (xfmr_encoder_infer) returns the training forward's bits.
+
+The reference of every case is xfmr_encoder_fwd with the same cfg, the same flags and dropout 0, and the assertion is
+``torch.equal`` on tok and key_mask -- no tolerance: the forward-only pass runs the same kernel forms in the same order, on
+instantiations that only leave out the stores a backward would read. Every case runs right-padded ragged histories (one of
+length 1, one of full length, padding rows = item 0). Before the call the workspace is filled with 0xFF bytes (NaN in fp32
+and bf16: nothing may be read before it is written) and sits between two 4 KiB guard bands that must come back untouched; a
+second call into the same, un-refilled workspace gives the same bits. The shapes are the smallest that reach each form
+(the plan is read back through xf_encoder_plan). Three cases are also held to the fp64 restatement of the encoder
+(oracle/encoder.py) at tests/helpers.py's `val` limits."""
+
+import ctypes as C
+
+import pytest
+import torch
+
+from helpers import assert_close, unit_table
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+V = 200
+GUARD = 4096
+BIDIRECTIONAL, LN_UNFUSED, FFN_UNFUSED = 1, 2, 4
+
+# name -> (B, L, H, heads, I, layers)
+SHAPES = {
+    "a": (3, 40, 64, 2, 128, 3),      # generic forms, both ping-pong parities, last layer
+    "b": (3, 40, 128, 2, 256, 2),     # head size 64
+    "c": (62, 200, 128, 4, 512, 2),   # 12 400 tokens: LayerNorm-fused GEMMs, FFN as two GEMMs
+    "d": (82, 200, 128, 4, 512, 3),   # 16 400 tokens: fused FFN
+    "e": (82, 200, 128, 4, 320, 2),   # LayerNorm-fused, I not a multiple of 128
+    "i": (2, 600, 64, 2, 128, 1),     # attention beyond the one-workgroup forms
+}
+# the forms (fuse_ln, fuse_ffn) the default-flag bf16 plan must reach for the case to test what its row says
+FORMS = {"a": (0, 0), "b": (0, 0), "c": (1, 0), "d": (1, 1), "e": (1, 0), "i": (0, 0)}
+
+
+def _lengths(B, L, seed):
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.randint(2, L, (B,), generator=g).tolist()
+    lens[0], lens[-1] = L, 1  # one full-length sequence, one of a single row
+    return lens
+
+
+_INPUTS = {}
+
+
+def inputs(name):
+    """(flat fp32 parameters, (B, L) item rows, lengths, table) of a case, on the device; made once."""
+    if name not in _INPUTS:
+        from oracle import encoder as OE
+        from xfmr_rec_amd.models import encoder_param_names
+
+        B, L, H, A, I, layers = SHAPES[name]
+        p = OE.init_params(H, layers, I, L, seed=7)
+        g = torch.Generator().manual_seed(11)
+        for k, v in p.items():  # biases and LayerNorm weights off their 0 / 1 defaults: every term of every epilogue counts
+            if v.dim() == 1:
+                v += 0.05 * torch.randn(v.shape, generator=g)
+        flat = torch.cat([p[k].reshape(-1) for k in encoder_param_names(layers)]).to(DEV)
+        lens = _lengths(B, L, seed=3)
+        idx = torch.zeros(B, L, dtype=torch.int64)
+        for b, n in enumerate(lens):
+            idx[b, :n] = torch.randint(1, V + 1, (n,), generator=g)
+        _INPUTS[name] = (flat, idx.to(DEV), lens, unit_table(V, H).to(DEV), p)
+    return _INPUTS[name]
+
+
+def make_cfg(ops, name, prec, flags=0, packed=None):
+    B, L, H, A, I, layers = SHAPES[name]
+    return ops.make_encoder_cfg(batch=B, seq_len=L, hidden=H, heads=A, inter=I, layers=layers, max_pos=L, precision=prec,
+                                flags=flags, seq_offsets=packed["seq_offsets"] if packed else None,
+                                row_pos=packed["row_pos"] if packed else None)
+
+
+def plan_of(cfg):
+    from xfmr_rec_amd import _native as N
+
+    lib = C.CDLL(str(N.LIB_PATH))
+    lib.xf_encoder_plan.restype, lib.xf_encoder_plan.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
+    out = (C.c_int32 * 16)()
+    assert lib.xf_encoder_plan(C.byref(cfg), out) == 0
+    return dict(T=out[1], fuse_ln=out[4], fuse_ffn=out[5], rederive=out[6])
+
+
+def infer_guarded(ops, cfg, flat, idx, table):
+    """Two calls of xfmr_encoder_infer into one workspace of exactly the library's size, NaN-filled before the first call
+    only, between two guard bands. Returns the first call's (tok, key_mask) after checking the second's and the guards."""
+    from xfmr_rec_amd import _native as N
+
+    nbytes = N.load().xfmr_encoder_infer_workspace_bytes(C.byref(cfg))
+    assert nbytes > 0 and nbytes % 16 == 0
+    buf = torch.empty(GUARD + nbytes + GUARD, dtype=torch.uint8, device=DEV)
+    buf[:GUARD] = 0xA5
+    buf[GUARD + nbytes:] = 0x5A
+    ws = buf[GUARD:GUARD + nbytes]
+    ws.fill_(0xFF)
+    tok, km, used = ops.encoder_infer_fwd(cfg, flat, idx, table, workspace=ws)
+    assert used.data_ptr() == ws.data_ptr() and used.numel() == nbytes
+    tok2, km2, _ = ops.encoder_infer_fwd(cfg, flat, idx, table, workspace=ws)
+    torch.cuda.synchronize()
+    assert bool((buf[:GUARD] == 0xA5).all()) and bool((buf[GUARD + nbytes:] == 0x5A).all()), "guard band written"
+    assert torch.equal(tok, tok2) and torch.equal(km, km2), "second call into the used workspace differs"
+    assert not tok.requires_grad and bool(torch.isfinite(tok).all())
+    return tok, km
+
+
+def check_case(name, prec, flags=0, packed=False, forms=None):
+    from xfmr_rec_amd import ops
+
+    flat, idx, lens, table, _ = inputs(name)
+    B, L = idx.shape
+    pk = None
+    item = idx
+    if packed:
+        order, offs64 = ops.length_order(lens)
+        rows = int(offs64[-1])
+        assert rows < B * L
+        pk = ops.pack_rows(idx, idx, None, offs64.to(DEV), rows, order=order.to(DEV))
+        item = pk["hist"]
+    cfg = make_cfg(ops, name, prec, flags, pk)
+    plan = plan_of(cfg)
+    if forms is not None:
+        assert (plan["fuse_ln"], plan["fuse_ffn"]) == forms, (name, plan)
+    want_tok, want_km, _acts = ops.encoder_fwd(cfg, flat, item, table)
+    tok, km = infer_guarded(ops, cfg, flat, item, table)
+    assert tok.shape == want_tok.shape and km.shape == want_km.shape
+    assert torch.equal(km, want_km), f"{name} {prec}: key_mask differs"
+    assert torch.equal(tok, want_tok), (f"{name} {prec} flags={flags} packed={packed}: tok differs in "
+                                        f"{int((tok != want_tok).sum())} of {tok.numel()} elements")
+    if not packed:
+        assert torch.equal(km.bool(), idx != 0)
+    return tok, km
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+@pytest.mark.parametrize("name", ["a", "b"])
+def test_generic_forms_equal_the_training_forward(name, prec):
+    check_case(name, prec, forms=FORMS[name] if prec == "bf16" else (0, 0))
+
+
+@pytest.mark.parametrize("name", ["c", "d", "e"])
+def test_fused_forms_equal_the_training_forward(name):
+    check_case(name, "bf16", forms=FORMS[name])
+
+
+@pytest.mark.parametrize("flag,forms", [(LN_UNFUSED, (0, 0)), (FFN_UNFUSED, (1, 0))], ids=["ln_unfused", "ffn_unfused"])
+def test_unfused_flags_equal_the_training_forward_under_the_same_flag(flag, forms):
+    check_case("d", "bf16", flags=flag, forms=forms)
+
+
+@pytest.mark.parametrize("name", ["a", "d"])
+def test_packed_layout_equals_the_training_forward(name):
+    tok, km = check_case(name, "bf16", packed=True, forms=FORMS[name])
+    assert tok.dim() == 2 and bool(km.all())  # only each sequence's own rows
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+def test_bidirectional_equals_the_training_forward(prec):
+    check_case("a", prec, flags=BIDIRECTIONAL)
+
+
+def test_long_sequences_equal_the_training_forward():
+    check_case("i", "bf16", forms=FORMS["i"])
+
+
+def test_the_stored_residual_gives_the_rederived_ones_bits():
+    """The training forward of the fused cases above re-derived its residuals (plan.rederive); the forward-only pass always
+    loads the stored LayerNorm output. XFMR_LN_STORE_X=1 makes the training forward load it too: the same bits again."""
+    import os
+
+    from xfmr_rec_amd import ops
+
+    flat, idx, _, table, _ = inputs("d")
+    cfg = make_cfg(ops, "d", "bf16")
+    assert plan_of(cfg)["rederive"] == 1
+    tok, km = infer_guarded(ops, cfg, flat, idx, table)
+    old = os.environ.get("XFMR_LN_STORE_X")
+    os.environ["XFMR_LN_STORE_X"] = "1"
+    try:
+        assert plan_of(cfg)["rederive"] == 0
+        want_tok, want_km, _ = ops.encoder_fwd(cfg, flat, idx, table)
+    finally:
+        if old is None:
+            del os.environ["XFMR_LN_STORE_X"]
+        else:
+            os.environ["XFMR_LN_STORE_X"] = old
+    assert torch.equal(tok, want_tok) and torch.equal(km, want_km)
+
+
+def test_refuses_dropout_and_a_short_workspace_on_the_device():
+    from xfmr_rec_amd import _native as N
+    from xfmr_rec_amd import ops
+
+    flat, idx, _, table, _ = inputs("a")
+    B, L, H, A, I, layers = SHAPES["a"]
+    kw = dict(batch=B, seq_len=L, hidden=H, heads=A, inter=I, layers=layers, max_pos=L, precision="bf16", flags=0)
+    with pytest.raises(RuntimeError, match="invalid argument"):
+        ops.encoder_infer_fwd(ops.make_encoder_cfg(**kw, hidden_dropout=0.1), flat, idx, table)
+    cfg = ops.make_encoder_cfg(**kw)
+    nbytes = N.load().xfmr_encoder_infer_workspace_bytes(C.byref(cfg))
+    with pytest.raises(RuntimeError, match="workspace too small"):
+        ops.encoder_infer_fwd(cfg, flat, idx, table, workspace=torch.empty(nbytes - 1, dtype=torch.uint8, device=DEV))
+
+
+@pytest.mark.parametrize("H", [64, 128, 256, 96])
+def test_layernorm_instantiations_without_statistics_round_like_the_training_ones(H):
+    """The LayerNorm kernels one at a time (internal entries): with pre / mean / rstd null the forward-only instantiation
+    runs, and writes the training instantiation's y, y16 and key_mask. (The vectorised kernels' sum of squares was once
+    contracted differently in the two: an ulp of rstd apart.) H = 96: the scalar kernel."""
+    from xfmr_rec_amd import _native as N
+
+    N.load()
+    lib, P = C.CDLL(str(N.LIB_PATH)), C.c_void_p
+    lib.xf_layernorm_fwd_ex.restype = C.c_int
+    lib.xf_layernorm_fwd_ex.argtypes = [P, P, P, P, P, P, P, C.c_int64, C.c_int32, C.c_float, P]
+    lib.xf_embed_ln_fwd_ex.restype = C.c_int
+    lib.xf_embed_ln_fwd_ex.argtypes = [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_float, C.c_float, N.Seed, C.c_uint32, P]
+    g = torch.Generator().manual_seed(H)
+    M, B, L = 123, 3, 41
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    dev = lambda *s: torch.randn(*s, generator=g).to(DEV)  # noqa: E731
+    x, gamma, beta = 3.0 * dev(M, H) + 1.0, dev(H), dev(H)
+    table, pos, typ = dev(V + 1, H), dev(L, H), dev(2, H)
+    table[0] = 0
+    idx = torch.randint(0, V + 1, (B, L), generator=g).to(DEV)
+    outs = []
+    for keep in (True, False):
+        y, y16 = torch.empty(M, H, device=DEV), torch.empty(M, H, dtype=torch.bfloat16, device=DEV)
+        mean, rstd = (torch.empty(M, device=DEV), torch.empty(M, device=DEV)) if keep else (None, None)
+        assert lib.xf_layernorm_fwd_ex(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(y16), ptr(mean), ptr(rstd), M, H, 1e-12,
+                                       N.stream()) == 0
+        o, o16 = torch.empty(B, L, H, device=DEV), torch.empty(B, L, H, dtype=torch.bfloat16, device=DEV)
+        km = torch.empty(B, L, dtype=torch.uint8, device=DEV)
+        pre, mu, rs = (torch.empty(B, L, H, device=DEV), torch.empty(B, L, device=DEV),
+                       torch.empty(B, L, device=DEV)) if keep else (None, None, None)
+        assert lib.xf_embed_ln_fwd_ex(ptr(idx), ptr(table), V + 1, ptr(pos), ptr(typ), ptr(gamma), ptr(beta), ptr(o), ptr(o16),
+                                      ptr(pre), ptr(mu), ptr(rs), ptr(km), B, L, H, 1e-12, 0.0, N.Seed(0, None), 0,
+                                      N.stream()) == 0
+        torch.cuda.synchronize()
+        outs.append((y, y16, o, o16, km))
+    for name, a, b in zip(("y", "y16", "embed.out", "embed.out16", "key_mask"), *outs):
+        assert torch.equal(a, b), f"H={H} {name}: {int((a != b).sum())} of {a.numel()} elements differ"
+    # half-given statistics are refused: all of them (training) or none (forward-only)
+    assert lib.xf_layernorm_fwd_ex(ptr(x), ptr(gamma), ptr(beta), ptr(outs[0][0]), None, ptr(torch.empty(M, device=DEV)), None,
+                                   M, H, 1e-12, N.stream()) == -1
+
+
+# ---- against fp64: the encoder restated in oracle/encoder.py, at helpers.TOL's `val` limits
+def _fp64_reference(name, layers=None):
+    from oracle import encoder as OE
+
+    _, idx, _, table, p = inputs(name)
+    if layers is not None:
+        p = {k: v for k, v in p.items() if not k.startswith("encoder.layer.") or int(k.split(".")[2]) < layers}
+    p64 = {k: v.double() for k, v in p.items()}
+    idx_c = idx.cpu()
+    emb = table.cpu().double()[idx_c]
+    return OE.encoder_forward(p64, emb, (idx_c != 0), SHAPES[name][3]), idx_c != 0
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+def test_generic_forms_against_fp64(prec):
+    from xfmr_rec_amd import ops
+
+    flat, idx, _, table, _ = inputs("a")
+    tok, _ = infer_guarded(ops, make_cfg(ops, "a", prec), flat, idx, table)
+    ref, valid = _fp64_reference("a")
+    assert_close("infer.tok", tok.cpu()[valid], ref[valid], prec)
+
+
+def test_fused_forms_against_fp64_one_layer():
+    from xfmr_rec_amd import ops
+    from xfmr_rec_amd.models import flat_layout
+
+    flat, idx, _, table, _ = inputs("d")
+    B, L, H, A, I, _ = SHAPES["d"]
+    cfg = ops.make_encoder_cfg(batch=B, seq_len=L, hidden=H, heads=A, inter=I, layers=1, max_pos=L, precision="bf16", flags=0)
+    assert (plan_of(cfg)["fuse_ln"], plan_of(cfg)["fuse_ffn"]) == (1, 1)
+    flat1 = flat[:flat_layout(H, I, L, 1)[3]].contiguous()  # (the flat buffer is layer-major: layer 0 is its head)
+    tok, _ = infer_guarded(ops, cfg, flat1, idx, table)
+    ref, valid = _fp64_reference("d", layers=1)
+    assert_close("infer.tok", tok.cpu()[valid], ref[valid], "bf16")

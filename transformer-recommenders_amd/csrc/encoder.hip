@@ -122,6 +122,12 @@ struct EncPlan {
   int half_layer;  // the layer behind which the upper half of the gradient is reduced early; -1: none
 };
 constexpr int64_t kDwSideTokens = 40960;
+// the token counts (batch x seq_len) from which the LayerNorm-fused GEMMs and the fused FFN kernel run: make_plan has the reasons
+constexpr int64_t kFfnFusedTokens = 16384;
+int64_t ln_fused_min_tokens() {
+  static const int64_t min_tokens = [] { const char* e = getenv("XFMR_LN_FUSED_MIN_TOKENS"); return e ? (int64_t)atoll(e) : (int64_t)12288; }();
+  return min_tokens;
+}
 EncPlan make_plan(const xfmr_encoder_cfg* c) {
   EncPlan p{};
   const uint32_t f = c->flags;
@@ -134,12 +140,11 @@ EncPlan make_plan(const xfmr_encoder_cfg* c) {
   // -1.5 % fused; batch 128: +0.9 %; 512: +1.8 %)
   // (round 4: from 12 288 tokens -- batch 64 x 200: 0.876 against 0.889 ms with the two LayerNorm-fused GEMMs and the FFN as
   //  separate GEMMs; at batch 32 nothing in it, 0.662 against 0.661-0.672. XFMR_LN_FUSED_MIN_TOKENS for experiments.)
-  static const int64_t min_tokens = [] { const char* e = getenv("XFMR_LN_FUSED_MIN_TOKENS"); return e ? (int64_t)atoll(e) : (int64_t)12288; }();
-  p.fuse_ln = p.mix && c->hidden == 128 && p.Tplan >= min_tokens && !(f & XFMR_ENC_LN_UNFUSED);
+  p.fuse_ln = p.mix && c->hidden == 128 && p.Tplan >= ln_fused_min_tokens() && !(f & XFMR_ENC_LN_UNFUSED);
   // FFN1 -> GELU -> FFN2 -> LayerNorm as one forward kernel (gemm.hip: ffn_fwd_fused_kernel): the same conditions plus I a
   // multiple of its chunk widths
   // (the fused FFN pair keeps its 16 384 tokens: at 12 800 it measured 0.887 against 0.876 ms for the separate GEMMs)
-  p.fuse_ffn = p.fuse_ln && p.Tplan >= 16384 && (c->inter % 128) == 0 && c->inter <= 1024 && !(f & XFMR_ENC_FFN_UNFUSED);
+  p.fuse_ffn = p.fuse_ln && p.Tplan >= kFfnFusedTokens && (c->inter % 128) == 0 && c->inter <= 1024 && !(f & XFMR_ENC_FFN_UNFUSED);
   // Under the LayerNorm-fused forms the fp32 LayerNorm outputs x0, x1 and x2 (of every layer but the last) are not stored: the
   // backward never reads them, and their one reader -- the next kernel's residual operand -- re-derives them from pre / mean /
   // rstd, which are stored for the backward anyway (XfLnResidual). XFMR_LN_STORE_X=1 (read per call: tests, A/B timing)
@@ -287,6 +292,65 @@ int check_cfg(const xfmr_encoder_cfg* c) {
   return XFMR_OK;
 }
 
+// ---- the forward-only pass (xfmr_encoder_infer): the same forms as the training forward, nothing kept for a backward
+// What one run of the forward routine (encoder_forward) reads and writes beside the caller's tensors: the embedding LayerNorm's
+// buffers, the bf16 parameter copy, every layer's LayerActs. Training hands it the workspace's per-layer blocks; the
+// forward-only pass two sets that alternate by layer, with nulls where nothing is kept.
+struct FwdBufs {
+  float *emb_pre, *emb_mean, *emb_rstd, *x0;
+  void *x0b, *wbf;
+  float* ln_tmp;  // forward-only, LayerNorm as a launch of its own: the [T][H] pre-LayerNorm sum between the two launches
+  LayerActs set[2];
+  const Workspace* ws;  // training: layer i's block is ws->layer(i); null: set[i & 1]
+  bool keep;            // training: pre / mean / rstd, u / gelu(u) / gelu'(u) are stored for the backward
+  LayerActs layer(int i) const { return ws ? ws->layer(i) : set[i & 1]; }
+};
+// The forward-only workspace: sized by the rows actually run (plan.T), whatever the layer count -- the embedding LayerNorm's
+// output, one qkv / ctx / lse, two sets of LayerNorm outputs, the [T][I] gelu output and the [T][H] pre-LayerNorm sum only
+// where the plan runs those as launches of their own, the bf16 parameter copy. base may be null (size query).
+struct InferSpace { FwdBufs b; size_t total; };
+InferSpace carve_infer(const xfmr_encoder_cfg* c, const EncPlan& plan, unsigned char* base) {
+  const size_t T = (size_t)plan.T, TH = T * c->hidden, TI = T * c->inter, es = plan.mix ? 2 : 4;
+  const size_t xb = plan.mix ? TH * 2 : 0;
+  Bump k{base, 0};
+  InferSpace s{};
+  FwdBufs& b = s.b;
+  b.x0 = k.f32(TH); b.x0b = k.bytes(xb);
+  LayerActs shared{};
+  shared.qkv = k.bytes(3 * TH * es); shared.ctx = k.bytes(TH * es);
+  shared.lse = k.f32((size_t)c->batch * c->heads * c->seq_len);
+  shared.g = k.bytes(plan.fuse_ffn ? 0 : TI * es);
+  b.ln_tmp = k.f32(plan.fuse_ln ? 0 : TH);
+  for (LayerActs& l : b.set) {
+    l = shared;
+    l.x1 = k.f32(TH); l.x1b = k.bytes(xb); l.x2 = k.f32(TH); l.x2b = k.bytes(xb);
+  }
+  b.wbf = k.bytes(plan.mix ? (size_t)xfmr_param_count(c) * 2 : 0);
+  s.total = k.o;
+  return s;
+}
+// What the call asks of its caller: the carve, and in the padded layout never less than a smaller batch or a shorter seq_len
+// would need -- a workspace sized for the largest batch serves every smaller one. The carve alone steps DOWN where a form
+// sets in (the fused FFN needs no [T][I] buffer, the LayerNorm-fused GEMMs no [T][H] one); the floor is the carve of the last
+// token count below each such step, and is overtaken within a fifth more tokens. (Packed rows: the forms follow batch x
+// seq_len, the size the rows run -- no step, no floor.)
+size_t infer_bytes(const xfmr_encoder_cfg* c, const EncPlan& plan, size_t carved) {
+  size_t need = carved;
+  if (c->seq_offsets) return need;
+  for (const int64_t tokens : {kFfnFusedTokens - 1, ln_fused_min_tokens() - 1}) {
+    if (tokens < 1 || tokens >= plan.Tplan || tokens > 0x7fffffff) continue;
+    xfmr_encoder_cfg below = *c;
+    below.batch = 1; below.seq_len = below.max_pos = (int32_t)tokens;
+    const size_t n = carve_infer(&below, make_plan(&below), nullptr).total;
+    if (n > need) need = n;
+  }
+  return need;
+}
+int check_infer_cfg(const xfmr_encoder_cfg* c) {
+  if (const int rc = check_cfg(c)) return rc;
+  return (c->hidden_dropout != 0.f || c->attn_dropout != 0.f) ? XFMR_EINVAL : XFMR_OK;  // this entry is eval
+}
+
 enum { SITE_EMB = 0 };
 inline uint32_t site_attn(int i) { return 1 + 4 * (uint32_t)i; }
 inline uint32_t site_out(int i) { return 2 + 4 * (uint32_t)i; }
@@ -382,28 +446,26 @@ int xfmr_context_destroy(void* context) {
   return XFMR_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
 // The residual operand of a "Linear + dropout + residual + LayerNorm": the output of an earlier LayerNorm, either loaded
 // (x: the stored fp32 copy) or, under EncPlan::rederive, re-derived from what that LayerNorm stored for its backward (re).
 struct Residual { const float* x; XfLnResidual re; };
 
-int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int64_t* item_idx,
-                     const float* table, int64_t n_rows, float* tok, uint8_t* key_mask, void* acts,
-                     size_t acts_bytes, void* stream) {
-  XF_TRY(check_cfg(cfg));
-  if (!params || !item_idx || !table || !tok || !key_mask || !acts) return XFMR_EINVAL;
-  if (!xf_aligned16(params) || !xf_aligned16(acts) || !xf_aligned16(tok) || !xf_aligned16(table)) return XFMR_EALIGN;
-  const EncPlan plan = make_plan(cfg);
-  const Workspace ws = carve(cfg, plan, (unsigned char*)acts);
-  const Acts& a = ws.a;
-  if (acts_bytes < a.total) return XFMR_EWORKSPACE;
+// The forward pass, written once: xfmr_encoder_fwd and xfmr_encoder_infer differ in the buffers they hand it (FwdBufs) and in
+// nothing else. With bufs.keep off (forward-only) every product goes through the same kernel form, in the same order, on an
+// instantiation that stores nothing a backward would read; the residual is always the stored fp32 LayerNorm output.
+int encoder_forward(const xfmr_encoder_cfg* cfg, const EncPlan& plan, const FwdBufs& a, const float* params,
+                    const int64_t* item_idx, const float* table, int64_t n_rows, float* tok, uint8_t* key_mask, hipStream_t st) {
   const int B = cfg->batch, L = cfg->seq_len, H = cfg->hidden, I = cfg->inter, A = cfg->heads;
   const int32_t* const offs = cfg->seq_offsets;
   const int64_t T = plan.T;
   const int prec = cfg->precision;
-  const bool mix = plan.mix, rederive = plan.rederive;
+  const bool mix = plan.mix, keep = a.keep, rederive = plan.rederive && keep;
   const float hdrop = cfg->hidden_dropout, eps = cfg->ln_eps;
-  hipStream_t st = (hipStream_t)stream;
-  const XfSeed sd(cfg->seed, cfg->step_device);
+  const XfSeed sd(cfg->seed, keep ? cfg->step_device : nullptr);
   ParamLayout pl;
   layer_base(cfg, 0, &pl);
   float* const x0 = rederive ? nullptr : a.x0;
@@ -431,21 +493,26 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
     return mix ? reinterpret_cast<const float*>((const __bf16*)a.wbf + off) : params + off;
   };
   // pre <- dropout(in W^T + bias) + res; y / y16 / mean / rstd <- LayerNorm(pre): in the GEMM epilogue with the residual
-  // re-derived or loaded (the tile spans whole rows), or as two launches
+  // re-derived or loaded (the tile spans whole rows), or as two launches. Forward-only: pre / mean / rstd are null -- the
+  // epilogue form that does not store them, or the two launches with the sum in a.ln_tmp and no statistics out.
   auto linear_ln = [&](const void* in, int64_t w, int64_t bias, int K, const Residual& res, uint32_t site, int64_t gamma,
                        int64_t beta, float* pre, float* y, void* y16, float* mean, float* rstd) -> int {
     if (rederive)
       return xf_linear_ln_fwd_re(in, W(w), params + bias, pre, T, H, K, &res.re, hdrop, sd, site, params + gamma,
                                  params + beta, eps, y, y16, mean, rstd, prec, sA | sB, st);
+    if (plan.fuse_ln && !keep)
+      return xf_linear_ln_fwd_infer(in, W(w), params + bias, T, H, K, res.x, params + gamma, params + beta, eps, y, y16, prec,
+                                    sA | sB, st);
     if (plan.fuse_ln)
       return xf_linear_ln_fwd_ex(in, W(w), params + bias, pre, T, H, K, res.x, hdrop, sd, site, params + gamma,
                                  params + beta, eps, y, y16, mean, rstd, prec, sA | sB, st);
-    XF_TRY(xf_linear_fwd_ex(in, W(w), params + bias, pre, T, H, K, XFMR_EPI_BIAS_DROP_RES, res.x, nullptr, hdrop, sd, site,
+    float* const sum = keep ? pre : a.ln_tmp;
+    XF_TRY(xf_linear_fwd_ex(in, W(w), params + bias, sum, T, H, K, XFMR_EPI_BIAS_DROP_RES, res.x, nullptr, hdrop, sd, site,
                             prec, sA | sB, st));
-    return xf_layernorm_fwd_ex(pre, params + gamma, params + beta, y, y16, mean, rstd, T, H, eps, st);
+    return xf_layernorm_fwd_ex(sum, params + gamma, params + beta, y, y16, mean, rstd, T, H, eps, st);
   };
   for (int i = 0; i < cfg->layers; ++i) {
-    const LayerActs l = ws.layer(i);
+    const LayerActs l = a.layer(i);
     const LayerParams p = layer_params(cfg, i);
     const bool last = i == cfg->layers - 1;
     // the fp32 LayerNorm outputs (null: not stored) and their bf16 copies (null: fp32 storage / nobody reads it)
@@ -466,13 +533,18 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
       XF_TRY(rederive ? xf_ffn_fwd_fused_re(l.x1b, W(p.w1), params + p.b1, W(p.w2), params + p.b2, l.f1, l.g, l.pre2, T, H,
                                             I, &r1.re, hdrop, sd, site_ffn(i), params + p.ln2g, params + p.ln2b, eps, out,
                                             x2b, l.mean2, l.rstd2, st)
+             : !keep  ? xf_ffn_fwd_fused_infer(l.x1b, W(p.w1), params + p.b1, W(p.w2), params + p.b2, T, H, I, r1.x,
+                                               params + p.ln2g, params + p.ln2b, eps, out, x2b, st)
                       : xf_ffn_fwd_fused_ex(l.x1b, W(p.w1), params + p.b1, W(p.w2), params + p.b2, l.f1, l.g, l.pre2, T, H,
                                             I, r1.x, hdrop, sd, site_ffn(i), params + p.ln2g, params + p.ln2b, eps, out,
                                             x2b, l.mean2, l.rstd2, st));
     } else {
-      XF_TRY(xf_linear_fwd_ex(mix ? (const void*)l.x1b : (const void*)l.x1, W(p.w1), params + p.b1, l.g, T, I, H,
-                              XFMR_EPI_BIAS_GELU, nullptr, l.f1, 0.f, 0, 0, prec,
-                              sC | sA | sB | XF_AUX_GELU_GRAD, st));  // f1 <- gelu'(pre)
+      const void* const x1g = mix ? (const void*)l.x1b : (const void*)l.x1;
+      if (keep)
+        XF_TRY(xf_linear_fwd_ex(x1g, W(p.w1), params + p.b1, l.g, T, I, H, XFMR_EPI_BIAS_GELU, nullptr, l.f1, 0.f, 0, 0, prec,
+                                sC | sA | sB | XF_AUX_GELU_GRAD, st));  // f1 <- gelu'(pre)
+      else
+        XF_TRY(xf_linear_gelu_fwd_infer(x1g, W(p.w1), params + p.b1, l.g, T, I, H, prec, sC | sA | sB, st));
       XF_TRY(linear_ln(l.g, p.w2, p.b2, I, r1, site_ffn(i), p.ln2g, p.ln2b, l.pre2, out, x2b, l.mean2, l.rstd2));
     }
     XF_TRY(prof(cfg, XFMR_PROF_FFN_FWD, i, 1, st));
@@ -481,6 +553,43 @@ int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int
     xg = mix ? (const void*)l.x2b : (const void*)out;
   }
   return XFMR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int xfmr_encoder_fwd(const xfmr_encoder_cfg* cfg, const float* params, const int64_t* item_idx,
+                     const float* table, int64_t n_rows, float* tok, uint8_t* key_mask, void* acts,
+                     size_t acts_bytes, void* stream) {
+  XF_TRY(check_cfg(cfg));
+  if (!params || !item_idx || !table || !tok || !key_mask || !acts) return XFMR_EINVAL;
+  if (!xf_aligned16(params) || !xf_aligned16(acts) || !xf_aligned16(tok) || !xf_aligned16(table)) return XFMR_EALIGN;
+  const EncPlan plan = make_plan(cfg);
+  const Workspace ws = carve(cfg, plan, (unsigned char*)acts);
+  const Acts& a = ws.a;
+  if (acts_bytes < a.total) return XFMR_EWORKSPACE;
+  FwdBufs b{};
+  b.emb_pre = a.emb_pre; b.emb_mean = a.emb_mean; b.emb_rstd = a.emb_rstd; b.x0 = a.x0; b.x0b = a.x0b; b.wbf = a.wbf;
+  b.ws = &ws; b.keep = true;
+  return encoder_forward(cfg, plan, b, params, item_idx, table, n_rows, tok, key_mask, (hipStream_t)stream);
+}
+
+size_t xfmr_encoder_infer_workspace_bytes(const xfmr_encoder_cfg* cfg) {
+  if (check_cfg(cfg)) return 0;
+  const EncPlan plan = make_plan(cfg);
+  return infer_bytes(cfg, plan, carve_infer(cfg, plan, nullptr).total);
+}
+
+int xfmr_encoder_infer(const xfmr_encoder_cfg* cfg, const float* params, const int64_t* item_idx, const float* table,
+                       int64_t n_rows, float* tok, uint8_t* key_mask, void* workspace, size_t workspace_bytes, void* stream) {
+  XF_TRY(check_infer_cfg(cfg));
+  if (!params || !item_idx || !table || !tok || !key_mask || !workspace) return XFMR_EINVAL;
+  if (!xf_aligned16(params) || !xf_aligned16(workspace) || !xf_aligned16(tok) || !xf_aligned16(table)) return XFMR_EALIGN;
+  const EncPlan plan = make_plan(cfg);
+  const InferSpace s = carve_infer(cfg, plan, (unsigned char*)workspace);
+  if (workspace_bytes < infer_bytes(cfg, plan, s.total)) return XFMR_EWORKSPACE;
+  return encoder_forward(cfg, plan, s.b, params, item_idx, table, n_rows, tok, key_mask, (hipStream_t)stream);
 }
 
 int xfmr_encoder_bwd(const xfmr_encoder_cfg* cfg, const float* params, float* grads, float* d_tok,

@@ -76,10 +76,17 @@ namespace {
 // EPI_DROP_RES_LN_RE / _RED: EPI_DROP_RES_LN whose residual operand is not loaded from a stored fp32 tensor but RE-DERIVED
 // from what the LayerNorm that produced it stored for its backward (its input, mean, rstd; gamma, beta) -- xf_ln_out_drop4;
 // _RED: ... followed by the dropout of that output (layer 0: the residual is the embedding LayerNorm's dropped-out output).
+// EPI_DROP_RES_LN_INFER: EPI_DROP_RES_LN (loaded residual) of the forward-only pass (xfmr_encoder_infer): Y / Y16 only -- no C
+// (pre), mean or rstd store, which only a backward reads. Same arithmetic in the same order: the same Y bits.
+// EPI_GELU_INFER: EPI_GELU without the C2 store (the pre-activation or gelu' the FFN2 dX epilogue would read); xf_gelu and
+// xf_gelu_both evaluate gelu by the same expression, so C has EPI_GELU's bits with or without XF_AUX_GELU_GRAD.
 // Separate instantiations: the variants cost registers the plain form does not pay.
 enum { EPI_STORE = 0, EPI_GELU = 1, EPI_DROP_RES = 2, EPI_GELU_GRAD = 3, EPI_SPLITK = 4, EPI_DROP_RES_LN = 5,
-       EPI_DX_LNBWD = 6, EPI_DROP_RES_LN_RE = 7, EPI_DROP_RES_LN_RED = 8 };
-constexpr bool epi_res_ln(int epi) { return epi == EPI_DROP_RES_LN || epi == EPI_DROP_RES_LN_RE || epi == EPI_DROP_RES_LN_RED; }
+       EPI_DX_LNBWD = 6, EPI_DROP_RES_LN_RE = 7, EPI_DROP_RES_LN_RED = 8, EPI_DROP_RES_LN_INFER = 9,
+       EPI_GELU_INFER = 10 };
+constexpr bool epi_res_ln(int epi) {
+  return epi == EPI_DROP_RES_LN || epi == EPI_DROP_RES_LN_RE || epi == EPI_DROP_RES_LN_RED || epi == EPI_DROP_RES_LN_INFER;
+}
 // residual operand of the EPI_DROP_RES_LN family: 0 = loaded (GemmArgs.R), 1 = re-derived, 2 = re-derived + dropout
 constexpr int epi_res_mode(int epi) { return epi == EPI_DROP_RES_LN_RE ? 1 : epi == EPI_DROP_RES_LN_RED ? 2 : 0; }
 
@@ -368,7 +375,8 @@ static RowTiles row_tiles(int64_t M, int BM, int64_t cus, bool short_on) {
 // columns, acc[j] = its 32 x 32 block j): bias + dropout + residual -> C (the pre-LayerNorm sum, kept for the backward),
 // LayerNorm -> Y (fp32) / Y16 (bf16 GEMM operand), mean / rstd per row. `smem`: >= 4 strips of 16 x 68 floats + 128
 // floats, free of live data (the callers alias their operand images after a barrier).
-template <int RES>  // epi_res_mode
+// KEEP = false (the forward-only forms): what only a backward reads -- C, mean, rstd -- is not stored.
+template <int RES, bool KEEP = true>  // RES: epi_res_mode
 __device__ __forceinline__ void epi_drop_res_ln_64x128(const f32x16 (&acc)[2], unsigned char* smem, const GemmArgs& g,
                                                        const int64_t m0, const int wid, const int lane) {
   // The wave owns 32 rows x 64 columns; a row's other 64 columns are with the partner wave (wc ^ 1). Lane ->
@@ -429,7 +437,7 @@ __device__ __forceinline__ void epi_drop_res_ln_64x128(const f32x16 (&acc)[2], u
       }
       v.x += res.x; v.y += res.y; v.z += res.z; v.w += res.w;
       if (m >= g.M) v = make_float4(0, 0, 0, 0);
-      else *reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + m * LDC + n) = v;
+      else if constexpr (KEEP) *reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + m * LDC + n) = v;
       vv[hf][ps] = v;
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -480,9 +488,11 @@ __device__ __forceinline__ void epi_drop_res_ln_64x128(const f32x16 (&acc)[2], u
       const float4 o = xf_ln_affine4(vv[hf][ps], rs, gm, bt);
       if (g.Y) *reinterpret_cast<float4*>(g.Y + m * LDC + n) = o;  // (null: the consumer re-derives it)
       if (g.Y16) xf_st4<true>(g.Y16, m * LDC + n, o);
-      if (wc == 0 && li == 0) {
-        g.ln_mean[m] = mean[hf][ps];
-        g.ln_rstd[m] = rs;
+      if constexpr (KEEP) {
+        if (wc == 0 && li == 0) {
+          g.ln_mean[m] = mean[hf][ps];
+          g.ln_rstd[m] = rs;
+        }
       }
     }
 }
@@ -722,7 +732,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g_in, const int bid) {
   // (one wave instruction = 4-8 rows x 128-256 B instead of 2 rows x 32 scattered 4- or 2-byte elements).
   __syncthreads();  // everyone is done with the operand images the scratch aliases
   if constexpr (epi_res_ln(EPI)) {
-    if constexpr (BM == 64 && BN == 128) epi_drop_res_ln_64x128<epi_res_mode(EPI)>(acc[0], smem, g, m0, wid, lane);
+    if constexpr (BM == 64 && BN == 128)
+      epi_drop_res_ln_64x128<epi_res_mode(EPI), EPI != EPI_DROP_RES_LN_INFER>(acc[0], smem, g, m0, wid, lane);
     return;
   }
   if constexpr (EPI == EPI_DX_LNBWD) {
@@ -838,6 +849,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g_in, const int bid) {
               d[q] = v[q];
               v[q].x = xf_gelu(v[q].x); v[q].y = xf_gelu(v[q].y); v[q].z = xf_gelu(v[q].z); v[q].w = xf_gelu(v[q].w);
             }
+          } else if (EPI == EPI_GELU_INFER) {
+            v[q].x = xf_gelu(v[q].x); v[q].y = xf_gelu(v[q].y); v[q].z = xf_gelu(v[q].z); v[q].w = xf_gelu(v[q].w);
           } else if (EPI == EPI_DROP_RES) {
             if (g.drop.on) {
               xf_drop4(g.drop, (uint32_t)m, (uint32_t)(n + 4 * q), v[q]);
@@ -939,9 +952,11 @@ struct WeightChunk {
 };
 
 // CH: columns of I per chunk: 128 (two workgroups' worth of registers) or 64. RE: the residual (this layer's LayerNorm 1
-// output) is re-derived from pre1 / mean1 / rstd1 in the epilogue (EPI_DROP_RES_LN_RE) instead of loaded.
-template <int CH, bool RE = false>
-__global__ __launch_bounds__(256, CH == 128 ? XF_FFN_MIN_WAVES : 3) void ffn_fwd_fused_kernel(const FfnFwdArgs f_in) {
+// output) is re-derived from pre1 / mean1 / rstd1 in the epilogue (EPI_DROP_RES_LN_RE) instead of loaded. KEEP = false (the
+// forward-only form, ffn_fwd_infer_kernel): U, G, pre, mean and rstd are not stored -- the row-major pass over sG only turns
+// u into gelu(u) in place.
+template <int CH, bool RE, bool KEEP>
+__device__ __forceinline__ void ffn_fwd_fused_body(const FfnFwdArgs& f_in) {
   FfnFwdArgs f = f_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
   XF_CHAIN_PRIO();
   f.e.drop = xf_drop_resolve(f.e.drop);
@@ -1046,9 +1061,11 @@ __global__ __launch_bounds__(256, CH == 128 ? XF_FFN_MIN_WAVES : 3) void ffn_fwd
       float4* cell = reinterpret_cast<float4*>(sG + row * LDC + ch * 8);
       const float4 u8 = *cell;
       const float4 g8 = xf_gelu_bf16x8(u8);
-      if (m0 + row < M) {
-        if (f.U) *reinterpret_cast<float4*>(f.U + (m0 + row) * I + c * CH + ch * 8) = u8;
-        if (f.G) *reinterpret_cast<float4*>(f.G + (m0 + row) * I + c * CH + ch * 8) = g8;
+      if constexpr (KEEP) {
+        if (m0 + row < M) {
+          if (f.U) *reinterpret_cast<float4*>(f.U + (m0 + row) * I + c * CH + ch * 8) = u8;
+          if (f.G) *reinterpret_cast<float4*>(f.G + (m0 + row) * I + c * CH + ch * 8) = g8;
+        }
       }
       *cell = g8;
     }
@@ -1070,8 +1087,16 @@ __global__ __launch_bounds__(256, CH == 128 ? XF_FFN_MIN_WAVES : 3) void ffn_fwd
   XF_STAMP(14);
   __syncthreads();  // everyone is done with sW: the epilogue's scratch aliases it
   XF_STAMP(15);
-  epi_drop_res_ln_64x128<RE ? 1 : 0>(accy, reinterpret_cast<unsigned char*>(sW), f.e, m0, wid, lane);
+  epi_drop_res_ln_64x128<RE ? 1 : 0, KEEP>(accy, reinterpret_cast<unsigned char*>(sW), f.e, m0, wid, lane);
   XF_STAMP(16);
+}
+template <int CH, bool RE = false>
+__global__ __launch_bounds__(256, CH == 128 ? XF_FFN_MIN_WAVES : 3) void ffn_fwd_fused_kernel(const FfnFwdArgs f_in) {
+  ffn_fwd_fused_body<CH, RE, true>(f_in);
+}
+template <int CH>
+__global__ __launch_bounds__(256, CH == 128 ? XF_FFN_MIN_WAVES : 3) void ffn_fwd_infer_kernel(const FfnFwdArgs f_in) {
+  ffn_fwd_fused_body<CH, false, false>(f_in);
 }
 
 // ---- fused FFN backward, dX chain (bf16 storage, H = 128) ----------------------------------------------------------------
@@ -1546,6 +1571,17 @@ GemmKernel tile_kernel(GemmOp op, int precision, uint32_t s16, int bm, int bn, i
     default: return nullptr;
   }
 }
+// The forward-only instantiation that goes with a kGemmLnFwd plan (same tile, slice depth and grid; EPI_DROP_RES_LN_INFER):
+// for the storage the encoder runs it with -- bf16 A and B operands on the whole-row tile. Null: no such kernel.
+// ... and with a kGemmFwdGelu plan (EPI_GELU_INFER): all fp32, or every operand bf16 (the encoder's two storages)
+GemmKernel gelu_infer_kernel(int precision, uint32_t s16, int bm, int bn, int bk) {
+  return tile_kernel_in<false, false, EPI_GELU_INFER, SABC>(precision, s16, bm, bn, bk);
+}
+GemmKernel ln_infer_kernel(int precision, uint32_t s16, int bm, int bn, int bk) {
+  if (precision != XFMR_PREC_BF16 || s16 != SAB || bm != 64 || bn != 128) return nullptr;
+  return bk == 64 ? gemm_kernel<PrecBF16, 64, 128, 64, false, false, EPI_DROP_RES_LN_INFER, SAB>
+                  : gemm_kernel<PrecBF16, 64, 128, 32, false, false, EPI_DROP_RES_LN_INFER, SAB>;
+}
 
 }  // namespace
 
@@ -1614,10 +1650,16 @@ int set_ln_residual(GemmArgs& g, const float* residual, const XfLnResidual* res,
 int linear_ln_fwd(const void* x, const float* w, const float* bias, float* pre, int64_t M, int32_t N, int32_t K,
                   const float* residual, const XfLnResidual* res, float dropout_p, XfSeed seed, uint32_t site,
                   const float* gamma, const float* beta, float eps, float* y, void* y16, float* mean, float* rstd,
-                  int32_t precision, uint32_t s16, hipStream_t st) {
-  if (!x || !w || !pre || !gamma || !beta || (!y && !y16) || !mean || !rstd) return XFMR_EINVAL;
+                  int32_t precision, uint32_t s16, hipStream_t st, bool infer = false) {
+  // infer: the forward-only form -- the kGemmLnFwd plan on its EPI_DROP_RES_LN_INFER instantiation; pre / mean / rstd are not taken
+  if (!x || !w || !gamma || !beta || (!y && !y16)) return XFMR_EINVAL;
+  if (infer ? (pre || mean || rstd || res) : (!pre || !mean || !rstd)) return XFMR_EINVAL;
   const GemmKey k{!res ? kGemmLnFwd : res->dropout_p > 0.f ? kGemmLnFwdReDrop : kGemmLnFwdRe, M, N, K, precision, s16, 1, xf_num_cus()};
-  const GemmPlan p = gemm_plan(k, gemm_switches_once());
+  GemmPlan p = gemm_plan(k, gemm_switches_once());
+  if (infer && !p.rc) {
+    p.kernel = (const void*)ln_infer_kernel(p.precision, p.s16, p.bm, p.bn, p.bk);
+    if (!p.kernel) p.rc = XFMR_EUNSUPPORTED;
+  }
   GemmArgs g{};
   g.A = x; g.B = w; g.C = pre; g.lda = K; g.ldb = K; g.ldc = N; g.M = M; g.N = N; g.K = K; g.k_chunk = 0;
   g.bias = bias;
@@ -1631,8 +1673,10 @@ int linear_ln_fwd(const void* x, const float* w, const float* bias, float* pre, 
 int ffn_fwd_fused(const void* x16, const void* w1_16, const float* b1, const void* w2_16, const float* b2, void* u16,
                   void* g16, float* pre, int64_t M, int32_t H, int32_t I, const float* residual, const XfLnResidual* res,
                   float dropout_p, XfSeed seed, uint32_t site, const float* gamma, const float* beta, float eps, float* y,
-                  void* y16, float* mean, float* rstd, hipStream_t st) {
-  if (!x16 || !w1_16 || !b1 || !w2_16 || !pre || !gamma || !beta || (!y && !y16) || !mean || !rstd) return XFMR_EINVAL;
+                  void* y16, float* mean, float* rstd, hipStream_t st, bool infer = false) {
+  // infer: the forward-only form (ffn_fwd_infer_kernel) on the kGemmFfnFwd plan; u16 / g16 / pre / mean / rstd are not taken
+  if (!x16 || !w1_16 || !b1 || !w2_16 || !gamma || !beta || (!y && !y16)) return XFMR_EINVAL;
+  if (infer ? (u16 || g16 || pre || mean || rstd || res) : (!pre || !mean || !rstd)) return XFMR_EINVAL;
   GemmPlan p = gemm_plan(GemmKey{res ? kGemmFfnFwdRe : kGemmFfnFwd, M, H, I, XFMR_PREC_BF16, 0, 1, xf_num_cus()}, gemm_switches());
   if (!p.rc_shape && res && res->dropout_p > 0.f) p.rc_shape = XFMR_EUNSUPPORTED;  // (no dropout on this kernel's residual)
   const bool aligned = xf_aligned16(x16) && xf_aligned16(w1_16) && xf_aligned16(w2_16) && xf_aligned16(pre) && xf_aligned16(y) &&
@@ -1651,8 +1695,9 @@ int ffn_fwd_fused(const void* x16, const void* w1_16, const float* b1, const voi
   g.drop = xf_make_dropout(dropout_p, seed, site);
   g.ln_gamma = gamma; g.ln_beta = beta; g.ln_eps = eps; g.Y = y; g.Y16 = y16; g.ln_mean = mean; g.ln_rstd = rstd;
   set_tiles(g, p);
-  const auto kernel = p.ffn_chunk == 64 ? (res ? ffn_fwd_fused_kernel<64, true> : ffn_fwd_fused_kernel<64, false>)
-                                        : (res ? ffn_fwd_fused_kernel<128, true> : ffn_fwd_fused_kernel<128, false>);
+  const auto kernel = infer ? (p.ffn_chunk == 64 ? ffn_fwd_infer_kernel<64> : ffn_fwd_infer_kernel<128>)
+                      : p.ffn_chunk == 64 ? (res ? ffn_fwd_fused_kernel<64, true> : ffn_fwd_fused_kernel<64, false>)
+                                          : (res ? ffn_fwd_fused_kernel<128, true> : ffn_fwd_fused_kernel<128, false>);
   hipLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3((unsigned)p.block), 0, st, f);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
@@ -1727,6 +1772,30 @@ int xf_linear_ln_fwd_re(const void* x, const float* w, const float* bias, float*
                        precision, s16, st);
 }
 
+int xf_linear_gelu_fwd_infer(const void* x, const float* w, const float* bias, void* y, int64_t M, int32_t N, int32_t K,
+                             int32_t precision, uint32_t s16, hipStream_t st) {
+  if (!x || !w || !y) return XFMR_EINVAL;
+  GemmPlan p = gemm_plan(GemmKey{kGemmFwdGelu, M, N, K, precision, s16, 1, 0}, gemm_switches_once());
+  if (!p.rc) {  // the plan's tile, slice depth and grid on the instantiation that stores no auxiliary output
+    p.kernel = (const void*)gelu_infer_kernel(p.precision, p.s16, p.bm, p.bn, p.bk);
+    if (!p.kernel) p.rc = XFMR_EUNSUPPORTED;
+  }
+  if (const int rc = plan_rc(p, xf_aligned16(x) && xf_aligned16(w) && xf_aligned16(y))) return rc;
+  GemmArgs g{};
+  g.A = x; g.B = w; g.C = y; g.lda = K; g.ldb = K; g.ldc = N; g.M = M; g.N = N; g.K = K; g.k_chunk = 0;
+  g.bias = bias;
+  g.drop = xf_make_dropout(0.f, 0, 0);
+  return launch_tile(p, g, st);
+}
+
+int xf_linear_ln_fwd_infer(const void* x, const float* w, const float* bias, int64_t M, int32_t N, int32_t K,
+                           const float* residual, const float* gamma, const float* beta, float eps, float* y, void* y16,
+                           int32_t precision, uint32_t s16, hipStream_t st) {
+  if (!residual || !y) return XFMR_EINVAL;
+  return linear_ln_fwd(x, w, bias, nullptr, M, N, K, residual, nullptr, 0.f, XfSeed(0, nullptr), 0, gamma, beta, eps, y, y16,
+                       nullptr, nullptr, precision, s16, st, true);
+}
+
 int xfmr_linear_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int32_t N, int32_t K,
                     int32_t epilogue, const float* residual, float* aux_out, float dropout_p, uint64_t seed,
                     uint32_t site, int32_t precision, void* stream) {
@@ -1749,6 +1818,14 @@ int xf_ffn_fwd_fused_re(const void* x16, const void* w1_16, const float* b1, con
   if (!res) return XFMR_EINVAL;
   return ffn_fwd_fused(x16, w1_16, b1, w2_16, b2, u16, g16, pre, M, H, I, nullptr, res, dropout_p, seed, site, gamma, beta,
                        eps, y, y16, mean, rstd, st);
+}
+
+int xf_ffn_fwd_fused_infer(const void* x16, const void* w1_16, const float* b1, const void* w2_16, const float* b2, int64_t M,
+                           int32_t H, int32_t I, const float* residual, const float* gamma, const float* beta, float eps,
+                           float* y, void* y16, hipStream_t st) {
+  if (!residual || !y) return XFMR_EINVAL;
+  return ffn_fwd_fused(x16, w1_16, b1, w2_16, b2, nullptr, nullptr, nullptr, M, H, I, residual, nullptr, 0.f, XfSeed(0, nullptr),
+                       0, gamma, beta, eps, y, y16, nullptr, nullptr, st, true);
 }
 
 int xf_ffn_bwd_dx_fused_ex(const void* dy16, const void* w2_16, const void* u16, const void* w1_16, void* di16, int64_t M,

@@ -115,6 +115,17 @@ int xf_linear_ln_fwd_re(const void* x, const float* w, const float* bias, float*
                         const XfLnResidual* res, float dropout_p, XfSeed seed, uint32_t site, const float* gamma,
                         const float* beta, float eps, float* y, void* y16, float* mean, float* rstd, int32_t precision,
                         uint32_t s16, hipStream_t st);
+// The forward-only forms (xfmr_encoder_infer): the plans of xf_linear_fwd_ex (GELU epilogue), xf_linear_ln_fwd_ex and
+// xf_ffn_fwd_fused_ex on instantiations that store nothing a backward would read -- no auxiliary GELU output, no pre / mean /
+// rstd, no u16 / g16. No dropout (eval); the residual is loaded. The outputs are the training forms' bits.
+int xf_linear_gelu_fwd_infer(const void* x, const float* w, const float* bias, void* y, int64_t M, int32_t N, int32_t K,
+                             int32_t precision, uint32_t s16, hipStream_t st);
+int xf_linear_ln_fwd_infer(const void* x, const float* w, const float* bias, int64_t M, int32_t N, int32_t K,
+                           const float* residual, const float* gamma, const float* beta, float eps, float* y, void* y16,
+                           int32_t precision, uint32_t s16, hipStream_t st);
+int xf_ffn_fwd_fused_infer(const void* x16, const void* w1_16, const float* b1, const void* w2_16, const float* b2, int64_t M,
+                           int32_t H, int32_t I, const float* residual, const float* gamma, const float* beta, float eps,
+                           float* y, void* y16, hipStream_t st);
 // The dX chain of the FFN backward in one kernel (bf16 storage, H = 128, I a multiple of 64; after the fused forward:
 // u16 = the saved pre-activation): di16 <- (dy16 W2) * gelu'(u16), then exactly xf_linear_bwd_dx_lnbwd_ex on di16 / W1.
 int xf_ffn_bwd_dx_fused_ex(const void* dy16, const void* w2_16, const void* u16, const void* w1_16, void* di16, int64_t M,
@@ -180,7 +191,8 @@ int xf_linear_bwd_dx_lnbwd_ex(const void* dy, const float* w, int64_t M, int32_t
 // (GemmPlan::records on this device; short last-round tiles: gemm.hip row_tiles)
 int xf_ln_row_tiles(int64_t M);
 // LayerNorm forward variants that also write a bf16 copy of the output (the operand of the GEMMs that consume it;
-// the fp32 output stays the residual stream). y16 / out16 may be null.
+// the fp32 output stays the residual stream). y16 / out16 may be null. mean / rstd (and the gather's pre) all null: the
+// forward-only instantiations, which store none of them and write the same output bits (xfmr_encoder_infer).
 int xf_layernorm_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y16, float* mean,
                         float* rstd, int64_t rows, int32_t H, float eps, hipStream_t stream);
 int xf_embed_ln_fwd_ex(const int64_t* item_idx, const float* table, int64_t n_rows, const float* pos_emb,

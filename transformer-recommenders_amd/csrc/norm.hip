@@ -26,8 +26,9 @@ struct LnFwdArgs {
   __bf16* y16;             // optional bf16 copy of y: the A / B operand of the GEMMs that consume the output
 };
 
-template <int NPL, bool GATHER>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a_in) {
+// KEEP = false (the forward-only forms, *_infer_kernel): pre, mean and rstd -- what only a backward reads -- are not stored.
+template <int NPL, bool GATHER, bool KEEP>
+__device__ __forceinline__ void ln_fwd_body(const LnFwdArgs& a_in) {
   LnFwdArgs a = a_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
   XF_CHAIN_PRIO();
   a.drop = xf_drop_resolve(a.drop);
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a_in) {
         e = src[c];
         nz |= (e != 0.f);
         e = (e + a.type_emb[c]) + pe[c];  // same association as TF:modeling_bert.py:100-104
-        a.pre[row * H + c] = e;
+        if constexpr (KEEP) a.pre[row * H + c] = e;
       }
       v[i] = e;
     }
@@ -76,9 +77,11 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a_in) {
   }
   const float var = xf_wave_sum(q) / (float)H;
   const float rstd = rsqrtf(var + a.eps);
-  if (lane == 0) {
-    a.mean[row] = mean;
-    a.rstd[row] = rstd;
+  if constexpr (KEEP) {
+    if (lane == 0) {
+      a.mean[row] = mean;
+      a.rstd[row] = rstd;
+    }
   }
 #pragma unroll
   for (int i = 0; i < NPL; ++i) {
@@ -91,6 +94,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a_in) {
     }
   }
 }
+template <int NPL, bool GATHER>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a_in) { ln_fwd_body<NPL, GATHER, true>(a_in); }
+template <int NPL, bool GATHER>
+__global__ __launch_bounds__(256) void ln_fwd_infer_kernel(const LnFwdArgs a_in) { ln_fwd_body<NPL, GATHER, false>(a_in); }
 
 // ---- LayerNorm backward --------------------------------------------------------------------------
 // dy is the gradient of the (possibly dropped-out, embedding site only) LayerNorm output.
@@ -182,8 +189,8 @@ __device__ __forceinline__ float row_sum(float v) {
   return v;
 }
 
-template <int LPR, bool GATHER>
-__global__ __launch_bounds__(256) void ln_fwd_v4_kernel(const LnFwdArgs a_in) {
+template <int LPR, bool GATHER, bool KEEP>
+__device__ __forceinline__ void ln_fwd_v4_body(const LnFwdArgs& a_in) {
   LnFwdArgs a = a_in;  // (device-side step counter -> dropout key: xf_drop_resolve)
   XF_CHAIN_PRIO();
   a.drop = xf_drop_resolve(a.drop);
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(const LnFwdArgs a_in) {
       const float4 ty = *reinterpret_cast<const float4*>(a.type_emb + c);
       const float4 pe = *reinterpret_cast<const float4*>(a.pos_emb + (int64_t)(a.row_pos ? a.row_pos[row] : (int)(row % a.L)) * H + c);
       v.x = (e.x + ty.x) + pe.x; v.y = (e.y + ty.y) + pe.y; v.z = (e.z + ty.z) + pe.z; v.w = (e.w + ty.w) + pe.w;
-      *reinterpret_cast<float4*>(a.pre + row * H + c) = v;
+      if constexpr (KEEP) *reinterpret_cast<float4*>(a.pre + row * H + c) = v;
     }
 #pragma unroll
     for (int o = LPR / 2; o > 0; o >>= 1) nz |= __shfl_xor(nz, o, 64);
@@ -213,12 +220,17 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(const LnFwdArgs a_in) {
   }
   const float mean = row_sum<LPR>((v.x + v.y) + (v.z + v.w)) / (float)H;
   const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
-  const float var = row_sum<LPR>((dx * dx + dy * dy) + (dz * dz + dw * dw)) / (float)H;
+  // (the sum of squares with its roundings written out -- two products rounded, two fmas --: what the compiler's contraction
+  //  made of (dx dx + dy dy) + (dz dz + dw dw) here, and did not make of it in the forward-only instantiation, whose
+  //  output then differed by an ulp of rstd. Both instantiations now round alike, by construction.)
+  const float var = row_sum<LPR>(__builtin_fmaf(dx, dx, dy * dy) + __builtin_fmaf(dz, dz, dw * dw)) / (float)H;
   const float rstd = rsqrtf(var + a.eps);
   if (!valid) return;
-  if (li == 0) {
-    a.mean[row] = mean;
-    a.rstd[row] = rstd;
+  if constexpr (KEEP) {
+    if (li == 0) {
+      a.mean[row] = mean;
+      a.rstd[row] = rstd;
+    }
   }
   const float4 g = *reinterpret_cast<const float4*>(a.gamma + c);
   const float4 b = *reinterpret_cast<const float4*>(a.beta + c);
@@ -229,6 +241,10 @@ __global__ __launch_bounds__(256) void ln_fwd_v4_kernel(const LnFwdArgs a_in) {
   if (a.y) *reinterpret_cast<float4*>(a.y + row * H + c) = o;  // (null: the consumer re-derives it -- xf_ln_out_drop4)
   if (a.y16) xf_st4<true>(a.y16, row * H + c, o);
 }
+template <int LPR, bool GATHER>
+__global__ __launch_bounds__(256) void ln_fwd_v4_kernel(const LnFwdArgs a_in) { ln_fwd_v4_body<LPR, GATHER, true>(a_in); }
+template <int LPR, bool GATHER>
+__global__ __launch_bounds__(256) void ln_fwd_v4_infer_kernel(const LnFwdArgs a_in) { ln_fwd_v4_body<LPR, GATHER, false>(a_in); }
 
 template <int LPR>
 __global__ __launch_bounds__(256) void ln_bwd_v4_kernel(const LnBwdArgs a_in) {
@@ -535,26 +551,39 @@ int npl_of(int H) { return (H + 63) / 64; }
 
 template <bool GATHER>
 int launch_ln_fwd(const LnFwdArgs& a, hipStream_t st) {
+  // pre (GATHER) / mean / rstd all null: the forward-only instantiations; all given: the training ones (the entries check)
+  const bool keep = a.mean != nullptr;
+  using Kernel = void (*)(const LnFwdArgs);
   dim3 block(256);
   if (a.H == 64 || a.H == 128 || a.H == 256) {
     const int rpw = 256 / a.H;  // rows per wave
     dim3 gridv((unsigned)((a.rows + 4 * rpw - 1) / (4 * rpw)));
-    if (a.H == 64) hipLaunchKernelGGL((ln_fwd_v4_kernel<16, GATHER>), gridv, block, 0, st, a);
-    else if (a.H == 128) hipLaunchKernelGGL((ln_fwd_v4_kernel<32, GATHER>), gridv, block, 0, st, a);
-    else hipLaunchKernelGGL((ln_fwd_v4_kernel<64, GATHER>), gridv, block, 0, st, a);
+    const Kernel k = a.H == 64    ? (keep ? ln_fwd_v4_kernel<16, GATHER> : ln_fwd_v4_infer_kernel<16, GATHER>)
+                     : a.H == 128 ? (keep ? ln_fwd_v4_kernel<32, GATHER> : ln_fwd_v4_infer_kernel<32, GATHER>)
+                                  : (keep ? ln_fwd_v4_kernel<64, GATHER> : ln_fwd_v4_infer_kernel<64, GATHER>);
+    hipLaunchKernelGGL(k, gridv, block, 0, st, a);
     XF_LAUNCH_CHECK();
     return XFMR_OK;
   }
   dim3 grid((unsigned)((a.rows + 3) / 4));
   const int npl = npl_of(a.H);
-  if (npl <= 1) hipLaunchKernelGGL((ln_fwd_kernel<1, GATHER>), grid, block, 0, st, a);
-  else if (npl <= 2) hipLaunchKernelGGL((ln_fwd_kernel<2, GATHER>), grid, block, 0, st, a);
-  else if (npl <= 4) hipLaunchKernelGGL((ln_fwd_kernel<4, GATHER>), grid, block, 0, st, a);
-  else if (npl <= 8) hipLaunchKernelGGL((ln_fwd_kernel<8, GATHER>), grid, block, 0, st, a);
-  else if (npl <= kMaxPerLane) hipLaunchKernelGGL((ln_fwd_kernel<16, GATHER>), grid, block, 0, st, a);
+  Kernel k;
+  if (npl <= 1) k = keep ? ln_fwd_kernel<1, GATHER> : ln_fwd_infer_kernel<1, GATHER>;
+  else if (npl <= 2) k = keep ? ln_fwd_kernel<2, GATHER> : ln_fwd_infer_kernel<2, GATHER>;
+  else if (npl <= 4) k = keep ? ln_fwd_kernel<4, GATHER> : ln_fwd_infer_kernel<4, GATHER>;
+  else if (npl <= 8) k = keep ? ln_fwd_kernel<8, GATHER> : ln_fwd_infer_kernel<8, GATHER>;
+  else if (npl <= kMaxPerLane) k = keep ? ln_fwd_kernel<16, GATHER> : ln_fwd_infer_kernel<16, GATHER>;
   else return XFMR_EUNSUPPORTED;
+  hipLaunchKernelGGL(k, grid, block, 0, st, a);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
+}
+
+// what a gather + LayerNorm keeps for its backward: all of pre / mean / rstd, or none of them (forward-only: `out` is then the
+// only fp32 copy of the output and has to be given)
+bool ln_keep_ok(const float* pre, const float* mean, const float* rstd, const float* out) {
+  const int n = (pre != nullptr) + (mean != nullptr) + (rstd != nullptr);
+  return n == 3 || (n == 0 && out != nullptr);
 }
 
 int ln_bwd_blocks(int64_t rows, int H, int* rows_per_block) {
@@ -660,6 +689,7 @@ int xfmr_embed_ln_fwd(const int64_t* item_idx, const float* table, int64_t n_row
                       const float* type_emb, const float* gamma, const float* beta, float* out, float* pre,
                       float* mean, float* rstd, uint8_t* key_mask, int32_t B, int32_t L, int32_t H, float eps,
                       float dropout_p, uint64_t seed, uint32_t site, void* stream) {
+  if (!pre || !mean || !rstd) return XFMR_EINVAL;  // (the public entry keeps them: the forward-only form is xfmr_encoder_infer's)
   return xf_embed_ln_fwd_ex(item_idx, table, n_rows, pos_emb, type_emb, gamma, beta, out, nullptr, pre, mean, rstd,
                             key_mask, B, L, H, eps, dropout_p, seed, site, (hipStream_t)stream);
 }
@@ -669,8 +699,9 @@ int xf_embed_ln_fwd_ex(const int64_t* item_idx, const float* table, int64_t n_ro
                        float* pre, float* mean, float* rstd, uint8_t* key_mask, int32_t B, int32_t L, int32_t H,
                        float eps, float dropout_p, XfSeed seed, uint32_t site, hipStream_t stream) {
   // (out may be null when out16 is given: the fp32 output is not stored -- its consumer re-derives it, xf_ln_out_drop4)
-  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !pre || !mean || !rstd || !key_mask)
-    return XFMR_EINVAL;
+  // (pre, mean and rstd all null: the forward-only form, nothing is kept for a backward -- the output is then stored)
+  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !key_mask) return XFMR_EINVAL;
+  if (!ln_keep_ok(pre, mean, rstd, out)) return XFMR_EINVAL;
   if (B <= 0 || L <= 0 || H <= 0 || n_rows <= 0) return XFMR_EINVAL;
   LnFwdArgs a{};
   a.x = nullptr; a.idx = item_idx; a.table = table; a.n_rows = n_rows; a.pos_emb = pos_emb; a.type_emb = type_emb;
@@ -686,8 +717,8 @@ int xf_embed_ln_fwd_packed_ex(const int64_t* item_idx, const float* table, int64
                               const float* type_emb, const float* gamma, const float* beta, float* out, void* out16,
                               float* pre, float* mean, float* rstd, uint8_t* key_mask, int64_t rows, const int32_t* row_pos,
                               int32_t H, float eps, float dropout_p, XfSeed seed, uint32_t site, hipStream_t stream) {
-  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !pre || !mean || !rstd || !key_mask || !row_pos)
-    return XFMR_EINVAL;
+  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !key_mask || !row_pos) return XFMR_EINVAL;
+  if (!ln_keep_ok(pre, mean, rstd, out)) return XFMR_EINVAL;
   if (rows <= 0 || H <= 0 || n_rows <= 0) return XFMR_EINVAL;
   LnFwdArgs a{};
   a.x = nullptr; a.idx = item_idx; a.table = table; a.n_rows = n_rows; a.pos_emb = pos_emb; a.type_emb = type_emb;
@@ -700,12 +731,14 @@ int xf_embed_ln_fwd_packed_ex(const int64_t* item_idx, const float* table, int64
 
 int xfmr_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                        int64_t rows, int32_t H, float eps, void* stream) {
+  if (!mean || !rstd) return XFMR_EINVAL;
   return xf_layernorm_fwd_ex(x, gamma, beta, y, nullptr, mean, rstd, rows, H, eps, (hipStream_t)stream);
 }
 
 int xf_layernorm_fwd_ex(const float* x, const float* gamma, const float* beta, float* y, void* y16, float* mean,
                         float* rstd, int64_t rows, int32_t H, float eps, hipStream_t stream) {
-  if (!x || !gamma || !beta || !y || !mean || !rstd || rows <= 0 || H <= 0) return XFMR_EINVAL;
+  // (mean and rstd both null: the forward-only form)
+  if (!x || !gamma || !beta || !y || (mean == nullptr) != (rstd == nullptr) || rows <= 0 || H <= 0) return XFMR_EINVAL;
   LnFwdArgs a{};
   a.x = x; a.gamma = gamma; a.beta = beta; a.y = y; a.mean = mean; a.rstd = rstd; a.rows = rows; a.H = H;
   a.eps = eps; a.L = 1;

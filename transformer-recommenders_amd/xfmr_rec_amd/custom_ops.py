@@ -8,6 +8,7 @@ contains them sees opaque, shape-inferable calls instead of ``ctypes`` and neith
 
     xfmr::encoder            gather + BertEmbeddings + N x BertLayer  (models.py:336-345, TF:modeling_bert.py:68-448)
     xfmr::encoder_bwd        its backward (the flat gradient of every trainable tensor)
+    xfmr::encoder_infer      the same forward for evaluation: the same bits, nothing saved, no autograd formula
     xfmr::sampled_loss       compute_embeds + the seven heads + LogitsStatistics on (B*L) positions (trainer.py:250-264)
     xfmr::sampled_loss_lists EmbedLoss.forward on [positive | shared negatives] / full-catalogue candidates
     xfmr::dense_loss         EmbedLoss.forward on a dense (N,C,H) candidate tensor (losses.py:128-155)
@@ -150,6 +151,36 @@ def _encoder_backward(ctx, d_tok, _d_mask, _d_acts):
 
 
 encoder.register_autograd(_encoder_backward, setup_context=_encoder_setup)
+
+
+@torch.library.custom_op("xfmr::encoder_infer", mutates_args=())
+def encoder_infer(flat_params: Tensor, item_idx: Tensor, table: Tensor, heads: int, inter: int, layers: int, max_pos: int,
+                  precision: str, ln_eps: float, hidden_dropout: float, attn_dropout: float, flags: int, seed: int,
+                  step_device: Optional[Tensor], handles: List[int], seq_offsets: Optional[Tensor],
+                  row_pos: Optional[Tensor], packed_seq_len: int) -> Tuple[Tensor, Tensor]:
+    """(token_embeddings, key_mask) of xfmr::encoder for the same arguments (dropout must be 0), bit for bit, through the
+    forward-only pass: no saved activations, no autograd formula (evaluation code under no_grad / inference_mode)."""
+    from . import ops
+
+    B, L = _batch_dims(item_idx, seq_offsets, packed_seq_len)
+    cfg = _encoder_cfg(B, L, table.shape[1], heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout,
+                       attn_dropout, flags, seed, None, handles, seq_offsets, row_pos)
+    tok, key_mask, _ws = ops.encoder_infer_fwd(cfg, flat_params, item_idx, table)
+    return tok, key_mask
+
+
+@encoder_infer.register_fake
+def _(flat_params, item_idx, table, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags,
+      seed, step_device, handles, seq_offsets, row_pos, packed_seq_len):
+    B, L = _batch_dims(item_idx, seq_offsets, packed_seq_len)
+    H = table.shape[1]
+    cfg = _encoder_cfg(B, L, H, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags, seed,
+                       None, handles)
+    nbytes = N.load().xfmr_encoder_infer_workspace_bytes(C.byref(cfg))  # a host-side size computation: no device needed
+    torch._check(nbytes > 0, lambda: "xfmr::encoder_infer: unsupported encoder configuration")
+    torch._check(hidden_dropout == 0.0 and attn_dropout == 0.0, lambda: "xfmr::encoder_infer: dropout must be 0 (eval)")
+    rows = (row_pos.shape[0],) if seq_offsets is not None else (B, L)
+    return flat_params.new_empty((*rows, H), dtype=torch.float32), flat_params.new_empty(rows, dtype=torch.uint8)
 
 
 # ------------------------------------------------------------------------------------------------ losses
@@ -378,6 +409,6 @@ def _(*a, **k):
     return None
 
 
-OP_NAMES = ("encoder", "encoder_bwd", "sampled_loss", "sampled_loss_lists", "dense_loss", "scale_by_device_scalar_",
+OP_NAMES = ("encoder", "encoder_bwd", "encoder_infer", "sampled_loss", "sampled_loss_lists", "dense_loss", "scale_by_device_scalar_",
             "scale_by_device_scalar",
             "l2_normalize", "l2_normalize_bwd", "pool", "adamw_")

@@ -340,11 +340,11 @@ class DeviceEvalSet:
             for c in self._chunks:
                 r0, r1 = c["rows"]
                 if self.packed:
-                    tok, _ = model._encode_tokens(packed=c["packed"])
+                    tok, _ = model._encode_tokens(packed=c["packed"], infer=True)
                     out[r0:r1] = ops.pool_rows(tok, c["packed"]["seq_offsets"], cfg.pooling_mode,
                                                normalize=bool(cfg.is_normalized))
                 else:
-                    out[r0:r1] = model(c["padded"])["sentence_embedding"]
+                    out[r0:r1] = model(c["padded"], inference=True)["sentence_embedding"]
         finally:
             model.train(was_training)
         return out

@@ -368,15 +368,21 @@ class RecommenderModel(torch.nn.Module):
             seq_offsets=packed["seq_offsets"] if packed else None, row_pos=packed["row_pos"] if packed else None,
         )
 
-    def _encode_tokens(self, item_idx=None, item_embeds=None, embed_event=None, packed=None):
+    def _encode_tokens(self, item_idx=None, item_embeds=None, embed_event=None, packed=None, infer=False):
         """tok, key_mask of the history. ``packed`` (ops.pack_rows's dict + "batch" / "seq_len"): the packed layout -- tok is
-        (rows, H), key_mask (rows,): only each sequence's own rows, in order."""
+        (rows, H), key_mask (rows,): only each sequence's own rows, in order. ``infer``: the forward-only pass
+        (ops.encoder_infer: the same bits, nothing kept for a backward, no autograd node) -- eval mode under no_grad /
+        inference_mode only; ``XFMR_INFER=0`` (read per call) takes the training forward again."""
         assert self.embeddings is not None, "call configure_embeddings() first"
+        if infer and self.training:
+            raise RuntimeError("the forward-only encoder pass is for evaluation: call model.eval() first")
+        # (looked up per call: ops.encoder is torch.ops.xfmr.encoder when traced, the autograd.Function in eager mode)
+        enc = ops.encoder_infer if infer and ops.infer_enabled() else ops.encoder
         if packed is not None:
             if self.training and not torch.compiler.is_compiling():
                 self._step += 1
             kw = self._cfg_kwargs(int(packed["batch"]), int(packed["seq_len"]), embed_event, packed)
-            return ops.encoder(self.flat, packed["hist"], self.embeddings, kw)
+            return enc(self.flat, packed["hist"], self.embeddings, kw)
         if item_embeds is not None:
             # the gather kernel reads rows by index: use the given embeddings as the table
             x = item_embeds[:, -self.max_seq_length :, :].to(self.device, torch.float32).contiguous()
@@ -393,12 +399,14 @@ class RecommenderModel(torch.nn.Module):
         if self.training and not torch.compiler.is_compiling():  # (traced training steps key dropout on the device)
             self._step += 1
         # torch.ops.xfmr.encoder when traced (custom_ops.py), the autograd.Function over the same C-ABI calls in eager mode
-        tok, key_mask = ops.encoder(self.flat, idx, table, self._cfg_kwargs(B, L, embed_event))
+        tok, key_mask = enc(self.flat, idx, table, self._cfg_kwargs(B, L, embed_event))
         return tok, key_mask
 
-    def forward(self, item_idx=None, *, item_embeds=None) -> dict[str, torch.Tensor]:
-        """``models.py:306-345``: returns token_embeddings (B,L,H), sentence_embedding (B,H), attention_mask."""
-        tok, key_mask = self._encode_tokens(item_idx, item_embeds)
+    def forward(self, item_idx=None, *, item_embeds=None, inference: bool = False) -> dict[str, torch.Tensor]:
+        """``models.py:306-345``: returns token_embeddings (B,L,H), sentence_embedding (B,H), attention_mask.
+        ``inference=True`` (eval mode, under no_grad / inference_mode): the forward-only encoder pass -- the same values bit
+        for bit, but ``token_embeddings`` cannot be back-propagated."""
+        tok, key_mask = self._encode_tokens(item_idx, item_embeds, infer=inference)
         with torch.no_grad():  # sentence_embedding is not on the training path (models.py:143-147)
             sent = ops.pool(tok.detach(), key_mask, self.config.pooling_mode)
             if self.config.is_normalized:
@@ -432,13 +440,13 @@ class RecommenderModel(torch.nn.Module):
                 order = order.to(dev)
                 packed = ops.pack_rows(hist, hist, None, offs64.to(dev), int(offs64[-1]), order=order)
                 packed |= {"batch": len(rows), "seq_len": L}
-                tok, _ = self._encode_tokens(packed=packed)
+                tok, _ = self._encode_tokens(packed=packed, infer=True)
                 sent = ops.pool_rows(tok, packed["seq_offsets"], self.config.pooling_mode,
                                      normalize=bool(self.config.is_normalized))
                 emb = torch.empty_like(sent)
                 emb[order] = sent  # packed slot b holds history order[b]
             else:
-                emb = self(hist)["sentence_embedding"]
+                emb = self(hist, inference=True)["sentence_embedding"]
         finally:
             self.train(was_training)
         out[torch.as_tensor(keep, dtype=torch.int64, device=dev)] = emb
@@ -452,7 +460,9 @@ class RecommenderModel(torch.nn.Module):
         ]
         vals = self.id2idx[known].to_numpy() if hasattr(self.id2idx, "index") else [self.id2idx[i] for i in known]
         item_idx = torch.as_tensor(vals, device=self.device, dtype=torch.int64)
-        return self(item_idx[None, :])["sentence_embedding"][0]
+        # (the sentence embedding never carries a gradient: in eval mode the forward-only pass computes it)
+        with torch.no_grad():
+            return self(item_idx[None, :], inference=not self.training)["sentence_embedding"][0]
 
     def compute_embeds(self, history_item_idx, pos_item_idx, neg_item_idx) -> dict:
         """``models.py:366-419``. ``query_embed`` is the compacted ``(Np, H)`` tensor (this needs the row count

@@ -612,6 +612,29 @@ def encoder_fwd(cfg: N.EncoderCfg, flat_params, item_idx, table):
     return tok, key_mask, acts
 
 
+def encoder_infer_fwd(cfg: N.EncoderCfg, flat_params, item_idx, table, workspace=None):
+    """xfmr_encoder_infer: (tok, key_mask, workspace) -- the bits of :func:`encoder_fwd` for the same cfg (dropout 0), with
+    nothing kept for a backward. ``workspace``: a byte tensor of at least xfmr_encoder_infer_workspace_bytes(cfg) bytes to
+    run in (scratch of this call only); None allocates one of exactly that size."""
+    lib = N.load()
+    H = cfg.hidden
+    rows = (cfg.packed_rows,) if cfg.packed_rows else (cfg.batch, cfg.seq_len)
+    tok = _empty((*rows, H), flat_params)
+    key_mask = _empty(rows, flat_params, torch.uint8)
+    nbytes = lib.xfmr_encoder_infer_workspace_bytes(C.byref(cfg))
+    if nbytes == 0:
+        raise RuntimeError("xfmr_encoder_infer_workspace_bytes: unsupported encoder configuration "
+                           "(head size must be 32 or 64, sizes positive, seq_len <= max_pos)")
+    if workspace is None:
+        workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=flat_params.device)
+    N.check(
+        lib.xfmr_encoder_infer(C.byref(cfg), N.ptr(flat_params), N.ptr(item_idx), N.ptr(table), table.shape[0],
+                               N.ptr(tok), N.ptr(key_mask), N.ptr(workspace), workspace.numel(), N.stream()),
+        "xfmr_encoder_infer",
+    )
+    return tok, key_mask, workspace
+
+
 last_encoder_grad_ptr = 0  # device address of the flat gradient buffer the last xfmr_encoder_bwd call wrote
 
 
@@ -804,6 +827,33 @@ def encoder(flat_params, item_idx, table, cfg_kwargs: dict):
         return tok, key_mask
     keep = (cfg_kwargs.get("seq_offsets"), cfg_kwargs.get("row_pos"))
     return EncoderFunction.apply(flat_params, item_idx, table, make_encoder_cfg(**cfg_kwargs), keep)
+
+
+def infer_enabled() -> bool:
+    """Whether the evaluation surfaces (``encode_batch``, ``encode``, ``DeviceEvalSet.encode`` and what goes through them)
+    take the forward-only entry. ``XFMR_INFER=0``, read per call, routes them through the training forward again (A/B
+    timing, bisecting): the results are the same bits either way."""
+    return os.environ.get("XFMR_INFER", "") != "0"
+
+
+last_infer_workspace_nbytes = 0  # size of the workspace tensor the last eager encoder_infer call ran in (tests)
+
+
+def encoder_infer(flat_params, item_idx, table, cfg_kwargs: dict):
+    """tok, key_mask of :func:`encoder` for the same ``cfg_kwargs`` (dropout 0), bit for bit, through the forward-only pass
+    (xfmr_encoder_infer): nothing is stored for a backward, the workspace is one byte tensor of exactly the library's size
+    that dies with the call. No autograd node: the outputs never require grad, and a call that would be expected to
+    deliver a gradient -- grad mode on and ``flat_params.requires_grad`` -- raises; use it under ``torch.no_grad()`` /
+    ``torch.inference_mode()``. Eager: the C ABI call; traced / XFMR_TORCH_OPS=1: torch.ops.xfmr.encoder_infer."""
+    global last_infer_workspace_nbytes
+    if torch.is_grad_enabled() and flat_params.requires_grad:
+        raise RuntimeError("ops.encoder_infer is forward-only and has no backward: call it under torch.no_grad() / "
+                           "torch.inference_mode(), or use ops.encoder for a differentiable forward")
+    if use_torch_ops():
+        return torch.ops.xfmr.encoder_infer(flat_params, item_idx, table, *encoder_op_args(**cfg_kwargs))
+    tok, key_mask, ws = encoder_infer_fwd(make_encoder_cfg(**cfg_kwargs), flat_params.detach(), item_idx, table)
+    last_infer_workspace_nbytes = ws.nbytes
+    return tok, key_mask
 
 
 _EAGER_ONLY_LOSS_OPTS = ("workspace", "prepared", "d_tok_zeroed", "profile_grad", "profile_log")

@@ -422,7 +422,8 @@ class RecommenderLightningModule(_Base):
         """``trainer.py:186-211``: nearest items to the pooled embedding of ``item_ids``, ``exclude_item_ids`` left
         out. Returns ``{"item_idx": (k,) int64 rows of the table (-1 = fewer than k left), "score": (k,)}``."""
         hist = self._to_idx(item_ids)
-        emb = self.model(torch.as_tensor(hist, dtype=torch.int64, device=self.model.device)[None, :])["sentence_embedding"]
+        emb = self.model(torch.as_tensor(hist, dtype=torch.int64, device=self.model.device)[None, :],
+                         inference=not self.model.training)["sentence_embedding"]
         excl = None if exclude_item_ids is None else [self._to_idx(exclude_item_ids)]
         idx, score = self.items_index.search(emb, excl, top_k=top_k or self.config.top_k)
         return {"item_idx": idx[0], "score": score[0]}
