@@ -57,7 +57,8 @@ def test_round_trip_survives_weights_only_and_checks_format_and_version(tmp_path
     flat = tr.module.model.flat.detach()
     pre = "model.model.0.auto_model."
     assert set(state["state_dict"]) == set(tr.module.state_dict()) and all(k.startswith(pre) for k in state["state_dict"])
-    assert all(torch.equal(v, tr.module.state_dict()[k]) for k, v in state["state_dict"].items())
+    live = {k: v.cpu() for k, v in tr.module.state_dict().items()}  # (the module sits on the device where there is one)
+    assert all(torch.equal(v, live[k]) for k, v in state["state_dict"].items())
     assert CK.state_flat_numel(state) == flat.numel()
     assert size < 3 * 4 * flat.numel() + 65536  # parameters and two moments, each ONCE (the keyed tensors share a storage)
     assert state["hyper_parameters"] == {"config": CK.plain(tr.module.config.model_dump())}
@@ -83,7 +84,8 @@ def test_round_trip_survives_weights_only_and_checks_format_and_version(tmp_path
     assert got == loop and ld2.state_dict() == {"epoch": 1, "next_batch": 2}
     assert torch.equal(new.module.model.flat, flat)
     st2 = new.optimizer.state[new.module.model.flat]
-    assert st2["step"] == 7 and torch.equal(st2["exp_avg"], st["exp_avg"]) and torch.equal(st2["exp_avg_sq"], st["exp_avg_sq"])
+    assert st2["step"] == 7 and torch.equal(st2["exp_avg"].cpu(), st["exp_avg"].cpu())
+    assert torch.equal(st2["exp_avg_sq"].cpu(), st["exp_avg_sq"].cpu())
     assert new.module.model._step == 7 and getattr(new.module.model, "step_device", None) is None
     assert new.val_history == loop["val_history"] and new.best_score == 0.25
     assert new.optimizer.param_groups[0]["betas"] == (0.9, 0.999)

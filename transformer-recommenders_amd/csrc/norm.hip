@@ -549,13 +549,25 @@ __global__ void table_rnorm_kernel(const float* table, float* out, int64_t rows,
 
 int npl_of(int H) { return (H + 63) / 64; }
 
+// The *_v4 kernels move 16 bytes per lane (8 into a bf16 copy): they are taken only when every pointer they touch that way
+// is aligned for it (a null one is never touched). Otherwise the generic kernel of the same width runs: NPL = 1 / 2 / 4.
+bool xf_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+bool ln_fwd_v4_aligned(const LnFwdArgs& a) {
+  return xf_aligned16(a.x) && xf_aligned16(a.table) && xf_aligned16(a.pos_emb) && xf_aligned16(a.type_emb) &&
+         xf_aligned16(a.pre) && xf_aligned16(a.gamma) && xf_aligned16(a.beta) && xf_aligned16(a.y) && xf_aligned8(a.y16);
+}
+bool ln_bwd_v4_aligned(const LnBwdArgs& a) {
+  return xf_aligned16(a.dy) && xf_aligned16(a.x) && xf_aligned16(a.gamma) && xf_aligned16(a.dx) &&
+         (a.lin16 ? xf_aligned8(a.d_lin) : xf_aligned16(a.d_lin));
+}
+
 template <bool GATHER>
 int launch_ln_fwd(const LnFwdArgs& a, hipStream_t st) {
   // pre (GATHER) / mean / rstd all null: the forward-only instantiations; all given: the training ones (the entries check)
   const bool keep = a.mean != nullptr;
   using Kernel = void (*)(const LnFwdArgs);
   dim3 block(256);
-  if (a.H == 64 || a.H == 128 || a.H == 256) {
+  if ((a.H == 64 || a.H == 128 || a.H == 256) && ln_fwd_v4_aligned(a)) {
     const int rpw = 256 / a.H;  // rows per wave
     dim3 gridv((unsigned)((a.rows + 4 * rpw - 1) / (4 * rpw)));
     const Kernel k = a.H == 64    ? (keep ? ln_fwd_v4_kernel<16, GATHER> : ln_fwd_v4_infer_kernel<16, GATHER>)
@@ -766,9 +778,10 @@ int xf_layernorm_bwd_impl(const float* dy, const float* x, const float* mean, co
   const size_t shmem = (size_t)12 * H * sizeof(float);
   const int npl = npl_of(H);
   dim3 grid(blocks), block(256);
-  if (H == 64) hipLaunchKernelGGL((ln_bwd_v4_kernel<16>), grid, block, 0, st, a);
-  else if (H == 128) hipLaunchKernelGGL((ln_bwd_v4_kernel<32>), grid, block, 0, st, a);
-  else if (H == 256) hipLaunchKernelGGL((ln_bwd_v4_kernel<64>), grid, block, 0, st, a);
+  const bool v4 = ln_bwd_v4_aligned(a);  // (else the generic kernel of the same width; the row plan holds for both)
+  if (v4 && H == 64) hipLaunchKernelGGL((ln_bwd_v4_kernel<16>), grid, block, 0, st, a);
+  else if (v4 && H == 128) hipLaunchKernelGGL((ln_bwd_v4_kernel<32>), grid, block, 0, st, a);
+  else if (v4 && H == 256) hipLaunchKernelGGL((ln_bwd_v4_kernel<64>), grid, block, 0, st, a);
   else if (npl <= 1) hipLaunchKernelGGL((ln_bwd_kernel<1>), grid, block, shmem, st, a);
   else if (npl <= 2) hipLaunchKernelGGL((ln_bwd_kernel<2>), grid, block, shmem, st, a);
   else if (npl <= 4) hipLaunchKernelGGL((ln_bwd_kernel<4>), grid, block, shmem, st, a);
