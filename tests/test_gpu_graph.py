@@ -217,6 +217,55 @@ def test_step_counter_is_one_sequence_across_eager_steps_replays_and_state_dict(
     assert all(st["step"] == 7 for st in tr3.optimizer.state.values())
 
 
+def test_fit_puts_back_what_it_changed_when_the_batch_source_raises(X):
+    """``fit(graph="on")`` changes four things for its duration: ``module.defer_logging``, the current stream, where the
+    step count lives, and ``loader.fixed_width``. A HOST exception out of the batch source -- nothing faults on the device
+    -- leaves all four as a finished call does. The generator fails behind its second batch: both batches are stepped on
+    first (the failed read-ahead is raised when its batch is due)."""
+    import numpy as np
+    from xfmr_rec_amd.data import DeviceSeqDataset, DeviceSeqLoader, SeqDataConfig
+
+    mod, batches = _setup(X)
+    tr = X.Trainer(mod)
+
+    def two_then_raise():
+        yield batches[0]
+        yield batches[1]
+        raise RuntimeError("no third batch")
+
+    mod.defer_logging = "auto"  # (the call makes it False for the capture's one stream)
+    caller = torch.cuda.current_stream()
+    with pytest.raises(RuntimeError, match="no third batch"):
+        tr.fit(two_then_raise(), graph="on")
+    assert mod.defer_logging == "auto"
+    assert torch.cuda.current_stream() == caller
+    assert int(tr.optimizer.state[mod.model.flat]["step"]) == 2
+    torch.cuda.synchronize()
+    assert int(mod.model.step_device.item()) == 2
+
+    class FailsOnce(DeviceSeqLoader):
+        failed = False
+
+        def __iter__(self):
+            if not self.failed:
+                self.failed = True
+                raise RuntimeError("no first batch")
+            return super().__iter__()
+
+    rng = np.random.default_rng(0)
+    lens = [int(n) for n in rng.integers(2, 30, 24)]
+    ds = DeviceSeqDataset(SeqDataConfig(max_seq_length=24, pos_lookahead=0), [rng.integers(1, 201, n) for n in lens],
+                          [np.ones(n, dtype=bool) for n in lens], 200)
+    ld = FailsOnce(ds, 8, seed=1)
+    mod2, _ = _setup(X)
+    tr2 = X.Trainer(mod2)
+    with pytest.raises(RuntimeError, match="no first batch"):
+        tr2.fit(ld, graph="on")
+    assert ld.fixed_width is False
+    assert len(tr2.fit(ld, graph="on")) == 3 and ld.fixed_width is False  # a fresh call finds the loader as it was built
+    ld.close()
+
+
 def test_deferred_step_logs_the_batch_constants_and_ring_needs_two_slots(X):
     """trainer.py:241-244 logs batch/size, batch/seq_len, batch/numel every step: the sync-free path carries them too (host
     constants, no device sync). PinnedBatchRing(slots=1) would stage into the slot the running step reads: refused."""

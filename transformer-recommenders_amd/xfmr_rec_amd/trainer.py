@@ -15,9 +15,7 @@ HIP kernels from ``libxfmr_hip.so``; torch supplies memory, streams, autograd bo
 
 from __future__ import annotations
 
-import contextlib
 import math
-import pathlib
 import time
 
 import torch
@@ -1005,6 +1003,16 @@ class Trainer:
     def _optimizer_steps(self) -> int:
         return int(max((st.get("step", 0) for st in self.optimizer.state.values()), default=0))
 
+    def _seed_device_step(self) -> None:
+        """The step counter the captured kernels read (dropout stream, AdamW's bias corrections) lives in HBM from here
+        on: a new one continues the optimizer's completed steps, so that the eager steps in front of a capture and the
+        replays after it are one sequence."""
+        mdl = self.module.model
+        if getattr(mdl, "step_device", None) is None:
+            mdl.use_device_step(True)
+            mdl.step_device.fill_(self._optimizer_steps())
+        self.optimizer.step_device = mdl.step_device
+
     @staticmethod
     def _empty_loop() -> dict:
         return {"batches_done": 0, "epoch": 0, "next_batch": 0, "tracker": None, "stopper": None, "val_history": [],
@@ -1108,7 +1116,9 @@ class Trainer:
         form runs the rest (replay wins where the host's launch rate bounds the step -- BASELINE config 1's shape: 0.31
         against 0.48 ms -- and changes nothing where the GPU does: DESIGN.md section 5). Every probe step is a real
         training step on its own batch. Batches of another shape (a short last batch) take the eager step. Single
-        process only; ``self.graph_choice`` records what ran.
+        process only; ``self.graph_choice`` records what ran. What the call changes for its duration (the current stream,
+        ``module.defer_logging``, a loader's ``fixed_width``) is put back, and the optimizer's host-side step count brought
+        up to the device's, when it raises, too.
 
         ``val`` (a :class:`~xfmr_rec_amd.evalset.DeviceEvalSet`): validate inside the loop, as Lightning does with the
         reference's ``ModelCheckpoint`` + ``EarlyStopping`` on ``val/retrieval_normalized_dcg`` (``trainer.py:334-341``).
@@ -1168,297 +1178,27 @@ class Trainer:
         budget again. None of the four is supported under ``world_size > 1`` (validation, early stopping and the best
         model are: above; full-state checkpoints and a host-clock limit inside a data-parallel loop are not)."""
         from . import checkpoint as CK
-        from .data import SEQ_BATCH_KEYS, DeviceSeqLoader, PinnedBatchRing
+        from . import fit_loop
+        from .data import DeviceSeqLoader
 
         t_fit = time.monotonic()
         self._check_val(val)
-        time_limit = CK.parse_max_time(max_time)
-        if self.world_size > 1 and (ckpt_path is not None or save_last or checkpoint_every_n_steps is not None
-                                    or max_time is not None):
-            raise ValueError("ckpt_path / save_last / checkpoint_every_n_steps / max_time inside a data-parallel run "
-                             "(world_size > 1) are not supported: ranks that read their own clocks would leave the all-reduce "
-                             "at different steps, and a multi-rank run has never executed (save_checkpoint / load_checkpoint "
-                             "work on any rank)")
-        if checkpoint_every_n_steps is not None:
-            n_ck = checkpoint_every_n_steps
-            if isinstance(n_ck, bool) or not isinstance(n_ck, int) or n_ck < 1:
-                raise ValueError(f"checkpoint_every_n_steps must be an integer >= 1 or None; got {n_ck!r}")
-            if n_ck % self.accumulate_grad_batches:
-                raise ValueError(f"checkpoint_every_n_steps = {n_ck} is not a multiple of accumulate_grad_batches = "
-                                 f"{self.accumulate_grad_batches}: a checkpoint would fall between the micro-batches of one step")
-        if (checkpoint_every_n_steps is not None or save_last) and checkpoint_dir is None:
-            raise ValueError("checkpoint_every_n_steps / save_last write checkpoint_dir / 'last.ckpt': pass checkpoint_dir")
-        last_path = pathlib.Path(checkpoint_dir) / "last.ckpt" if checkpoint_dir is not None else None
         loader = batches if isinstance(batches, DeviceSeqLoader) else None
-        if max_epochs is None:
-            if limit_train_batches is not None or check_val_every_n_epoch != 1:
-                raise ValueError("limit_train_batches / check_val_every_n_epoch belong to the epoch loop: pass max_epochs")
-        else:
-            if loader is None:
-                raise ValueError(f"max_epochs needs a DeviceSeqLoader to run epochs over; got {type(batches).__name__}")
-            for name, v, least in (("max_epochs", max_epochs, 0), ("check_val_every_n_epoch", check_val_every_n_epoch, 1),
-                                   ("limit_train_batches", limit_train_batches, 0)):
-                if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < least):
-                    raise ValueError(f"{name} must be an integer >= {least}; got {v!r}")
-        if loader is not None and loader.world_size != self.world_size:
-            raise ValueError(f"the loader shards its epochs over world_size = {loader.world_size}, this trainer runs "
-                             f"world_size = {self.world_size}")
-        if val_check_interval is not None:
-            if isinstance(val_check_interval, bool) or not isinstance(val_check_interval, int) or val_check_interval < 1:
-                raise ValueError(f"val_check_interval must be an integer >= 1 or None; got {val_check_interval!r}")
-            if val_check_interval % self.accumulate_grad_batches:
-                raise ValueError(f"val_check_interval = {val_check_interval} is not a multiple of accumulate_grad_batches = "
-                                 f"{self.accumulate_grad_batches}: a pass would fall between the micro-batches of one step")
-        if not isinstance(monitor, dict) or set(monitor) != {"name", "mode"}:
-            raise ValueError(f"monitor must be {{'name', 'mode'}}; got {monitor!r}")
-        stage, _, metric_name = str(monitor["name"]).rpartition("/")
-        tracker = EarlyStopping(monitor["mode"], patience=None)  # the best value: strict improvements (ModelCheckpoint)
-        stopper = _early_stopping_from(early_stopping, monitor["mode"])
-        if val_cutoffs is not None:
-            from .retrieval import normalize_cutoffs
-
-            val_cutoffs = normalize_cutoffs(val_cutoffs)
-        if val is not None:
-            from .retrieval import METRIC_NAMES
-
-            metric_name, at, at_k = metric_name.partition("@")
-            if not stage or metric_name not in METRIC_NAMES:
-                raise ValueError(f"monitor name {monitor['name']!r}: expected '<stage>/<metric>' with a metric of {METRIC_NAMES}")
-            if at and (val_cutoffs is None or not at_k.isdecimal() or str(int(at_k)) != at_k or int(at_k) not in val_cutoffs):
-                raise ValueError(f"monitor name {monitor['name']!r}: '@<K>' needs K among val_cutoffs = {val_cutoffs!r}")
+        plan = fit_loop.FitPlan.build(
+            batches, loader, world_size=self.world_size, accumulate_grad_batches=self.accumulate_grad_batches,
+            max_steps=max_steps, ring_slots=ring_slots, graph=graph, graph_probe_steps=graph_probe_steps, val=val,
+            val_check_interval=val_check_interval, monitor=monitor, early_stopping=early_stopping,
+            checkpoint_dir=checkpoint_dir, val_cutoffs=val_cutoffs, max_epochs=max_epochs,
+            check_val_every_n_epoch=check_val_every_n_epoch, limit_train_batches=limit_train_batches, ckpt_path=ckpt_path,
+            save_last=save_last, checkpoint_every_n_steps=checkpoint_every_n_steps, max_time=max_time)
         self.val_history: list[dict] = []
         self.best_score = self.best_step = self.best_model_path = None
         self.stopped_early = self.stopped_on_time = False
         self.val_elapsed = self.ckpt_elapsed = 0.0
-        # the loop's position is its OWN: batches done over all calls (`base` + this call's `i`) and the (epoch, batch) the
-        # next step reads -- the loader's state is a batch ahead of the step, and after a finished epoch e it reads
-        # (e, 0), which the epoch loop below takes for "start at epoch 0"
-        base, resumed, seconds_before = 0, False, 0.0
         self._loader_fields = CK.loader_fields(loader)
-        if ckpt_path is not None:
-            loop = self.load_checkpoint(ckpt_path, loader=loader)  # (checks first; sets val_history and the best_* fields)
-            base, resumed, seconds_before = int(loop["batches_done"]), True, float(loop["train_seconds"])
-            pos = (int(loop["epoch"]), int(loop["next_batch"]))
-            if loop["tracker"] is not None:
-                tracker.load_state_dict(loop["tracker"])
-            if stopper is not None and loop["stopper"] is not None:
-                stopper.load_state_dict(loop["stopper"])
-        elif loader is not None:
-            pos = (loader.epoch if (loader.next_batch > 0 or max_epochs is None) else 0, loader.next_batch)
-        else:
-            pos = (0, 0)
-
-        if graph not in ("off", "on", "auto"):
-            raise ValueError(f"graph must be 'off', 'on' or 'auto', got {graph!r}")
-        if graph != "off" and self.accumulate_grad_batches > 1:
-            raise ValueError(_NO_ACCUMULATED_CAPTURE)
-        if self.world_size != 1:
-            graph = "off"  # (the all-reduce of a data-parallel step is not captured)
-        defer_before = getattr(self.module, "defer_logging", "auto")
-        if graph != "off":
-            _refuse_capture_after_default_stream_steps(self)
-            # the step counter the captured kernels read (dropout stream, AdamW bias corrections) lives in HBM from the
-            # first step on, so that the eager steps in front of the capture and the replays after it are one sequence
-            mdl = self.module.model
-            if getattr(mdl, "step_device", None) is None:
-                mdl.use_device_step(True)
-                done = max((st.get("step", 0) for st in self.optimizer.state.values()), default=0)
-                mdl.step_device.fill_(int(done))
-            self.optimizer.step_device = mdl.step_device
-            if getattr(self.module, "defer_logging", "auto") == "auto":
-                self.module.defer_logging = False  # one stream: what the capture records (GraphedStep)
-        gstep, use_graph = None, False
-        probe: dict = {}
-        self.graph_choice = "eager"
-        n_warm = 3
-
-        def _sync_time():
-            torch.cuda.synchronize(self.module.model.device)
-            return time.perf_counter()
-
-        def _validate(batches_done: int) -> bool:
-            """One pass between two steps; True when the loop should stop."""
-            dev_ = self.module.model.device
-            torch.cuda.current_stream(dev_).synchronize()  # the steps enqueued so far are not validation time
-            tv = time.perf_counter()
-            metrics = val.evaluate(stage) if val_cutoffs is None else val.evaluate(stage, cutoffs=val_cutoffs)
-            self.val_elapsed += time.perf_counter() - tv
-            self.module.log_dict(metrics)
-            self.val_history.append({"step": batches_done, **({"epoch": ep["epoch"]} if max_epochs is not None else {}),
-                                     **metrics})
-            value = metrics[monitor["name"]]
-            tracker.update(value)
-            if tracker.improved:
-                self.best_score, self.best_step = tracker.best, batches_done
-                if checkpoint_dir is not None:
-                    path = pathlib.Path(checkpoint_dir) / "best"
-                    if self.world_size == 1:
-                        self.module.save(path)
-                    else:  # replicas hold the same weights: rank 0 writes, nobody goes on before the directory is whole
-                        if val.rank == 0:
-                            self.module.save(path)
-                        torch.distributed.barrier(self.process_group)
-                    self.best_model_path = str(path)
-            stop = stopper.update(value) if stopper is not None else False
-            # the "auto" probe compares STEPS: whatever a pass (and its checkpoint) took leaves the open window
-            _out_of_probe(time.perf_counter() - tv)
-            return stop
-
-        def _out_of_probe(spent: float) -> None:
-            for k0, k1 in (("eager_t0", "eager_ms"), ("graph_t0", "graph_ms")):
-                if k0 in probe and k1 not in probe:
-                    probe[k0] += spent
-
-        def _loop_state(batches_done: int) -> dict:
-            return {"batches_done": batches_done, "epoch": pos[0], "next_batch": pos[1], "tracker": tracker.state_dict(),
-                    "stopper": stopper.state_dict() if stopper is not None else None,
-                    "val_history": [dict(h) for h in self.val_history], "best_score": self.best_score,
-                    "best_step": self.best_step, "best_model_path": self.best_model_path,
-                    "train_seconds": seconds_before + (time.monotonic() - t_fit)}  # (for information only)
-
-        def _checkpoint(batches_done: int) -> None:
-            """``last.ckpt`` between two steps, on the loop's stream: one stream sync, the device-to-host copies, the write."""
-            assert not torch.cuda.is_current_stream_capturing()
-            torch.cuda.current_stream(self.module.model.device).synchronize()  # the steps enqueued so far are not its time
-            tc = time.perf_counter()
-            self._loop = _loop_state(batches_done)
-            self.save_checkpoint(last_path)
-            spent = time.perf_counter() - tc
-            self.ckpt_elapsed += spent
-            _out_of_probe(spent)
-
-        out = []
-        t0 = time.time()
-        ring = None
-        # torch's capture protocol: the eager steps in front of a capture run on a NON-default stream (autograd's
-        # AccumulateGrad nodes are bound to the stream of their first backward; captured from the default stream the
-        # capture faults). The whole loop therefore runs on a side stream when a graph may be captured.
-        dev = self.module.model.device
-        cur = torch.cuda.current_stream(dev) if graph != "off" else None
-        side = torch.cuda.Stream(device=dev) if graph != "off" else None
-        if side is not None:
-            side.wait_stream(cur)
-        # the epoch loop's state at the batch in hand: its epoch, its index in the epoch, whether it ends the epoch
-        ep = {"epoch": 0, "j": 0, "last": False}
-
-        def _epochs():
-            # a loader restored mid-epoch goes on from there; a restored LOOP names its epoch itself (load_state_dict has put
-            # the loader there: after the last batch of epoch e that is (e + 1, 0))
-            e0 = pos[0] if resumed else (loader.epoch if loader.next_batch > 0 else 0)
-            for e in range(e0, max_epochs):
-                if e > e0 or loader.next_batch == 0:
-                    loader.set_epoch(e)
-                n_b = len(loader) if limit_train_batches is None else min(len(loader), limit_train_batches)
-                it_e = iter(loader)
-                for j in range(loader.next_batch, n_b):
-                    b_ = next(it_e)
-                    ep["epoch"], ep["j"], ep["last"] = e, j, j + 1 == n_b
-                    yield b_
-                it_e.close()
-                loader.set_epoch(e)  # (an epoch cut short by limit_train_batches is over, not half done)
-
-        def _one_pass():
-            n_b = len(loader)
-            for j, b_ in enumerate(loader, loader.next_batch):  # what is left of the loader's current epoch
-                ep["epoch"], ep["j"], ep["last"] = loader.epoch, j, j + 1 == n_b
-                yield b_
-
-        fixed_before = loader.fixed_width if loader is not None else None
-        if loader is not None and graph != "off":
-            loader.fixed_width = True  # one shape for the captured step -- and one layout for the steps around it
-        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            it = _epochs() if max_epochs is not None else (_one_pass() if loader is not None else iter(batches))
-            # `i` counts this call's batches (the capture's warm-up and the probe are this call's), `base + i` all of them
-            nxt = next(it, None) if (not resumed or max_steps is None or base < max_steps) else None
-            i = 0
-            while nxt is not None and (max_steps is None or base + i < max_steps):
-                b = nxt
-                on_host = not b[SEQ_BATCH_KEYS[0]].is_cuda
-                if on_host:
-                    if ring is None or b[SEQ_BATCH_KEYS[0]].shape[0] > ring.shape[1] or b[SEQ_BATCH_KEYS[0]].shape[1] > ring.shape[2]:
-                        if ring is not None:
-                            ring.close()
-                        bs, width = b[SEQ_BATCH_KEYS[0]].shape
-                        ring = PinnedBatchRing(self.module.model.device, bs, max(width, self.module.model.max_seq_length),
-                                               slots=ring_slots)
-                    if ring.pending == 0:
-                        ring.stage(b)
-                    dev_b = ring.take()
-                    if graph != "off":
-                        # a captured step has fixed launch sizes: it runs the padded layout, and so do the eager steps around
-                        # it (one sequence of steps, one layout) -- the rows' lengths are not passed on
-                        dev_b = {k: dev_b[k] for k in SEQ_BATCH_KEYS}
-                elif loader is not None and graph != "off":
-                    dev_b = {k: b[k] for k in SEQ_BATCH_KEYS}  # (as above: no lengths, the padded layout)
-                else:
-                    dev_b = b
-                if loader is None:
-                    nxt = next(it, None)
-                if nxt is not None and ring is not None and not nxt[SEQ_BATCH_KEYS[0]].is_cuda \
-                        and nxt[SEQ_BATCH_KEYS[0]].shape[0] <= ring.shape[1] and nxt[SEQ_BATCH_KEYS[0]].shape[1] <= ring.shape[2]:
-                    ring.stage(nxt)  # in flight while this step computes
-                if graph != "off" and i >= n_warm:
-                    if graph == "auto" and "eager_t0" not in probe:
-                        probe["eager_t0"], probe["eager_i0"] = _sync_time(), i
-                    eager_done = graph == "on" or i - probe["eager_i0"] >= graph_probe_steps
-                    if gstep is None and eager_done:
-                        if graph == "auto":
-                            probe["eager_ms"] = (_sync_time() - probe["eager_t0"]) / (i - probe["eager_i0"]) * 1e3
-                        gstep = GraphedStep(self, dev_b, warmup=0)
-                        use_graph = True
-                        if graph == "auto":
-                            probe["graph_t0"], probe["graph_i0"] = _sync_time(), i
-                    elif graph == "auto" and gstep is not None and "graph_ms" not in probe \
-                            and i - probe["graph_i0"] >= graph_probe_steps:
-                        probe["graph_ms"] = (_sync_time() - probe["graph_t0"]) / (i - probe["graph_i0"]) * 1e3
-                        use_graph = probe["graph_ms"] < probe["eager_ms"]
-                    self.graph_choice = "graph" if use_graph else "eager"
-                if use_graph and gstep.matches(dev_b):
-                    out.append(gstep(dev_b).clone())  # (the captured loss tensor is overwritten by the next replay)
-                else:
-                    out.append(self.fit_step(dev_b))
-                i += 1
-                done = base + i
-                if loader is None:
-                    pos = (0, done)
-                else:  # from the loop's own counters: the batch after the last one of epoch e is batch 0 of epoch e + 1
-                    pos = (ep["epoch"] + 1, 0) if ep["last"] else (ep["epoch"], ep["j"] + 1)
-                stop = False
-                if val is not None and val_check_interval is not None and done % val_check_interval == 0:
-                    stop = _validate(done)
-                elif (val is not None and val_check_interval is None and max_epochs is not None and ep["last"]
-                        and (ep["epoch"] + 1) % check_val_every_n_epoch == 0):
-                    stop = _validate(done)
-                if checkpoint_every_n_steps is not None and done % checkpoint_every_n_steps == 0:
-                    _checkpoint(done)  # behind the pass that fell on this batch: the file carries it
-                if stop:
-                    self.stopped_early = True
-                    break
-                if time_limit is not None and time.monotonic() - t_fit >= time_limit:  # (a host clock: no device sync)
-                    self.stopped_on_time = True
-                    break
-                if loader is not None:
-                    # a loader's slots are rewritten underneath the steps: the next batch is asked for once this step is enqueued
-                    # (and only if it will be stepped on: the loader's state then names the batch a resumed run starts with)
-                    nxt = next(it, None) if max_steps is None or done < max_steps else None
-            if val is not None and val_check_interval is None and max_epochs is None and i > 0:
-                _validate(base + i)
-            self._loop = _loop_state(base + i)
-            if save_last:
-                _checkpoint(base + i)
-        if loader is not None:
-            loader.fixed_width = fixed_before
-        if side is not None:
-            cur.wait_stream(side)
-        if graph != "off":
-            self.module.defer_logging = defer_before  # (the capture needed one stream; the caller's setting comes back)
-            self.optimizer.sync_step_from_device()  # replays advanced the counter on the device only
-        self.graph_probe = {k: round(v, 4) for k, v in probe.items() if k.endswith("_ms")}
-        if ring is not None:
-            ring.release()
-            ring.close()
-        self.elapsed = time.time() - t0
-        return [float(v) for v in out]  # (one host sync at the end, not one per step)
+        # (load_checkpoint checks compatibility first; it sets val_history and the best_* fields)
+        loop = self.load_checkpoint(ckpt_path, loader=loader) if ckpt_path is not None else None
+        return fit_loop.FitRun(self, plan, batches, loader, val, loop, t_fit).run()
 
 
 _NO_ACCUMULATED_CAPTURE = ("a captured step cannot accumulate micro-batches (accumulate_grad_batches > 1): the device-side step "
@@ -1518,13 +1258,7 @@ class GraphedStep:
             m.defer_logging = True
         elif getattr(m, "defer_logging", "auto") == "auto":
             m.defer_logging = False  # one stream inside the capture
-        if getattr(m.model, "step_device", None) is None:
-            # the counter continues the optimizer's completed steps (AdamW's bias corrections and the dropout stream go on
-            # from where the eager steps stopped, as Trainer.fit seeds it)
-            m.model.use_device_step(True)
-            done = max((st.get("step", 0) for st in trainer.optimizer.state.values()), default=0)
-            m.model.step_device.fill_(int(done))
-        trainer.optimizer.step_device = m.model.step_device
+        trainer._seed_device_step()
         m.train()
         m._pending_out = None  # nothing of an earlier step (its tensors, their autograd graph) reaches into the capture
         m.last_out = None
