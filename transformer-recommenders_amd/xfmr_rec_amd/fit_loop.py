@@ -413,7 +413,7 @@ class FitRun:
         their first backward, and captured from the default stream the capture faults."""
         tr, loader, graphed = self.trainer, self.loader, self.plan.graph != "off"
         module, dev = tr.module, tr.module.model.device
-        defer_before = getattr(module, "defer_logging", "auto")
+        defer_before = module.defer_logging
         fixed_before = loader.fixed_width if loader is not None else None
         cur = side = None
         if graphed:

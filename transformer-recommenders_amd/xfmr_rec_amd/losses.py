@@ -28,6 +28,7 @@ import torch
 
 from . import _native as N
 from . import ops
+from .step_plan import KEY_TABLE
 
 
 class LossConfig(pydantic.BaseModel):
@@ -218,12 +219,7 @@ class LogitsStatistics(EmbedLoss):
 
 def stats_to_dict(s: list[float]) -> dict[str, float]:
     """Device statistics vector -> the reference's key names (``losses.py:392-404``)."""
-    out = {"logits/neg/density": s[N.STAT["neg_density"]]}
-    if s[N.STAT["n_query"]] > 0:
-        out |= {f"logits/pos/{k}": s[N.STAT[f"pos_{k}"]] for k in ("mean", "std", "min", "max")}
-    if s[N.STAT["neg_count"]] > 0:
-        out |= {f"logits/neg/{k}": s[N.STAT[f"neg_{k}"]] for k in ("mean", "std", "min", "max")}
-    return out
+    return {k: s[i] for k, _, i, gate in KEY_TABLE if k.startswith("logits/") and (gate is None or s[gate] > 0)}
 
 
 class AlignmentLoss(EmbedLoss):

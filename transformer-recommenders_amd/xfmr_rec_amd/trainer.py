@@ -15,16 +15,19 @@ HIP kernels from ``libxfmr_hip.so``; torch supplies memory, streams, autograd bo
 
 from __future__ import annotations
 
+import ctypes
 import math
+import os
 import time
 
 import torch
 
 from . import _native as N
 from . import ops
-from .losses import LOSS_CLASSES, LossConfig, LossType, stats_to_dict
+from .losses import LOSS_CLASSES, LossConfig, LossType
 from .models import ModelConfig, RecommenderModel
 from .params import METRIC, TOP_K
+from .step_plan import StepPlan, device_values, host_values, step_result
 
 try:  # pragma: no cover - lightning is not installed in the build image
     import lightning.pytorch as _lp
@@ -159,6 +162,15 @@ class RecommenderLightningModule(_Base):
         self.items_dataset = None
         self.loss_fns: torch.nn.ModuleList | None = None
         self.logged: dict = {}
+        # ---- the training step's state (compute_losses / training_step / on_train_batch_end)
+        self.defer_logging: bool | str = "auto"  # training_step's form: True / False, or "auto" (StepPlan: by the batch's size)
+        self.profile_events = None   # bench.py: (gradient pass, logging pass) hipEvent pairs handed to the loss calls
+        self.last_plan: StepPlan | None = None  # what the last compute_losses call decided
+        self.last_out: dict | None = None       # the last finished step's raw device outputs (detached)
+        self._pending_out: dict | None = None   # training_step's outputs until on_train_batch_end logs them
+        self._side = None                # the logging stream (lowest priority), made by the first overlapped step
+        self._logging_pending = False    # a logging pass is in flight on it: sync_logging() joins
+        self._ev_embed = self._ev_prep = None  # overlapped step: "the key mask is written" / "both loss calls are prepared"
 
     # lightning supplies .device; the plain-module build derives it from the parameters
     def _device(self):
@@ -189,14 +201,11 @@ class RecommenderLightningModule(_Base):
         return self.model(item_idx.to(self.model.device))
 
     def _side_stream(self):
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             # lowest priority: the logging pass fills what the training chain leaves idle instead of competing with it
             # (XFMR_LOG_STREAM_PRIORITY overrides; torch: lower number = higher priority, 0 = the default stream's)
             # (torch offers only "normal" and "high": the stream comes from the library. XFMR_LOG_STREAM_PRIORITY=0:
             # a normal-priority torch stream.)
-            import ctypes
-            import os
-
             if os.environ.get("XFMR_LOG_STREAM_PRIORITY", "low") == "0":
                 self._side = torch.cuda.Stream(device=self.model.device)
             else:
@@ -208,188 +217,139 @@ class RecommenderLightningModule(_Base):
 
     def sync_logging(self) -> None:
         """Join the side stream of a deferred logging pass (see compute_losses(defer_logging=True))."""
-        if getattr(self, "_logging_pending", False):
+        if self._logging_pending:
             torch.cuda.current_stream().wait_stream(self._side)
             self._logging_pending = False
 
-    def compute_losses(self, batch, *, sync_metrics: bool = True, defer_logging: bool = False, profile_grad=None,
+    def compute_losses(self, batch, *, sync_metrics: bool = True, defer_logging: bool | str = False, profile_grad=None,
                        profile_log=None) -> dict:
         """``trainer.py:213-264``: every head's summed loss and ``...Mean``, batch and logits statistics.
 
         One encoder forward + ONE fused loss launch sequence produce all of it (the reference recomputes the
         logits eight times). ``loss/{train_loss}`` carries the gradient; the other heads are logging values.
         ``sync_metrics=False`` keeps the statistics on the device (no host sync in the step).
-        ``defer_logging=True`` (implies device-side metrics) runs the logging heads on a side stream; the non-train
-        entries of the returned dict must then only be read after ``sync_logging()``.
+        ``defer_logging=True`` (implies device-side metrics; "auto": by the batch's size) runs the logging heads on a side
+        stream; the non-train entries of the returned dict must then only be read after ``sync_logging()``.
         ``profile_grad`` / ``profile_log``: (start, stop) hipEvent_t handles recorded around the gradient-pass /
         logging-pass kernel of the loss (``bench.py``'s roofline figures).
+        What the call decides is a :class:`~xfmr_rec_amd.step_plan.StepPlan` (kept as ``last_plan``); what it returns is
+        ``step_plan.step_result``'s dict.
         """
         assert self.model is not None
         m, c = self.model, self.config
-        if c.negatives not in ("in_batch", "catalogue"):
-            raise ValueError(f"invalid {c.negatives = }")
-        catalogue = c.negatives == "catalogue"
-        if not catalogue and c.target_position != "first":
-            raise ValueError("the training path scores [positive | shared negatives]: target_position='first'")
-        if catalogue and c.target_position is not None:
-            raise ValueError("negatives='catalogue' names the positive by `target` (= pos_item_idx): "
-                             "target_position=None (losses.py:233-238)")
         dev = m.device
         hist = batch["history_item_idx"]
-        L = min(hist.shape[1], m.max_seq_length)  # what _encode_tokens keeps of the history
-        pos = batch["pos_item_idx"][:, -L:].to(dev, torch.int64).contiguous()
-        neg = None if catalogue else batch["neg_item_idx"][:, -L:].to(dev, torch.int64).contiguous()
-        # PACKED rows (xfmr_encoder_cfg.seq_offsets): when the batch carries its rows' lengths on the HOST -- the collate that
-        # right-padded them knows them (data.py:799-805); PinnedBatchRing hands them over -- the encoder and the loss run on
-        # each sequence's own rows only. The reference's padded layout computes the padding rows too and then drops them
-        # (models.py:392); on MovieLens-like lengths that is half of the encoder's work.
-        packed = None
-        padded_positions = 0
         lens = batch.get("lengths")
-        if torch.is_tensor(lens) and lens.is_cuda:
-            lens = None  # (the launch sizes need the row count on the HOST: device-side lengths would cost a sync per step)
-        if (lens is not None and hist.shape[1] == L and m.supports_packed_rows(L) and not torch.compiler.is_compiling()
-                and not torch.cuda.is_current_stream_capturing()):
-            rows = int(batch["packed_rows"]) if "packed_rows" in batch else int(lens.sum())
-            if 0 < rows <= 0.97 * hist.shape[0] * L:  # (a nearly full batch gains nothing)
-                # the sequences go into the packed layout by length, LONGEST first (ops.length_order: nothing depends on the order
-                # of a batch's rows -- every loss is a sum over them -- and the attention kernels start their longest workgroups
-                # first); PinnedBatchRing ships the order and the offsets in that order with the batch
-                offs64, order = batch.get("offsets"), batch.get("order")
-                if offs64 is None:
-                    order, offs64 = ops.length_order(lens)
-                    order, offs64 = order.to(dev), offs64.to(dev)
-                packed = ops.pack_rows(hist.to(dev, torch.int64).contiguous(), pos, neg, offs64, rows, order=order)
-                packed |= {"batch": hist.shape[0], "seq_len": L}
-                pos, neg = packed["pos"], packed["neg"]
-                padded_positions = hist.shape[0] * L
-        opts = dict(train_head=c.train_loss, all_heads=c.log_all_losses, mask_false_negatives=c.mask_false_negatives,
-                    mode=N.NEG_CATALOG if catalogue else N.NEG_SHARED, scale=c.scale, margin=c.margin, precision=c.precision,
-                    table_bf16=m.table_bf16, num_hard_negatives=c.num_hard_negatives, padded_positions=padded_positions)
-        overlap = (defer_logging and c.log_all_losses and m.flat.requires_grad and torch.is_grad_enabled()
-                   and m.table_bf16 is not None and c.precision == "bf16" and c.num_hard_negatives == 0
-                   # unmasked InfoNCE: ONE call runs the logging pass first and pins the gradient pass's running
-                   # maximum from its records (lean epilogue) -- worth more than the overlap
-                   and not (c.train_loss == "InfoNCELoss" and not c.mask_false_negatives))
-        prep = None
-        if overlap:
-            # The index-only half of both loss calls (query compaction, multiplicities, distinct negatives: 7 small launches
-            # each) needs the key mask, not the token embeddings: it runs on the side stream underneath the forward, behind an
-            # event the encoder forward records right after the launch that writes the mask -- instead of 40 us of small
-            # launches between the forward's last kernel and the loss kernels.
-            H, n_rows, T = m.config.hidden_size, m.embeddings.shape[0], (pos.numel() if packed else hist.shape[0] * L)
-            if getattr(self, "_ev_embed", None) is None:
-                self._ev_embed, self._ev_prep = torch.cuda.Event(), torch.cuda.Event()
-                self._ev_embed.record()  # (creates the handle)
-            ws_log = ops.sampled_loss_workspace(m.flat, T, H, n_rows, **opts)
-            ws_grad = ops.sampled_loss_workspace(m.flat, T, H, n_rows, **opts)
-            prep = (ws_log, ws_grad, H, n_rows)
+        tracing = torch.compiler.is_compiling()
+        # what only a packed plan needs is asked only where one is possible: the lengths are on the HOST (the launch sizes
+        # need the row count there: device-side lengths would cost a sync per step) and the step is not being traced (the
+        # model's answer reads the environment)
+        ask = lens is not None and not (torch.is_tensor(lens) and lens.is_cuda) and not tracing
+        plan = self.last_plan = StepPlan.build(
+            c, batch=hist.shape[0], width=hist.shape[1], max_seq_length=m.max_seq_length, has_lengths=ask,
+            rows=(int(batch["packed_rows"]) if "packed_rows" in batch else int(lens.sum())) if ask else 0,
+            supports_packed=ask and m.supports_packed_rows(min(hist.shape[1], m.max_seq_length)), tracing=tracing,
+            capturing=ask and torch.cuda.is_current_stream_capturing(), defer_logging=defer_logging,
+            grad=m.flat.requires_grad and torch.is_grad_enabled(), has_table_bf16=m.table_bf16 is not None)
+        pos = batch["pos_item_idx"][:, -plan.L:].to(dev, torch.int64).contiguous()
+        neg = None if plan.catalogue else batch["neg_item_idx"][:, -plan.L:].to(dev, torch.int64).contiguous()
+        packed = None
+        if plan.packed:
+            packed = self._pack_rows(batch, plan, pos, neg)
+            pos, neg = packed["pos"], packed["neg"]
+        opts = plan.opts | {"table_bf16": m.table_bf16}
+        ws = self._overlap_workspaces(plan, opts) if plan.overlap else None
         # (the forward records the event right after the launch that writes the key mask: xfmr_encoder_cfg.embed_event)
-        tok, key_mask = m._encode_tokens(None if packed else hist, embed_event=self._ev_embed.cuda_event if overlap else None,
+        tok, key_mask = m._encode_tokens(None if packed else hist, embed_event=self._ev_embed.cuda_event if plan.overlap else None,
                                          packed=packed)
         if m.config.is_normalized:  # models.py:393-394: the queries are the L2-normalised token embeddings
             tok = ops.l2_normalize(tok)
-        assert packed is not None or tok.shape[1] == L
-        if overlap:
-            # The six logging heads + statistics do not feed the gradient: evaluate them on a side stream so the
-            # (VALU-bound) logging pass runs underneath the (latency-bound) encoder backward. The caller joins
-            # with sync_logging() before reading them (Trainer.fit_step / bench.py do, after optimizer.step()).
-            main = torch.cuda.current_stream()
-            side = self._side_stream()
-            ws_log, ws_grad, H, n_rows = prep
-            side.wait_event(self._ev_embed)  # the key mask exists (the forward is still running)
-            with torch.cuda.stream(side):
-                for ws, heads in ((ws_log, 2), (ws_grad, False)):
-                    ops.sampled_loss_prepare(ws, key_mask, pos, neg, m.table_rnorm, n_rows, H, **(opts | {"all_heads": heads}))
-                d_tok0 = torch.zeros_like(tok)  # the gradient buffer, zeroed here instead of in front of the gradient pass
-                self._ev_prep.record(side)
-            # enqueued BEFORE the gradient pass: it needs the forward's output only, and at its lowest priority it takes
-            # what the gradient pass (800 workgroups on 512 slots: 1.56 rounds) leaves idle, then the encoder backward's gaps
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                # all_heads=2: every head except the train head (its value comes from the launch below)
-                losses, stats, _ = ops.sampled_loss(
-                    tok.detach(), key_mask, pos, neg, m.embeddings, m.table_rnorm, need_grad=False,
-                    **(opts | {"all_heads": 2, "workspace": ws_log, "prepared": True, "profile_log": profile_log})
-                )
-            main.wait_event(self._ev_prep)  # (recorded long ago)
-            train_loss, losses_train, stats_t = ops.sampled_loss_train(
-                tok, key_mask, pos, neg, m.embeddings, m.table_rnorm,
-                opts | {"all_heads": False, "workspace": ws_grad, "prepared": True, "d_tok_zeroed": d_tok0,
-                        "profile_grad": profile_grad}
-            )
-            for tns in (ws_log, ws_grad):
-                tns.record_stream(side)
-            d_tok0.record_stream(main)  # allocated on the side stream, used on the main one
-            for tns in (tok, key_mask, pos, neg):
-                if tns is not None:
-                    tns.record_stream(side)
-            self._logging_pending = True
+        assert packed is not None or tok.shape[1] == plan.L
+        if plan.overlap:
+            train_loss, losses, losses_train, stats = self._losses_overlapped(opts, ws, tok, key_mask, pos, neg, profile_grad,
+                                                                              profile_log)
         else:
             train_loss, losses, stats = ops.sampled_loss_train(
                 tok, key_mask, pos, neg, m.embeddings, m.table_rnorm,
                 opts | {"profile_grad": profile_grad, "profile_log": profile_log}
             )
-        out: dict = {}
-        n_query = stats[N.STAT["n_query"]]
-        names = [cls.__name__ for cls in LOSS_CLASSES]
-        for i, name in enumerate(names):
-            if not c.log_all_losses and name != c.train_loss:
-                continue
-            val = train_loss if name == c.train_loss else losses[i]
-            out[f"loss/{name}"] = val
-            if not overlap:
-                out[f"loss/{name}Mean"] = losses[N.NUM_LOSSES + i]  # computed by the final kernel
-        if overlap:  # raw device vectors: the side-stream pass (train head entries = 0) and the gradient call (train head only)
-            out["losses/device"] = losses
-            out["losses_train/device"] = losses_train
-        batch_size, seq_len = hist.shape[0], L  # (the padded shape, also when the rows were packed)
-        numel = batch_size * seq_len
-        # trainer.py:241-244: known without a device sync, logged on every path
-        out |= {"batch/size": batch_size, "batch/seq_len": seq_len, "batch/numel": numel}
-        if sync_metrics and not overlap:
-            s = stats.tolist()  # one device->host sync (the reference does 11 .item() calls)
-            attn_nz, pos_nz = int(s[N.STAT["n_valid"]]), int(s[N.STAT["n_query"]])
-            out |= {
-                "batch/attention_non_zero": attn_nz, "batch/attention_density": attn_nz / (numel + 1e-9),
-                "batch/positive_non_zero": pos_nz, "batch/positive_density": pos_nz / (attn_nz + 1e-9),
-            }
-            if c.log_all_losses:
-                out |= stats_to_dict(s)
-        else:
-            out["stats/device"] = stats
-        return out
+            losses_train = None
+        return step_result(plan, train_loss, losses, losses_train, stats, sync=sync_metrics)
+
+    def _pack_rows(self, batch, plan: StepPlan, pos, neg) -> dict:
+        """The batch in the packed layout (``ops.pack_rows``'s dict, with the padded shape it came from)."""
+        dev = self.model.device
+        # the sequences go into the packed layout by length, LONGEST first (ops.length_order: nothing depends on the order
+        # of a batch's rows -- every loss is a sum over them -- and the attention kernels start their longest workgroups
+        # first); PinnedBatchRing ships the order and the offsets in that order with the batch
+        offs64, order = batch.get("offsets"), batch.get("order")
+        if offs64 is None:
+            order, offs64 = ops.length_order(batch["lengths"])
+            order, offs64 = order.to(dev), offs64.to(dev)
+        packed = ops.pack_rows(batch["history_item_idx"].to(dev, torch.int64).contiguous(), pos, neg, offs64, plan.rows, order=order)
+        return packed | {"batch": plan.batch, "seq_len": plan.L}
+
+    def _overlap_workspaces(self, plan: StepPlan, opts: dict) -> tuple:
+        """In front of the forward of an overlapped step: the two events (made once) and the two loss calls' workspaces,
+        the logging pass's first."""
+        m = self.model
+        if self._ev_embed is None:
+            self._ev_embed, self._ev_prep = torch.cuda.Event(), torch.cuda.Event()
+            self._ev_embed.record()  # (creates the handle)
+        H, n_rows = m.config.hidden_size, m.embeddings.shape[0]
+        return (ops.sampled_loss_workspace(m.flat, plan.rows, H, n_rows, **opts),
+                ops.sampled_loss_workspace(m.flat, plan.rows, H, n_rows, **opts))
+
+    def _losses_overlapped(self, opts: dict, ws: tuple, tok, key_mask, pos, neg, profile_grad, profile_log) -> tuple:
+        """The overlapped form: ``(train_loss, losses, losses_train, stats)`` of the logging pass on the side stream and
+        the gradient pass on the main one."""
+        m = self.model
+        # The index-only half of both loss calls (query compaction, multiplicities, distinct negatives: 7 small launches
+        # each) needs the key mask, not the token embeddings: it runs on the side stream underneath the forward, behind an
+        # event the encoder forward records right after the launch that writes the mask -- instead of 40 us of small
+        # launches between the forward's last kernel and the loss kernels.
+        # The six logging heads + statistics do not feed the gradient: evaluate them on a side stream so the
+        # (VALU-bound) logging pass runs underneath the (latency-bound) encoder backward. The caller joins
+        # with sync_logging() before reading them (Trainer.fit_step / bench.py do, after optimizer.step()).
+        main = torch.cuda.current_stream()
+        side = self._side_stream()
+        (ws_log, ws_grad), H, n_rows = ws, m.config.hidden_size, m.embeddings.shape[0]
+        side.wait_event(self._ev_embed)  # the key mask exists (the forward is still running)
+        with torch.cuda.stream(side):
+            for w, heads in ((ws_log, 2), (ws_grad, False)):
+                ops.sampled_loss_prepare(w, key_mask, pos, neg, m.table_rnorm, n_rows, H, **(opts | {"all_heads": heads}))
+            d_tok0 = torch.zeros_like(tok)  # the gradient buffer, zeroed here instead of in front of the gradient pass
+            self._ev_prep.record(side)
+        # enqueued BEFORE the gradient pass: it needs the forward's output only, and at its lowest priority it takes
+        # what the gradient pass (800 workgroups on 512 slots: 1.56 rounds) leaves idle, then the encoder backward's gaps
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            # all_heads=2: every head except the train head (its value comes from the launch below)
+            losses, stats, _ = ops.sampled_loss(
+                tok.detach(), key_mask, pos, neg, m.embeddings, m.table_rnorm, need_grad=False,
+                **(opts | {"all_heads": 2, "workspace": ws_log, "prepared": True, "profile_log": profile_log})
+            )
+        main.wait_event(self._ev_prep)  # (recorded long ago)
+        train_loss, losses_train, _ = ops.sampled_loss_train(
+            tok, key_mask, pos, neg, m.embeddings, m.table_rnorm,
+            opts | {"all_heads": False, "workspace": ws_grad, "prepared": True, "d_tok_zeroed": d_tok0,
+                    "profile_grad": profile_grad}
+        )
+        for tns in (ws_log, ws_grad):
+            tns.record_stream(side)
+        d_tok0.record_stream(main)  # allocated on the side stream, used on the main one
+        for tns in (tok, key_mask, pos, neg):
+            if tns is not None:
+                tns.record_stream(side)
+        self._logging_pending = True
+        return train_loss, losses, losses_train, stats
 
     def logged_values(self, out: dict) -> dict[str, float]:
-        """Host-side view of a ``compute_losses(..., defer_logging=True)`` result: joins the side stream and
-        returns every ``loss/<Class>``, ``loss/<Class>Mean``, ``batch/*`` and ``logits/*`` entry as floats
-        (one device->host sync), exactly the keys the reference logs (``trainer.py:241-263``)."""
+        """Host-side view of a ``compute_losses`` result (``step_plan.host_values``): joins the side stream and returns
+        every ``loss/<Class>``, ``loss/<Class>Mean``, ``batch/*`` and ``logits/*`` entry as floats (one device->host sync
+        per vector), exactly the keys the reference logs (``trainer.py:241-263``)."""
         self.sync_logging()
-        c = self.config
-        if "stats/device" not in out:
-            return {k: float(v) for k, v in out.items() if not k.endswith("/device")}
-        s = out["stats/device"].tolist()
-        attn_nz, pos_nz = int(s[N.STAT["n_valid"]]), int(s[N.STAT["n_query"]])
-        res: dict[str, float] = {}
-        dev = out.get("losses/device")
-        vals = dev.tolist() if dev is not None else None
-        for i, cls in enumerate(LOSS_CLASSES):
-            k = f"loss/{cls.__name__}"
-            if k not in out:
-                continue
-            v = float(out[k]) if (vals is None or cls.__name__ == c.train_loss) else vals[i]
-            res[k] = v
-            res[k + "Mean"] = v / (pos_nz + 1e-9)
-        res |= {k: out[k] for k in ("batch/size", "batch/seq_len", "batch/numel") if k in out}
-        res |= {
-            "batch/attention_non_zero": attn_nz, "batch/positive_non_zero": pos_nz,
-            "batch/positive_density": pos_nz / (attn_nz + 1e-9),
-        }
-        if "batch/numel" in out:
-            res["batch/attention_density"] = attn_nz / (out["batch/numel"] + 1e-9)
-        if c.log_all_losses:
-            res |= stats_to_dict(s)
-        return res
+        return host_values(out, self.config)
 
     # ------------------------------------------------------------------ validation path (trainer.py:186-325)
     @property
@@ -552,15 +512,9 @@ class RecommenderLightningModule(_Base):
         six logging heads + statistics go to the lowest-priority side stream underneath the backward. The train loss is
         logged here; everything else is logged by :meth:`on_train_batch_end` -- after the side stream has been joined --
         as 0-dim DEVICE tensors (Lightning's ``log_dict`` takes them and converts at its own logging interval)."""
-        prof = getattr(self, "profile_events", None) or (None, None)  # bench.py: hipEvent pairs around the two loss passes
-        defer = getattr(self, "defer_logging", "auto")
-        if defer == "auto":
-            # the side-stream logging pass pays once it is long enough to be worth hiding: B x L >= 51 200 tokens
-            # (round 4, bench.py --overlap on / off, one box: batch 256 x 200 1.918-1.947 against 1.958-1.962 ms, batch 128
-            #  1.193 against 1.178; round 1 had measured -1.4 % at 256 and set 102 400)
-            h = batch["history_item_idx"]
-            defer = h.shape[0] * min(h.shape[1], self.model.max_seq_length) >= 51200
-        out = self.compute_losses(batch, sync_metrics=False, defer_logging=bool(defer),
+        prof = self.profile_events or (None, None)  # bench.py: hipEvent pairs around the two loss passes
+        # ("auto": the plan's rule, by the batch's size)
+        out = self.compute_losses(batch, sync_metrics=False, defer_logging=self.defer_logging,
                                   profile_grad=prof[0], profile_log=prof[1])
         key = f"loss/{self.config.train_loss}"
         # only DETACHED tensors outlive the step: a retained train loss would keep the step's autograd graph -- the saved
@@ -582,7 +536,7 @@ class RecommenderLightningModule(_Base):
 
     def on_train_batch_end(self, outputs=None, batch=None, batch_idx: int = 0) -> None:
         """Lightning hook (after ``optimizer.step``): join the logging stream and log the step's remaining values."""
-        out = getattr(self, "_pending_out", None)
+        out = self._pending_out
         if out is None:
             return
         self._pending_out = None
@@ -592,37 +546,9 @@ class RecommenderLightningModule(_Base):
 
     def device_log_dict(self, out: dict) -> dict[str, torch.Tensor]:
         """Every key the reference logs (``trainer.py:241-263``, ``losses.py:392-404``) as 0-dim device tensors -- views
-        of the kernels' output vectors, no host sync, no torch arithmetic. Call after :meth:`sync_logging`.
-        (``logits/{pos,neg}/*`` of an empty selection are NaN here where the reference omits the key.)"""
-        c = self.config
-        res: dict[str, torch.Tensor] = {}
-        stats = out.get("stats/device")
-        if stats is None:  # a synchronous compute_losses result: already complete
-            return {k: torch.as_tensor(v) for k, v in out.items() if not k.endswith("/device")}
-        side, own = out.get("losses/device"), out.get("losses_train/device")
-        for i, cls in enumerate(LOSS_CLASSES):
-            k = f"loss/{cls.__name__}"
-            if k not in out:
-                continue
-            is_train = cls.__name__ == c.train_loss
-            res[k] = out[k].detach()
-            if k + "Mean" in out:
-                res[k + "Mean"] = out[k + "Mean"]
-            elif side is not None:
-                res[k + "Mean"] = (own if is_train and own is not None else side)[N.NUM_LOSSES + i]
-        for k in ("batch/size", "batch/seq_len", "batch/numel"):  # host constants (trainer.py:241-244)
-            if k in out:
-                res[k] = torch.as_tensor(out[k])
-        res["batch/attention_non_zero"] = stats[N.STAT["n_valid"]]
-        res["batch/positive_non_zero"] = stats[N.STAT["n_query"]]
-        res["batch/attention_density"] = stats[N.STAT["attn_density"]]
-        res["batch/positive_density"] = stats[N.STAT["pos_density"]]
-        if c.log_all_losses:
-            res["logits/neg/density"] = stats[N.STAT["neg_density"]]
-            for side_ in ("pos", "neg"):
-                for kk in ("mean", "std", "min", "max"):
-                    res[f"logits/{side_}/{kk}"] = stats[N.STAT[f"{side_}_{kk}"]]
-        return res
+        of the kernels' output vectors, no host sync, no torch arithmetic (``step_plan.device_values``). Call after
+        :meth:`sync_logging`. (``logits/{pos,neg}/*`` of an empty selection are NaN here where the reference omits the key.)"""
+        return device_values(out, self.config)
 
     def log_dict(self, d, *a, **k):  # noqa: D401 - lightning API
         if _lp is not None and getattr(self, "_trainer", None) is not None:  # pragma: no cover
@@ -1256,7 +1182,7 @@ class GraphedStep:
         if overlap:
             m.model.enc_flags = getattr(m.model, "enc_flags", 0) | N.ENC_DW_SIDE_ANY
             m.defer_logging = True
-        elif getattr(m, "defer_logging", "auto") == "auto":
+        elif m.defer_logging == "auto":
             m.defer_logging = False  # one stream inside the capture
         trainer._seed_device_step()
         m.train()
