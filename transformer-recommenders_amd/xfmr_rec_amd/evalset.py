@@ -1,8 +1,8 @@
 """A validation set prepared ONCE and kept in HBM (a peer of ``data.DeviceSeqDataset`` for the validation path).
 
 ``RecommenderLightningModule.evaluate(rows)`` redoes, on every call, host work that depends on the rows only and never on
-the model: id -> row conversion, truncation, padding, the length order, the packed layout behind an upload, one
-``np.unique`` per user for the exclusions, the targets CSR, and a read-back + host sum per pass (profiles/eval_batched.md:
+the model: id -> row conversion, truncation, padding, the length order, the packed layout behind an upload, the sorted
+exclusions, the targets CSR, and a read-back + host sum per pass (profiles/eval_batched.md:
 0.18-0.29 s for 6 040 users, host-bound). Here all of that is :func:`plan_eval_rows` (numpy, once) + one upload;
 a pass is then the packed forward, one pooling launch and one tiled top-k per chunk, ONE ``xfmr_retrieval_metrics_sum``
 over all rows, and a 64-byte read-back. ``Trainer.fit(val=...)`` runs it between steps.
@@ -21,9 +21,8 @@ import dataclasses
 import numpy as np
 import torch
 
-from . import _native as N
-from . import ops
-from .retrieval import METRIC_NAMES, METRICS, normalize_cutoffs, rank_metrics_sum, retrieval_metrics_sum
+from . import eval_rows as E
+from .retrieval import normalize_cutoffs, rank_metrics_sum, retrieval_metrics_sum
 
 
 @dataclasses.dataclass
@@ -78,13 +77,22 @@ class EvalPlan:
         return self.targets[self.target_pos], off
 
 
-def _flat(lists, rows) -> tuple[np.ndarray, np.ndarray]:
-    lens = np.asarray([len(lists[r]) for r in rows], dtype=np.int64)
-    off = np.zeros(len(rows) + 1, dtype=np.int64)
-    np.cumsum(lens, out=off[1:])
-    parts = [np.asarray(lists[r], dtype=np.int64).reshape(-1) for r in rows]
-    flat = np.concatenate(parts) if off[-1] else np.zeros(0, dtype=np.int64)
-    return flat, off
+def _exact_csr(lists) -> tuple[np.ndarray, np.ndarray]:
+    """``eval_rows.flat_csr`` without the placeholder element of an empty CSR: a plan's arrays hold their entries and
+    nothing else (the shards index them by position)."""
+    flat, off = E.flat_csr(lists)
+    return flat[: off[-1]], off
+
+
+@dataclasses.dataclass
+class DeviceChunk:
+    """An :class:`EvalChunk` on the device: its rows, its view of the resident exclusion offsets and its encoder input --
+    what ``RecommenderModel.sentence_embeddings`` takes: the host-planned packed dict, or the right-padded tensor."""
+
+    row0: int
+    row1: int
+    excl_offsets: torch.Tensor
+    tokens: dict | torch.Tensor
 
 
 def _take_csr(off: np.ndarray, rows: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
@@ -203,23 +211,15 @@ def plan_eval_rows(hist_idx_lists, target_idx_lists, max_seq_length: int, batch_
     order = np.argsort(-trunc, kind="stable")
     kept, lengths = keep[order].astype(np.int64), trunc[order]
     n = kept.size
-    full, full_off = _flat(hist_idx_lists, kept)
+    full, full_off = _exact_csr([hist_idx_lists[r] for r in kept])
     tok_off = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(lengths, out=tok_off[1:])
     # the last `lengths[i]` entries of each full history: token t of row i is full[full_off[i + 1] - lengths[i] + t]
     row_of_tok = np.repeat(np.arange(n, dtype=np.int64), lengths)
     pos = np.arange(tok_off[-1], dtype=np.int64) - tok_off[:-1][row_of_tok]
     hist = full[(full_off[1:] - lengths)[row_of_tok] + pos] if n else np.zeros(0, dtype=np.int64)
-    # exclusions: sort (row, item) pairs, drop repeats within a row
-    row_of_full = np.repeat(np.arange(n, dtype=np.int64), np.diff(full_off))
-    o = np.lexsort((full, row_of_full))
-    fs, rs = full[o], row_of_full[o]
-    first = np.ones(fs.size, dtype=bool)
-    first[1:] = (fs[1:] != fs[:-1]) | (rs[1:] != rs[:-1])
-    excl = fs[first]
-    excl_off = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(rs[first], minlength=n), out=excl_off[1:])
-    targets, target_off = _flat(target_idx_lists, kept)
+    excl, excl_off = E.sort_unique_rows(full, full_off)  # exclusions: each row's WHOLE history, sorted, repeats dropped
+    targets, target_off = _exact_csr([target_idx_lists[r] for r in kept])
     plan = EvalPlan(kept=kept, lengths=lengths, hist=hist, row_pos=pos.astype(np.int32), tok_offsets=tok_off,
                     chunks=_chunks(tok_off, lengths, bs), excl=excl, excl_offsets=excl_off, targets=targets,
                     target_offsets=target_off, max_seq_length=L, batch_size=bs)
@@ -253,8 +253,8 @@ class DeviceEvalSet:
         model = module.model
         assert model is not None and model.embeddings is not None, "configure_model() and an item table come first"
         top_k = int(module.config.top_k)
-        if top_k > 128 and not cutoffs_only:
-            raise ValueError(f"top_k = {top_k}: the tiled top-k (xfmr_topk_tiled) returns at most 128 items per row")
+        if not cutoffs_only:
+            E.check_tiled_top_k(top_k)
         self.cutoffs_only = bool(cutoffs_only)
         if plan.world_size == 1 and int(world_size) > 1:
             plan = shard_eval_plan(plan, rank, world_size)
@@ -292,17 +292,12 @@ class DeviceEvalSet:
         self.packed = bool(model.supports_packed_rows(plan.chunks[0].max_len if plan.chunks else plan.max_seq_length))
         self._chunks = []
         for c in plan.chunks:
-            d = {"rows": (c.row0, c.row1), "excl_offsets": self.excl_offsets[c.row0 : c.row1 + 1]}
             if self.packed:
-                d["packed"] = {"hist": self.hist[c.tok0 : c.tok1], "row_pos": self.row_pos[c.tok0 : c.tok1],
-                               "seq_offsets": up(c.seq_offsets), "batch": c.row1 - c.row0, "seq_len": c.max_len}
-            else:
-                # right-padded (b, L_chunk) with the padding row 0, as encode_batch builds it
-                lens = plan.lengths[c.row0 : c.row1]
-                pad = np.zeros((c.row1 - c.row0, c.max_len), dtype=np.int64)
-                pad[np.arange(c.max_len)[None, :] < lens[:, None]] = plan.hist[c.tok0 : c.tok1]
-                d["padded"] = up(pad)
-            self._chunks.append(d)
+                tokens = {"hist": self.hist[c.tok0 : c.tok1], "row_pos": self.row_pos[c.tok0 : c.tok1],
+                          "seq_offsets": up(c.seq_offsets), "batch": c.row1 - c.row0, "seq_len": c.max_len}
+            else:  # right-padded (b, L_chunk) with the padding row 0, as encode_batch builds it
+                tokens = up(E.pad_histories(plan.lengths[c.row0 : c.row1], plan.hist[c.tok0 : c.tok1]))
+            self._chunks.append(DeviceChunk(c.row0, c.row1, self.excl_offsets[c.row0 : c.row1 + 1], tokens))
         torch.cuda.synchronize(dev)  # (the uploads came from pageable numpy memory)
 
     @classmethod
@@ -316,12 +311,9 @@ class DeviceEvalSet:
         uploads that rank's shard only (see the class)."""
         if module.model is None:
             module.configure_model()
-        if int(module.config.top_k) > 128 and not cutoffs_only:
-            raise ValueError(f"top_k = {module.config.top_k}: the tiled top-k (xfmr_topk_tiled) returns at most 128 items per row")
-        hists, tgts = [], []
-        for r in rows:
-            hists.append(module._to_idx_or_empty(list(r["history"]["item_id"])))
-            tgts.append(module._to_idx_or_empty([i for i, l in zip(r["target"]["item_id"], r["target"]["label"]) if l]))
+        if not cutoffs_only:
+            E.check_tiled_top_k(module.config.top_k)
+        hists, tgts = E.read_rows(rows, module._to_idx_or_empty)
         return cls(module, plan_eval_rows(hists, tgts, module.model.max_seq_length, batch_size), cutoffs_only=cutoffs_only,
                    rank=rank, world_size=world_size, process_group=process_group)
 
@@ -332,48 +324,27 @@ class DeviceEvalSet:
     def encode(self) -> torch.Tensor:
         """Sentence embeddings (n_local, H) in plan order, in eval mode."""
         model = self.module.model
-        cfg = model.config
-        out = torch.empty((self.n_local, cfg.hidden_size), dtype=torch.float32, device=self.device)
-        was_training = model.training
-        model.eval()
-        try:
+        out = torch.empty((self.n_local, model.config.hidden_size), dtype=torch.float32, device=self.device)
+        with model.eval_mode():
             for c in self._chunks:
-                r0, r1 = c["rows"]
-                if self.packed:
-                    tok, _ = model._encode_tokens(packed=c["packed"], infer=True)
-                    out[r0:r1] = ops.pool_rows(tok, c["packed"]["seq_offsets"], cfg.pooling_mode,
-                                               normalize=bool(cfg.is_normalized))
-                else:
-                    out[r0:r1] = model(c["padded"], inference=True)["sentence_embedding"]
-        finally:
-            model.train(was_training)
+                out[c.row0 : c.row1] = model.sentence_embeddings(c.tokens)
         return out
 
     @torch.no_grad()
     def recommend(self, embedding: torch.Tensor | None = None):
         """``(item_idx (n_local, k) int64, -1 padded; score (n_local, k))``: xfmr_topk_tiled per chunk over the module's
         ``items_index`` (its metric, table and norms), each row's whole history excluded."""
-        if self.top_k > 128:
-            raise ValueError(f"top_k = {self.top_k}: the tiled top-k (xfmr_topk_tiled) returns at most 128 items per row; "
-                             "this set was built with cutoffs_only=True: evaluate it with cutoffs")
+        E.check_tiled_top_k(self.top_k, "; this set was built with cutoffs_only=True: evaluate it with cutoffs")
         emb = self.encode() if embedding is None else embedding
-        index = self.module.items_index
-        k, n_rows, H = self.top_k, index.table.shape[0], emb.shape[1]
-        idx = torch.empty((self.n_local, k), dtype=torch.int64, device=self.device)
-        score = torch.empty((self.n_local, k), dtype=torch.float32, device=self.device)
-        rnorm = index.rnorm if index.metric == METRICS["cosine"] else None
-        sqnorm = index.sqnorm if index.metric == METRICS["l2"] else None
-        lib = N.load()
+        if emb.dtype != torch.float32 or emb.dim() != 2 or emb.shape[0] != self.n_local or not emb.is_contiguous():
+            raise ValueError(f"embedding must be a contiguous float32 ({self.n_local}, H) tensor; got {emb.dtype}, "
+                             f"{tuple(emb.shape)}")
+        search = self.module.items_index._tiled_search(self.top_k)
+        idx = torch.empty((self.n_local, self.top_k), dtype=torch.int64, device=self.device)
+        score = torch.empty((self.n_local, self.top_k), dtype=torch.float32, device=self.device)
         for c in self._chunks:
-            r0, r1 = c["rows"]
-            nbytes = lib.xfmr_topk_tiled_workspace(r1 - r0, n_rows, k)
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
-            N.check(
-                lib.xfmr_topk_tiled(N.ptr(emb[r0:r1]), N.ptr(index.table), N.ptr(rnorm), N.ptr(sqnorm), n_rows, r1 - r0, H,
-                                    N.ptr(self.excl), N.ptr(c["excl_offsets"]), k, index.metric, N.ptr(idx[r0:r1]),
-                                    N.ptr(score[r0:r1]), N.ptr(ws), nbytes, N.stream()),
-                "xfmr_topk_tiled",
-            )
+            r0, r1 = c.row0, c.row1
+            search(emb[r0:r1], self.excl, c.excl_offsets, idx[r0:r1], score[r0:r1])
         return idx, score
 
     @torch.no_grad()
@@ -397,14 +368,10 @@ class DeviceEvalSet:
         ranks = torch.empty((self.local_targets.numel(),), dtype=torch.int32, device=self.device)
         toff = self._local_toff
         for c in self._chunks:
-            r0, r1 = c["rows"]
+            r0, r1 = c.row0, c.row1
             index.rank_targets(emb[r0:r1], (self.local_targets, self.local_target_offsets[r0 : r1 + 1]),
-                               (self.excl, c["excl_offsets"]), n_targets=int(toff[r1] - toff[r0]), out=ranks)
+                               (self.excl, c.excl_offsets), n_targets=int(toff[r1] - toff[r0]), out=ranks)
         return ranks
-
-    def _cutoffs(self, cutoffs) -> tuple[int, ...]:
-        cut = normalize_cutoffs(cutoffs)
-        return cut if self.top_k in cut else cut + (self.top_k,)
 
     @torch.no_grad()
     def evaluate_ranks_device(self, cutoffs) -> torch.Tensor:
@@ -426,21 +393,7 @@ class DeviceEvalSet:
         gives every target's exact rank, one launch pair the metrics at every cutoff, one read-back of 64 bytes per
         cutoff. Adds ``{stage}/<metric>@<K>`` for every cutoff; the plain keys are those of cutoff ``config.top_k``
         (added to the cutoffs when missing), equal to what the call without cutoffs returns."""
-        if cutoffs is not None:
-            cut = self._cutoffs(cutoffs)
-            sums = self.evaluate_ranks_device(cut).tolist()
-            out = {}
-            for K, s in zip(cut, sums):
-                n = int(s[7])
-                for i, name in enumerate(METRIC_NAMES):
-                    out[f"{stage}/{name}@{K}"] = s[i] / n if n else float("nan")
-                if K == self.top_k:
-                    for i, name in enumerate(METRIC_NAMES):
-                        out[f"{stage}/{name}"] = out[f"{stage}/{name}@{K}"]
-                    out[f"{stage}/num_rows"] = n
-            return out
-        s = self.evaluate_device().tolist()
-        n = int(s[7])
-        out = {f"{stage}/{name}": (s[i] / n if n else float("nan")) for i, name in enumerate(METRIC_NAMES)}
-        out[f"{stage}/num_rows"] = n
-        return out
+        if cutoffs is None:
+            return E.metrics_dict(stage, self.evaluate_device().tolist(), top_k=self.top_k)
+        cut = E.eval_cutoffs(cutoffs, self.top_k)
+        return E.metrics_dict(stage, self.evaluate_ranks_device(cut).tolist(), cut, self.top_k)

@@ -34,6 +34,7 @@ import torch
 
 from . import _native as N
 from . import ops
+from .eval_rows import eval_mode, lookup_rows, pad_histories
 from .losses import SharedNegatives
 from .params import (
     ATTENTION_PROBS_DROPOUT_PROB,
@@ -413,6 +414,21 @@ class RecommenderModel(torch.nn.Module):
                 sent = ops.l2_normalize(sent)
         return {"token_embeddings": tok, "sentence_embedding": sent, "attention_mask": key_mask.long()}
 
+    def eval_mode(self):
+        """Context manager: eval mode for the block; the ``training`` flag is put back afterwards, also when the block
+        raises (``eval_rows.eval_mode``). Nothing inside moves the dropout step count."""
+        return eval_mode(self)
+
+    def sentence_embeddings(self, chunk) -> torch.Tensor:
+        """Sentence embeddings (b, H) of one chunk of histories by the forward-only pass. ``chunk``: a packed dict
+        (``ops.pack_rows``'s keys with ``batch`` and ``seq_len``, built on the device or planned on the host) -> one row per
+        packed sequence, pooled by xfmr_pool_rows with the normalisation fused; or a right-padded ``(b, L)`` tensor."""
+        if isinstance(chunk, dict):
+            tok, _ = self._encode_tokens(packed=chunk, infer=True)
+            return ops.pool_rows(tok, chunk["seq_offsets"], self.config.pooling_mode,
+                                 normalize=bool(self.config.is_normalized))
+        return self(chunk, inference=True)["sentence_embedding"]
+
     @torch.no_grad()
     def encode_batch(self, histories) -> torch.Tensor:
         """Sentence embeddings (B, H) of a list of histories (lists of table rows), in eval mode: each history truncated
@@ -428,38 +444,24 @@ class RecommenderModel(torch.nn.Module):
         rows = [rows[b] for b in keep]
         lens = [len(r) for r in rows]
         L = max(lens)
-        lens_np = np.asarray(lens, dtype=np.int64)
-        hist_np = np.zeros((len(rows), L), dtype=np.int64)  # right-padded with the padding row 0
-        hist_np[np.arange(L)[None, :] < lens_np[:, None]] = np.concatenate([np.asarray(r, dtype=np.int64) for r in rows])
-        hist = torch.from_numpy(hist_np).to(dev)
-        was_training = self.training
-        self.eval()
-        try:
+        hist = torch.from_numpy(pad_histories(lens, np.concatenate([np.asarray(r, dtype=np.int64) for r in rows]))).to(dev)
+        with self.eval_mode():
             if self.supports_packed_rows(L):
                 order, offs64 = ops.length_order(lens)
                 order = order.to(dev)
                 packed = ops.pack_rows(hist, hist, None, offs64.to(dev), int(offs64[-1]), order=order)
-                packed |= {"batch": len(rows), "seq_len": L}
-                tok, _ = self._encode_tokens(packed=packed, infer=True)
-                sent = ops.pool_rows(tok, packed["seq_offsets"], self.config.pooling_mode,
-                                     normalize=bool(self.config.is_normalized))
+                sent = self.sentence_embeddings(packed | {"batch": len(rows), "seq_len": L})
                 emb = torch.empty_like(sent)
                 emb[order] = sent  # packed slot b holds history order[b]
             else:
-                emb = self(hist, inference=True)["sentence_embedding"]
-        finally:
-            self.train(was_training)
+                emb = self.sentence_embeddings(hist)
         out[torch.as_tensor(keep, dtype=torch.int64, device=dev)] = emb
         return out
 
     def encode(self, item_ids: list[str]) -> torch.Tensor:
         """Pooled embedding of a list of item ids; unknown ids are dropped (``models.py:347-364``)."""
         assert self.id2idx is not None
-        known = [i for i in item_ids if i in self.id2idx.index] if hasattr(self.id2idx, "index") else [
-            i for i in item_ids if i in self.id2idx
-        ]
-        vals = self.id2idx[known].to_numpy() if hasattr(self.id2idx, "index") else [self.id2idx[i] for i in known]
-        item_idx = torch.as_tensor(vals, device=self.device, dtype=torch.int64)
+        item_idx = torch.as_tensor(lookup_rows(self.id2idx, item_ids), device=self.device, dtype=torch.int64)
         # (the sentence embedding never carries a gradient: in eval mode the forward-only pass computes it)
         with torch.no_grad():
             return self(item_idx[None, :], inference=not self.training)["sentence_embedding"][0]

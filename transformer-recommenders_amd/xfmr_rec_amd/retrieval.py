@@ -11,33 +11,22 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import _native as N
+from .eval_rows import METRIC_NAMES, flat_csr, normalize_cutoffs  # noqa: F401 - (names of this module too)
 
 METRICS = {"cosine": 0, "dot": 1, "l2": 2}
-METRIC_NAMES = (  # metrics.py:7-15, in the order of XFMR_RM_*
-    "retrieval_normalized_dcg", "retrieval_average_precision", "retrieval_auroc", "retrieval_precision",
-    "retrieval_recall", "retrieval_hit_rate", "retrieval_reciprocal_rank",
-)
 
 
-def _flat_csr(rows):
-    off = np.zeros(len(rows) + 1, dtype=np.int64)
-    np.cumsum([len(r) for r in rows], out=off[1:])
-    flat = np.concatenate(rows) if off[-1] else np.zeros(1, dtype=np.int64)  # (one placeholder element: never read)
-    return flat, off
-
-
-def _csr(lists, device):
-    return tuple(torch.from_numpy(x).to(device) for x in _flat_csr([np.asarray(x, dtype=np.int64) for x in lists]))
+def _csr(lists, device, sort_unique: bool = False):
+    return tuple(torch.from_numpy(x).to(device) for x in flat_csr(lists, sort_unique))
 
 
 def sorted_exclusion_csr(lists):
     """Host side of xfmr_topk_tiled's exclusions: each query's list sorted ascending with duplicates removed, as one
-    flat int64 array + (B + 1) int64 offsets (numpy). The kernel binary-searches each list."""
-    return _flat_csr([np.unique(np.asarray(x, dtype=np.int64).reshape(-1)) for x in lists])
+    flat int64 array + (B + 1) int64 offsets (numpy; ``eval_rows.flat_csr``). The kernel binary-searches each list."""
+    return flat_csr(lists, sort_unique=True)
 
 
 def _queries(embedding):
@@ -112,7 +101,7 @@ class ExactItemIndex:
         """:meth:`search` for a batch of users through xfmr_topk_tiled: score tiles on the matrix cores and a streaming
         top-k, no (B, n_items) workspace. Same results as :meth:`search` up to the summation order of the scores (so up
         to near-tied scores at the k-th place). top_k <= 128."""
-        q, B, H, dev = _queries(embedding)
+        q, B, _, dev = _queries(embedding)
         idx = torch.empty((B, top_k), dtype=torch.int64, device=dev)
         score = torch.empty((B, top_k), dtype=torch.float32, device=dev)
         if B == 0:
@@ -121,18 +110,32 @@ class ExactItemIndex:
         if exclude_item_idx is not None:
             if len(exclude_item_idx) != B:
                 raise ValueError(f"exclude_item_idx has {len(exclude_item_idx)} lists for {B} queries")
-            ex, exo = (torch.from_numpy(x).to(dev) for x in sorted_exclusion_csr(exclude_item_idx))
-        n_rows = self.table.shape[0]
-        rnorm, sqnorm = self._norms()
-        lib = N.load()
-        nbytes = lib.xfmr_topk_tiled_workspace(B, n_rows, top_k)
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        N.check(
-            lib.xfmr_topk_tiled(N.ptr(q), N.ptr(self.table), N.ptr(rnorm), N.ptr(sqnorm), n_rows, B, H, N.ptr(ex),
-                                N.ptr(exo), top_k, self.metric, N.ptr(idx), N.ptr(score), N.ptr(ws), nbytes, N.stream()),
-            "xfmr_topk_tiled",
-        )
+            ex, exo = _csr(exclude_item_idx, dev, sort_unique=True)
+        self._tiled_search(top_k)(q, ex, exo, idx, score)
         return idx, score
+
+    def _tiled_search(self, top_k: int):
+        """The one xfmr_topk_tiled call, as the function of a pass: what stays the same from chunk to chunk (library, table,
+        norms, metric, ``top_k``) is bound here once. ``run(q, ex, exo, idx, score)`` then searches the non-empty contiguous
+        float32 queries ``q`` (B, H) (:func:`_queries`; a row range of such a tensor is one) into ``idx`` (B, top_k) int64
+        and ``score`` (B, top_k) float32; ``ex`` / ``exo``: the exclusions as int64 device CSR, each row sorted ascending
+        (:func:`sorted_exclusion_csr`; B + 1 offsets, a view into a longer array with absolute values is fine), or None.
+        Private: the callers allocate and shape every tensor themselves, nothing is checked here beyond ``N.ptr``."""
+        lib, metric = N.load(), self.metric
+        table, n_rows = N.ptr(self.table), self.table.shape[0]
+        rnorm, sqnorm = (N.ptr(x) for x in self._norms())
+
+        def run(q, ex, exo, idx, score):
+            B, H = q.shape
+            nbytes = lib.xfmr_topk_tiled_workspace(B, n_rows, top_k)
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
+            N.check(
+                lib.xfmr_topk_tiled(N.ptr(q), table, rnorm, sqnorm, n_rows, B, H, N.ptr(ex), N.ptr(exo), top_k, metric,
+                                    N.ptr(idx), N.ptr(score), N.ptr(ws), nbytes, N.stream()),
+                "xfmr_topk_tiled",
+            )
+
+        return run
 
     def rank_targets(self, embedding: torch.Tensor, targets_csr, exclude_csr=None, *, n_targets: int | None = None,
                      out: torch.Tensor | None = None, return_scores: bool = False):
@@ -168,21 +171,6 @@ class ExactItemIndex:
             "xfmr_target_ranks",
         )
         return (out, score) if return_scores else out
-
-
-def normalize_cutoffs(cutoffs) -> tuple[int, ...]:
-    """The cutoffs as given, repeats dropped, each a positive int below 2^31 (ValueError otherwise)."""
-    if isinstance(cutoffs, (int, np.integer)) and not isinstance(cutoffs, bool):
-        cutoffs = (cutoffs,)
-    out = []
-    for k in cutoffs:
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 < int(k) < 2**31:
-            raise ValueError(f"cutoffs must be positive integers below 2^31; got {k!r}")
-        if int(k) not in out:
-            out.append(int(k))
-    if not out:
-        raise ValueError("cutoffs is empty")
-    return tuple(out)
 
 
 def rank_metrics_sum(ranks: torch.Tensor, targets_csr, cutoffs, use: torch.Tensor | None = None, per_row: bool = False):

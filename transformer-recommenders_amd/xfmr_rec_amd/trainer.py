@@ -20,9 +20,11 @@ import math
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import _native as N
+from . import eval_rows as E
 from . import ops
 from .losses import LOSS_CLASSES, LossConfig, LossType
 from .models import ModelConfig, RecommenderModel
@@ -367,13 +369,13 @@ class RecommenderLightningModule(_Base):
 
     def _to_idx(self, item_ids) -> list[int]:
         """Item ids -> table rows; unknown ids are dropped (``models.py:347-364``). Integer inputs are rows already."""
-        m = self.model
         if len(item_ids) and not isinstance(item_ids[0], (str, bytes)):
             return [int(i) for i in item_ids]
-        assert m.id2idx is not None, "configure_embeddings(items_dataset) provides the id -> row mapping"
-        if hasattr(m.id2idx, "index"):
-            return [int(m.id2idx[i]) for i in item_ids if i in m.id2idx.index]
-        return [int(m.id2idx[i]) for i in item_ids if i in m.id2idx]
+        assert self.model.id2idx is not None, "configure_embeddings(items_dataset) provides the id -> row mapping"
+        return E.lookup_rows(self.model.id2idx, item_ids)
+
+    def _to_idx_or_empty(self, item_ids) -> list[int]:
+        return self._to_idx(item_ids) if len(item_ids) else []
 
     @torch.no_grad()
     def recommend(self, item_ids, *, top_k: int = 0, exclude_item_ids=None):
@@ -391,9 +393,6 @@ class RecommenderLightningModule(_Base):
         hist = list(row["history"]["item_id"])
         return self.recommend(hist, top_k=self.config.top_k, exclude_item_ids=hist)
 
-    def _to_idx_or_empty(self, item_ids) -> list[int]:
-        return self._to_idx(item_ids) if len(item_ids) else []
-
     @torch.no_grad()
     def recommend_batch(self, item_ids_lists, *, top_k: int = 0, exclude_item_ids=None):
         """:meth:`recommend` for many users in one pass: one batched encoder forward (``encode_batch``) and one
@@ -401,8 +400,12 @@ class RecommenderLightningModule(_Base):
         unknown ids are dropped) gets all -1 / -inf."""
         hists = [self._to_idx_or_empty(list(x)) for x in item_ids_lists]
         excl = None if exclude_item_ids is None else [self._to_idx_or_empty(list(x)) for x in exclude_item_ids]
+        return self._recommend_rows(hists, excl, top_k or self.config.top_k)
+
+    def _recommend_rows(self, hists, excl, top_k: int):
+        """:meth:`recommend_batch` behind the id conversion: histories and exclusions are lists of table rows."""
         emb = self.model.encode_batch(hists)
-        idx, score = self.items_index.search_batch(emb, excl, top_k=top_k or self.config.top_k)
+        idx, score = self.items_index.search_batch(emb, excl, top_k=top_k)
         empty = [b for b, h in enumerate(hists) if not h]
         if empty:
             e = torch.as_tensor(empty, dtype=torch.int64, device=idx.device)
@@ -426,75 +429,52 @@ class RecommenderLightningModule(_Base):
         ``cutoffs`` (e.g. ``(5, 10, 20, 500)``): the rank path -- per pass ``encode_batch``, every target's exact rank
         over the whole catalogue (``ExactItemIndex.rank_targets``) and the metrics at every cutoff from the ranks. Adds
         ``{stage}/<metric>@<K>`` per cutoff; the plain keys are those of cutoff ``config.top_k`` (added when missing), which
-        may then exceed 128."""
-        import numpy as np
+        may then exceed 128.
 
-        from .retrieval import METRIC_NAMES, retrieval_metrics
-
-        rows = list(rows)
-        if cutoffs is not None:
-            return self._evaluate_ranks(rows, stage, max(1, int(batch_size)), cutoffs)
-        total = np.zeros(len(METRIC_NAMES), dtype=np.float64)
-        n = 0
-        for b0 in range(0, len(rows), max(1, int(batch_size))):
-            chunk = rows[b0 : b0 + max(1, int(batch_size))]
-            recs = self.predict_batch(chunk)["item_idx"]
-            tgts = [self._to_idx_or_empty([i for i, l in zip(r["target"]["item_id"], r["target"]["label"]) if l])
-                    for r in chunk]
-            vals, valid = retrieval_metrics(recs, tgts, self.config.top_k)
-            vals, valid = vals.cpu().numpy().astype(np.float64), valid.cpu().numpy()
-            has_hist = np.asarray([bool(self._to_idx_or_empty(list(r["history"]["item_id"]))) for r in chunk])
-            use = valid & has_hist
-            total += vals[use].sum(axis=0)
-            n += int(use.sum())
-        out = {f"{stage}/{name}": (float(total[i] / n) if n else float("nan")) for i, name in enumerate(METRIC_NAMES)}
-        out[f"{stage}/num_rows"] = n
-        return out
+        Every id is converted once (``eval_rows.read_rows``); the list pass then runs what :meth:`predict_batch` runs
+        behind its id conversion (``_recommend_rows``), not :meth:`predict_batch` itself."""
+        rows, bs = list(rows), max(1, int(batch_size))
+        cut = None if cutoffs is None else E.eval_cutoffs(cutoffs, self.config.top_k)
+        total = np.zeros(8 if cut is None else (len(cut), 8), dtype=np.float64)
+        for b0 in range(0, len(rows), bs):
+            hists, tgts = E.read_rows(rows[b0 : b0 + bs], self._to_idx_or_empty)
+            total += self._list_pass(hists, tgts) if cut is None else self._rank_pass(hists, tgts, cut)
+        return E.metrics_dict(stage, total, cut, int(self.config.top_k))
 
     def _evaluate_ranks(self, rows, stage: str, batch_size: int, cutoffs) -> dict[str, float]:
-        import numpy as np
+        """:meth:`evaluate` with ``cutoffs`` (kept under its earlier name)."""
+        return self.evaluate(rows, stage, batch_size, cutoffs)
 
-        from .retrieval import METRIC_NAMES, normalize_cutoffs, rank_metrics_sum, sorted_exclusion_csr
+    def _list_pass(self, hists, tgts) -> np.ndarray:
+        """One chunk through the ranked lists: the per-row values are read back and added here, in float64 and in row
+        order, over the rows with a target and a history -> the 7 sums and the number of rows."""
+        from .retrieval import retrieval_metrics
 
-        cut = normalize_cutoffs(cutoffs)
-        top_k = int(self.config.top_k)
-        if top_k not in cut:
-            cut += (top_k,)
+        recs = self._recommend_rows(hists, hists, self.config.top_k)["item_idx"]
+        vals, valid = retrieval_metrics(recs, tgts, self.config.top_k)
+        vals, valid = vals.cpu().numpy().astype(np.float64), valid.cpu().numpy()
+        use = valid & np.asarray([bool(h) for h in hists])
+        return np.append(vals[use].sum(axis=0), float(use.sum()))
+
+    def _rank_pass(self, hists, tgts, cut) -> np.ndarray:
+        """One chunk through the target ranks: ``(len(cut), 8)`` sums, formed on the device and read back."""
+        from .retrieval import _csr, rank_metrics_sum
+
         dev = self.model.device
-        total = np.zeros((len(cut), 8), dtype=np.float64)
-        for b0 in range(0, len(rows), batch_size):
-            chunk = rows[b0 : b0 + batch_size]
-            hists = [self._to_idx_or_empty(list(r["history"]["item_id"])) for r in chunk]
-            tgts = [self._to_idx_or_empty([i for i, l in zip(r["target"]["item_id"], r["target"]["label"]) if l])
-                    for r in chunk]
-            emb = self.model.encode_batch(hists)
-            ex, exo = sorted_exclusion_csr(hists)
-            tg = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in tgts] + [np.zeros(1, dtype=np.int64)])
-            tgo = np.zeros(len(tgts) + 1, dtype=np.int64)
-            np.cumsum([len(t) for t in tgts], out=tgo[1:])
-            csr = (torch.from_numpy(tg).to(dev), torch.from_numpy(tgo).to(dev))
-            ranks = self.items_index.rank_targets(emb, csr, (torch.from_numpy(ex).to(dev), torch.from_numpy(exo).to(dev)),
-                                                  n_targets=int(tgo[-1]))
-            use = torch.from_numpy(np.asarray([bool(h) for h in hists], dtype=np.uint8)).to(dev)
-            total += rank_metrics_sum(ranks, csr, cut, use).cpu().numpy()
-        out = {}
-        for K, s in zip(cut, total):
-            n = int(s[7])
-            for i, name in enumerate(METRIC_NAMES):
-                out[f"{stage}/{name}@{K}"] = float(s[i] / n) if n else float("nan")
-            if K == top_k:
-                for i, name in enumerate(METRIC_NAMES):
-                    out[f"{stage}/{name}"] = out[f"{stage}/{name}@{K}"]
-                out[f"{stage}/num_rows"] = n
-        return out
+        emb = self.model.encode_batch(hists)
+        excl = _csr(hists, dev, sort_unique=True)
+        csr = _csr(tgts, dev)
+        ranks = self.items_index.rank_targets(emb, csr, excl, n_targets=sum(len(t) for t in tgts))
+        use = torch.from_numpy(np.asarray([bool(h) for h in hists], dtype=np.uint8)).to(dev)
+        return rank_metrics_sum(ranks, csr, cut, use).cpu().numpy()
 
     def compute_metrics(self, row, stage: str = "val") -> dict[str, torch.Tensor]:
         """``trainer.py:266-286``: the seven retrieval metrics of one validation row under ``{stage}/<name>``."""
         from .retrieval import compute_retrieval_metrics
 
         recs = self.predict_step(row)
-        tgt_ids = [i for i, l in zip(row["target"]["item_id"], row["target"]["label"]) if l]
-        metrics = compute_retrieval_metrics(recs["item_idx"], self._to_idx(tgt_ids), top_k=self.config.top_k)
+        tgt = self._to_idx(E.positive_target_ids(row))
+        metrics = compute_retrieval_metrics(recs["item_idx"], tgt, top_k=self.config.top_k)
         return {f"{stage}/{k}": v for k, v in metrics.items()}
 
     def validation_step(self, row, batch_idx: int = 0):
