@@ -103,6 +103,7 @@ class Seed(C.Structure):
 
 
 TARGET_FIRST, TARGET_DIAGONAL, TARGET_EXPLICIT = 0, 1, 2
+TARGET_MODES = {"first": TARGET_FIRST, "diagonal": TARGET_DIAGONAL, None: TARGET_EXPLICIT}  # LossConfig.target_position
 POOL_MODES = {"mean": 0, "max": 1, "cls": 2, "lasttoken": 3}
 
 _P = C.c_void_p

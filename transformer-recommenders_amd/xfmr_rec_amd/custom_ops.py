@@ -30,37 +30,13 @@ forces the registered ops in eager mode too -- the two routes are compared bit f
 from __future__ import annotations
 
 import ctypes as C
+import operator
 from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from . import _native as N
-
-_PREC_NAME = {v: k for k, v in N.PRECISIONS.items()}
-_U64 = (1 << 64) - 1
-N_HANDLES = 7  # embed_event, context, grads_half_event, profile_kernel, profile_layer, profile_event0, profile_event1
-
-
-def _signed64(x: int) -> int:
-    x &= _U64
-    return x - (1 << 64) if x >= (1 << 63) else x
-
-
-def _encoder_cfg(B, L, H, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags, seed,
-                 step_device, handles, seq_offsets=None, row_pos=None) -> N.EncoderCfg:
-    h = [int(x) & _U64 for x in handles] + [0] * (N_HANDLES - len(handles))
-    return N.EncoderCfg(
-        batch=int(B), seq_len=int(L), hidden=int(H), heads=heads, inter=inter, layers=layers, max_pos=max_pos,
-        precision=N.precision_id(precision), ln_eps=ln_eps, hidden_dropout=hidden_dropout, attn_dropout=attn_dropout,
-        flags=int(flags) & 0xFFFFFFFF, seed=int(seed) & _U64,
-        step_device=step_device.data_ptr() if step_device is not None else None,
-        embed_event=h[0] or None, context=h[1] or None, grads_half_event=h[2] or None,
-        profile_kernel=h[3], profile_layer=h[4], profile_events=(C.c_void_p * 2)(h[5] or None, h[6] or None),
-        seq_offsets=seq_offsets.data_ptr() if seq_offsets is not None else None,
-        row_pos=row_pos.data_ptr() if row_pos is not None else None,
-        packed_rows=int(row_pos.numel()) if row_pos is not None else 0,
-    )
 
 
 def _batch_dims(item_idx, seq_offsets, packed_seq_len):
@@ -72,6 +48,20 @@ def _batch_dims(item_idx, seq_offsets, packed_seq_len):
 
 
 # ------------------------------------------------------------------------------------------------ encoder
+def _fake_outputs(op, size_entry, flat_params, item_idx, table, *scalars):
+    """(tok, key_mask, nbytes of ``size_entry``) of a fake forward: the shapes of ops._encoder_outputs; the size is the
+    library's own host-side computation on the cfg without its device pointers (no device needed)."""
+    from . import ops
+
+    *cfg_scalars, _step_device, handles, seq_offsets, row_pos, packed_seq_len = scalars
+    B, L = _batch_dims(item_idx, seq_offsets, packed_seq_len)
+    H = table.shape[1]
+    nbytes = getattr(N.load(), size_entry)(C.byref(ops.encoder_cfg(B, L, H, *cfg_scalars, None, handles)))
+    torch._check(nbytes > 0, lambda: f"xfmr::{op}: unsupported encoder configuration")
+    rows = (row_pos.shape[0],) if seq_offsets is not None else (B, L)
+    return flat_params.new_empty((*rows, H), dtype=torch.float32), flat_params.new_empty(rows, dtype=torch.uint8), nbytes
+
+
 @torch.library.custom_op("xfmr::encoder", mutates_args=())
 def encoder(flat_params: Tensor, item_idx: Tensor, table: Tensor, heads: int, inter: int, layers: int, max_pos: int,
             precision: str, ln_eps: float, hidden_dropout: float, attn_dropout: float, flags: int, seed: int,
@@ -82,23 +72,15 @@ def encoder(flat_params: Tensor, item_idx: Tensor, table: Tensor, heads: int, in
     from . import ops
 
     B, L = _batch_dims(item_idx, seq_offsets, packed_seq_len)
-    cfg = _encoder_cfg(B, L, table.shape[1], heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout,
-                       attn_dropout, flags, seed, step_device, handles, seq_offsets, row_pos)
+    cfg = ops.encoder_cfg(B, L, table.shape[1], heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout,
+                          attn_dropout, flags, seed, step_device, handles, seq_offsets, row_pos)
     return ops.encoder_fwd(cfg, flat_params, item_idx, table)
 
 
 @encoder.register_fake
-def _(flat_params, item_idx, table, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags,
-      seed, step_device, handles, seq_offsets, row_pos, packed_seq_len):
-    B, L = _batch_dims(item_idx, seq_offsets, packed_seq_len)
-    H = table.shape[1]
-    cfg = _encoder_cfg(B, L, H, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags, seed,
-                       None, handles)
-    nbytes = N.load().xfmr_encoder_workspace_bytes(C.byref(cfg))  # a host-side size computation: no device needed
-    torch._check(nbytes > 0, lambda: "xfmr::encoder: unsupported encoder configuration")
-    rows = (row_pos.shape[0],) if seq_offsets is not None else (B, L)
-    return (flat_params.new_empty((*rows, H), dtype=torch.float32), flat_params.new_empty(rows, dtype=torch.uint8),
-            flat_params.new_empty((max(int(nbytes), 16),), dtype=torch.uint8))
+def _(flat_params, item_idx, table, *scalars):
+    tok, key_mask, nbytes = _fake_outputs("encoder", "xfmr_encoder_workspace_bytes", flat_params, item_idx, table, *scalars)
+    return tok, key_mask, flat_params.new_empty((max(int(nbytes), 16),), dtype=torch.uint8)
 
 
 @torch.library.custom_op("xfmr::encoder_bwd", mutates_args=("d_tok",))
@@ -111,8 +93,8 @@ def encoder_bwd(flat_params: Tensor, d_tok: Tensor, key_mask: Tensor, acts: Tens
 
     H = d_tok.shape[-1]
     B, L = (d_tok.shape[0], d_tok.shape[1]) if seq_offsets is None else (seq_offsets.shape[0] - 1, packed_seq_len)
-    cfg = _encoder_cfg(B, L, H, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags, seed,
-                       step_device, handles, seq_offsets, row_pos)
+    cfg = ops.encoder_cfg(B, L, H, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags,
+                          seed, step_device, handles, seq_offsets, row_pos)
     return ops.encoder_bwd(cfg, flat_params, d_tok, key_mask, acts)
 
 
@@ -133,17 +115,15 @@ def _encoder_setup(ctx, inputs, output):
 
 
 def _encoder_backward(ctx, d_tok, _d_mask, _d_acts):
+    from . import ops
+
     n_in = 18
     if d_tok is None:
         return (None,) * n_in
     flat_params, key_mask, acts, *rest = ctx.saved_tensors
     step_device = rest.pop(0) if ctx.have[0] else None
     seq_offsets, row_pos = (rest[0], rest[1]) if ctx.have[1] else (None, None)
-    d = d_tok.contiguous()
-    # the kernel sequence uses this buffer as scratch: in place only when the producer handed it over (ops._consumable)
-    # (`d is d_tok`: contiguous() returned its argument -- no data_ptr() here, this also runs on fake tensors when traced)
-    if d is d_tok and not getattr(d_tok, "_xfmr_consumable", False):
-        d = d.clone()
+    d = ops.backward_scratch(d_tok, operator.is_)  # (no data_ptr() here: this also runs on fake tensors when traced)
     *sc, handles = ctx.scalars
     grads = torch.ops.xfmr.encoder_bwd(flat_params, d, key_mask, acts, *sc, step_device, handles, seq_offsets, row_pos,
                                        ctx.packed_seq_len)
@@ -163,33 +143,21 @@ def encoder_infer(flat_params: Tensor, item_idx: Tensor, table: Tensor, heads: i
     from . import ops
 
     B, L = _batch_dims(item_idx, seq_offsets, packed_seq_len)
-    cfg = _encoder_cfg(B, L, table.shape[1], heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout,
-                       attn_dropout, flags, seed, None, handles, seq_offsets, row_pos)
+    cfg = ops.encoder_cfg(B, L, table.shape[1], heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout,
+                          attn_dropout, flags, seed, None, handles, seq_offsets, row_pos)
     tok, key_mask, _ws = ops.encoder_infer_fwd(cfg, flat_params, item_idx, table)
     return tok, key_mask
 
 
 @encoder_infer.register_fake
-def _(flat_params, item_idx, table, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags,
-      seed, step_device, handles, seq_offsets, row_pos, packed_seq_len):
-    B, L = _batch_dims(item_idx, seq_offsets, packed_seq_len)
-    H = table.shape[1]
-    cfg = _encoder_cfg(B, L, H, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags, seed,
-                       None, handles)
-    nbytes = N.load().xfmr_encoder_infer_workspace_bytes(C.byref(cfg))  # a host-side size computation: no device needed
-    torch._check(nbytes > 0, lambda: "xfmr::encoder_infer: unsupported encoder configuration")
+def _(flat_params, item_idx, table, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, *rest):
+    tok, key_mask, _ = _fake_outputs("encoder_infer", "xfmr_encoder_infer_workspace_bytes", flat_params, item_idx, table,
+                                     heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, *rest)
     torch._check(hidden_dropout == 0.0 and attn_dropout == 0.0, lambda: "xfmr::encoder_infer: dropout must be 0 (eval)")
-    rows = (row_pos.shape[0],) if seq_offsets is not None else (B, L)
-    return flat_params.new_empty((*rows, H), dtype=torch.float32), flat_params.new_empty(rows, dtype=torch.uint8)
+    return tok, key_mask
 
 
 # ------------------------------------------------------------------------------------------------ losses
-def _loss_kw(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives):
-    return dict(train_head=int(train_head), all_heads=int(all_heads), mask_false_negatives=bool(mask_false_negatives),
-                mode=int(mode), scale=float(scale), margin=float(margin), precision=precision,
-                num_hard_negatives=int(num_hard_negatives))
-
-
 @torch.library.custom_op("xfmr::scale_by_device_scalar_", mutates_args=("x",))
 def scale_by_device_scalar_(x: Tensor, g: Tensor) -> None:
     N.check(N.load().xfmr_scale_by_device_scalar(N.ptr(x), x.numel(), N.ptr(g), N.stream()), "xfmr_scale_by_device_scalar")
@@ -226,10 +194,10 @@ def sampled_loss(tok: Tensor, key_mask: Tensor, pos_idx: Tensor, neg_idx: Option
     workspace prepared on another stream, profile events -- exist on the ``autograd.Function`` route of :mod:`ops` only.)"""
     from . import ops
 
-    losses, stats, d_tok = ops.sampled_loss(
-        tok, key_mask, pos_idx, neg_idx, table, rnorm, table_bf16=table_bf16, need_grad=need_grad,
-        nsplit=plan[0] if plan else 0, nsplit_grad=plan[1] if len(plan) > 1 else 0,
-        **_loss_kw(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives))
+    opts = ops.LossOpts(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives,
+                        nsplit=plan[0] if plan else 0, nsplit_grad=plan[1] if len(plan) > 1 else 0)
+    losses, stats, d_tok = ops.sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts, table_bf16=table_bf16,
+                                            need_grad=need_grad)
     return losses[train_head].clone(), losses, stats, d_tok if d_tok is not None else tok.new_empty((0,))
 
 
@@ -245,26 +213,31 @@ def _(tok, key_mask, pos_idx, neg_idx, table, rnorm, table_bf16, train_head, all
     return _loss_fake(tok, tok, need_grad)
 
 
-def _loss_setup(ctx, inputs, output):
-    ctx.save_for_backward(output[3])
-    ctx.n_in = len(inputs)
-    ctx.set_materialize_grads(False)
+def _register_loss_autograd(op, n_grads: int, hand_over: bool):
+    """The autograd formula of a registered loss, the same pair as ops.LossFunction's: the op's outputs behind (train_loss,
+    losses, stats) are the gradient buffers of its first ``n_grads`` inputs ((0,) where not wanted), computed in the
+    forward's pass; the backward scales each by the incoming gradient, a device scalar, into a NEW tensor. ``hand_over``:
+    the (B*L) form marks that fresh tensor for the encoder backward to use as scratch."""
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(*output[3:3 + n_grads])
+        ctx.n_in = len(inputs)
+        ctx.set_materialize_grads(False)
 
-
-def _make_loss_backward(hand_over: bool):
-    def backward(ctx, g, _gl, _gs, _gd):
-        (d,) = ctx.saved_tensors
-        if g is None or d.numel() == 0:
+    def backward(ctx, g, *_):
+        if g is None:
             return (None,) * ctx.n_in
-        d = torch.ops.xfmr.scale_by_device_scalar(d, g.contiguous().to(torch.float32))
-        if hand_over and not torch.is_grad_enabled():  # a fresh buffer: the encoder backward may use it as scratch
-            d._xfmr_consumable = True
-        return (d,) + (None,) * (ctx.n_in - 1)
+        g = g.contiguous().to(torch.float32)
+        outs = [torch.ops.xfmr.scale_by_device_scalar(d, g) if d.numel() else None for d in ctx.saved_tensors]
+        if hand_over and not torch.is_grad_enabled():
+            for d in outs:
+                if d is not None:
+                    d._xfmr_consumable = True
+        return (*outs, *(None,) * (ctx.n_in - n_grads))
 
-    return backward
+    op.register_autograd(backward, setup_context=setup)
 
 
-sampled_loss.register_autograd(_make_loss_backward(True), setup_context=_loss_setup)
+_register_loss_autograd(sampled_loss, 1, True)
 
 
 @torch.library.custom_op("xfmr::sampled_loss_lists", mutates_args=())
@@ -275,9 +248,9 @@ def sampled_loss_lists(query: Tensor, pos_items: Tensor, neg_items: Optional[Ten
     """List form (compacted queries; losses.py:128-155 on structured candidates): (train_loss, losses, stats, d_query)."""
     from . import ops
 
-    losses, stats, d_q = ops.sampled_loss_lists(
-        query, pos_items, neg_items, table, rnorm, table_bf16=table_bf16, need_grad=need_grad,
-        **_loss_kw(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives))
+    opts = ops.LossOpts(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives)
+    losses, stats, d_q = ops.sampled_loss_lists(query, pos_items, neg_items, table, rnorm, opts, table_bf16=table_bf16,
+                                                need_grad=need_grad)
     return losses[train_head].clone(), losses, stats, d_q if d_q is not None else query.new_empty((0,))
 
 
@@ -287,7 +260,7 @@ def _(query, pos_items, neg_items, table, rnorm, table_bf16, train_head, all_hea
     return _loss_fake(query, query, need_grad)
 
 
-sampled_loss_lists.register_autograd(_make_loss_backward(False), setup_context=_loss_setup)
+_register_loss_autograd(sampled_loss_lists, 1, False)
 
 
 @torch.library.custom_op("xfmr::dense_loss", mutates_args=())
@@ -299,13 +272,10 @@ def dense_loss(query: Tensor, cand: Tensor, target: Optional[Tensor], target_mod
     target_mode: XFMR_TARGET_*."""
     from . import ops
 
-    tp = {N.TARGET_FIRST: "first", N.TARGET_DIAGONAL: "diagonal", N.TARGET_EXPLICIT: None}[int(target_mode)]
-    out = ops.dense_loss(query, cand, target, target_position=tp, train_head=int(train_head), all_heads=int(all_heads),
-                         mask_false_negatives=bool(mask_false_negatives), num_hard_negatives=int(num_hard_negatives),
-                         scale=float(scale), margin=float(margin), need_grad=need_query_grad or need_cand_grad,
-                         need_cand_grad=need_cand_grad)
-    losses, stats, d_q = out[:3]
-    d_c = out[3] if need_cand_grad else None
+    opts = ops.LossOpts(train_head, all_heads, mask_false_negatives, scale=scale, margin=margin,
+                        num_hard_negatives=num_hard_negatives)
+    losses, stats, d_q, d_c = ops.dense_loss_mode(query, cand, target, target_mode, opts,
+                                                  need_grad=need_query_grad or need_cand_grad, need_cand_grad=need_cand_grad)
     empty = query.new_empty((0,))
     return (losses[train_head].clone(), losses, stats, d_q if (need_query_grad and d_q is not None) else empty,
             d_c if d_c is not None else empty)
@@ -318,23 +288,7 @@ def _(query, cand, target, target_mode, train_head, all_heads, mask_false_negati
     return a + (torch.empty_like(cand, dtype=torch.float32) if need_cand_grad else query.new_empty((0,), dtype=torch.float32),)
 
 
-def _dense_setup(ctx, inputs, output):
-    ctx.save_for_backward(output[3], output[4])
-    ctx.n_in = len(inputs)
-    ctx.set_materialize_grads(False)
-
-
-def _dense_backward(ctx, g, _gl, _gs, _gq, _gc):
-    if g is None:
-        return (None,) * ctx.n_in
-    g = g.contiguous().to(torch.float32)
-    outs = []
-    for t in ctx.saved_tensors:
-        outs.append(torch.ops.xfmr.scale_by_device_scalar(t, g) if t.numel() else None)
-    return (outs[0], outs[1]) + (None,) * (ctx.n_in - 2)
-
-
-dense_loss.register_autograd(_dense_backward, setup_context=_dense_setup)
+_register_loss_autograd(dense_loss, 2, False)
 
 
 # ------------------------------------------------------------------------------------------------ small ops

@@ -161,9 +161,9 @@ class EmbedLoss(torch.nn.Module, abc.ABC):
             assert target.size(0) == n_rows, f"{target.size(0) = } != {n_rows = }"
         return target
 
-    def _opts(self, mode: int, *, all_heads: bool = False) -> dict:
+    def _opts(self, mode: int, *, all_heads: bool = False) -> ops.LossOpts:
         c = self.config
-        return dict(
+        return ops.LossOpts(
             train_head=self.kind if self.kind in N.LOSS_IDS else "InfoNCELoss", all_heads=all_heads,
             mask_false_negatives=c.mask_false_negatives, mode=mode, scale=c.scale, margin=c.margin,
             precision=self.precision, num_hard_negatives=c.num_hard_negatives,
@@ -178,29 +178,22 @@ class EmbedLoss(torch.nn.Module, abc.ABC):
                 raise ValueError("SharedNegatives candidates put the positive at column 0: target_position='first'")
             return ops.sampled_loss_lists_train(
                 q, candidate_embed.pos_items, candidate_embed.neg_items, candidate_embed.table,
-                candidate_embed.table_rnorm,
-                self._opts(N.NEG_SHARED, all_heads=all_heads) | {"table_bf16": candidate_embed.table_bf16},
+                candidate_embed.table_rnorm, self._opts(N.NEG_SHARED, all_heads=all_heads),
+                table_bf16=candidate_embed.table_bf16,
             )
         if isinstance(candidate_embed, CatalogCandidates):
             if target is None:
                 raise ValueError("CatalogCandidates need `target` (the positive item index per row)")
-            opts = self._opts(N.NEG_CATALOG, all_heads=all_heads) | {"table_bf16": candidate_embed.table_bf16}
-            if opts["mask_false_negatives"]:
-                # the reference would additionally mask catalogue items scoring above the positive; supported
-                pass
+            # (mask_false_negatives: the reference additionally masks catalogue items scoring above the positive; supported)
             return ops.sampled_loss_lists_train(
-                q, target.contiguous(), None, candidate_embed.table, candidate_embed.table_rnorm, opts
+                q, target.contiguous(), None, candidate_embed.table, candidate_embed.table_rnorm,
+                self._opts(N.NEG_CATALOG, all_heads=all_heads), table_bf16=candidate_embed.table_bf16,
             )
         # the reference's own calling convention: a dense (N,C,H) tensor (xfmr_dense_loss, C <= 8192). The training
         # path never builds it -- compute_embeds returns the structured forms above.
-        c = self.config
-        opts = dict(
-            target_position=c.target_position, train_head=self.kind if self.kind in N.LOSS_IDS else "InfoNCELoss",
-            all_heads=all_heads, mask_false_negatives=c.mask_false_negatives,
-            num_hard_negatives=c.num_hard_negatives, scale=c.scale, margin=c.margin,
-        )
         tgt = None if target is None else target.contiguous().to(torch.int64)
-        return ops.dense_loss_train(q, candidate_embed.contiguous().to(torch.float32), tgt, opts)
+        return ops.dense_loss_train(q, candidate_embed.contiguous().to(torch.float32), tgt,
+                                    self._opts(N.NEG_SHARED, all_heads=all_heads), target_position=self.config.target_position)
 
     def forward(self, query_embed, candidate_embed, target=None):
         """Summed loss over the batch (``losses.py:128-155``)."""

@@ -8,6 +8,7 @@ arithmetic is never torch's.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 import torch
@@ -349,28 +350,103 @@ def grad_accumulate_(acc, grads, first: bool):
     return acc
 
 
-def _plan_flags(nsplit: int = 0, nsplit_grad: int = 0) -> int:
-    """XFMR_LOSS_NSPLIT(n) | XFMR_LOSS_NSPLIT_GRAD(n): launch-plan overrides inside xfmr_loss_cfg.flags (0 = library's plan)."""
-    assert 0 <= nsplit < 256 and 0 <= nsplit_grad < 256
-    return (nsplit << 8) | (nsplit_grad << 16)
+@dataclasses.dataclass(frozen=True)
+class LossOpts:
+    """The options of a loss call that reach ``xfmr_loss_cfg``, with their one set of defaults. What belongs to a single call
+    -- ``table_bf16``, ``workspace``, ``prepared``, ``d_tok_zeroed``, the profile events -- is an argument of that call.
+    Reads like the dict it replaces: ``opts["mode"]``, ``opts == {...}``."""
+
+    train_head: str | int               # a name of N.LOSS_IDS, or its id
+    all_heads: bool | int = True        # False: the train head alone; True: every head; 2: every head but the train head
+    mask_false_negatives: bool = True
+    mode: int = N.NEG_SHARED
+    scale: float = 1.0
+    margin: float = 0.5
+    precision: str | int = "bf16"
+    num_hard_negatives: int = 0
+    padded_positions: int = 0           # packed rows: the padded batch's B * L, the densities' denominator (0: the rows given)
+    nsplit: int = 0                     # column splits of the launch plan forced by the caller (0: the library's plan;
+    nsplit_grad: int = 0                # parity tests walk several plans)
+
+    @classmethod
+    def of(cls, opts=None, /, **kw) -> "LossOpts":
+        """A record as it is (``kw`` replacing fields), or the record of a dict and / or keywords."""
+        if isinstance(opts, cls):
+            return opts.replace(**kw) if kw else opts
+        return cls(**(dict(opts or {}) | kw))
+
+    def replace(self, **kw) -> "LossOpts":
+        """``dataclasses.replace`` without its walk over the fields (4 us a call; the overlapped step makes four variants)."""
+        if kw.keys() - self.__dict__.keys():
+            raise TypeError(f"LossOpts has no field {sorted(kw.keys() - self.__dict__.keys())}")
+        new = object.__new__(LossOpts)
+        new.__dict__.update(self.__dict__, **kw)
+        return new
+
+    def __getitem__(self, field: str):
+        return getattr(self, field)
+
+    def __eq__(self, other):
+        if isinstance(other, dict):  # a dict equals the record it would make
+            try:
+                other = LossOpts(**other)
+            except TypeError:
+                return False
+        return isinstance(other, LossOpts) and dataclasses.astuple(self) == dataclasses.astuple(other)
+
+    @property
+    def head_id(self) -> int:
+        head = self.train_head
+        return N.LOSS_IDS[head] if isinstance(head, str) else int(head)
+
+    def cfg(self, *, flags: int = 0, profile_grad=None, profile_log=None) -> N.LossCfg:
+        """xfmr_loss_cfg: ``flags`` OR-ed with XFMR_LOSS_NSPLIT(nsplit) | XFMR_LOSS_NSPLIT_GRAD(nsplit_grad);
+        ``profile_grad`` / ``profile_log``: (start, stop) hipEvent_t handles recorded around the gradient-pass / the
+        values-only logging-pass kernel (measurement)."""
+        assert 0 <= self.nsplit < 256 and 0 <= self.nsplit_grad < 256
+        cfg = N.LossCfg(
+            train_head=self.head_id, all_heads=int(self.all_heads), mask_false_negatives=int(self.mask_false_negatives),
+            mode=self.mode, precision=N.precision_id(self.precision), scale=float(self.scale), margin=float(self.margin),
+            num_hard_negatives=int(self.num_hard_negatives), flags=int(flags) | (self.nsplit << 8) | (self.nsplit_grad << 16),
+            padded_positions=int(self.padded_positions),
+        )
+        if profile_grad is not None:
+            cfg.profile_grad[0], cfg.profile_grad[1] = profile_grad
+        if profile_log is not None:
+            cfg.profile_log[0], cfg.profile_log[1] = profile_log
+        return cfg
+
+    def op_scalars(self) -> tuple:
+        """The eight scalars torch.ops.xfmr.sampled_loss / sampled_loss_lists take, in the schema's (= the fields') order."""
+        return (self.head_id, int(self.all_heads), bool(self.mask_false_negatives), int(self.mode), float(self.scale),
+                float(self.margin), str(self.precision), int(self.num_hard_negatives))
 
 
-def sampled_loss_workspace(like, T, H, n_rows, *, train_head, all_heads=True, mask_false_negatives=True, mode=N.NEG_SHARED,
-                           scale=1.0, margin=0.5, precision="bf16", num_hard_negatives=0, nsplit=0, nsplit_grad=0, **_):
-    """An (unprepared) workspace for sampled_loss(..., workspace=...) on `like`'s device."""
-    cfg = _loss_cfg(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives,
-                    flags=_plan_flags(nsplit, nsplit_grad))
+def _entry_opts(opts, kw: dict, all_heads: bool) -> LossOpts:
+    """The options of a public loss entry: the record it was given, or its keywords over the entry's own ``all_heads``
+    default (every head for the (B*L) entries, the train head alone for the list and the dense form). A keyword that is no
+    field of the record is a TypeError."""
+    return LossOpts.of(opts, **kw) if opts is not None else LossOpts(**({"all_heads": all_heads} | kw))
+
+
+def sampled_loss_workspace(like, T, H, n_rows, opts=None, *, table_bf16=None, **kw):
+    """An (unprepared) workspace for sampled_loss(..., workspace=...) on `like`'s device. ``opts`` / ``**kw``: a
+    :class:`LossOpts` or its fields by keyword. The size depends on T, H, n_rows, on ``nsplit`` and on whether
+    ``num_hard_negatives`` > 0 (csrc/loss.hip: loss_carve); the library is handed the cfg the call will run with.
+    ``table_bf16`` is taken so that the keywords of that call can be passed here as they are; the size does not depend on
+    it. Any other keyword that is no field of the record is a TypeError."""
+    cfg = _entry_opts(opts, kw, True).cfg()
     return _bytes(N.load().xfmr_sampled_loss_workspace_cfg(C.byref(cfg), T, H, n_rows), like)
 
 
-def sampled_loss_prepare(ws, key_mask, pos_idx, neg_idx, rnorm, n_rows, H, *, train_head, all_heads=True,
-                         mask_false_negatives=True, mode=N.NEG_SHARED, scale=1.0, margin=0.5, precision="bf16",
-                         num_hard_negatives=0, nsplit=0, nsplit_grad=0, **_):
+def sampled_loss_prepare(ws, key_mask, pos_idx, neg_idx, rnorm, n_rows, H, opts=None, *, table_bf16=None, **kw):
     """The index-only half of the loss (query compaction, multiplicities, distinct negatives) into `ws`, on the
     current stream: needs the key mask, not the token embeddings. Follow with sampled_loss(..., workspace=ws,
-    prepared=True) with the same options."""
-    cfg = _loss_cfg(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives,
-                    flags=_plan_flags(nsplit, nsplit_grad))
+    prepared=True) with the same options. The pass depends on ``mode`` (shared negatives are histogrammed) and, through the
+    workspace's carve, on ``nsplit`` and ``num_hard_negatives`` > 0. ``padded_positions`` is read by neither this pass nor
+    the size query -- only by the final reduction of the loss call (run_loss) -- so all three are handed the same cfg.
+    ``table_bf16``: as in :func:`sampled_loss_workspace` (the pass reads indices and inverse norms, not the table)."""
+    cfg = _entry_opts(opts, kw, True).cfg()
     N.check(
         N.load().xfmr_sampled_loss_prepare(C.byref(cfg), N.ptr(key_mask), N.ptr(pos_idx), N.ptr(neg_idx), N.ptr(rnorm),
                                            n_rows, key_mask.numel(), H, N.ptr(ws), ws.numel(), N.stream()),
@@ -378,25 +454,22 @@ def sampled_loss_prepare(ws, key_mask, pos_idx, neg_idx, rnorm, n_rows, H, *, tr
     )
 
 
-def sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, *, train_head, all_heads=True,
-                 mask_false_negatives=True, mode=N.NEG_SHARED, scale=1.0, margin=0.5, precision="bf16",
-                 need_grad=True, table_bf16=None, num_hard_negatives=0, workspace=None, prepared=False, d_tok_zeroed=None,
-                 profile_grad=None, profile_log=None, nsplit=0, nsplit_grad=0, padded_positions=0):
-    """Returns (losses[7], stats[16], d_tok or None). tok: (T,H) or (B,L,H). `workspace` (sampled_loss_workspace) +
-    `prepared=True`: sampled_loss_prepare already ran on it; `d_tok_zeroed`: a zero-filled buffer like tok to take the
-    gradient (the call then skips its own memset); `profile_grad` / `profile_log`: (start, stop) hipEvent_t handles
-    recorded around the gradient-pass / logging-pass kernel (measurement); `nsplit` / `nsplit_grad`: column-split counts
-    of the launch plan forced by the caller (0 = the library's plan; parity tests walk several plans)."""
+def sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts=None, *, need_grad=True, table_bf16=None,
+                 workspace=None, prepared=False, d_tok_zeroed=None, profile_grad=None, profile_log=None, **kw):
+    """Returns (losses[7], stats[16], d_tok or None). tok: (T,H) or (B,L,H). ``opts`` / ``**kw``: a :class:`LossOpts` or
+    its fields by keyword. `workspace` (sampled_loss_workspace) + `prepared=True`: sampled_loss_prepare already ran on it;
+    `d_tok_zeroed`: a zero-filled buffer like tok to take the gradient (the call then skips its own memset);
+    `profile_grad` / `profile_log`: as in :meth:`LossOpts.cfg`."""
+    o = _entry_opts(opts, kw, True)
     H = tok.shape[-1]
     T = tok.numel() // H
     lib = N.load()
     d_tok = (d_tok_zeroed if d_tok_zeroed is not None else torch.empty_like(tok)) if need_grad else None
-    flags = _plan_flags(nsplit, nsplit_grad)
+    flags = 0
     if d_tok_zeroed is not None and need_grad:
         assert d_tok.shape == tok.shape and d_tok.dtype == tok.dtype
-        flags |= N.LOSS_DTOK_ZEROED
-    cfg = _loss_cfg(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives,
-                    flags=flags, profile_grad=profile_grad, profile_log=profile_log, padded_positions=padded_positions)
+        flags = N.LOSS_DTOK_ZEROED
+    cfg = o.cfg(flags=flags, profile_grad=profile_grad, profile_log=profile_log)
     n_rows = table.shape[0]
     losses = _empty((2 * N.NUM_LOSSES,), tok)
     stats = _empty((N.NUM_STATS,), tok)
@@ -415,55 +488,42 @@ def sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, *, train_head, a
     return losses, stats, d_tok
 
 
-def _loss_cfg(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision,
-              num_hard_negatives=0, *, flags=0, profile_grad=None, profile_log=None, padded_positions=0) -> N.LossCfg:
-    cfg = N.LossCfg(
-        train_head=N.LOSS_IDS[train_head] if isinstance(train_head, str) else int(train_head),
-        all_heads=int(all_heads), mask_false_negatives=int(mask_false_negatives), mode=mode,
-        precision=N.precision_id(precision), scale=float(scale), margin=float(margin),
-        num_hard_negatives=int(num_hard_negatives), flags=int(flags), padded_positions=int(padded_positions),
-    )
-    if profile_grad is not None:  # (start, stop) hipEvent_t handles around the gradient-pass kernel
-        cfg.profile_grad[0], cfg.profile_grad[1] = profile_grad
-    if profile_log is not None:  # ... around the values-only logging pass
-        cfg.profile_log[0], cfg.profile_log[1] = profile_log
-    return cfg
-
-
-def dense_loss(query, cand, target=None, *, target_position="first", train_head, all_heads=False,
-               mask_false_negatives=True, num_hard_negatives=0, scale=1.0, margin=0.5, need_grad=True,
-               need_cand_grad=False):
+def dense_loss(query, cand, target=None, opts=None, *, target_position="first", need_grad=True, need_cand_grad=False, **kw):
     """``EmbedLoss.forward`` on a dense (N,C,H) candidate tensor (``losses.py:128-155``):
     returns (losses[14], stats[16], d_query or None[, d_cand when ``need_cand_grad``])."""
+    out = dense_loss_mode(query, cand, target, N.TARGET_MODES[target_position], _entry_opts(opts, kw, False),
+                          need_grad=need_grad, need_cand_grad=need_cand_grad)
+    return out if need_cand_grad else out[:3]
+
+
+def dense_loss_mode(query, cand, target, target_mode: int, opts: LossOpts, *, need_grad=True, need_cand_grad=False):
+    """:func:`dense_loss` by XFMR_TARGET_* id: always (losses, stats, d_query or None, d_cand or None). The dense kernel is
+    fp32 on the candidates it is given: of ``opts`` it reads the heads, ``mask_false_negatives``, ``scale``, ``margin`` and
+    ``num_hard_negatives``; ``mode``, ``precision``, ``padded_positions`` and the launch-plan overrides do not apply to it."""
     Nq, H = query.shape
     Cn = cand.shape[1]
-    mode = {"first": N.TARGET_FIRST, "diagonal": N.TARGET_DIAGONAL, None: N.TARGET_EXPLICIT}[target_position]
     lib = N.load()
-    cfg = _loss_cfg(train_head, all_heads, mask_false_negatives, N.NEG_SHARED, scale, margin, "fp32",
-                    num_hard_negatives)
+    cfg = opts.replace(mode=N.NEG_SHARED, precision="fp32", padded_positions=0, nsplit=0, nsplit_grad=0).cfg()
     losses, stats = _empty((2 * N.NUM_LOSSES,), query), _empty((N.NUM_STATS,), query)
     d_q = torch.empty_like(query) if need_grad else None
     nbytes = lib.xfmr_dense_loss_workspace(Nq, Cn, H)
     ws = _bytes(nbytes, query)
     d_c = torch.empty_like(cand) if need_cand_grad else None
     N.check(
-        lib.xfmr_dense_loss_grads(C.byref(cfg), N.ptr(query), N.ptr(cand), N.ptr(target), mode, Nq, Cn, H, N.ptr(losses),
-                                  N.ptr(stats), N.ptr(d_q), N.ptr(d_c), N.ptr(ws), nbytes, N.stream()),
+        lib.xfmr_dense_loss_grads(C.byref(cfg), N.ptr(query), N.ptr(cand), N.ptr(target), int(target_mode), Nq, Cn, H,
+                                  N.ptr(losses), N.ptr(stats), N.ptr(d_q), N.ptr(d_c), N.ptr(ws), nbytes, N.stream()),
         "xfmr_dense_loss_grads",
     )
-    return (losses, stats, d_q, d_c) if need_cand_grad else (losses, stats, d_q)
+    return losses, stats, d_q, d_c
 
 
-def sampled_loss_lists(query, pos_items, neg_items, table, rnorm, *, train_head, all_heads=False,
-                       mask_false_negatives=True, mode=N.NEG_SHARED, scale=1.0, margin=0.5, precision="bf16",
-                       need_grad=True, table_bf16=None, num_hard_negatives=0, nsplit=0, nsplit_grad=0):
-    """List form (compacted queries): returns (losses[7], stats[16], d_query or None). `nsplit` / `nsplit_grad`: as in
-    sampled_loss (0 = the library's plan)."""
+def sampled_loss_lists(query, pos_items, neg_items, table, rnorm, opts=None, *, need_grad=True, table_bf16=None, **kw):
+    """List form (compacted queries): returns (losses[7], stats[16], d_query or None). ``opts`` / ``**kw``: a
+    :class:`LossOpts` or its fields by keyword."""
     Np, H = query.shape
     Nn = 0 if neg_items is None else neg_items.numel()
     lib = N.load()
-    cfg = _loss_cfg(train_head, all_heads, mask_false_negatives, mode, scale, margin, precision, num_hard_negatives,
-                    flags=_plan_flags(nsplit, nsplit_grad))
+    cfg = _entry_opts(opts, kw, False).cfg()
     n_rows = table.shape[0]
     losses, stats = _empty((2 * N.NUM_LOSSES,), query), _empty((N.NUM_STATS,), query)
     d_q = torch.empty_like(query) if need_grad else None
@@ -506,32 +566,64 @@ def encoder_flags_from_env() -> int:
     return f
 
 
-def make_encoder_cfg(*, batch, seq_len, hidden, heads, inter, layers, max_pos, precision, ln_eps=1e-12,
-                     hidden_dropout=0.0, attn_dropout=0.0, seed=0, causal=True, flags=None, step_device=None,
-                     embed_event=None, context=None, grads_half_event=None, extra_flags=0, profile=None,
-                     seq_offsets=None, row_pos=None) -> N.EncoderCfg:
-    """``step_device``: a uint32 device tensor (or pointer) mixed into the dropout stream on the device;
+N_HANDLES = 7  # embed_event, context, grads_half_event, profile_kernel, profile_layer, profile_event0, profile_event1
+_U64 = (1 << 64) - 1
+
+
+def encoder_op_args(*, heads, inter, layers, max_pos, precision, ln_eps=1e-12, hidden_dropout=0.0, attn_dropout=0.0,
+                    seed=0, causal=True, flags=None, step_device=None, embed_event=None, context=None,
+                    grads_half_event=None, extra_flags=0, profile=None, seq_offsets=None, row_pos=None, seq_len=0,
+                    batch=0, hidden=0):
+    """make_encoder_cfg's keyword arguments -> plain scalars, in plain Python (no ctypes: this runs inside traced code):
+    (heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags, seed, step_device, handles,
+    seq_offsets, row_pos, packed_seq_len) -- the arguments of torch.ops.xfmr.encoder behind its three tensors. The rules of
+    the cfg live here and nowhere else: ``flags`` None reads the A/B switches of the environment, ``extra_flags`` is
+    OR-ed in, ``causal=False`` sets XFMR_ENC_BIDIRECTIONAL; the seed is the signed form of its 64 bits (a schema int);
+    ``handles`` = the three event / context handles and the unpacked ``profile``. ``batch`` / ``hidden`` are the tensors'."""
+    f = encoder_flags_from_env() if flags is None else int(flags)
+    f |= int(extra_flags)
+    if not causal:
+        f |= N.ENC_BIDIRECTIONAL
+    seed = int(seed) & _U64
+    if seed >= 1 << 63:
+        seed -= 1 << 64
+    if not isinstance(precision, str):  # an id: the schema carries the name
+        precision = next(k for k, v in N.PRECISIONS.items() if v == int(precision))
+    prof = list(profile) if profile else [0, 0, 0, 0]
+    handles = [int(embed_event or 0), int(context or 0), int(grads_half_event or 0)] + [int(x or 0) for x in prof]
+    return (int(heads), int(inter), int(layers), int(max_pos), precision, float(ln_eps), float(hidden_dropout),
+            float(attn_dropout), f, seed, step_device, handles, seq_offsets, row_pos,
+            int(seq_len) if seq_offsets is not None else 0)
+
+
+def encoder_cfg(B, L, H, heads, inter, layers, max_pos, precision, ln_eps, hidden_dropout, attn_dropout, flags, seed,
+                step_device, handles, seq_offsets=None, row_pos=None) -> N.EncoderCfg:
+    """THE constructor of xfmr_encoder_cfg: the call's shape + :func:`encoder_op_args`'s scalars (all but the last). The
+    eager route and the registered ops both build their struct here. ``step_device``: a device tensor or a pointer."""
+    h = [int(x) & _U64 for x in handles] + [0] * (N_HANDLES - len(handles))
+    if isinstance(step_device, torch.Tensor):
+        assert step_device.dtype in (torch.int32, torch.uint32) and step_device.is_cuda
+        step_device = step_device.data_ptr()
+    return N.EncoderCfg(
+        batch=int(B), seq_len=int(L), hidden=int(H), heads=heads, inter=inter, layers=layers, max_pos=max_pos,
+        precision=N.precision_id(precision), ln_eps=ln_eps, hidden_dropout=hidden_dropout, attn_dropout=attn_dropout,
+        flags=int(flags) & 0xFFFFFFFF, seed=int(seed) & _U64, step_device=step_device or None,
+        embed_event=h[0] or None, context=h[1] or None, grads_half_event=h[2] or None,
+        profile_kernel=h[3], profile_layer=h[4], profile_events=(C.c_void_p * 2)(h[5] or None, h[6] or None),
+        seq_offsets=N.ptr(seq_offsets), row_pos=N.ptr(row_pos), packed_rows=0 if row_pos is None else int(row_pos.numel()),
+    )
+
+
+def make_encoder_cfg(*, batch, seq_len, hidden, **kw) -> N.EncoderCfg:
+    """xfmr_encoder_cfg of (batch, seq_len, hidden) and :func:`encoder_op_args`'s keywords: ``heads``, ``inter``, ``layers``,
+    ``max_pos``, ``precision``; ``ln_eps``, ``hidden_dropout``, ``attn_dropout``, ``seed``, ``causal``, ``flags``,
+    ``extra_flags``; ``step_device``: a uint32 device tensor (or pointer) mixed into the dropout stream on the device;
     ``embed_event``: a hipEvent_t handle the forward records once the key mask exists; ``context``: an
     ``xfmr_context`` handle (side stream of the backward's weight-gradient GEMMs); ``profile``: (N.PROF_*, layer,
     event0, event1) -- HIP events recorded around that part of the encoder (measurement); ``seq_offsets`` (batch + 1,
     int32) + ``row_pos`` (packed rows, int32): the PACKED layout (pack_rows) -- the token axis holds only each
     sequence's own rows."""
-    f = encoder_flags_from_env() if flags is None else int(flags)
-    f |= int(extra_flags)
-    if not causal:
-        f |= N.ENC_BIDIRECTIONAL
-    if isinstance(step_device, torch.Tensor):
-        assert step_device.dtype in (torch.int32, torch.uint32) and step_device.is_cuda
-        step_device = step_device.data_ptr()
-    return N.EncoderCfg(
-        batch=batch, seq_len=seq_len, hidden=hidden, heads=heads, inter=inter, layers=layers, max_pos=max_pos,
-        precision=N.precision_id(precision), ln_eps=ln_eps, hidden_dropout=hidden_dropout,
-        attn_dropout=attn_dropout, flags=f, seed=seed, step_device=step_device, embed_event=embed_event,
-        context=context, grads_half_event=grads_half_event,
-        profile_kernel=int(profile[0]) if profile else 0, profile_layer=int(profile[1]) if profile else 0,
-        profile_events=(C.c_void_p * 2)(profile[2], profile[3]) if profile else (C.c_void_p * 2)(None, None),
-        seq_offsets=N.ptr(seq_offsets), row_pos=N.ptr(row_pos), packed_rows=0 if row_pos is None else int(row_pos.numel()),
-    )
+    return encoder_cfg(batch, seq_len, hidden, *encoder_op_args(**kw)[:-1])
 
 
 class Context:
@@ -590,23 +682,25 @@ def length_order(lengths):
     return order, off
 
 
-def encoder_fwd(cfg: N.EncoderCfg, flat_params, item_idx, table):
-    lib = N.load()
-    T, H = cfg.batch * cfg.seq_len, cfg.hidden
-    if cfg.packed_rows:  # packed layout: the token axis holds the sequences' own rows only
-        tok = _empty((cfg.packed_rows, H), flat_params)
-        key_mask = _empty((cfg.packed_rows,), flat_params, torch.uint8)
-    else:
-        tok = _empty((cfg.batch, cfg.seq_len, H), flat_params)
-        key_mask = _empty((cfg.batch, cfg.seq_len), flat_params, torch.uint8)
-    nbytes = lib.xfmr_encoder_workspace_bytes(C.byref(cfg))
+def _encoder_outputs(cfg: N.EncoderCfg, flat_params, size_entry: str, head_sizes: str):
+    """(tok, key_mask, nbytes of ``size_entry``) for a forward of ``cfg``: (B, L, H) + (B, L), or -- packed layout: the
+    token axis holds the sequences' own rows only -- (rows, H) + (rows,). A cfg the library does not build is refused."""
+    rows = (cfg.packed_rows,) if cfg.packed_rows else (cfg.batch, cfg.seq_len)
+    tok = _empty((*rows, cfg.hidden), flat_params)
+    key_mask = _empty(rows, flat_params, torch.uint8)
+    nbytes = getattr(N.load(), size_entry)(C.byref(cfg))
     if nbytes == 0:
-        raise RuntimeError("xfmr_encoder_workspace_bytes: unsupported encoder configuration "
-                           "(head size must be 32, sizes positive, seq_len <= max_pos)")
+        raise RuntimeError(f"{size_entry}: unsupported encoder configuration "
+                           f"(head size must be {head_sizes}, sizes positive, seq_len <= max_pos)")
+    return tok, key_mask, nbytes
+
+
+def encoder_fwd(cfg: N.EncoderCfg, flat_params, item_idx, table):
+    tok, key_mask, nbytes = _encoder_outputs(cfg, flat_params, "xfmr_encoder_workspace_bytes", "32")
     acts = _bytes(nbytes, flat_params)
     N.check(
-        lib.xfmr_encoder_fwd(C.byref(cfg), N.ptr(flat_params), N.ptr(item_idx), N.ptr(table), table.shape[0],
-                             N.ptr(tok), N.ptr(key_mask), N.ptr(acts), nbytes, N.stream()),
+        N.load().xfmr_encoder_fwd(C.byref(cfg), N.ptr(flat_params), N.ptr(item_idx), N.ptr(table), table.shape[0],
+                                  N.ptr(tok), N.ptr(key_mask), N.ptr(acts), nbytes, N.stream()),
         "xfmr_encoder_fwd",
     )
     return tok, key_mask, acts
@@ -616,20 +710,12 @@ def encoder_infer_fwd(cfg: N.EncoderCfg, flat_params, item_idx, table, workspace
     """xfmr_encoder_infer: (tok, key_mask, workspace) -- the bits of :func:`encoder_fwd` for the same cfg (dropout 0), with
     nothing kept for a backward. ``workspace``: a byte tensor of at least xfmr_encoder_infer_workspace_bytes(cfg) bytes to
     run in (scratch of this call only); None allocates one of exactly that size."""
-    lib = N.load()
-    H = cfg.hidden
-    rows = (cfg.packed_rows,) if cfg.packed_rows else (cfg.batch, cfg.seq_len)
-    tok = _empty((*rows, H), flat_params)
-    key_mask = _empty(rows, flat_params, torch.uint8)
-    nbytes = lib.xfmr_encoder_infer_workspace_bytes(C.byref(cfg))
-    if nbytes == 0:
-        raise RuntimeError("xfmr_encoder_infer_workspace_bytes: unsupported encoder configuration "
-                           "(head size must be 32 or 64, sizes positive, seq_len <= max_pos)")
+    tok, key_mask, nbytes = _encoder_outputs(cfg, flat_params, "xfmr_encoder_infer_workspace_bytes", "32 or 64")
     if workspace is None:
         workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=flat_params.device)
     N.check(
-        lib.xfmr_encoder_infer(C.byref(cfg), N.ptr(flat_params), N.ptr(item_idx), N.ptr(table), table.shape[0],
-                               N.ptr(tok), N.ptr(key_mask), N.ptr(workspace), workspace.numel(), N.stream()),
+        N.load().xfmr_encoder_infer(C.byref(cfg), N.ptr(flat_params), N.ptr(item_idx), N.ptr(table), table.shape[0],
+                                    N.ptr(tok), N.ptr(key_mask), N.ptr(workspace), workspace.numel(), N.stream()),
         "xfmr_encoder_infer",
     )
     return tok, key_mask, workspace
@@ -652,6 +738,18 @@ def encoder_bwd(cfg: N.EncoderCfg, flat_params, d_tok, key_mask, acts, grads=Non
     return grads
 
 
+def backward_scratch(d_tok, same):
+    """The buffer an encoder backward runs on. Its kernel sequence uses the incoming gradient as scratch, and may do so in
+    place only when the producer handed the buffer over by marking it ``_xfmr_consumable`` (the fused (B*L) loss does: its
+    saved gradient is dead after its own backward); otherwise it works on a copy. ``same(d, d_tok)``: whether
+    ``contiguous()`` returned its argument -- ``data_ptr()`` equality on real tensors, ``is`` where the tensors may be fake
+    (a traced backward)."""
+    d = d_tok.contiguous()
+    if same(d, d_tok) and not getattr(d_tok, "_xfmr_consumable", False):
+        d = d.clone()
+    return d
+
+
 class EncoderFunction(torch.autograd.Function):
     """tok, key_mask = encoder(flat_params, item_idx); backward fills the flat gradient."""
 
@@ -670,11 +768,7 @@ class EncoderFunction(torch.autograd.Function):
         flat_params, key_mask, acts = ctx.saved_tensors
         if d_tok is None:
             return None, None, None, None, None
-        d = d_tok.contiguous()
-        # the kernel sequence reuses this buffer as scratch: it may only do so in place when the producer hands the
-        # buffer over (the fused loss does: its saved gradient is dead after its own backward)
-        if d.data_ptr() == d_tok.data_ptr() and not getattr(d_tok, "_xfmr_consumable", False):
-            d = d.clone()
+        d = backward_scratch(d_tok, lambda a, b: a.data_ptr() == b.data_ptr())
         grads = encoder_bwd(ctx.cfg, flat_params, d, key_mask, acts)
         return grads, None, None, None, None
 
@@ -704,88 +798,41 @@ def _is_unit_grad(g: torch.Tensor) -> bool:
     return hit
 
 
-class SampledLossFunction(torch.autograd.Function):
-    """(train_loss, losses[7], stats[16]) = fused_loss(tok, ...). Only train_loss carries a gradient; it was
-    computed in the same pass as the forward and is scaled by the incoming gradient in backward."""
+class LossFunction(torch.autograd.Function):
+    """(train_loss, losses[14], stats[16]) = ``run(need, *inputs)``, the node of all three loss forms. Only train_loss
+    carries a gradient: the kernels computed it in the same pass as the values, into one buffer per input of ``slots`` that
+    requires a gradient (``need``: which of them do; ``run`` returns ``(losses, stats, buffers)`` with None where not
+    needed), and the backward scales the buffers by the incoming gradient, a device scalar. ``sampled``: the (B*L) form of
+    the training step, which alone knows the unit gradient, hands its buffer over to the encoder backward and asks for no
+    zero-filled gradients of the logging outputs."""
 
     @staticmethod
-    def forward(ctx, tok, key_mask, pos_idx, neg_idx, table, rnorm, opts):
-        need = tok.requires_grad
-        losses, stats, d_tok = sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, need_grad=need, **opts)
-        head = opts["train_head"]
-        head = N.LOSS_IDS[head] if isinstance(head, str) else head
-        if need:
-            ctx.save_for_backward(d_tok)
+    def forward(ctx, run, head: int, slots: tuple, sampled: bool, *inputs):
+        losses, stats, grads = run(tuple(inputs[i].requires_grad for i in slots), *inputs)
+        ctx.slots = tuple(4 + i for i, d in zip(slots, grads) if d is not None)  # positions among forward's arguments
+        ctx.n_in, ctx.sampled = 4 + len(inputs), sampled
+        ctx.save_for_backward(*(d for d in grads if d is not None))
         ctx.mark_non_differentiable(losses, stats)
-        ctx.set_materialize_grads(False)  # no zero-filled gradients for the logging outputs
+        if sampled:
+            ctx.set_materialize_grads(False)
         return losses[head].clone(), losses, stats
 
     @staticmethod
     def backward(ctx, g, _gl, _gs):
-        if g is None:
-            return (None,) * 7
-        (d_tok,) = ctx.saved_tensors
-        if not _is_unit_grad(g):  # (the persistent unit gradient: nothing to multiply by)
+        out = [None] * ctx.n_in
+        if g is None:  # (the sampled form alone can see None: the others get a zero-filled gradient)
+            return tuple(out)
+        saved = ctx.saved_tensors
+        if not (ctx.sampled and _is_unit_grad(g)):  # (the persistent unit gradient: nothing to multiply by)
             g = g.contiguous().to(f32)
-            N.check(N.load().xfmr_scale_by_device_scalar(N.ptr(d_tok), d_tok.numel(), N.ptr(g), N.stream()),
-                    "xfmr_scale_by_device_scalar")
-        if not torch.is_grad_enabled():  # not under create_graph: the buffer is dead after this backward
-            d_tok._xfmr_consumable = True
-        return d_tok, None, None, None, None, None, None
-
-
-class SampledLossListsFunction(torch.autograd.Function):
-    """List form of :class:`SampledLossFunction`: compacted queries, explicit item-id lists."""
-
-    @staticmethod
-    def forward(ctx, query, pos_items, neg_items, table, rnorm, opts):
-        need = query.requires_grad
-        losses, stats, d_q = sampled_loss_lists(query, pos_items, neg_items, table, rnorm, need_grad=need, **opts)
-        head = opts["train_head"]
-        head = N.LOSS_IDS[head] if isinstance(head, str) else head
-        if need:
-            ctx.save_for_backward(d_q)
-        ctx.mark_non_differentiable(losses, stats)
-        return losses[head].clone(), losses, stats
-
-    @staticmethod
-    def backward(ctx, g, _gl, _gs):
-        (d_q,) = ctx.saved_tensors
-        g = g.contiguous().to(f32)
-        N.check(N.load().xfmr_scale_by_device_scalar(N.ptr(d_q), d_q.numel(), N.ptr(g), N.stream()),
-                "xfmr_scale_by_device_scalar")
-        return d_q, None, None, None, None, None
-
-
-class DenseLossFunction(torch.autograd.Function):
-    """``EmbedLoss.forward`` on dense candidates, differentiable in the query and -- when they require a gradient -- in
-    the candidates (``losses.py:128-155``)."""
-
-    @staticmethod
-    def forward(ctx, query, cand, target, opts):
-        need, need_c = query.requires_grad, cand.requires_grad
-        out = dense_loss(query, cand, target, need_grad=need or need_c, need_cand_grad=need_c, **opts)
-        losses, stats, d_q = out[:3]
-        head = opts["train_head"]
-        head = N.LOSS_IDS[head] if isinstance(head, str) else head
-        ctx.flags = (need, need_c)
-        ctx.save_for_backward(*([d_q] if need else []), *([out[3]] if need_c else []))
-        ctx.mark_non_differentiable(losses, stats)
-        return losses[head].clone(), losses, stats
-
-    @staticmethod
-    def backward(ctx, g, _gl, _gs):
-        need, need_c = ctx.flags
-        saved = list(ctx.saved_tensors)
-        g = g.contiguous().to(f32)
-        outs = []
-        for t in saved:
-            N.check(N.load().xfmr_scale_by_device_scalar(N.ptr(t), t.numel(), N.ptr(g), N.stream()),
-                    "xfmr_scale_by_device_scalar")
-            outs.append(t)
-        d_q = outs.pop(0) if need else None
-        d_c = outs.pop(0) if need_c else None
-        return d_q, d_c, None, None
+            for d in saved:
+                N.check(N.load().xfmr_scale_by_device_scalar(N.ptr(d), d.numel(), N.ptr(g), N.stream()),
+                        "xfmr_scale_by_device_scalar")
+        for slot, d in zip(ctx.slots, saved):
+            if ctx.sampled and not torch.is_grad_enabled():  # not under create_graph: the buffer is dead after this backward
+                d._xfmr_consumable = True
+            out[slot] = d
+        return tuple(out)
 
 
 # ------------------------------------------------------------------------------------------------ torch.ops.xfmr.*
@@ -798,25 +845,6 @@ from . import custom_ops  # noqa: E402  (registers torch.ops.xfmr.*)
 
 def use_torch_ops() -> bool:
     return torch.compiler.is_compiling() or os.environ.get("XFMR_TORCH_OPS", "") == "1"
-
-
-def encoder_op_args(*, heads, inter, layers, max_pos, precision, ln_eps=1e-12, hidden_dropout=0.0, attn_dropout=0.0,
-                    seed=0, causal=True, flags=None, step_device=None, embed_event=None, context=None,
-                    grads_half_event=None, extra_flags=0, profile=None, seq_offsets=None, row_pos=None, seq_len=0, **_shape):
-    """make_encoder_cfg's keyword arguments -> the scalar arguments of torch.ops.xfmr.encoder, in plain Python (no ctypes:
-    this runs inside traced code). Returns (scalars..., step_device, handles)."""
-    f = encoder_flags_from_env() if flags is None else int(flags)
-    f |= int(extra_flags)
-    if not causal:
-        f |= N.ENC_BIDIRECTIONAL
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    if seed >= 1 << 63:
-        seed -= 1 << 64
-    prof = list(profile) if profile else [0, 0, 0, 0]
-    handles = [int(embed_event or 0), int(context or 0), int(grads_half_event or 0)] + [int(x or 0) for x in prof]
-    return (int(heads), int(inter), int(layers), int(max_pos), str(precision), float(ln_eps), float(hidden_dropout),
-            float(attn_dropout), f, seed, step_device, handles, seq_offsets, row_pos,
-            int(seq_len) if seq_offsets is not None else 0)
 
 
 def encoder(flat_params, item_idx, table, cfg_kwargs: dict):
@@ -856,42 +884,55 @@ def encoder_infer(flat_params, item_idx, table, cfg_kwargs: dict):
     return tok, key_mask
 
 
-_EAGER_ONLY_LOSS_OPTS = ("workspace", "prepared", "d_tok_zeroed", "profile_grad", "profile_log")
+def _grad_on(t) -> bool:
+    return bool(t.requires_grad and torch.is_grad_enabled())
 
 
-def _loss_op_scalars(opts: dict):
-    head = opts["train_head"]
-    return (N.LOSS_IDS[head] if isinstance(head, str) else int(head), int(opts.get("all_heads", True)),
-            bool(opts.get("mask_false_negatives", True)), int(opts.get("mode", N.NEG_SHARED)), float(opts.get("scale", 1.0)),
-            float(opts.get("margin", 0.5)), str(opts.get("precision", "bf16")), int(opts.get("num_hard_negatives", 0)))
-
-
-def sampled_loss_train(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts: dict):
-    """(train_loss, losses[14], stats[16]) on (B*L) positions; train_loss carries the gradient w.r.t. `tok`."""
-    if use_torch_ops() and not any(opts.get(k) for k in _EAGER_ONLY_LOSS_OPTS):
-        out = torch.ops.xfmr.sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts.get("table_bf16"),
-                                          *_loss_op_scalars(opts), bool(tok.requires_grad and torch.is_grad_enabled()),
-                                          [int(opts.get("nsplit", 0)), int(opts.get("nsplit_grad", 0))])
+def sampled_loss_train(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts, *, table_bf16=None, **eager_only):
+    """(train_loss, losses[14], stats[16]) on (B*L) positions; train_loss carries the gradient w.r.t. `tok`. ``opts``: a
+    :class:`LossOpts` (or its dict). ``eager_only``: sampled_loss's ``workspace``, ``prepared``, ``d_tok_zeroed``,
+    ``profile_grad``, ``profile_log`` -- a call that sets one of them takes the eager route whatever use_torch_ops() says
+    (an autograd-registered op must be functional)."""
+    o = LossOpts.of(opts)
+    if use_torch_ops() and all(v is None or v is False for v in eager_only.values()):
+        out = torch.ops.xfmr.sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, table_bf16, *o.op_scalars(),
+                                          _grad_on(tok), [int(o.nsplit), int(o.nsplit_grad)])
         return out[0], out[1], out[2]
-    return SampledLossFunction.apply(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts)
+
+    def run(need, *tensors):
+        losses, stats, d_tok = sampled_loss(*tensors, o, need_grad=need[0], table_bf16=table_bf16, **eager_only)
+        return losses, stats, (d_tok,)
+
+    return LossFunction.apply(run, o.head_id, (0,), True, tok, key_mask, pos_idx, neg_idx, table, rnorm)
 
 
-def sampled_loss_lists_train(query, pos_items, neg_items, table, rnorm, opts: dict):
+def sampled_loss_lists_train(query, pos_items, neg_items, table, rnorm, opts, *, table_bf16=None):
+    """List form of :func:`sampled_loss_train`: compacted queries, explicit item-id lists."""
+    o = LossOpts.of(opts)
     if use_torch_ops():
-        out = torch.ops.xfmr.sampled_loss_lists(query, pos_items, neg_items, table, rnorm, opts.get("table_bf16"),
-                                                *_loss_op_scalars(opts), bool(query.requires_grad and torch.is_grad_enabled()))
+        out = torch.ops.xfmr.sampled_loss_lists(query, pos_items, neg_items, table, rnorm, table_bf16, *o.op_scalars(),
+                                                _grad_on(query))
         return out[0], out[1], out[2]
-    return SampledLossListsFunction.apply(query, pos_items, neg_items, table, rnorm, opts)
+
+    def run(need, *tensors):
+        losses, stats, d_q = sampled_loss_lists(*tensors, o, need_grad=need[0], table_bf16=table_bf16)
+        return losses, stats, (d_q,)
+
+    return LossFunction.apply(run, o.head_id, (0,), False, query, pos_items, neg_items, table, rnorm)
 
 
-def dense_loss_train(query, cand, target, opts: dict):
+def dense_loss_train(query, cand, target, opts, *, target_position="first"):
+    """``EmbedLoss.forward`` on dense candidates, differentiable in the query and -- when they require a gradient -- in
+    the candidates (``losses.py:128-155``)."""
+    o, mode = LossOpts.of(opts), N.TARGET_MODES[target_position]
     if use_torch_ops():
-        mode = {"first": N.TARGET_FIRST, "diagonal": N.TARGET_DIAGONAL, None: N.TARGET_EXPLICIT}[opts.get("target_position", "first")]
-        head = opts["train_head"]
-        grad_on = torch.is_grad_enabled()
-        out = torch.ops.xfmr.dense_loss(
-            query, cand, target, mode, N.LOSS_IDS[head] if isinstance(head, str) else int(head), int(opts.get("all_heads", False)),
-            bool(opts.get("mask_false_negatives", True)), float(opts.get("scale", 1.0)), float(opts.get("margin", 0.5)),
-            int(opts.get("num_hard_negatives", 0)), bool(query.requires_grad and grad_on), bool(cand.requires_grad and grad_on))
+        s = o.op_scalars()  # (the dense op's schema: no mode, no precision)
+        out = torch.ops.xfmr.dense_loss(query, cand, target, mode, s[0], s[1], s[2], s[4], s[5], s[7], _grad_on(query),
+                                        _grad_on(cand))
         return out[0], out[1], out[2]
-    return DenseLossFunction.apply(query, cand, target, opts)
+
+    def run(need, *tensors):
+        losses, stats, d_q, d_c = dense_loss_mode(*tensors, mode, o, need_grad=any(need), need_cand_grad=need[1])
+        return losses, stats, (d_q if need[0] else None, d_c)
+
+    return LossFunction.apply(run, o.head_id, (0, 1), False, query, cand, target)

@@ -14,6 +14,7 @@ from typing import NamedTuple
 import torch
 
 from . import _native as N
+from .ops import LossOpts
 
 HEADS = tuple(N.LOSS_IDS)  # head i of the kernels' loss vector is LOSS_CLASSES[i] (tests/test_step_plan_host.py)
 
@@ -49,7 +50,7 @@ class StepPlan(NamedTuple):
     train_loss: str
     log_all_losses: bool
     heads: tuple            # logged_heads(train_loss, log_all_losses)
-    opts: dict              # the loss calls' scalar options (the caller adds the tensor, table_bf16)
+    opts: LossOpts          # the loss calls' options (what belongs to one call -- table_bf16, a workspace -- is its argument)
 
     @classmethod
     def build(cls, cfg, *, batch: int, width: int, max_seq_length: int, has_lengths: bool = False, rows: int = 0,
@@ -89,9 +90,9 @@ class StepPlan(NamedTuple):
                    # a traced step is one stream (the overlapped form hands a raw event handle to the forward)
                    and not tracing)
         padded_positions = batch * L if packed else 0
-        opts = dict(train_head=c.train_loss, all_heads=c.log_all_losses, mask_false_negatives=c.mask_false_negatives,
-                    mode=N.NEG_CATALOG if catalogue else N.NEG_SHARED, scale=c.scale, margin=c.margin, precision=c.precision,
-                    num_hard_negatives=c.num_hard_negatives, padded_positions=padded_positions)
+        opts = LossOpts(train_head=c.train_loss, all_heads=c.log_all_losses, mask_false_negatives=c.mask_false_negatives,
+                        mode=N.NEG_CATALOG if catalogue else N.NEG_SHARED, scale=c.scale, margin=c.margin,
+                        precision=c.precision, num_hard_negatives=c.num_hard_negatives, padded_positions=padded_positions)
         return cls(catalogue=catalogue, batch=batch, L=L, packed=packed, rows=rows if packed else batch * L,
                    padded_positions=padded_positions, defer=bool(defer_logging), overlap=overlap, train_loss=c.train_loss,
                    log_all_losses=c.log_all_losses, heads=logged_heads(c.train_loss, c.log_all_losses), opts=opts)

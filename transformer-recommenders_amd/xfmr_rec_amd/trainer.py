@@ -259,8 +259,7 @@ class RecommenderLightningModule(_Base):
         if plan.packed:
             packed = self._pack_rows(batch, plan, pos, neg)
             pos, neg = packed["pos"], packed["neg"]
-        opts = plan.opts | {"table_bf16": m.table_bf16}
-        ws = self._overlap_workspaces(plan, opts) if plan.overlap else None
+        ws = self._overlap_workspaces(plan) if plan.overlap else None
         # (the forward records the event right after the launch that writes the key mask: xfmr_encoder_cfg.embed_event)
         tok, key_mask = m._encode_tokens(None if packed else hist, embed_event=self._ev_embed.cuda_event if plan.overlap else None,
                                          packed=packed)
@@ -268,12 +267,12 @@ class RecommenderLightningModule(_Base):
             tok = ops.l2_normalize(tok)
         assert packed is not None or tok.shape[1] == plan.L
         if plan.overlap:
-            train_loss, losses, losses_train, stats = self._losses_overlapped(opts, ws, tok, key_mask, pos, neg, profile_grad,
-                                                                              profile_log)
+            train_loss, losses, losses_train, stats = self._losses_overlapped(plan.opts, ws, tok, key_mask, pos, neg,
+                                                                              profile_grad, profile_log)
         else:
             train_loss, losses, stats = ops.sampled_loss_train(
-                tok, key_mask, pos, neg, m.embeddings, m.table_rnorm,
-                opts | {"profile_grad": profile_grad, "profile_log": profile_log}
+                tok, key_mask, pos, neg, m.embeddings, m.table_rnorm, plan.opts, table_bf16=m.table_bf16,
+                profile_grad=profile_grad, profile_log=profile_log
             )
             losses_train = None
         return step_result(plan, train_loss, losses, losses_train, stats, sync=sync_metrics)
@@ -291,7 +290,7 @@ class RecommenderLightningModule(_Base):
         packed = ops.pack_rows(batch["history_item_idx"].to(dev, torch.int64).contiguous(), pos, neg, offs64, plan.rows, order=order)
         return packed | {"batch": plan.batch, "seq_len": plan.L}
 
-    def _overlap_workspaces(self, plan: StepPlan, opts: dict) -> tuple:
+    def _overlap_workspaces(self, plan: StepPlan) -> tuple:
         """In front of the forward of an overlapped step: the two events (made once) and the two loss calls' workspaces,
         the logging pass's first."""
         m = self.model
@@ -299,10 +298,10 @@ class RecommenderLightningModule(_Base):
             self._ev_embed, self._ev_prep = torch.cuda.Event(), torch.cuda.Event()
             self._ev_embed.record()  # (creates the handle)
         H, n_rows = m.config.hidden_size, m.embeddings.shape[0]
-        return (ops.sampled_loss_workspace(m.flat, plan.rows, H, n_rows, **opts),
-                ops.sampled_loss_workspace(m.flat, plan.rows, H, n_rows, **opts))
+        return (ops.sampled_loss_workspace(m.flat, plan.rows, H, n_rows, plan.opts),
+                ops.sampled_loss_workspace(m.flat, plan.rows, H, n_rows, plan.opts))
 
-    def _losses_overlapped(self, opts: dict, ws: tuple, tok, key_mask, pos, neg, profile_grad, profile_log) -> tuple:
+    def _losses_overlapped(self, opts: ops.LossOpts, ws: tuple, tok, key_mask, pos, neg, profile_grad, profile_log) -> tuple:
         """The overlapped form: ``(train_loss, losses, losses_train, stats)`` of the logging pass on the side stream and
         the gradient pass on the main one."""
         m = self.model
@@ -319,7 +318,7 @@ class RecommenderLightningModule(_Base):
         side.wait_event(self._ev_embed)  # the key mask exists (the forward is still running)
         with torch.cuda.stream(side):
             for w, heads in ((ws_log, 2), (ws_grad, False)):
-                ops.sampled_loss_prepare(w, key_mask, pos, neg, m.table_rnorm, n_rows, H, **(opts | {"all_heads": heads}))
+                ops.sampled_loss_prepare(w, key_mask, pos, neg, m.table_rnorm, n_rows, H, opts.replace(all_heads=heads))
             d_tok0 = torch.zeros_like(tok)  # the gradient buffer, zeroed here instead of in front of the gradient pass
             self._ev_prep.record(side)
         # enqueued BEFORE the gradient pass: it needs the forward's output only, and at its lowest priority it takes
@@ -328,14 +327,13 @@ class RecommenderLightningModule(_Base):
         with torch.cuda.stream(side):
             # all_heads=2: every head except the train head (its value comes from the launch below)
             losses, stats, _ = ops.sampled_loss(
-                tok.detach(), key_mask, pos, neg, m.embeddings, m.table_rnorm, need_grad=False,
-                **(opts | {"all_heads": 2, "workspace": ws_log, "prepared": True, "profile_log": profile_log})
+                tok.detach(), key_mask, pos, neg, m.embeddings, m.table_rnorm, opts.replace(all_heads=2), need_grad=False,
+                table_bf16=m.table_bf16, workspace=ws_log, prepared=True, profile_log=profile_log
             )
         main.wait_event(self._ev_prep)  # (recorded long ago)
         train_loss, losses_train, _ = ops.sampled_loss_train(
-            tok, key_mask, pos, neg, m.embeddings, m.table_rnorm,
-            opts | {"all_heads": False, "workspace": ws_grad, "prepared": True, "d_tok_zeroed": d_tok0,
-                    "profile_grad": profile_grad}
+            tok, key_mask, pos, neg, m.embeddings, m.table_rnorm, opts.replace(all_heads=False), table_bf16=m.table_bf16,
+            workspace=ws_grad, prepared=True, d_tok_zeroed=d_tok0, profile_grad=profile_grad
         )
         for tns in (ws_log, ws_grad):
             tns.record_stream(side)
