@@ -26,9 +26,9 @@ def X():
     return x
 
 
-def _model(X, *, H, A, I, nL, Lmax, prec, state=None, table=None, is_decoder=True):
+def _model(X, *, H, A, I, nL, Lmax, prec, state=None, table=None, is_decoder=True, pooling="mean"):
     cfg = X.ModelConfig(hidden_size=H, num_attention_heads=A, intermediate_size=I, num_hidden_layers=nL,
-                        max_seq_length=Lmax, is_decoder=is_decoder)
+                        max_seq_length=Lmax, is_decoder=is_decoder, pooling_mode=pooling)
     m = X.RecommenderModel(cfg, device=DEV, precision=prec)
     if state is not None:
         m.load_encoder_state_dict(state)
@@ -278,18 +278,24 @@ def _oracle_run(key, params, table, idx, A, L, is_decoder, w, feed=None, patch=N
 
 
 def _encoder_shape_vs_oracle(X, prec, *, B, L, H, A, I, nL, V, lengths, is_decoder=True, state=None, scale=0.05,
-                             side_stream=None, dropout=None, packed=False, device_step=None):
+                             side_stream=None, dropout=None, packed=False, device_step=None, history=None, pooling="mean"):
     """`state="perturbed"`: _perturbed_state's parameters instead of the constructor's, and the oracle in fp64 on the same
     tensors (shared between the cases of one shape). `side_stream`: a pytest monkeypatch -- the model runs in TRAINING mode
     with both dropout rates patched to 0, which is what gives the backward the model's xfmr_context (the side stream of the
     weight-gradient GEMMs; eval mode passes none). `dropout`: a pytest monkeypatch -- the model under m.train() with the
     product's rates, the oracle in training mode under the host model's masks of that very forward (seed rule of
     models.py::_cfg_kwargs; `device_step`: use_device_step(True) with the counter at that value; `packed`: the packed layout
-    through ops.pack_rows and _encode_tokens(packed=...), as the trainer runs it). Prints and returns the worst per-tensor
-    gradient error."""
+    through ops.pack_rows and _encode_tokens(packed=...), as the trainer runs it). `history`: a (B, L) id tensor used instead of
+    ragged_batch's right-padded one (id 0 = padding, anywhere in a row; `lengths` is then unused); `pooling`: the model's
+    pooling_mode, the sentence embedding held to the oracle's restatement of that mode. Prints and returns the worst
+    per-tensor gradient error."""
     table = unit_table(V, H)
     batch, lengths = ragged_batch(B, L, V, lengths=lengths, seed=2)
-    m = _model(X, H=H, A=A, I=I, nL=nL, Lmax=L, prec=prec, table=table, is_decoder=is_decoder)
+    if history is not None:
+        assert tuple(history.shape) == (B, L) and not packed
+        batch = dict(batch, history_item_idx=history)
+        lengths = history.flatten().tolist()  # (the shared oracle run is keyed by it)
+    m = _model(X, H=H, A=A, I=I, nL=nL, Lmax=L, prec=prec, table=table, is_decoder=is_decoder, pooling=pooling)
     key = None
     if state is not None:
         assert state == "perturbed"
@@ -343,7 +349,12 @@ def _encoder_shape_vs_oracle(X, prec, *, B, L, H, A, I, nL, V, lengths, is_decod
         out = m(batch["history_item_idx"].to(DEV))
         assert torch.equal(out["attention_mask"].cpu().bool(), valid)
         e_tok = assert_close("tok", out["token_embeddings"].cpu()[valid], ref["tok"][valid], prec)
-        e_sent = assert_close("sentence_embedding", out["sentence_embedding"], ref["sent"], prec)
+        sent = ref["sent"]
+        if pooling != "mean":
+            from oracle import encoder as enc
+
+            sent = enc.pool(ref["tok"], valid, pooling)
+        e_sent = assert_close("sentence_embedding", out["sentence_embedding"], sent, prec)
         (out["token_embeddings"] * w.to(DEV) * valid.to(DEV)[..., None]).sum().backward()
     got = m.grad_state_dict()
     errs = {k: rel_l2(got[k], g) for k, g in ref["grads"].items() if not k.endswith("key.bias")}
@@ -404,6 +415,32 @@ def test_encoder_config2_shape_perturbed_vs_fp64_oracle(X, prec):
     that is not near uniform. Measured worst gradient: fp32 3.7e-7 (limit 1e-4), bf16 4.8e-3 (limit 3e-2); the other B = 3
     shapes below, bf16: config 4 5.8e-3, config 5 at L = 512 5.1e-3, 384 / 6 heads 7.1e-3, bidirectional 3.9e-3."""
     _encoder_shape_vs_oracle(X, prec, B=3, L=200, H=128, A=4, I=512, nL=2, V=300, lengths=[200, 131, 17], state="perturbed")
+
+
+def _history_with_padding_in_front_and_inside(B, L, V):
+    """(4, 70) ids: left-padded by 33 (a whole 32-key tile and one key), left-padded by 1, id 0 at positions 32..63 (a whole
+    interior tile), and an ordinary right-padded row."""
+    assert (B, L) == (4, 70)
+    h = torch.randint(1, V + 1, (B, L), generator=torch.Generator().manual_seed(9))
+    h[0, :33] = 0
+    h[1, :1] = 0
+    h[2, 32:64] = 0
+    h[3, 41:] = 0
+    return h
+
+
+@pytest.mark.parametrize("pooling", ["mean", "lasttoken"])
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_encoder_with_padding_ids_in_front_and_inside_vs_fp64_oracle(X, prec, pooling):
+    """embed_ln_fwd derives the key mask from the ids, so padding id 0 can sit anywhere in a history: two layers (the second
+    reads the first's padding rows as keys: a NaN there would spread through p = 0 in the P V product) of H = 64, two heads of
+    32 (bf16: the one-workgroup forward and the fused backward; fp32: the generic panel kernels). The oracle takes its mask
+    from the ids the same way; tokens, the pooled sentence embedding and every parameter gradient are compared as
+    everywhere. A query in front of the first visible key has no key at all: the kernels give ctx = 0 there, the oracle
+    (HF's finite mask bias) a uniform average -- both on padding rows only, which no valid row reads."""
+    B, L, V = 4, 70, 300
+    _encoder_shape_vs_oracle(X, prec, B=B, L=L, H=64, A=2, I=128, nL=2, V=V, lengths=None, state="perturbed",
+                             history=_history_with_padding_in_front_and_inside(B, L, V), pooling=pooling)
 
 
 def test_encoder_config4_shape_perturbed_vs_fp64_oracle(X):
