@@ -455,9 +455,15 @@ typedef struct xfmr_loss_cfg {
                                    mask's numel); 0 = `positions`                                                  */
 } xfmr_loss_cfg;
 enum {
-  XFMR_LOSS_DTOK_ZEROED = 1u    /* xfmr_sampled_loss_prepared: d_tok is already zero-filled (rows that are not queries
+  XFMR_LOSS_DTOK_ZEROED = 1u,   /* xfmr_sampled_loss_prepared: d_tok is already zero-filled (rows that are not queries
                                    must read 0) -- the caller did it, e.g. on another stream underneath the encoder
                                    forward (52 MB at T = 102 400) -- so the call skips its memset                  */
+  XFMR_LOSS_STATS_ELSEWHERE = 2u /* this call's stats[] are not read (the gradient half of a step whose statistics come
+                                   from its all_heads == 2 logging call): an InfoNCE gradient pass may then skip the
+                                   count of counted negatives, which only the statistics use -- XFMR_STAT_NEG_DENSITY
+                                   and XFMR_STAT_NEG_COUNT of this call are then 0 (and the logits/neg statistics
+                                   undefined, as with all_heads == 0 anyway). losses[] and d_tok keep every bit.
+                                   Heads whose gradient divides by the count ignore the flag.                      */
 };
 /* Launch-plan overrides inside `flags` (0 = the library's own plan, which depends on the number of 128-query blocks):
  * bits 8-15 the column-split count of the plan (the logging pass's), bits 16-23 the gradient pass's (clamped to the

@@ -229,6 +229,12 @@ int xf_attn_switches();
 int xf_loss_plan(int64_t T, int32_t H, int64_t n_rows, int32_t train_head, int32_t all_heads, int32_t mask_false_negatives,
                  int32_t mode, int32_t precision, int32_t num_hard_negatives, uint32_t flags, int32_t has_d_tok,
                  int32_t has_table_bf16, int32_t cus, uint64_t switches, int32_t out[40]);
+// The plan's later fields, for the same key (xf_loss_plan's layout stays as its test reads it): ext[0] = the gradient pass
+// keeps no count of the counted logits (a lean InfoNCE code beside a logging pass, or under XFMR_LOSS_STATS_ELSEWHERE);
+// then zeros. Same return code.
+int xf_loss_plan_ext(int64_t T, int32_t H, int64_t n_rows, int32_t train_head, int32_t all_heads, int32_t mask_false_negatives,
+                     int32_t mode, int32_t precision, int32_t num_hard_negatives, uint32_t flags, int32_t has_d_tok,
+                     int32_t has_table_bf16, int32_t cus, uint64_t switches, int32_t ext[8]);
 uint64_t xf_loss_switches();
 // d_lin (optional): the gradient of the Linear output feeding this LayerNorm (dropout-scaled dx), bf16 if lin16
 // d_gamma == d_beta == d_bias == nullptr defers the reduction of `partials` ([blocks][3][H], blocks returned in

@@ -962,8 +962,12 @@ struct LossPlan {
   // CombineArgs: need_grad, the split counts of the gradient's and of the values' records, the values' buffer (0 = part:
   // the gradient's), lse_from_grad, skip_train_head; then the kernel variant and its blocks (kValueRows / kCombineRows)
   int32_t need_grad, nsplit, nsplit_loss, loss_buf, lse_from_grad, skip_train_head, values_only, blocks;
+  // The gradient pass keeps no count of the counted logits (LossArgs::no_count, loss_common.h): the lean InfoNCE codes
+  // when nobody reads it -- its records' R_CNTD is then 0. (Behind the fields xf_loss_plan shows: xf_loss_plan_ext.)
+  int32_t grad_no_count;
 };
 constexpr int kLossPlanInts = sizeof(LossPlan) / sizeof(int32_t);
+constexpr int kLossPlanBaseInts = offsetof(LossPlan, grad_no_count) / sizeof(int32_t);  // what xf_loss_plan copies out
 
 // what check_loss_args and the plan refuse of the key alone
 bool loss_key_ok(int64_t rows, int64_t n_rows, int train_head, int num_hard) {
@@ -1078,6 +1082,13 @@ int loss_plan(const LossKey& k, LossPlan& lp) {
     lp.loss_buf = grad_pass && log_pass;
     lp.nsplit_loss = lp.loss_buf ? ns : lp.nsplit;
     lp.lse_from_grad = lp.loss_buf && lse_elsewhere;
+    // The count of the lean InfoNCE gradient epilogues (one select and one add per logit) feeds no InfoNCE result: the
+    // gradient and the log-sum-exp never divide by it (in the kernel's finish and in loss_combine_kernel inv_d is for the
+    // NCE / hinge / logistic heads). Its readers are the density and count statistics, and those come from the logging
+    // records when a logging pass runs in this call (loss_buf: the combine kernel takes them from V, not G) -- or are not
+    // read at all, which only the caller knows: XFMR_LOSS_STATS_ELSEWHERE. Every other head's gradient needs its count.
+    lp.grad_no_count = grad_pass && (gcode == HEAD_INFONCE_MASKED || gcode == HEAD_INFONCE_PINNED) &&
+                       (lp.loss_buf || (k.flags & XFMR_LOSS_STATS_ELSEWHERE) != 0);
   }
   lp.need_grad = k.d_tok && !finish;  // finish: the gradient pass wrote d_tok itself
   lp.skip_train_head = k.all_heads == 2 && !k.d_tok;
@@ -1156,7 +1167,20 @@ int xf_loss_plan(int64_t T, int32_t H, int64_t n_rows, int32_t train_head, int32
                                    num_hard_negatives, flags, has_d_tok != 0, has_table_bf16 != 0, cus,
                                    switches_of(switches)}, lp);
   memset(out, 0, 40 * sizeof(int32_t));
-  memcpy(out, &lp, sizeof(lp));
+  memcpy(out, &lp, kLossPlanBaseInts * sizeof(int32_t));
+  return rc;
+}
+// ... and the fields added since, in LossPlan's order: ext[0] = grad_no_count
+int xf_loss_plan_ext(int64_t T, int32_t H, int64_t n_rows, int32_t train_head, int32_t all_heads, int32_t mask_false_negatives,
+                     int32_t mode, int32_t precision, int32_t num_hard_negatives, uint32_t flags, int32_t has_d_tok,
+                     int32_t has_table_bf16, int32_t cus, uint64_t switches, int32_t ext[8]) {
+  static_assert(kLossPlanInts - kLossPlanBaseInts <= 8, "xf_loss_plan_ext's array");
+  LossPlan lp;
+  const int rc = loss_plan(LossKey{T, n_rows, H, train_head, all_heads, mask_false_negatives, mode, precision,
+                                   num_hard_negatives, flags, has_d_tok != 0, has_table_bf16 != 0, cus,
+                                   switches_of(switches)}, lp);
+  memset(ext, 0, 8 * sizeof(int32_t));
+  memcpy(ext, (const int32_t*)&lp + kLossPlanBaseInts, (kLossPlanInts - kLossPlanBaseInts) * sizeof(int32_t));
   return rc;
 }
 
@@ -1209,6 +1233,7 @@ static int run_loss(const xfmr_loss_cfg* cfg, const float* tok, const float* tab
     LossArgs l = a;
     l.nsplit = ps.nsplit; l.part = part[ps.buf];
     if (ps.role == kPassLog) l.need_grad = 0;
+    else l.no_count = lp.grad_no_count;
     if (ps.finish) l.d_tok = d_tok;
     if (ps.pinned) { l.pin_part = part[lp.loss_buf]; l.pin_nsplit = lp.nsplit_loss; }  // (the logging pass's records)
     if (ps.image) {

@@ -1,6 +1,7 @@
 // Shared between loss.hip (generic / fp32 main kernel, compaction, combine, host code) and the per-H
 // translation units of the LDS-DMA bf16 main kernel (loss_dma_h*.hip).
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace xfl {  // named: LossArgs crosses translation units
@@ -58,6 +59,10 @@ struct LossArgs {
   int T; int nsplit;
   int H;                  // generic kernel: the rows' real width (= their stride); <= the kernel's template width, % 32 == 0
   int train_head, mask_fn, mode, need_grad;
+  // HEAD_INFONCE_MASKED / HEAD_INFONCE_PINNED only: the pass keeps no count of the counted logits (its records carry
+  // R_CNTD = 0). The InfoNCE gradient never divides by the count; its only readers are the density / count statistics,
+  // and the plan sets this where they come from a logging pass or are not read at all (loss.hip: loss_plan).
+  int no_count;
   float scale, margin;
 };
 
@@ -211,8 +216,13 @@ __device__ __forceinline__ void loss_epilogue_t(f32x16& s, RowState& st, f32x16 
 // column of the sub-block a real negative. With masking the running maximum is pinned at the positive's logit
 // (m = scale * pos), a counted logit is one with s < pos (an exact tie by item id is not), the gradient weight IS the
 // softmax term (sum of weights == l) and the count is an integer add-with-carry: ~8 issue slots per element
-// instead of ~23 (VALU issue, not the matrix pipe, bounds this kernel).
-template <bool CHECK_VALID>
+// instead of ~23 (VALU issue, not the matrix pipe, bounds this kernel). COUNT = false (LossArgs::no_count): without the
+// count -- a select and an add per logit that no InfoNCE result reads; `cnt` is left as it is.
+// SPLIT_SUM (the H > 128 translation units): the term as a rounded product, then added to l, with contraction off. Those
+// units' vectoriser pairs l with the count and adds the rounded product; without the count the pairing goes and the
+// compiler fuses one term in sixteen into fma(2^x, mu, l) -- another rounding of l wherever a multiplicity is no power of
+// two. The H <= 128 units (built without that vectoriser) take the sum the same way with and without the count: as written.
+template <bool CHECK_VALID, bool COUNT = true, bool SPLIT_SUM = false>
 __device__ __forceinline__ void loss_epilogue_infonce_masked(f32x16& s, float& l, float& cnt, float pos_dot, float sc2,
                                                              float m, int pos_item, const int* nid_sb,
                                                              const float* mu_sb, int hh) {
@@ -227,10 +237,17 @@ __device__ __forceinline__ void loss_epilogue_infonce_masked(f32x16& s, float& l
       const int r = 4 * g + u;
       bool counted = (s[r] < pos_dot) & (nn[u] != pos_item);
       if (CHECK_VALID) counted &= nn[u] >= 0;  // only the last tile of the range can hold past-the-end columns
-      cnt += counted ? mu[u] : 0.f;
-      const float e = xf_exp2(counted ? fmaf(s[r], sc2, -m) : -INFINITY) * mu[u];
-      l += e;
-      s[r] = e;
+      if (COUNT) cnt += counted ? mu[u] : 0.f;
+      if constexpr (SPLIT_SUM) {
+#pragma clang fp contract(off)
+        const float e = xf_exp2(counted ? fmaf(s[r], sc2, -m) : -INFINITY) * mu[u];
+        l += e;
+        s[r] = e;
+      } else {
+        const float e = xf_exp2(counted ? fmaf(s[r], sc2, -m) : -INFINITY) * mu[u];
+        l += e;
+        s[r] = e;
+      }
     }
   }
 }
@@ -297,7 +314,7 @@ __device__ __forceinline__ void loss_epilogue_cos_masked(f32x16& s, float& contr
 
 // The unmasked counterpart (HEAD_INFONCE_PINNED): every valid column counts (the positive's own item only in the
 // in-batch form, with the positive's logit, as losses.py has it); m >= every counted logit by construction.
-template <bool CHECK_VALID>
+template <bool CHECK_VALID, bool COUNT = true, bool SPLIT_SUM = false>
 __device__ __forceinline__ void loss_epilogue_infonce_pinned(f32x16& s, float& l, float& cnt, float pos_dot, float sc2,
                                                              float m, int pos_item, bool catalog, const int* nid_sb,
                                                              const float* mu_sb, int hh) {
@@ -315,10 +332,17 @@ __device__ __forceinline__ void loss_epilogue_infonce_pinned(f32x16& s, float& l
       bool counted = !(catalog & same);
       if (CHECK_VALID) counted &= nn[u] >= 0;
       const float w = counted ? mu[u] : 0.f;
-      cnt += w;
-      const float e = xf_exp2(fminf(fmaf(sv, sc2, -m), 0.f)) * w;
-      l += e;
-      s[r] = e;
+      if (COUNT) cnt += w;
+      if constexpr (SPLIT_SUM) {  // (as in loss_epilogue_infonce_masked)
+#pragma clang fp contract(off)
+        const float e = xf_exp2(fminf(fmaf(sv, sc2, -m), 0.f)) * w;
+        l += e;
+        s[r] = e;
+      } else {
+        const float e = xf_exp2(fminf(fmaf(sv, sc2, -m), 0.f)) * w;
+        l += e;
+        s[r] = e;
+      }
     }
   }
 }

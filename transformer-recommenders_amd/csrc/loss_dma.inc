@@ -64,6 +64,36 @@ constexpr int loss_dma_waves() {
          // 64 KB tile-buffer pairs + side data = 152 KB of LDS per CU)
          : (H <= 128 || (H <= 256 && (HEAD_CODE < 0 || loss_dma_hparts(H, HEAD_CODE) > 1))) ? 2 : 1;
 }
+// The tile loop's two address economies, per variant (both leave every value as it is). Budgets: 168 registers for the
+// three-wave masked logging kernels, 256 for the others, the parent's waves per SIMD, no scratch in the tile loop.
+//  * unrolled: the two sub-blocks of a tile and the two tile buffers as compile-time constants, so the LDS fragment reads
+//    take their sub-block / buffer offsets as immediates (tile_step in the kernel). The two lean InfoNCE gradient codes up
+//    to H = 256 -- the benchmark's gradient pass among them: 214-218 registers at H = 128, as rolled. Everything else
+//    STAYED ROLLED: with four sub-block bodies in the loop the compiler's register demand leaves the budget (H = 128: the
+//    masked logging kernels 141-149 -> 168 + 184-236 B of scratch, the lean BPR / cosine codes 200-211 -> 256 + 164-416 B,
+//    the general heads worse; H = 64 the same picture; the two InfoNCE codes at H = 384: 84-228 B, and there the offsets
+//    exceed the 16-bit field anyway). XFL_TILE_UNROLL=0: rolled everywhere (A/B).
+//  * gather_resident: the NI per-piece (row, swizzled chunk) lane constants of the gather kept in registers across the
+//    loop: the gradient passes at two waves per SIMD or fewer up to H = 256. Not the logging passes (three waves at 168
+//    registers, or two whose register count decides how many more fit: H = 64 unmasked 95 -> 105 loses the fifth wave),
+//    not H = 384 (NI = 12: 24 registers; 20-250 B of scratch in most variants), and not the three general heads that sit
+//    at the register limit already -- the two cosine heads and the online-maximum InfoNCE (H = 128: 238-242 -> 256 + up
+//    to 28 B more scratch; H = 256 InfoNCE 136 -> 240 B). They recompute the constants per call, with an unsigned
+//    divide. XFL_GATHER_RESIDENT=0: recomputed everywhere (A/B).
+#ifndef XFL_TILE_UNROLL
+#define XFL_TILE_UNROLL 1
+#endif
+#ifndef XFL_GATHER_RESIDENT
+#define XFL_GATHER_RESIDENT 1
+#endif
+template <int H, int HEAD_CODE>
+constexpr bool loss_dma_unrolled() {
+  return XFL_TILE_UNROLL != 0 && H <= 256 && (HEAD_CODE == HEAD_INFONCE_MASKED || HEAD_CODE == HEAD_INFONCE_PINNED);
+}
+template <int H, int HEAD_CODE>
+constexpr bool loss_dma_gather_resident() {
+  return XFL_GATHER_RESIDENT != 0 && loss_dma_waves<H, HEAD_CODE>() <= 2 && H <= 256 && HEAD_CODE > (int)XFMR_LOSS_INFONCE;
+}
 // (Balanced spans -- one workgroup per resident slot, each walking an equal contiguous run of the (query block, tile)
 // units, at most two query prologues each, no partly filled last round -- were built and measured for the logging
 // kernels in round 3: 417 us against 399 for one workgroup per (query block, split) on the same box, 405-408 with two
@@ -104,9 +134,13 @@ int xf_launch_loss_qprep_t(const LossArgs& a, __bf16* qimg, float2* qaux, dim3 g
 // QIMG: the query rows come from the bf16 image (LossArgs::qimg). A compile-time form: with both prologues behind a
 // run-time test in one kernel the masked logging pass at H = 128 needed 168 registers and spilled 64 B per lane (143
 // and none with either prologue alone), and the H = 256 logging kernels spilled 170-220 B.
-template <int H, int HEAD_CODE, bool QIMG>
+// COUNT = false (LossArgs::no_count; the two lean InfoNCE codes only): the epilogue keeps no count, R_CNTD is written 0.
+template <int H, int HEAD_CODE, bool QIMG, bool COUNT = true>
 __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_main_dma_kernel(
     LossArgs a, const __bf16* tbf) {
+  static_assert(COUNT || HEAD_CODE == HEAD_INFONCE_MASKED || HEAD_CODE == HEAD_INFONCE_PINNED, "every other head needs its count");
+  constexpr bool UNROLLED = loss_dma_unrolled<H, HEAD_CODE>();
+  constexpr bool SPLIT_SUM = H > 128;  // the lean InfoNCE epilogues' running sum (loss_common.h)
   constexpr bool PINNED = HEAD_CODE == HEAD_INFONCE_PINNED;  // unmasked InfoNCE, row maximum known (loss_common.h)
   constexpr bool LEAN = HEAD_CODE == HEAD_INFONCE_MASKED || PINNED;  // lean epilogue only
   constexpr bool LOGU = HEAD_CODE == HEAD_LOG_UNMASKED_CATALOG;  // ... its unmasked full-catalogue form (loss_common.h)
@@ -233,21 +267,45 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
   const uint32_t tbf_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)tbf);
   const uint32_t tbf_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uintptr_t)tbf >> 32));
   const __bf16* const tbf_u = reinterpret_cast<const __bf16*>(((uint64_t)tbf_hi << 32) | (uint64_t)tbf_lo);
-  auto issue_gather = [&](int lt, int buf) {  // lt: tile index inside the chunk
-    __bf16* base = sEb + buf * TILE_ELEMS;
-    // (the lane index made opaque here: the per-piece lane constants below -- row, swizzled position -- are then recomputed
-    //  per call, a few vector instructions, instead of living in NI registers across the whole tile loop, where the
-    //  register-bound variants spilled them and reloaded one in front of every piece: a vmcnt wait that serialises the
-    //  pieces of a gather)
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
+  // Per-piece lane constants of the gather -- the image row r of this lane's 16-byte piece and the byte offset of its
+  // swizzled source chunk. Variants at two waves per SIMD or fewer have the registers to keep all NI pairs resident across
+  // the tile loop (pinned by opaque moves, or the compiler rematerialises them per call); three-wave variants recompute
+  // them per call (loss_dma_gather_resident).
+  constexpr bool GRES = loss_dma_gather_resident<H, HEAD_CODE>();
+  uint32_t g_row[GRES ? NI : 1], g_cb[GRES ? NI : 1];
+  if constexpr (GRES) {
 #pragma unroll
     for (int k = 0; k < NI; ++k) {
-      const int q = wid * NI + k;
-      const int g = q * 64 + ln;  // this lane's 16-byte piece of the image: row g / CPR, position g % CPR
-      const int r = g / SI::CPR, c = g % SI::CPR;
-      const int id = max(sNid[lt * BN + r], 0);  // past-the-end columns read the (finite) padding row
-      xf_glds16_raw_so(tbf_u, (uint32_t)id * (uint32_t)(2 * H) + (uint32_t)(16 * (c ^ SI::swz(r))), base + q * 512);
+      const uint32_t g = (uint32_t)((wid * NI + k) * 64) + (uint32_t)lane;
+      const uint32_t r = g / (uint32_t)SI::CPR, c = g % (uint32_t)SI::CPR;
+      g_row[k] = r;
+      g_cb[k] = 16u * (c ^ (uint32_t)SI::swz((int)r));
+      asm volatile("" : "+v"(g_row[k]), "+v"(g_cb[k]));
+    }
+  }
+  auto issue_gather = [&](int lt, int buf) {  // lt: tile index inside the chunk
+    __bf16* base = sEb + buf * TILE_ELEMS;
+    if constexpr (GRES) {
+#pragma unroll
+      for (int k = 0; k < NI; ++k) {
+        const int id = max(sNid[lt * BN + (int)g_row[k]], 0);  // past-the-end columns read the (finite) padding row
+        xf_glds16_raw_so(tbf_u, (uint32_t)id * (uint32_t)(2 * H) + g_cb[k], base + (wid * NI + k) * 512);
+      }
+    } else {
+      // (the lane index made opaque here: the per-piece lane constants -- row, swizzled position -- are then recomputed
+      //  per call, a few vector instructions, instead of living in NI registers across the whole tile loop, where the
+      //  register-bound variants spilled them and reloaded one in front of every piece: a vmcnt wait that serialises the
+      //  pieces of a gather)
+      uint32_t ln = (uint32_t)lane;
+      asm volatile("" : "+v"(ln));
+#pragma unroll
+      for (int k = 0; k < NI; ++k) {
+        const int q = wid * NI + k;
+        const uint32_t g = (uint32_t)(q * 64) + ln;  // this lane's 16-byte piece of the image: row g / CPR, position g % CPR
+        const uint32_t r = g / (uint32_t)SI::CPR, c = g % (uint32_t)SI::CPR;  // (unsigned: no sign fix-ups)
+        const int id = max(sNid[lt * BN + (int)r], 0);  // past-the-end columns read the (finite) padding row
+        xf_glds16_raw_so(tbf_u, (uint32_t)id * (uint32_t)(2 * H) + 16u * (c ^ (uint32_t)SI::swz((int)r)), base + q * 512);
+      }
     }
   };
 
@@ -278,16 +336,28 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
       sMul[e] = ((LOGM || BPRM || COSM) && j >= N) ? 0.f : (nmul ? nmul[jc] : 1.f);
     }
     __syncthreads();
-    issue_gather(0, 0);
-    for (int tile = c0; tile < c1; ++tile) {
-      const int lt = tile - c0, buf = lt & 1;
+    issue_gather(0, 0);  // every chunk starts at buffer 0
+    // Unrolled form (loss_dma_unrolled): the tiles of the chunk in PAIRS -- buffers 0 and 1, the second trip skipped for the
+    // tail of an odd count -- and both sub-blocks of a tile unrolled, so the sub-block's row offset sb * 32 * H * 2 and the
+    // buffer's buf * TILE_BYTES are compile-time. The swizzle reads the row's low four bits only and both are multiples of
+    // 32 rows: every fragment address is then a lane constant -- computed once, resident -- plus a constant that goes
+    // into the ds_read's 16-bit offset field, instead of being rebuilt per sub-block. One sub-block's temporaries live at a
+    // time (sched_barrier, as between the epilogues' runs). Rolled form: TU = 1, buf = lt & 1, the sub-block loop as it is.
+    constexpr int TU = UNROLLED ? 2 : 1, SBU = UNROLLED ? 2 : 1;  // tiles per trip; sub-block unroll count
+    static_assert(BN / 32 == 2, "two sub-blocks per tile");
+    for (int tile0 = c0; tile0 < c1; tile0 += TU) {
+#pragma unroll
+    for (int tu = 0; tu < TU; ++tu) {
+      const int tile = tile0 + tu;
+      if (TU > 1 && tile >= c1) break;
+      const int lt = tile - c0, buf = UNROLLED ? tu : (lt & 1);
       // this wave's gather of `tile` has landed; then everyone's has, and all reads of the other buffer are done.
       // Raw barrier + asm wait: nothing else in the loop waits on vmcnt.
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       if (tile + 1 < c1 && !((XFL_DBG & 8) && lt > 0)) issue_gather(lt + 1, buf ^ 1);
       const __bf16* E = sEb + buf * TILE_ELEMS;
-#pragma unroll 1
+#pragma unroll SBU
       for (int sb = 0; sb < BN / 32; ++sb) {
         f32x16 s;
 #pragma unroll
@@ -301,18 +371,18 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
           for (int r = 0; r < 16; ++r) st.l += s[r];
         } else if (PINNED) {
           if ((tile + 1) * BN <= N)
-            loss_epilogue_infonce_pinned<false>(s, st.l, lean_cnt, pos_dot, sc2, st.m, pos_item, catalog,
-                                                &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
+            loss_epilogue_infonce_pinned<false, COUNT, SPLIT_SUM>(s, st.l, lean_cnt, pos_dot, sc2, st.m, pos_item, catalog,
+                                                       &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
           else
-            loss_epilogue_infonce_pinned<true>(s, st.l, lean_cnt, pos_dot, sc2, st.m, pos_item, catalog,
-                                               &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
+            loss_epilogue_infonce_pinned<true, COUNT, SPLIT_SUM>(s, st.l, lean_cnt, pos_dot, sc2, st.m, pos_item, catalog,
+                                                      &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
         } else if (LEAN) {
           if ((tile + 1) * BN <= N)
-            loss_epilogue_infonce_masked<false>(s, st.l, lean_cnt, pos_dot, sc2, st.m, pos_item,
-                                                &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
+            loss_epilogue_infonce_masked<false, COUNT, SPLIT_SUM>(s, st.l, lean_cnt, pos_dot, sc2, st.m, pos_item,
+                                                       &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
           else
-            loss_epilogue_infonce_masked<true>(s, st.l, lean_cnt, pos_dot, sc2, st.m, pos_item,
-                                               &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
+            loss_epilogue_infonce_masked<true, COUNT, SPLIT_SUM>(s, st.l, lean_cnt, pos_dot, sc2, st.m, pos_item,
+                                                      &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
         } else if (BPRM) {
           loss_epilogue_bpr_masked(s, st.logi, st.cnt_d, st.sw, pos_dot, pos_dot * (1.f - a.margin), pos_item,
                                    &sNid[lt * BN + sb * 32], &sMul[lt * BN + sb * 32], hh);
@@ -356,7 +426,9 @@ __global__ __launch_bounds__(256, (loss_dma_waves<H, HEAD_CODE>())) void loss_ma
             for (int i = 0; i < NO; ++i) SI::tile_xb_tr(o[i], E, hpart * NO + i, sb * 32, s);
           }
         }
+        if (UNROLLED) __builtin_amdgcn_sched_barrier(0);
       }
+    }
     }
   }
 
@@ -466,6 +538,15 @@ constexpr bool loss_dma_built(int H, int code) {
 template <int H, int HEAD_CODE>
 int xfl_launch_code(const LossArgs& a, const __bf16* tbf, dim3 grid, hipStream_t st) {
   if constexpr (loss_dma_built(H, HEAD_CODE)) {
+    constexpr bool LEAN_NCE = HEAD_CODE == HEAD_INFONCE_MASKED || HEAD_CODE == HEAD_INFONCE_PINNED;
+    if constexpr (LEAN_NCE) {
+      if (a.no_count) {
+        if (a.qimg != nullptr) hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, true, false>), grid, dim3(256), 0, st, a, tbf);
+        else hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, false, false>), grid, dim3(256), 0, st, a, tbf);
+        XF_LAUNCH_CHECK();
+        return XFMR_OK;
+      }
+    } else if (a.no_count) return XFMR_EINVAL;  // (loss_plan asks for it with the two lean InfoNCE codes only)
     if (a.qimg != nullptr) hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, true>), grid, dim3(256), 0, st, a, tbf);
     else hipLaunchKernelGGL((loss_main_dma_kernel<H, HEAD_CODE, false>), grid, dim3(256), 0, st, a, tbf);
     XF_LAUNCH_CHECK();

@@ -27,6 +27,7 @@ ATTN_STREAM_KEYS = 2  # OR-ed into the attn_mode above: the key-streaming form a
 ENC_BIDIRECTIONAL, ENC_LN_UNFUSED, ENC_FFN_UNFUSED, ENC_FFN_BWD_UNFUSED, ENC_DW_INLINE, ENC_DW_SIDE_ANY = 1, 2, 4, 8, 16, 32
 ENC_DW_UNPAIRED, ENC_REDUCE_HALF_EARLY = 64, 128
 LOSS_DTOK_ZEROED = 1  # xfmr_loss_cfg.flags
+LOSS_STATS_ELSEWHERE = 2  # ... the call's stats[] are not read: an InfoNCE gradient pass skips its count
 ABI_VERSION = 3
 ECOMM = -6  # XFMR_ECOMM: RCCL not loadable / an RCCL call failed (xfmr_comm_last_error has RCCL's text)
 NUM_LOSSES, NUM_STATS = 7, 16

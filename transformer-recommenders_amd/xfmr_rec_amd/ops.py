@@ -455,10 +455,13 @@ def sampled_loss_prepare(ws, key_mask, pos_idx, neg_idx, rnorm, n_rows, H, opts=
 
 
 def sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts=None, *, need_grad=True, table_bf16=None,
-                 workspace=None, prepared=False, d_tok_zeroed=None, profile_grad=None, profile_log=None, **kw):
+                 workspace=None, prepared=False, d_tok_zeroed=None, stats_elsewhere=False, profile_grad=None,
+                 profile_log=None, **kw):
     """Returns (losses[7], stats[16], d_tok or None). tok: (T,H) or (B,L,H). ``opts`` / ``**kw``: a :class:`LossOpts` or
     its fields by keyword. `workspace` (sampled_loss_workspace) + `prepared=True`: sampled_loss_prepare already ran on it;
     `d_tok_zeroed`: a zero-filled buffer like tok to take the gradient (the call then skips its own memset);
+    `stats_elsewhere`: the caller does not read this call's `stats` (XFMR_LOSS_STATS_ELSEWHERE: an InfoNCE gradient pass
+    then keeps no count of its negatives; the count-derived entries of `stats` are 0, `losses` and `d_tok` unchanged);
     `profile_grad` / `profile_log`: as in :meth:`LossOpts.cfg`."""
     o = _entry_opts(opts, kw, True)
     H = tok.shape[-1]
@@ -469,6 +472,8 @@ def sampled_loss(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts=None, *, ne
     if d_tok_zeroed is not None and need_grad:
         assert d_tok.shape == tok.shape and d_tok.dtype == tok.dtype
         flags = N.LOSS_DTOK_ZEROED
+    if stats_elsewhere:
+        flags |= N.LOSS_STATS_ELSEWHERE
     cfg = o.cfg(flags=flags, profile_grad=profile_grad, profile_log=profile_log)
     n_rows = table.shape[0]
     losses = _empty((2 * N.NUM_LOSSES,), tok)
@@ -891,7 +896,7 @@ def _grad_on(t) -> bool:
 def sampled_loss_train(tok, key_mask, pos_idx, neg_idx, table, rnorm, opts, *, table_bf16=None, **eager_only):
     """(train_loss, losses[14], stats[16]) on (B*L) positions; train_loss carries the gradient w.r.t. `tok`. ``opts``: a
     :class:`LossOpts` (or its dict). ``eager_only``: sampled_loss's ``workspace``, ``prepared``, ``d_tok_zeroed``,
-    ``profile_grad``, ``profile_log`` -- a call that sets one of them takes the eager route whatever use_torch_ops() says
+    ``stats_elsewhere``, ``profile_grad``, ``profile_log`` -- a call that sets one of them takes the eager route whatever use_torch_ops() says
     (an autograd-registered op must be functional)."""
     o = LossOpts.of(opts)
     if use_torch_ops() and all(v is None or v is False for v in eager_only.values()):

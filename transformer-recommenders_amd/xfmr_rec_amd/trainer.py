@@ -331,9 +331,10 @@ class RecommenderLightningModule(_Base):
                 table_bf16=m.table_bf16, workspace=ws_log, prepared=True, profile_log=profile_log
             )
         main.wait_event(self._ev_prep)  # (recorded long ago)
+        # stats_elsewhere: this call's statistics are dropped right here -- they are the logging call's above
         train_loss, losses_train, _ = ops.sampled_loss_train(
             tok, key_mask, pos, neg, m.embeddings, m.table_rnorm, opts.replace(all_heads=False), table_bf16=m.table_bf16,
-            workspace=ws_grad, prepared=True, d_tok_zeroed=d_tok0, profile_grad=profile_grad
+            workspace=ws_grad, prepared=True, d_tok_zeroed=d_tok0, stats_elsewhere=True, profile_grad=profile_grad
         )
         for tns in (ws_log, ws_grad):
             tns.record_stream(side)
