@@ -497,7 +497,12 @@ int xfmr_sampled_loss_lists(const xfmr_loss_cfg* cfg, const float* query, const 
  * explicit `target` (N) of column indices (:211-261), false-negative mask (:263-293), top-k hard negatives
  * (:295-330, ties at the k-th logit share the remaining weight), the seven heads + LogitsStatistics, and
  * d_query (N,H) = dL(train_head)/dquery (may be NULL). cfg->mode and cfg->precision are ignored (fp32 vector arithmetic).
- * losses[14] / stats[16] as for xfmr_sampled_loss, with N_VALID = C and N_QUERY = N. */
+ * losses[14] / stats[16] as for xfmr_sampled_loss, with N_VALID = C and N_QUERY = N.
+ * An explicit target[row] outside [0, C) -- where the reference's gather raises; an item id passed for a column index
+ * looks like this -- is not refused (no host sync, nothing changes in a captured step) and not silently clamped: that
+ * row's seven loss values, its d_query row and its d_cand rows are NaN, so both halves of losses[14] read NaN. The
+ * other rows' gradients and the statistics are what they are without it (the statistics take that row at a clamped
+ * column). */
 enum { XFMR_TARGET_FIRST = 0, XFMR_TARGET_DIAGONAL = 1, XFMR_TARGET_EXPLICIT = 2 };
 size_t xfmr_dense_loss_workspace(int64_t N, int32_t C, int32_t H);
 int xfmr_dense_loss(const xfmr_loss_cfg* cfg, const float* query, const float* cand, const int64_t* target,

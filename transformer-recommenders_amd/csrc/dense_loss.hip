@@ -37,7 +37,21 @@ __device__ __forceinline__ unsigned sort_key(float f) {  // monotone: a < b  <=>
 }
 
 struct BlockRed {
-  float* red;  // [8]
+  float* red;    // [8]
+  double* redd;  // [4]
+  // fp64: the sums behind logits/neg/std. Their difference sum l^2 - (sum l)^2 / n is the variance times n, and an fp32
+  // rounding of either (2^-24 of mean^2) under the square root is 2.4e-4 of the mean when the selected logits are equal.
+  __device__ __forceinline__ double sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int lo = __shfl_xor(__double2loint(v), o, 64), hi = __shfl_xor(__double2hiint(v), o, 64);
+      v += __hiloint2double(hi, lo);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) redd[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (redd[0] + redd[1]) + (redd[2] + redd[3]);
+  }
   __device__ __forceinline__ float sum(float v) {
     v = xf_wave_sum(v);
     __syncthreads();
@@ -103,7 +117,7 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
   float* sRc = sCos + C;         // [C]
   float* sW = sRc + C;           // [C] gradient weight of the train head
   float* sRed = sW + C;          // [8]
-  BlockRed br{sRed};
+  BlockRed br{sRed, reinterpret_cast<double*>(sRed + 8)};  // ([4] doubles: 8-byte aligned, H % 4 == 0)
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
   const float* q = a.q + row * H;
@@ -146,10 +160,13 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
   __syncthreads();
 
   // ---- 2. target, masks, top-k thresholds ---------------------------------------------------------------
-  int tgt = 0;
-  if (a.target_mode == 1) tgt = (int)row;
-  else if (a.target_mode == 2) tgt = (int)a.target[row];
-  tgt = min(max(tgt, 0), C - 1);  // the reference's gather would raise on an out-of-range target
+  // An explicit target outside [0, C) -- the reference's gather would raise; an item id passed where a column index is
+  // meant looks like this -- is clamped for addressing only: the row's loss values and gradients are written as NaN.
+  int64_t tgt64 = 0;
+  if (a.target_mode == 1) tgt64 = row;
+  else if (a.target_mode == 2) tgt64 = a.target[row];
+  const bool bad_target = tgt64 < 0 || tgt64 >= (int64_t)C;
+  const int tgt = (int)(tgt64 < 0 ? 0 : (tgt64 >= (int64_t)C ? (int64_t)C - 1 : tgt64));
   const float pos_dot = sDot[tgt], cpos = sCos[tgt], rcpos = sRc[tgt];
   const bool mask_fn = a.mask_fn != 0;
   auto counted_d = [&](int c) { return c != tgt && (!mask_fn || sDot[c] < pos_dot); };
@@ -172,8 +189,9 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
       if (counted_d(c) && td.weight(sDot[c]) > 0.f) mx = fmaxf(mx, sDot[c] * sc2);
     M = br.max(mx);
   }
-  float cnt_d = 0.f, l = 0.f, nce = 0.f, hinge = 0.f, logi = 0.f, cnt_c = 0.f, contr = 0.f, ssum = 0.f, ssq = 0.f,
-        smin = INFINITY, smax = -INFINITY, sw = 0.f;
+  float cnt_d = 0.f, l = 0.f, nce = 0.f, hinge = 0.f, logi = 0.f, cnt_c = 0.f, contr = 0.f, smin = INFINITY,
+        smax = -INFINITY, sw = 0.f;
+  double ssum = 0.0, ssq = 0.0;
   for (int c = tid; c < C; c += 256) {
     float w = 0.f;
     if (need_dot) {
@@ -190,8 +208,8 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
       if (head == XFMR_LOSS_PAIRWISE_HINGE) w = d > 0.f ? md : 0.f;
       logi = fmaf(xf_softplus(d), md, logi);
       if (head == XFMR_LOSS_PAIRWISE_LOGISTIC) w = md * xf_sigmoid(d);
-      ssum = fmaf(sv, md, ssum);
-      ssq = fmaf(sv * sv, md, ssq);
+      ssum += (double)sv * (double)md;
+      ssq += (double)sv * (double)sv * (double)md;
       if (md > 0.f) { smin = fminf(smin, sv); smax = fmaxf(smax, sv); }
     }
     if (need_cos) {
@@ -211,6 +229,9 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
 
   const float epos = exp2f(pos_dot * sc2 - M);
   const float ltot = l + epos;
+  // the negatives' softmax mass, the size of InfoNCE's pull on the positive (not 1 - epos / ltot: that loses a mass below
+  // 2^-24 to cancellation while the negatives' own terms keep it, so a confident row's gradient came out unbalanced)
+  const float pneg = l / ltot;
   const float inv_d = 1.f / (cnt_d + 1e-9f), inv_c = 1.f / (cnt_c + 1e-9f);
   if (tid == 0) {
     double acc[BP];
@@ -234,6 +255,8 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
       for (int k = 0; k < XFMR_NUM_LOSSES; ++k)
         if (k != head) acc[k] = 0.0;
     }
+    if (bad_target)
+      for (int k = 0; k < XFMR_NUM_LOSSES; ++k) acc[k] = (double)NAN;
 #pragma unroll
     for (int k = 0; k < BP; ++k) a.blockpart[(int64_t)k * gridDim.x + blockIdx.x] = acc[k];
   }
@@ -251,7 +274,7 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
       float coef;  // dL/d(logit of candidate c), in the head's own logit space
       const bool is_t = c == tgt;
       switch (head) {
-        case XFMR_LOSS_INFONCE: coef = is_t ? -a.scale * (1.f - epos / ltot) : a.scale * sW[c] / ltot; break;
+        case XFMR_LOSS_INFONCE: coef = is_t ? -a.scale * pneg : a.scale * sW[c] / ltot; break;
         case XFMR_LOSS_NCE: coef = is_t ? -xf_sigmoid(-pos_dot) : sW[c] * inv_d; break;
         case XFMR_LOSS_PAIRWISE_HINGE:
         case XFMR_LOSS_PAIRWISE_LOGISTIC: coef = is_t ? -(1.f - a.margin) * sw * inv_d : sW[c] * inv_d; break;
@@ -270,7 +293,7 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
         g = cclamped ? coef * rc * qh : coef * rc * (qh - (e * rc) * sCos[c]);
         (void)qclamped;
       }
-      dc[idx] = g;
+      dc[idx] = bad_target ? NAN : g;
     }
   }
 
@@ -290,7 +313,7 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
       for (int c = 0; c < C; ++c) O = fmaf(sW[c], cand[(int64_t)c * H + h], O);
     const float e = cand[(int64_t)tgt * H + h];
     switch (head) {
-      case XFMR_LOSS_INFONCE: g[u] = a.scale * (O / ltot - (1.f - epos / ltot) * e); break;
+      case XFMR_LOSS_INFONCE: g[u] = a.scale * (O / ltot - pneg * e); break;
       case XFMR_LOSS_NCE: g[u] = -xf_sigmoid(-pos_dot) * e + O * inv_d; break;
       case XFMR_LOSS_PAIRWISE_HINGE:
       case XFMR_LOSS_PAIRWISE_LOGISTIC: g[u] = (O - (1.f - a.margin) * sw * e) * inv_d; break;
@@ -312,7 +335,7 @@ __global__ __launch_bounds__(256) void dense_loss_kernel(DenseArgs a) {
 #pragma unroll
   for (int u = 0; u < HPT; ++u) {
     const int h = tid + 256 * u;
-    if (h < H) a.d_query[row * H + h] = g[u];
+    if (h < H) a.d_query[row * H + h] = bad_target ? NAN : g[u];
   }
 }
 
@@ -361,7 +384,7 @@ int xfmr_dense_loss_grads(const xfmr_loss_cfg* cfg, const float* query, const fl
   a.train_head = cfg->train_head; a.all_heads = cfg->all_heads; a.mask_fn = cfg->mask_false_negatives;
   a.k_hard = cfg->num_hard_negatives; a.scale = cfg->scale; a.margin = cfg->margin;
   a.d_query = d_query; a.blockpart = blockpart; a.d_cand = d_cand;
-  const size_t smem = ((size_t)H + 4 * (size_t)C + 8) * sizeof(float);
+  const size_t smem = ((size_t)H + 4 * (size_t)C + 8) * sizeof(float) + 4 * sizeof(double);
   if (hipFuncSetAttribute((const void*)dense_loss_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) !=
       hipSuccess)
     return XFMR_EHIP;
