@@ -648,6 +648,35 @@ int xfmr_target_ranks(const float* query, const float* table, const float* table
                       int64_t n_rows, int64_t n_query, int32_t H, const int64_t* exclude, const int64_t* exclude_offsets,
                       const int64_t* targets, const int64_t* target_offsets, int64_t n_targets, int32_t metric,
                       int32_t* out_rank, float* out_target_score, void* workspace, size_t workspace_bytes, void* stream);
+/* xfmr_candidate_ranks: the targets' ranks among a GIVEN per-query candidate list (the sampled-candidate protocol: one
+ * held-out item against 100 sampled negatives) and the candidates' scores (re-ranking). query, table, table_rnorm,
+ * table_sqnorm, n_rows, n_query, H, metric, the SORTED exclusion CSR and targets / target_offsets as xfmr_target_ranks.
+ * candidates / candidate_offsets (n_query + 1): a CSR of item indices, each query's list SORTED ascending. Repeats, ids
+ * outside [1, n_rows) and the query's own targets may occur in a list: each is skipped or counted once. Every offsets
+ * array may be a view into a longer one (absolute values; the first need not be 0).
+ *   The items of query q are S_q = distinct(candidates_q U targets_q), restricted to the ELIGIBLE items of
+ *   xfmr_target_ranks (1 <= j < n_rows, not in q's exclusion list, finite score). For the CSR entry e holding target t
+ *     out_rank[e] = 1 + the items c of S_q, c != t, that beat t (higher score first, then the lower index)  if t is eligible,
+ *     out_rank[e] = XFMR_RANK_NONE                                                                         otherwise.
+ *   Repeats of a target share its rank. When S_q holds every eligible item the ranks are xfmr_target_ranks'.
+ *   out_target_score (parallel to targets; may be NULL) and out_candidate_score (parallel to candidates, repeats
+ *   included; may be NULL) hold the item's score, -inf for an item that is not eligible.
+ *   targets == NULL is the score-only form: target_offsets, out_rank and out_target_score are NULL too and
+ *   out_candidate_score is required.
+ * Scores are the fmaf chain the f32 MFMA tile equals (a target's own score in xfmr_target_ranks): bit for bit what
+ * xfmr_topk_tiled returns for the item. Only integer counts are accumulated (integer atomics): two calls on the same
+ * input give the same bits; out_rank need not be zeroed. Cost: one dot product per candidate and target entry (once more
+ * per further 128 target entries of a query); a long list is spread over the grid. No workspace.
+ * XFMR_EINVAL (pointers, sizes, metric, the norm array the metric reads) < XFMR_EUNSUPPORTED (H not a multiple of 4 or
+ * above 1024; n_rows, n_query >= 2^31) < XFMR_EALIGN (query, table). The list sizes are on the device: the call reads the
+ * ends of both offsets arrays back (it waits for the stream once) and refuses 2^31 or more candidates or targets with
+ * XFMR_EUNSUPPORTED (offsets that run backwards: XFMR_EINVAL) after those checks, before any launch. */
+int xfmr_candidate_ranks(const float* query, const float* table, const float* table_rnorm, const float* table_sqnorm,
+                         int64_t n_rows, int64_t n_query, int32_t H,
+                         const int64_t* candidates, const int64_t* candidate_offsets,
+                         const int64_t* exclude, const int64_t* exclude_offsets,
+                         const int64_t* targets, const int64_t* target_offsets, int32_t metric,
+                         int32_t* out_rank, float* out_target_score, float* out_candidate_score, void* stream);
 /* xfmr_rank_metrics_sum: the seven XFMR_RM_* metrics at up to 8 cutoffs from the ranks above, and their fp64 sums.
  * ranks parallels `targets` (xfmr_target_ranks' out_rank); the CSR counts a row's DISTINCT targets and repeats are
  * skipped; `use` as xfmr_retrieval_metrics_sum; cutoffs: HOST array of n_cutoffs (1..8) positive values, any size (also

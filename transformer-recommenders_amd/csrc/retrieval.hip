@@ -5,7 +5,8 @@
 // (xfmr_rec/trainer.py:186-211, 266-325; index.py:214-255; metrics.py:17-79). Here a batch of users is scored EXACTLY
 // against the whole table (the ANN's limit of full probing): a scan for one query (xfmr_topk), score tiles on the matrix
 // cores for a user set (xfmr_topk_tiled), or every target's exact rank with no list at all (xfmr_target_ranks); the seven
-// metrics come from a ranked list or from the ranks. Each section below describes its kernels.
+// metrics come from a ranked list or from the ranks. xfmr_candidate_ranks ranks the targets among a GIVEN candidate list
+// instead (the sampled-candidate protocol, re-ranking) under the same rules. Each section below describes its kernels.
 // The contract between the paths: a target's rank is its place in the tiled list, the score the rank pre-pass reports is
 // the list's score bit for bit, and the rank metrics are the list metrics bit for bit. It holds because each piece is
 // written ONCE: the order (tt_better), the eligibility test (tt_finite), the score formula (rk_score), the query norm
@@ -722,6 +723,144 @@ __global__ __launch_bounds__(256) void rank_finish_kernel(RankArgs a) {
     a.out_rank[base + e] = a.tI[e] != TT_IDX_NONE ? a.exb[e0 + a.pos[e]] : TT_IDX_NONE;
 }
 
+// ---- ranks among given candidates (xfmr_candidate_ranks) -----------------------------------------------------------------
+// The sampled-candidate protocol and re-ranking: query q's items are S_q = distinct(candidates_q U targets_q) instead of
+// the catalogue, eligibility, order and score are the ones above, rank(t) = 1 + the eligible items of S_q that are
+// tt_better than t. S_q is walked as one list of nc + nt places: the candidate places (each list SORTED ascending, so a
+// repeat is the place whose left neighbour holds the same id) and then the target places (one counts when it is the
+// target's first entry and the target is not a candidate: a binary search). n_candidates dot products, not n_rows, so
+// there is no MFMA tile to fill: one lane per place runs rk_item_score, the tile's fmaf chain, and a wave has 64 rows in
+// flight by 16-byte loads. Two launches:
+//   cand_init_kernel   one wave per query: out_rank = 1 (XFMR_RANK_NONE for a target that is not eligible) and the
+//                      targets' scores. Skipped by the score-only form (no targets).
+//   cand_count_kernel  grid (query, part). The query row is staged in LDS once. Per chunk of CD_T target entries: their
+//                      scores into LDS (the chain again: no workspace), then the workgroup's batches of CD_B places
+//                      (batch b belongs to part b % parts, so a list of thousands spreads over the grid and a short one
+//                      costs the other parts two loads): scores of the batch into LDS, then every (place, target) pair
+//                      is compared once, 256 threads as (target, slice of the batch), counts kept in registers over the
+//                      batches, added over the slices by an integer LDS atomic and to out_rank by one integer global
+//                      atomic per live target, chunk and workgroup. A query with more than CD_T entries scores its
+//                      places once per chunk.
+// Integer counts only: two calls give the same bits.
+constexpr int CD_T = 128;  // target entries per chunk
+constexpr int CD_B = 256;  // places per batch: one per thread
+constexpr int CD_MAX_PARTS = 256;
+constexpr int CD_TARGET_WG = 1024;
+
+struct CandArgs : ScoreArgs {
+  const int64_t* cand; const int64_t* cand_off;
+  const int64_t* tgt; const int64_t* tgt_off;  // null: the score-only form
+  int* out_rank; float* out_tscore; float* out_cscore;
+  int parts;
+};
+
+// id in the sorted list v[lo..hi)
+__device__ __forceinline__ bool cd_listed(const int64_t* v, int64_t lo, int64_t hi, int64_t id) {
+  const int64_t end = hi;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (v[mid] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < end && v[lo] == id;
+}
+
+// the score of item id for the query in sQ when the item is eligible, -inf otherwise
+__device__ __forceinline__ float cd_eligible_score(const CandArgs& a, const float* sQ, float rq, float qq, int64_t x0,
+                                                   int64_t x1, int64_t id) {
+  if (id < 1 || id >= a.n_rows || (a.excl && tt_excluded(a.excl, x0, x1, (int)id))) return -INFINITY;
+  const float v = rk_item_score(a, sQ, rq, qq, (int)id);
+  return tt_finite(v) ? v : -INFINITY;
+}
+
+// the query row into sQ (all threads of the workgroup; the caller's barrier follows); |q|^2 in every thread
+__device__ __forceinline__ float cd_stage_query(const CandArgs& a, int qi, float* sQ) {
+  const float* qr = a.q + (int64_t)qi * a.H;
+  for (int h = threadIdx.x; h < a.H; h += blockDim.x) sQ[h] = qr[h];
+  return rk_query_sqnorm(qr, a.H, threadIdx.x & 7);
+}
+
+__global__ __launch_bounds__(64) void cand_init_kernel(CandArgs a) {
+  __shared__ __attribute__((aligned(16))) float sQ[TOPK_MAX_H];
+  const int qi = blockIdx.x;
+  const float qq = cd_stage_query(a, qi, sQ);
+  const float rq = rk_inv_norm(qq);
+  const int64_t x0 = a.excl ? a.excl_off[qi] : 0, x1 = a.excl ? a.excl_off[qi + 1] : 0;
+  __syncthreads();
+  for (int64_t e = a.tgt_off[qi] + threadIdx.x; e < a.tgt_off[qi + 1]; e += 64) {
+    const float s = cd_eligible_score(a, sQ, rq, qq, x0, x1, a.tgt[e]);
+    a.out_rank[e] = tt_finite(s) ? 1 : TT_IDX_NONE;
+    if (a.out_tscore) a.out_tscore[e] = s;
+  }
+}
+
+__global__ __launch_bounds__(256) void cand_count_kernel(CandArgs a) {
+  __shared__ __attribute__((aligned(16))) float sQ[TOPK_MAX_H];
+  __shared__ float bS[CD_B], tS[CD_T];
+  __shared__ int bI[CD_B], tI[CD_T], cnt[CD_T];
+  const int tid = threadIdx.x;
+  const int qi = blockIdx.x, part = blockIdx.y;
+  const int64_t c0 = a.cand_off[qi], t0 = a.tgt ? a.tgt_off[qi] : 0;
+  const int64_t nc = a.cand_off[qi + 1] - c0, nt = a.tgt ? a.tgt_off[qi + 1] - t0 : 0;
+  const int64_t places = nc + nt;
+  if ((int64_t)part * CD_B >= places) return;  // (uniform: no batch for this part)
+  const int64_t x0 = a.excl ? a.excl_off[qi] : 0, x1 = a.excl ? a.excl_off[qi + 1] : 0;
+  const float qq = cd_stage_query(a, qi, sQ);
+  const float rq = rk_inv_norm(qq);
+  __syncthreads();
+  for (int64_t m0 = 0; m0 == 0 || m0 < nt; m0 += CD_T) {
+    const int n = (int)(nt - m0 < CD_T ? nt - m0 : CD_T);  // entries of this chunk (0: the score-only form)
+    if (tid < CD_T) {
+      float s = -INFINITY;
+      int64_t id = 0;
+      if (tid < n) {
+        id = a.tgt[t0 + m0 + tid];
+        s = cd_eligible_score(a, sQ, rq, qq, x0, x1, id);
+      }
+      tS[tid] = s;
+      tI[tid] = tt_finite(s) ? (int)id : TT_IDX_NONE;
+      cnt[tid] = 0;
+    }
+    // threads as (entry m, slice of the batch): n2 = the power of two that holds the chunk's entries
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    const int m = tid & (n2 - 1), i0 = (tid / n2) * n2;
+    int beat = 0;
+    for (int64_t b0 = (int64_t)part * CD_B; b0 < places; b0 += (int64_t)a.parts * CD_B) {
+      const int64_t x = b0 + tid;
+      float s = -INFINITY;
+      int it = TT_IDX_NONE;  // a place that does not count
+      if (x < nc) {
+        const int64_t id = a.cand[c0 + x];
+        s = cd_eligible_score(a, sQ, rq, qq, x0, x1, id);
+        if (a.out_cscore && m0 == 0) a.out_cscore[c0 + x] = s;
+        if (tt_finite(s) && !(x > 0 && a.cand[c0 + x - 1] == id)) it = (int)id;
+      } else if (x < places && n > 0) {
+        const int64_t f = x - nc, id = a.tgt[t0 + f];
+        bool counts = id >= 1 && id < a.n_rows && !cd_listed(a.cand, c0, c0 + nc, id);
+        for (int64_t g = 0; counts && g < f; ++g) counts = a.tgt[t0 + g] != id;
+        if (counts) {
+          s = cd_eligible_score(a, sQ, rq, qq, x0, x1, id);
+          if (tt_finite(s)) it = (int)id;
+        }
+      }
+      __syncthreads();  // (the previous batch's reads; the chunk's tS / tI / cnt)
+      bS[tid] = s;
+      bI[tid] = it;
+      __syncthreads();
+      if (m < n && tI[m] != TT_IDX_NONE) {
+        const float ts = tS[m];
+        const int ti = tI[m];
+        for (int i = i0; i < i0 + n2; ++i) beat += (bI[i] != TT_IDX_NONE && tt_better(bS[i], bI[i], ts, ti)) ? 1 : 0;
+      }
+    }
+    if (beat) atomicAdd(&cnt[m], beat);
+    __syncthreads();
+    if (tid < n && cnt[tid]) atomicAdd(&a.out_rank[t0 + m0 + tid], cnt[tid]);
+    __syncthreads();
+  }
+}
+
 // ---- the seven metrics: from a ranked list, or from the ranks ---------------------------------------------------------
 // v = ndcg, map, auroc, precision, recall, hit, mrr with torchmetrics' definitions for a strictly decreasing score
 // vector over [recommendations | missing targets] (metrics.py:66-79). The list torchmetrics sees: max(len(rec), top_k)
@@ -984,6 +1123,16 @@ static RankWs rank_ws(int64_t n_query, int64_t n_targets, int splits) {
   return {0, t, 2 * t, 3 * t, 4 * t, 5 * t, 6 * t, 6 * t + q, 6 * t + q + (size_t)splits * t};
 }
 
+// parts of cand_count_kernel's grid: enough workgroups to cover the chip when there are few queries, never more than the
+// batches the longest possible list has (`places` bounds every query's candidates + targets)
+static int cand_parts(int64_t n_query, int64_t places) {
+  int64_t p = (CD_TARGET_WG + n_query - 1) / n_query;
+  const int64_t batches = (places + CD_B - 1) / CD_B;
+  if (p > batches) p = batches;
+  if (p > CD_MAX_PARTS) p = CD_MAX_PARTS;
+  return p < 1 ? 1 : (int)p;
+}
+
 static int64_t ms_partials(int64_t n_query) { return (n_query + MS_ROWS - 1) / MS_ROWS; }
 
 // The search entries' common refusals, in their common precedence: EINVAL (pointers, sizes, the exclusion pair, the
@@ -1130,6 +1279,52 @@ int xfmr_target_ranks(const float* query, const float* table, const float* table
   XF_LAUNCH_CHECK();
   hipLaunchKernelGGL(rank_finish_kernel, dim3((unsigned)n_query), dim3(256), 0, (hipStream_t)stream, a);
   XF_LAUNCH_CHECK();
+  return XFMR_OK;
+}
+
+int xfmr_candidate_ranks(const float* query, const float* table, const float* table_rnorm, const float* table_sqnorm,
+                         int64_t n_rows, int64_t n_query, int32_t H, const int64_t* candidates,
+                         const int64_t* candidate_offsets, const int64_t* exclude, const int64_t* exclude_offsets,
+                         const int64_t* targets, const int64_t* target_offsets, int32_t metric, int32_t* out_rank,
+                         float* out_target_score, float* out_candidate_score, void* stream) {
+  // with targets: their offsets and out_rank; without: no target output, and the candidates' scores are the result
+  const bool own = candidates && candidate_offsets &&
+                   (targets ? target_offsets && out_rank
+                            : !target_offsets && !out_rank && !out_target_score && out_candidate_score);
+  // (no workspace: the table, whose own checks these are, stands in for it)
+  const int rc = search_check(query, table, table_rnorm, table_sqnorm, n_rows, n_query, H, exclude, exclude_offsets, metric,
+                              table, false, own, true);
+  if (rc != XFMR_OK) return rc;
+  // The list sizes live on the device: the ends of both offset arrays are read back (the call's one wait) and checked
+  // last, still before any launch.
+  int64_t ends[4] = {0, 0, 0, 0};
+  const hipStream_t st = (hipStream_t)stream;
+  bool read = hipMemcpyAsync(ends, candidate_offsets, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
+              hipMemcpyAsync(ends + 1, candidate_offsets + n_query, 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (read && targets)
+    read = hipMemcpyAsync(ends + 2, target_offsets, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipMemcpyAsync(ends + 3, target_offsets + n_query, 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (!read || hipStreamSynchronize(st) != hipSuccess) {
+    (void)hipGetLastError();
+    return XFMR_EHIP;
+  }
+  const int64_t n_cand = ends[1] - ends[0], n_tgt = ends[3] - ends[2];
+  if (n_cand < 0 || n_tgt < 0) return XFMR_EINVAL;
+  if (n_cand >= (1ll << 31) || n_tgt >= (1ll << 31)) return XFMR_EUNSUPPORTED;
+  CandArgs a{};
+  fill_score_args(a, query, table, table_rnorm, table_sqnorm, n_rows, n_query, H, exclude, exclude_offsets, metric,
+                  TiledPlan{1, 0, 0});
+  a.cand = candidates; a.cand_off = candidate_offsets; a.tgt = targets; a.tgt_off = target_offsets;
+  a.out_rank = out_rank; a.out_tscore = out_target_score; a.out_cscore = out_candidate_score;
+  a.parts = cand_parts(n_query, n_cand + n_tgt);
+  if (targets) {
+    hipLaunchKernelGGL(cand_init_kernel, dim3((unsigned)n_query), dim3(64), 0, st, a);
+    XF_LAUNCH_CHECK();
+  }
+  if (n_cand + n_tgt > 0) {
+    hipLaunchKernelGGL(cand_count_kernel, dim3((unsigned)n_query, (unsigned)a.parts), dim3(256), 0, st, a);
+    XF_LAUNCH_CHECK();
+  }
   return XFMR_OK;
 }
 

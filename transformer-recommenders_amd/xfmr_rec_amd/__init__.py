@@ -5,13 +5,13 @@ interfaces over hand-written gfx950 HIP kernels (``libxfmr_hip.so``, C ABI in ``
 """
 
 from .checkpoint import parse_max_time, read_checkpoint, reference_checkpoint_options, write_checkpoint  # noqa: F401
-from .evalset import DeviceEvalSet, EvalPlan, plan_eval_rows, shard_eval_plan  # noqa: F401
+from .evalset import DeviceEvalSet, EvalPlan, SampledEvalSet, plan_eval_rows, shard_eval_plan  # noqa: F401
 from .losses import LOSS_CLASSES, EmbedLoss, LossConfig, LossType  # noqa: F401
 from .models import ModelConfig, RecommenderModel  # noqa: F401
 from .trainer import EarlyStopping, FusedAdamW, GraphedStep, LightningConfig, RecommenderLightningModule, Trainer  # noqa: F401
 
 __all__ = [
     "LOSS_CLASSES", "EmbedLoss", "LossConfig", "LossType", "ModelConfig", "RecommenderModel",
-    "DeviceEvalSet", "EarlyStopping", "EvalPlan", "plan_eval_rows", "shard_eval_plan", "FusedAdamW", "GraphedStep", "LightningConfig", "RecommenderLightningModule", "Trainer",
+    "DeviceEvalSet", "SampledEvalSet", "EarlyStopping", "EvalPlan", "plan_eval_rows", "shard_eval_plan", "FusedAdamW", "GraphedStep", "LightningConfig", "RecommenderLightningModule", "Trainer",
     "parse_max_time", "read_checkpoint", "reference_checkpoint_options", "write_checkpoint",
 ]

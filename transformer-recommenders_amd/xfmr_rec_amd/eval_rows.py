@@ -82,6 +82,56 @@ def pad_histories(lengths, flat) -> np.ndarray:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ sampled candidates
+def candidates_csr(lists) -> tuple[np.ndarray, np.ndarray]:
+    """Explicit per-row candidate lists (table rows) as xfmr_candidate_ranks takes them: each row sorted ascending,
+    repeats dropped (:func:`flat_csr`)."""
+    return flat_csr(lists, sort_unique=True)
+
+
+def map_candidates(candidates, to_idx) -> list:
+    """Per-row lists of candidate item IDS -> lists of table rows through ``to_idx`` (the module's ``_to_idx_or_empty``, or
+    ``lambda ids: lookup_rows(id2idx, ids)``): unknown ids are dropped, as the histories' are."""
+    return [to_idx(list(c)) for c in candidates]
+
+
+def sample_eval_negatives(hist_lists, target_lists, n_items: int, num_negatives: int, seed: int,
+                          weights=None) -> tuple[np.ndarray, np.ndarray]:
+    """The negatives of the sampled-candidate protocol (one held-out item against ``num_negatives`` sampled ones), as a
+    sorted-unique CSR ``(flat int64, offsets int64)`` over the rows of ``hist_lists`` / ``target_lists`` (table rows).
+
+    Row i draws ``num_negatives`` DISTINCT items from ``1 .. n_items - 1`` minus (its history U its targets): uniformly,
+    or with ``weights`` (``n_items`` non-negative numbers by table row, e.g. popularity counts) in proportion to the
+    weights without replacement -- an item of weight 0 is never drawn. A row with fewer items to draw from than asked
+    takes all of them. The generator of row i is keyed by ``(seed, i)`` alone: a row's negatives do not depend on which
+    other rows there are, on their order or on how the rows are batched."""
+    n_items, k = int(n_items), int(num_negatives)
+    if n_items < 1 or k < 0 or int(seed) < 0:
+        raise ValueError(f"n_items must be >= 1, num_negatives and seed >= 0; got {n_items}, {num_negatives}, {seed}")
+    if len(hist_lists) != len(target_lists):
+        raise ValueError(f"{len(hist_lists)} histories for {len(target_lists)} target lists")
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != n_items or not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError(f"weights must be {n_items} finite non-negative numbers")
+    free = np.empty(n_items, dtype=bool)
+    parts = []
+    for i, (h, t) in enumerate(zip(hist_lists, target_lists)):
+        free[:] = True if w is None else w > 0
+        free[0] = False
+        for own in (h, t):
+            own = np.asarray(own, dtype=np.int64).reshape(-1)
+            free[own[(own >= 0) & (own < n_items)]] = False
+        pool = np.flatnonzero(free)
+        if pool.size > k:
+            rng = np.random.default_rng((int(seed), i))
+            p = None if w is None else w[pool] / w[pool].sum()
+            pool = np.sort(rng.choice(pool, size=k, replace=False, p=p))
+        parts.append(pool.astype(np.int64))
+    return flat_csr(parts)
+
+
 # ------------------------------------------------------------------------------------------------ config rules
 def check_tiled_top_k(top_k: int, hint: str = "") -> None:
     """The one refusal of a list longer than xfmr_topk_tiled returns."""

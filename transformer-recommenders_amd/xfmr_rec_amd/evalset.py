@@ -397,3 +397,90 @@ class DeviceEvalSet:
             return E.metrics_dict(stage, self.evaluate_device().tolist(), top_k=self.top_k)
         cut = E.eval_cutoffs(cutoffs, self.top_k)
         return E.metrics_dict(stage, self.evaluate_ranks_device(cut).tolist(), cut, self.top_k)
+
+
+class SampledEvalSet(DeviceEvalSet):
+    """A :class:`DeviceEvalSet` under the SAMPLED-CANDIDATE protocol (SASRec, BERT4Rec: HR@10 / NDCG@10 of the held-out
+    item against 100 sampled negatives): a row's targets are ranked among the row's own candidate list, not the catalogue.
+
+        val = SampledEvalSet.from_rows(module, rows, num_negatives=100, seed=0)   # negatives drawn once, resident
+        val.evaluate(cutoffs=(10,))                                               # val/retrieval_hit_rate@10, ...
+        trainer.fit(batches, val=val, val_cutoffs=(10,), monitor={"name": "val/retrieval_normalized_dcg@10", "mode": "max"})
+
+    The plan, the encoder input, the exclusions (each row's whole history: a history item is neither drawn as a negative
+    nor eligible) and the targets are the full-catalogue set's, so the two sets differ only in the items a target is
+    ranked among. ``candidates`` is the resident sorted CSR of those items per plan row: the drawn negatives
+    (``eval_rows.sample_eval_negatives``, keyed by ``(seed, input row)``: a row's negatives do not depend on the other
+    rows or on ``batch_size``), or the explicit lists given. Every pass takes the rank path
+    (``ExactItemIndex.rank_among`` per chunk, ``rank_metrics_sum`` once): there is no ranked list, so no limit on
+    ``top_k`` or a cutoff. Attributes: ``protocol`` ("sampled" or "candidates"), ``num_negatives`` (None for explicit
+    candidates), ``seed``. Single process only: a sharded sampled set is not built (``world_size > 1`` raises)."""
+
+    def __init__(self, module, plan: EvalPlan, candidates, *, protocol: str = "candidates", num_negatives=None,
+                 seed: int = 0, world_size: int = 1):
+        """``candidates``: ``(flat, offsets)`` numpy int64 CSR over the PLAN's rows, each row sorted ascending."""
+        if int(world_size) != 1 or plan.world_size != 1:
+            raise ValueError(f"SampledEvalSet runs in a single process: world_size = {max(int(world_size), plan.world_size)} "
+                             "(a sharded sampled set) is not supported; evaluate it on one rank")
+        super().__init__(module, plan, cutoffs_only=True)
+        flat, off = (np.asarray(x, dtype=np.int64) for x in candidates)
+        if off.size != self.n_local + 1:
+            raise ValueError(f"candidates offsets have {off.size} entries for {self.n_local} rows")
+        self.protocol, self.num_negatives, self.seed = str(protocol), num_negatives, int(seed)
+        self.candidates = torch.from_numpy(np.ascontiguousarray(flat if flat.size else np.zeros(1, np.int64))).to(self.device)
+        self.candidate_offsets = torch.from_numpy(np.ascontiguousarray(off)).to(self.device)
+        torch.cuda.synchronize(self.device)
+
+    @classmethod
+    def from_rows(cls, module, rows, num_negatives: int = 100, seed: int = 0, weights=None, candidates=None,
+                  batch_size: int = 1024, *, rank: int = 0, world_size: int = 1) -> "SampledEvalSet":
+        """``rows`` as :meth:`DeviceEvalSet.from_rows`. Without ``candidates``: every row draws ``num_negatives`` distinct
+        negatives outside its history and targets, uniformly or in proportion to ``weights`` (one non-negative number per
+        table row). ``candidates``: per input row, the item ids to rank the row's targets among instead (mapped through the
+        module's id lookup; unknown ids are dropped)."""
+        if int(world_size) != 1:
+            raise ValueError(f"SampledEvalSet runs in a single process: world_size = {world_size} (a sharded sampled set) is "
+                             "not supported; evaluate it on one rank")
+        if module.model is None:
+            module.configure_model()
+        rows = list(rows)
+        hists, tgts = E.read_rows(rows, module._to_idx_or_empty)
+        plan = plan_eval_rows(hists, tgts, module.model.max_seq_length, batch_size)
+        if candidates is None:
+            n_items = int(module.model.embeddings.shape[0])
+            lists = _rows_of_csr(E.sample_eval_negatives(hists, tgts, n_items, num_negatives, seed, weights), plan.kept)
+            return cls(module, plan, E.candidates_csr(lists), protocol="sampled", num_negatives=int(num_negatives), seed=seed)
+        candidates = list(candidates)
+        if len(candidates) != len(rows):
+            raise ValueError(f"{len(candidates)} candidate lists for {len(rows)} rows")
+        lists = E.map_candidates(candidates, module._to_idx_or_empty)
+        return cls(module, plan, E.candidates_csr([lists[r] for r in plan.kept]), protocol="candidates", seed=seed)
+
+    @torch.no_grad()
+    def target_ranks(self, embedding: torch.Tensor | None = None) -> torch.Tensor:
+        """The rank of every target among its row's candidates and targets (int32, parallel to ``self.targets``;
+        ``_native.RANK_NONE`` where a target is in the row's history): one encode, then ``ExactItemIndex.rank_among``
+        per chunk into one resident tensor."""
+        emb = self.encode() if embedding is None else embedding
+        index = self.module.items_index
+        ranks = torch.empty((self.targets.numel(),), dtype=torch.int32, device=self.device)
+        for c in self._chunks:
+            r0, r1 = c.row0, c.row1
+            index.rank_among(emb[r0:r1], (self.candidates, self.candidate_offsets[r0 : r1 + 1]),
+                             (self.targets, self.target_offsets[r0 : r1 + 1]), (self.excl, c.excl_offsets), out=ranks)
+        return ranks
+
+    def recommend(self, embedding=None):
+        raise ValueError("a SampledEvalSet has no ranked list over the catalogue: use evaluate(cutoffs=) or target_ranks()")
+
+    def evaluate(self, stage: str = "val", cutoffs=None) -> dict[str, float]:
+        """The keys of ``DeviceEvalSet.evaluate(stage, cutoffs=...)`` under the sampled protocol: always the rank path.
+        ``cutoffs`` defaults to ``(config.top_k,)``; ``config.top_k`` is added when missing and gives the plain keys."""
+        cut = E.eval_cutoffs((self.top_k,) if cutoffs is None else cutoffs, self.top_k)
+        return E.metrics_dict(stage, self.evaluate_ranks_device(cut).tolist(), cut, self.top_k)
+
+
+def _rows_of_csr(csr, rows) -> list:
+    """The CSR's rows ``rows`` as a list of arrays."""
+    flat, off = csr
+    return [flat[off[r] : off[r + 1]] for r in rows]

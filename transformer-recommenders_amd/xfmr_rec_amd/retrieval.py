@@ -172,6 +172,54 @@ class ExactItemIndex:
         )
         return (out, score) if return_scores else out
 
+    def _candidate_ranks(self, q, cand, ex, tg, out, tscore, cscore):
+        """The one xfmr_candidate_ranks call: ``q`` from :func:`_queries`, the CSR pairs as checked by the callers
+        (``ex`` and ``tg`` may be ``(None, None)``), the outputs allocated by them."""
+        B, H = q.shape
+        rnorm, sqnorm = self._norms()
+        N.check(
+            N.load().xfmr_candidate_ranks(N.ptr(q), N.ptr(self.table), N.ptr(rnorm), N.ptr(sqnorm), self.table.shape[0], B,
+                                          H, N.ptr(cand[0]), N.ptr(cand[1]), N.ptr(ex[0]), N.ptr(ex[1]), N.ptr(tg[0]),
+                                          N.ptr(tg[1]), self.metric, N.ptr(out), N.ptr(tscore), N.ptr(cscore), N.stream()),
+            "xfmr_candidate_ranks",
+        )
+
+    def rank_among(self, embedding: torch.Tensor, candidates_csr, targets_csr, exclude_csr=None, *,
+                   out: torch.Tensor | None = None, candidate_scores: bool = False):
+        """The rank of every target among the query's GIVEN candidates (xfmr_candidate_ranks): the sampled-candidate
+        protocol. ``candidates_csr``, ``targets_csr``, ``exclude_csr``: ``(flat, offsets)`` int64 DEVICE tensors as
+        :meth:`rank_targets` takes them; each row of the candidates (``eval_rows.candidates_csr``) and of the exclusions
+        SORTED ascending. A query's items are its distinct candidates and targets that are eligible (in [1, n_items),
+        not excluded, finite score); a target's rank is 1 + those that beat it, so with every item as a candidate the
+        result is :meth:`rank_targets`'. Returns int32 ranks parallel to the flat targets (``out``: a tensor to write
+        into; entries outside the offsets are left alone), ``_native.RANK_NONE`` for a target that is not eligible.
+        ``candidate_scores=True`` also returns the candidates' scores, parallel to the flat candidates (-inf: not
+        eligible; float32, the bits :meth:`search_batch` reports for the item)."""
+        q, B, _, dev = _queries(embedding)
+        cand = _check_csr("candidates_csr", candidates_csr, B)
+        tg = _check_csr("targets_csr", targets_csr, B)
+        ex = (None, None) if exclude_csr is None else _check_csr("exclude_csr", exclude_csr, B)
+        if out is None:
+            out = torch.full((tg[0].numel(),), N.RANK_NONE, dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or out.numel() != tg[0].numel():
+            raise ValueError(f"out must be int32 with {tg[0].numel()} entries")
+        cscore = torch.full((cand[0].numel(),), float("-inf"), dtype=torch.float32, device=dev) if candidate_scores else None
+        if B > 0:
+            self._candidate_ranks(q, cand, ex, tg, out, None, cscore)
+        return (out, cscore) if candidate_scores else out
+
+    def score_candidates(self, embedding: torch.Tensor, candidates_csr, exclude_csr=None) -> torch.Tensor:
+        """The scores of each query's given candidates (the score-only form of xfmr_candidate_ranks; re-ranking):
+        float32 parallel to the flat candidates, -inf for a candidate that is not eligible. CSR arguments as
+        :meth:`rank_among`."""
+        q, B, _, dev = _queries(embedding)
+        cand = _check_csr("candidates_csr", candidates_csr, B)
+        ex = (None, None) if exclude_csr is None else _check_csr("exclude_csr", exclude_csr, B)
+        cscore = torch.full((cand[0].numel(),), float("-inf"), dtype=torch.float32, device=dev)
+        if B > 0:
+            self._candidate_ranks(q, cand, ex, (None, None), None, None, cscore)
+        return cscore
+
 
 def rank_metrics_sum(ranks: torch.Tensor, targets_csr, cutoffs, use: torch.Tensor | None = None, per_row: bool = False):
     """The seven metrics at every cutoff from the ranks of :meth:`ExactItemIndex.rank_targets`

@@ -440,6 +440,50 @@ class RecommenderLightningModule(_Base):
             total += self._list_pass(hists, tgts) if cut is None else self._rank_pass(hists, tgts, cut)
         return E.metrics_dict(stage, total, cut, int(self.config.top_k))
 
+    def evaluate_sampled(self, rows, num_negatives: int = 100, seed: int = 0, cutoffs=None, stage: str = "val",
+                         weights=None, batch_size: int = 1024) -> dict[str, float]:
+        """:meth:`evaluate` under the sampled-candidate protocol: every row's targets are ranked among ``num_negatives``
+        negatives drawn for the row (``eval_rows.sample_eval_negatives``: outside its history and targets, keyed by
+        ``(seed, row)``, uniform or in proportion to ``weights``) instead of the catalogue. One
+        :class:`~xfmr_rec_amd.evalset.SampledEvalSet` built from ``rows`` and evaluated once: its dict (``cutoffs``
+        defaults to ``(config.top_k,)``)."""
+        from .evalset import SampledEvalSet
+
+        return SampledEvalSet.from_rows(self, rows, num_negatives=num_negatives, seed=seed, weights=weights,
+                                        batch_size=batch_size).evaluate(stage, cutoffs=cutoffs)
+
+    @torch.no_grad()
+    def score_candidates(self, histories, candidate_item_ids) -> list:
+        """Re-ranking: per history (a list of item ids), the given candidates best first -- ``(item_ids, scores)`` with
+        the ids as given, ordered by score descending and then by table row, and their float32 scores (the bits
+        :meth:`recommend_batch` reports for the item). One ``encode_batch`` and one ``ExactItemIndex.score_candidates``
+        call. Unknown ids are dropped, as :meth:`recommend_batch` drops them, and a candidate given twice is scored once;
+        an empty history gets ``([], no scores)``."""
+        from .retrieval import _csr
+
+        hists = [self._to_idx_or_empty(list(x)) for x in histories]
+        given = [list(x) for x in candidate_item_ids]
+        if len(given) != len(hists):
+            raise ValueError(f"{len(given)} candidate lists for {len(hists)} histories")
+        if not hists:
+            return []
+        # (table row, id as given) per known candidate: one lookup per id, so that a row's id can be handed back
+        pairs = [[(r, i) for i in c for r in self._to_idx_or_empty([i])] if h else [] for h, c in zip(hists, given)]
+        flat, off = E.candidates_csr([[r for r, _ in p] for p in pairs])
+        dev = self.model.device
+        emb = self.model.encode_batch(hists)
+        score = self.items_index.score_candidates(emb, (torch.from_numpy(flat).to(dev), torch.from_numpy(off).to(dev)))
+        score = score.cpu().numpy()
+        out = []
+        for b, p in enumerate(pairs):
+            name = {}
+            for row, item in p:
+                name.setdefault(row, item)
+            f, s = flat[off[b] : off[b + 1]], score[off[b] : off[b + 1]]
+            order = np.lexsort((f, -s.astype(np.float64)))
+            out.append(([name[int(x)] for x in f[order]], s[order]))
+        return out
+
     def _evaluate_ranks(self, rows, stage: str, batch_size: int, cutoffs) -> dict[str, float]:
         """:meth:`evaluate` with ``cutoffs`` (kept under its earlier name)."""
         return self.evaluate(rows, stage, batch_size, cutoffs)
