@@ -11,13 +11,6 @@ import torch
 from xfmr_rec_amd import _native as N
 
 lib = N.load()
-class Item(C.Structure):
-    _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("N", C.c_int32), ("K", C.c_int32), ("slabs", C.c_void_p),
-                ("bias_part", C.c_void_p), ("splits", C.c_void_p)]
-lib.xf_linear_bwd_dw_group.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]
-lib.xf_dw_ring_launch.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
-lib.xf_linear_bwd_dw_slab_bytes.restype = C.c_size_t
-lib.xf_linear_bwd_dw_slab_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 102400
 H, I = 128, 512
@@ -35,10 +28,10 @@ for name, (n, k, bias) in shapes.items():
     ops[name] = (dy, x, n, k, slabs, bparts, splits)
 
 def items(names, which):
-    arr = (Item * len(names))()
+    arr = (N.DwItem * len(names))()
     for i, nm in enumerate(names):
         dy, x, n, k, slabs, bparts, splits = ops[nm]
-        arr[i] = Item(dy.data_ptr(), x.data_ptr(), n, k, slabs[which].data_ptr(),
+        arr[i] = N.DwItem(dy.data_ptr(), x.data_ptr(), n, k, slabs[which].data_ptr(),
                       bparts[which].data_ptr() if bparts[which] is not None else None, C.addressof(splits[which]))
     return arr
 

@@ -2,7 +2,6 @@
 """Where does ffn_fwd_fused_kernel's time go? Times xf_ffn_fwd_fused_ex at the benchmark's row count with pieces of its
 work switched off through its own arguments (null outputs skip the u / g stores; dropout off skips the mask hash).
     python scripts/probe/ffn_fwd_probe.py            (on the GPU box)"""
-import ctypes as C
 import pathlib
 import sys
 
@@ -32,9 +31,6 @@ y16 = torch.empty(M, H, device=DEV, dtype=torch.bfloat16)
 mean = torch.empty(M, device=DEV)
 rstd = torch.empty(M, device=DEV)
 fn = lib.xf_ffn_fwd_fused_ex
-fn.restype = C.c_int
-fn.argtypes = [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_float, N.Seed, C.c_uint32,
-                                  C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5
 
 
 def run(store_u=True, store_g=True, p=0.1, y16_out=True, rows=M):

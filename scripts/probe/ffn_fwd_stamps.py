@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Phase timeline of ffn_fwd_fused_kernel from s_memtime stamps (probe build: hipcc -DXF_FFN_STAMP, see gemm.hip).
     XFMR_HIP_LIB=build/libxfmr_hip_stamp.so python scripts/probe/ffn_fwd_stamps.py"""
-import ctypes as C
 import os
 import pathlib
 import sys
@@ -37,9 +36,6 @@ def run(M):
     stamps = torch.zeros(nblk, 64, dtype=torch.int64, device=DEV)
     os.environ["XFMR_FFN_STAMPS"] = hex(stamps.data_ptr())
     fn = lib.xf_ffn_fwd_fused_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_float, N.Seed, C.c_uint32,
-                                      C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5
     for _ in range(3):
         rc = fn(N.ptr(x16), N.ptr(w1), N.ptr(b1), N.ptr(w2), N.ptr(b2), N.ptr(u), N.ptr(gg), N.ptr(pre), M, H, I, N.ptr(res),
                 0.1, 5, 9, N.ptr(gamma), N.ptr(beta), 1e-12, N.ptr(y), N.ptr(y16), N.ptr(mean), N.ptr(rstd), N.stream())

@@ -28,15 +28,8 @@ rstd = (lnx.var(-1, unbiased=False) + 1e-12).rsqrt().contiguous()
 gamma = (1 + 0.1 * torch.randn(K, generator=g)).to(DEV)
 
 fn = lib.xf_linear_bwd_dx_lnbwd_ex
-fn.restype = C.c_int
-fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [
-    C.c_float, N.Seed, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int32, C.c_uint32,
-    C.c_void_p, C.c_float, C.c_uint32]
-
-
-PROD = C.CDLL(str(ROOT / "transformer-recommenders_amd" / "xfmr_rec_amd" / "libxfmr_hip.so"))  # the in-tree build
+PROD = N.bind(C.CDLL(str(ROOT / "transformer-recommenders_amd" / "xfmr_rec_amd" / "libxfmr_hip.so")))  # the in-tree build
 fn_prod = PROD.xf_linear_bwd_dx_lnbwd_ex
-fn_prod.restype, fn_prod.argtypes = fn.restype, fn.argtypes
 
 
 DBG = None
@@ -47,8 +40,7 @@ if hasattr(lib, "xf_diag_set_buffer"):  # a build with XF_LN_DIAG & 4: per (row,
     lib.xf_diag_set_buffer(N.ptr(DBG))
 
 
-lib.xf_ln_row_tiles.restype, lib.xf_ln_row_tiles.argtypes = C.c_int, [C.c_int64]
-N_TILES = max(lib.xf_ln_row_tiles(M), PROD.xf_ln_row_tiles(M)) if hasattr(lib, "xf_ln_row_tiles") else (M + 63) // 64
+N_TILES = max(lib.xf_ln_row_tiles(M), PROD.xf_ln_row_tiles(M))
 
 
 def run_bwd(p_drop, fn=fn):

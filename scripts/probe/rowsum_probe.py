@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Which segments set the reduction launch's time? xf_multi_rowsum on the encoder backward's real segment set at batch
 512 (4 layers: split-K slabs of the four weights, bias partial rows, LayerNorm partial records), whole and in parts."""
-import ctypes as C
 import pathlib
 import sys
 
@@ -10,10 +9,6 @@ import torch
 ROOT = pathlib.Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT / "transformer-recommenders_amd"))
 from xfmr_rec_amd import _native as N  # noqa: E402
-
-
-class Seg(C.Structure):
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("ld", C.c_int), ("pad", C.c_int)]
 
 
 DEV = "cuda"
@@ -28,7 +23,7 @@ def seg(rows, cols, ld=None, off=0, buf=None):
         keep.append(buf)
     dst = torch.empty(cols, device=DEV)
     keep.append(dst)
-    return Seg(buf.data_ptr() + 4 * off, dst.data_ptr(), rows, cols, ld, 0)
+    return N.ReduceSeg(buf.data_ptr() + 4 * off, dst.data_ptr(), rows, cols, ld, 0)
 
 
 def layer():
@@ -47,19 +42,17 @@ for _ in range(4):
     w, b, ln = layer()
     W += w; B += b; LN += ln
 fn = N.load().xf_multi_rowsum
-fn.restype = C.c_int
-fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
 
 
 def timeit(label, segs):
-    arr = (Seg * len(segs))(*segs)
+    arr = (N.ReduceSeg * len(segs))(*segs)
     for _ in range(3):
-        assert fn(C.cast(arr, C.c_void_p), len(segs), N.stream()) == 0
+        assert fn(arr, len(segs), N.stream()) == 0
     torch.cuda.synchronize()
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
     for _ in range(20):
-        fn(C.cast(arr, C.c_void_p), len(segs), N.stream())
+        fn(arr, len(segs), N.stream())
     t1.record()
     torch.cuda.synchronize()
     mb = sum(s.rows * s.cols * 4 for s in segs) / 1e6

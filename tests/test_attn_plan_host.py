@@ -11,12 +11,11 @@ import itertools
 import os
 import pathlib
 import re
-import subprocess
-import sys
 
 import pytest
 
 import test_encoder_plan_host as EP
+from abi_worker import run_worker
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 F32, BF16 = 0, 1
@@ -226,8 +225,7 @@ def native():
 
 @pytest.fixture(scope="module")
 def plan(native):
-    lib = C.CDLL(str(native.LIB_PATH))
-    lib.xf_attn_plan.restype, lib.xf_attn_plan.argtypes = C.c_int, [C.c_int32] * 11 + [C.POINTER(C.c_int32)]
+    lib = native.load()
 
     def ask(c, bwd):
         out = (C.c_int32 * 8)(*([-1] * 8))
@@ -387,10 +385,7 @@ def test_every_configuration_the_encoder_accepts_has_a_plan(native, plan):
 
 
 SWITCH_WORKER = r"""
-import ctypes as C, sys
-lib = C.CDLL(sys.argv[1])
-lib.xf_attn_switches.restype, lib.xf_attn_switches.argtypes = C.c_int, []
-print(lib.xf_attn_switches(), lib.xf_attn_switches())
+report(lib.xf_attn_switches(), lib.xf_attn_switches())
 """
 
 
@@ -407,19 +402,17 @@ print(lib.xf_attn_switches(), lib.xf_attn_switches())
 def test_switches_as_the_library_reads_them(native, env, want):
     """A fresh process each (the two split switches are read once per process); no GPU."""
     clean = {k: v for k, v in os.environ.items() if not k.startswith("XFMR_ATTN_")}
-    r = subprocess.run([sys.executable, "-c", SWITCH_WORKER, str(native.LIB_PATH)], env=clean | env, capture_output=True,
-                       text=True, check=True)
-    assert r.stdout.split() == [str(want)] * 2
+    torch_imported, got = run_worker(SWITCH_WORKER, native.LIB_PATH, clean | env)
+    assert torch_imported is False and got == [want] * 2
 
 
 def test_split_switches_are_read_once_and_the_backward_form_per_call(native):
-    worker = SWITCH_WORKER.replace("print(", "import os\nfirst = lib.xf_attn_switches()\n"
+    worker = SWITCH_WORKER.replace("report(", "first = lib.xf_attn_switches()\n"
                                    "os.environ.update(XFMR_ATTN_FWD_SPLIT='1', XFMR_ATTN_BWD_SPLIT='1', "
-                                   "XFMR_ATTN_BWD_FORM='roles')\nprint(first, ")
+                                   "XFMR_ATTN_BWD_FORM='roles')\nreport(first, ")
     clean = {k: v for k, v in os.environ.items() if not k.startswith("XFMR_ATTN_")}
-    r = subprocess.run([sys.executable, "-c", worker, str(native.LIB_PATH)], env=clean, capture_output=True, text=True,
-                       check=True)
-    assert r.stdout.split() == ["0", str(BWD_ROLES), str(BWD_ROLES)]
+    torch_imported, got = run_worker(worker, native.LIB_PATH, clean)
+    assert torch_imported is False and got == [0, BWD_ROLES, BWD_ROLES]
 
 
 def test_plan_entry_is_internal(native):

@@ -4,16 +4,15 @@ environment variables. The rules are written here a second time, in Python, and 
 on both sides of every boundary. The workspace size of a dozen configurations is pinned to the values of the commit before the
 plan existed: the carve's total must not move unless a change means to resize the workspace (which then updates the literals)."""
 
-import ctypes as C
 import itertools
 import json
 import os
 import pathlib
 import re
-import subprocess
-import sys
 
 import pytest
+
+from abi_worker import run_worker
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 F32, BF16 = 0, 1
@@ -90,16 +89,12 @@ def decision_table():
 TABLE = decision_table()
 
 WORKER = r"""
-import ctypes as C, json, sys
-lib = C.CDLL(sys.argv[1])
-lib.xf_encoder_plan.restype, lib.xf_encoder_plan.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
-lib.xfmr_encoder_workspace_bytes.restype, lib.xfmr_encoder_workspace_bytes.argtypes = C.c_size_t, [C.c_void_p]
 res = []
 for raw in json.load(sys.stdin):
-    buf, out = C.create_string_buffer(bytes.fromhex(raw)), (C.c_int32 * 16)()
-    rc = lib.xf_encoder_plan(buf, out)
-    res.append([rc, list(out), lib.xfmr_encoder_workspace_bytes(buf)])
-print(json.dumps(res))
+    cfg, out = abi.EncoderCfg.from_buffer_copy(bytes.fromhex(raw)), (C.c_int32 * 16)()
+    rc = lib.xf_encoder_plan(C.byref(cfg), out)
+    res.append([rc, list(out), lib.xfmr_encoder_workspace_bytes(C.byref(cfg))])
+report(res)
 """
 
 
@@ -124,9 +119,9 @@ def run_table(native, table, env):
                               packed_rows=c["packed_rows"])
         raw.append(bytes(s).hex())
     clean = {k: v for k, v in os.environ.items() if k not in ENV_NAMES}
-    r = subprocess.run([sys.executable, "-c", WORKER, str(native.LIB_PATH)], input=json.dumps(raw), env=clean | env,
-                       capture_output=True, text=True, check=True)
-    return [(rc, dict(zip(FIELDS, out)), out[len(FIELDS):], nbytes) for rc, out, nbytes in json.loads(r.stdout)]
+    torch_imported, (res,) = run_worker(WORKER, native.LIB_PATH, clean | env, json.dumps(raw))
+    assert torch_imported is False
+    return [(rc, dict(zip(FIELDS, out)), out[len(FIELDS):], nbytes) for rc, out, nbytes in res]
 
 
 @pytest.mark.parametrize("env", [{}, {"XFMR_ACT_FP32": "1"}, {"XFMR_ACT_FP32": "0"}, {"XFMR_LN_STORE_X": "1"},

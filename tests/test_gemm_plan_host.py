@@ -13,10 +13,10 @@ import json
 import os
 import pathlib
 import re
-import subprocess
-import sys
 
 import pytest
+
+from abi_worker import run_worker
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 F32, BF16 = 0, 1
@@ -275,12 +275,7 @@ def rules(c, sw):
 
 # ---------------------------------------------------------------------------------------------- the library
 WORKER = r"""
-import ctypes as C, json, sys
-lib = C.CDLL(sys.argv[1])
 I32 = C.c_int32
-lib.xf_gemm_plan.restype = C.c_int
-lib.xf_gemm_plan.argtypes = [I32, C.c_int64, I32, I32, I32, C.c_uint32, I32, I32, C.POINTER(I32), C.POINTER(I32)]
-lib.xf_gemm_switches.restype, lib.xf_gemm_switches.argtypes = None, [C.POINTER(I32)]
 sw = (I32 * 16)()
 lib.xf_gemm_switches(sw)
 res = []
@@ -288,7 +283,7 @@ for c in json.load(sys.stdin):
     out = (I32 * 24)()
     rc = lib.xf_gemm_plan(c["op"], c["M"], c["N"], c["K"], c["prec"], c["s16"], c["items"], c["cus"], sw, out)
     res.append([rc, list(out)])
-print(json.dumps([list(sw), res]))
+report(list(sw), res)
 """
 
 
@@ -303,9 +298,9 @@ def native():
 
 def run_script(native, script, env, stdin=""):
     clean = {k: v for k, v in os.environ.items() if k not in ENV_NAMES}
-    r = subprocess.run([sys.executable, "-c", script, str(native.LIB_PATH)], input=stdin, env=clean | env, capture_output=True,
-                       text=True, check=True)
-    return json.loads(r.stdout)
+    torch_imported, values = run_worker(script, native.LIB_PATH, clean | env, stdin)
+    assert torch_imported is False
+    return values
 
 
 def run_table(native, table, env):
@@ -481,15 +476,7 @@ def test_fused_ffn_plan_follows_the_rules(native, env):
 
 
 ROOM_WORKER = r"""
-import ctypes as C, json, sys
-lib = C.CDLL(sys.argv[1])
 I32 = C.c_int32
-lib.xf_gemm_plan.restype = C.c_int
-lib.xf_gemm_plan.argtypes = [I32, C.c_int64, I32, I32, I32, C.c_uint32, I32, I32, C.POINTER(I32), C.POINTER(I32)]
-lib.xf_gemm_switches.restype, lib.xf_gemm_switches.argtypes = None, [C.POINTER(I32)]
-lib.xfmr_linear_bwd_dw_workspace.restype, lib.xfmr_linear_bwd_dw_workspace.argtypes = C.c_size_t, [C.c_int64, I32, I32]
-lib.xf_dw_split_plan.restype, lib.xf_dw_split_plan.argtypes = C.c_int, [C.c_int64, I32, I32, C.POINTER(C.c_int)]
-lib.xf_ln_row_tiles.restype, lib.xf_ln_row_tiles.argtypes = C.c_int, [C.c_int64]
 req = json.load(sys.stdin)
 sw, off = (I32 * 16)(), (I32 * 16)()
 lib.xf_gemm_switches(sw)
@@ -510,7 +497,7 @@ for n, k in req["weights"]:
     worst.append([room] + most[:2])
 records = max(lib.xf_ln_row_tiles(t) for t in range(1, T + 1))
 sizes = [lib.xfmr_linear_bwd_dw_workspace(*c) for c in req["pinned"]]
-print(json.dumps([worst, records, lib.xf_ln_row_tiles(T), sizes]))
+report(worst, records, lib.xf_ln_row_tiles(T), sizes)
 """
 
 # xfmr_linear_bwd_dw_workspace(M, N, K) of the parent commit's library (d94dca2), default environment
@@ -537,15 +524,12 @@ def test_room_holds_every_token_count(native, env):
 
 
 SWITCH_WORKER = r"""
-import ctypes as C, json, os, sys
-lib = C.CDLL(sys.argv[1])
 sw = (C.c_int32 * 16)()
-lib.xf_gemm_switches.restype, lib.xf_gemm_switches.argtypes = None, [C.POINTER(C.c_int32)]
 lib.xf_gemm_switches(sw)
 first = list(sw)
 os.environ.update(json.load(sys.stdin))
 lib.xf_gemm_switches(sw)
-print(json.dumps([first, list(sw)]))
+report(first, list(sw))
 """
 
 

@@ -40,9 +40,7 @@ def forms():
     """(forward form, backward form) of a call, under the switches the library reads from the environment right now."""
     from xfmr_rec_amd import _native as N
 
-    lib = C.CDLL(str(N.LIB_PATH))
-    lib.xf_attn_plan.restype, lib.xf_attn_plan.argtypes = C.c_int, [C.c_int32] * 11 + [C.POINTER(C.c_int32)]
-    lib.xf_attn_switches.restype, lib.xf_attn_switches.argtypes = C.c_int, []
+    lib = N.load()
 
     def ask(prec, dh, B, L, *, causal=True, stream_keys=False, packed=False, s16=False):
         got = []

@@ -10,7 +10,6 @@ test_dropout_model_host.py) and against fp64 references that apply that mask -- 
 A slip that forward and backward share -- the mask keyed by the wrong head, a lost 1 / (1 - p), dropout on the wrong side of
 the bias -- passes every forward-against-backward and kernel-against-kernel check; it fails here."""
 
-import ctypes as C
 import functools
 
 import numpy as np
@@ -38,17 +37,7 @@ def ops():
 def lib():
     from xfmr_rec_amd import _native as N
 
-    lb = N.load()
-    fn = lb.xf_linear_ln_fwd_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_float, N.Seed, C.c_uint32,
-                                      C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4 + [C.c_int32, C.c_uint32,
-                                                                                               C.c_void_p]
-    fn = lb.xf_ffn_fwd_fused_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_float, N.Seed, C.c_uint32,
-                                      C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5
-    return lb
+    return N.load()
 
 
 def _is_the_mask(tag, y, keep, p):

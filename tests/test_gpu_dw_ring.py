@@ -10,38 +10,27 @@ import ctypes as C
 import pytest
 import torch
 
+from xfmr_rec_amd._native import DwItem, load
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-class Item(C.Structure):
-    _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("N", C.c_int32), ("K", C.c_int32), ("slabs", C.c_void_p),
-                ("bias_part", C.c_void_p), ("splits", C.c_void_p)]
-
-
 @pytest.fixture(scope="module")
 def lib():
-    from xfmr_rec_amd import _native as N
-
-    lib = N.load()
-    lib.xf_linear_bwd_dw_group.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]
-    lib.xf_dw_ring_takes.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.c_uint32]
-    lib.xf_dw_ring_takes.restype = C.c_bool
-    lib.xf_linear_bwd_dw_slab_bytes.restype = C.c_size_t
-    lib.xf_linear_bwd_dw_slab_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    return lib
+    return load()
 
 
 def _run(lib, T, shapes, seed=0):
     g = torch.Generator().manual_seed(seed)
-    keep, arr = [], (Item * len(shapes))()
+    keep, arr = [], (DwItem * len(shapes))()
     for i, (n, k, bias) in enumerate(shapes):
         dy = (torch.randn(T, n, generator=g) * 0.5).to(torch.bfloat16).to(DEV)
         x = (torch.randn(T, k, generator=g) * 0.5).to(torch.bfloat16).to(DEV)
         slabs = torch.full((lib.xf_linear_bwd_dw_slab_bytes(T, n, k) // 4,), float("nan"), device=DEV)
         bpart = torch.full((256 * n,), float("nan"), device=DEV) if bias else None
         splits = (C.c_int * 1)()
-        arr[i] = Item(dy.data_ptr(), x.data_ptr(), n, k, slabs.data_ptr(), bpart.data_ptr() if bias else None,
+        arr[i] = DwItem(dy.data_ptr(), x.data_ptr(), n, k, slabs.data_ptr(), bpart.data_ptr() if bias else None,
                       C.addressof(splits))
         keep.append((dy, x, n, k, slabs, bpart, splits))
     assert lib.xf_dw_ring_takes(arr, len(shapes), T, 1, 3), "shape not routed to the ring kernel"
@@ -82,11 +71,11 @@ def test_ring_tile_counts_of_the_wider_models(lib, shape):
 
 
 def test_shapes_outside_the_ring_keep_the_generic_kernel(lib):
-    arr = (Item * 1)()
+    arr = (DwItem * 1)()
     t = torch.zeros(64, 192, dtype=torch.bfloat16, device=DEV)
     sp = (C.c_int * 1)()
-    arr[0] = Item(t.data_ptr(), t.data_ptr(), 192, 64, t.data_ptr(), None, C.addressof(sp))  # d_model 64: 64-wide weights
+    arr[0] = DwItem(t.data_ptr(), t.data_ptr(), 192, 64, t.data_ptr(), None, C.addressof(sp))  # d_model 64: 64-wide weights
     assert not lib.xf_dw_ring_takes(arr, 1, 64, 1, 3)
-    arr[0] = Item(t.data_ptr(), t.data_ptr(), 128, 128, t.data_ptr(), None, C.addressof(sp))
+    arr[0] = DwItem(t.data_ptr(), t.data_ptr(), 128, 128, t.data_ptr(), None, C.addressof(sp))
     assert not lib.xf_dw_ring_takes(arr, 1, 64, 0, 0)  # fp32 parity policy
     assert lib.xf_dw_ring_takes(arr, 1, 64, 1, 3)

@@ -38,18 +38,7 @@ BF16, F32 = torch.bfloat16, torch.float32
 def lib():
     from xfmr_rec_amd import _native as N
 
-    lb = N.load()
-    fn = lb.xf_ffn_bwd_dx_fused_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [
-        C.c_float, N.Seed, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
-    fn = lb.xf_linear_bwd_dx_lnbwd_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [
-        C.c_float, N.Seed, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int32,
-        C.c_uint32, C.c_void_p, C.c_float, C.c_uint32]
-    lb.xf_ln_row_tiles.restype, lb.xf_ln_row_tiles.argtypes = C.c_int, [C.c_int64]
-    return lb
+    return N.load()
 
 
 # ------------------------------------------------------------------------------------------------ guards, masks

@@ -24,13 +24,7 @@ H = 128
 def lib():
     from xfmr_rec_amd import _native as N
 
-    lb = N.load()
-    fn = lb.xf_ffn_bwd_dx_fused_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [
-        C.c_float, N.Seed, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
-    lb.xf_ln_row_tiles.restype, lb.xf_ln_row_tiles.argtypes = C.c_int, [C.c_int64]
-    return lb
+    return N.load()
 
 
 def _inputs(M, I):

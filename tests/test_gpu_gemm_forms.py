@@ -19,20 +19,15 @@ from test_gemm_plan_host import (AB, BF16, DW, DW_DEFERRED, DW_GROUP, DX, DX_GEL
                                  EPI_DROP_RES_LN_RE, EPI_DROP_RES_LN_RED, EPI_DX_LNBWD, EPI_SPLITK, F32, FFN_BWD, FFN_BWD_KERNEL,
                                  FFN_FWD, FFN_FWD_KERNEL, FIELDS, FWD_BIAS, FWD_DROP_RES, FWD_GELU, GROUP, LN_FWD, LN_FWD_RE,
                                  LN_FWD_RE_DROP, OK, RING, RING_LDS, TILE)
-from test_gpu_dw_ring import Item
 from test_gpu_ffn_bwd_reference import _check_ln_stage, _guarded, _lnbwd_inputs, _run_ffn
 from test_gpu_ffn_weight_ring import _inputs as _ffn_bwd_inputs
+from xfmr_rec_amd._native import DwItem, LnResidual
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 H = 128
 SEED, SITE, SITE_RES = 5, 9, 2
 PREC = {BF16: "bf16", F32: "fp32"}
-
-
-class LnResidual(C.Structure):  # csrc/internal.h XfLnResidual
-    _fields_ = [("pre", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
-                ("dropout_p", C.c_float), ("site", C.c_uint32)]
 
 
 @pytest.fixture(scope="module")
@@ -44,28 +39,7 @@ def N():
 
 @pytest.fixture(scope="module")
 def lib(N):
-    lb = N.load()
-    I32, VP = C.c_int32, C.c_void_p
-    lb.xf_gemm_plan.restype = C.c_int
-    lb.xf_gemm_plan.argtypes = [I32, C.c_int64, I32, I32, I32, C.c_uint32, I32, I32, C.POINTER(I32), C.POINTER(I32)]
-    lb.xf_gemm_switches.restype, lb.xf_gemm_switches.argtypes = None, [C.POINTER(I32)]
-    lb.xf_linear_bwd_dw_slab_bytes.restype, lb.xf_linear_bwd_dw_slab_bytes.argtypes = C.c_size_t, [C.c_int64, I32, I32]
-    lb.xf_linear_bwd_dw_group.restype, lb.xf_linear_bwd_dw_group.argtypes = C.c_int, [VP, C.c_int, C.c_int64, I32, C.c_uint32, VP]
-    lb.xf_linear_bwd_dw_deferred.restype = C.c_int
-    lb.xf_linear_bwd_dw_deferred.argtypes = [VP, VP, C.c_int64, I32, I32, I32, C.c_uint32, VP, VP, C.POINTER(C.c_int), VP]
-    ln_tail = [C.c_float, N.Seed, C.c_uint32, VP, VP, C.c_float] + [VP] * 4 + [I32, C.c_uint32, VP]
-    for fn in (lb.xf_linear_ln_fwd_ex, lb.xf_linear_ln_fwd_re):
-        fn.restype, fn.argtypes = C.c_int, [VP] * 4 + [C.c_int64, I32, I32, VP] + ln_tail
-    lb.xf_ffn_bwd_dx_fused_ex.restype = C.c_int
-    lb.xf_ffn_bwd_dx_fused_ex.argtypes = [VP] * 5 + [C.c_int64, I32, I32] + [VP] * 5 + [C.c_float, N.Seed, C.c_uint32, VP, VP, VP,
-                                                                                     C.POINTER(C.c_int), VP]
-    lb.xf_linear_bwd_dx_lnbwd_ex.restype = C.c_int
-    lb.xf_linear_bwd_dx_lnbwd_ex.argtypes = [VP, VP, C.c_int64, I32, I32] + [VP] * 5 + [
-        C.c_float, N.Seed, C.c_uint32, VP, VP, VP, C.POINTER(C.c_int), I32, C.c_uint32, VP, C.c_float, C.c_uint32]
-    lb.xf_ln_row_tiles.restype, lb.xf_ln_row_tiles.argtypes = C.c_int, [C.c_int64]
-    lb.xf_ffn_fwd_fused_ex.restype = C.c_int
-    lb.xf_ffn_fwd_fused_ex.argtypes = [VP] * 8 + [C.c_int64, I32, I32, VP, C.c_float, N.Seed, C.c_uint32, VP, VP, C.c_float] + [VP] * 5
-    return lb
+    return N.load()
 
 
 @pytest.fixture(scope="module")
@@ -152,12 +126,12 @@ def test_tile_kernel_dx(lib, N, plan, prec, M, Nn, K, want, want_gelu):
 # ------------------------------------------------------------------------------------------------ the weight gradients
 def _items(lib, T, shapes, seed=0):
     """bf16 operands and NaN-filled slab / bias-row buffers of one XfDwItem per (N, K)."""
-    keep, arr = [], (Item * len(shapes))()
+    keep, arr = [], (DwItem * len(shapes))()
     for i, (n, k) in enumerate(shapes):
         dy, x = rand(T, n, seed=seed + 2 * i, scale=0.5, bf16=True), rand(T, k, seed=seed + 2 * i + 1, scale=0.5, bf16=True)
         slabs, bpart = nan((lib.xf_linear_bwd_dw_slab_bytes(T, n, k) // 4,)), nan((256 * n,))
         splits = (C.c_int * 1)()
-        arr[i] = Item(dy.data_ptr(), x.data_ptr(), n, k, slabs.data_ptr(), bpart.data_ptr(), C.addressof(splits))
+        arr[i] = DwItem(dy.data_ptr(), x.data_ptr(), n, k, slabs.data_ptr(), bpart.data_ptr(), C.addressof(splits))
         keep.append(dict(dy=dy, x=x, N=n, K=k, slabs=slabs, bias=bpart, splits=splits))
     return arr, keep
 

@@ -483,13 +483,7 @@ def test_multi_segment_row_reduction(ops):
     backward): tall strided segments (the LayerNorm records: 1600 x 128 out of a [1600][3][128] buffer), wide short ones
     (weight slabs), a segment whose width is not a multiple of 4 (one-column form), fewer rows than row groups -- against
     fp64 sums, and bit-for-bit equal over repeated launches."""
-    import ctypes as C
-
     from xfmr_rec_amd import _native as N
-
-    class Seg(C.Structure):
-        _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("ld", C.c_int),
-                    ("pad", C.c_int)]
 
     g = torch.Generator().manual_seed(0)
     rec = torch.randn(1600, 3, 128, generator=g).to(DEV)           # LayerNorm partial records
@@ -500,18 +494,16 @@ def test_multi_segment_row_reduction(ops):
     cases = [(rec[:, 0], 1600, 128, 384), (rec[:, 1], 1600, 128, 384), (rec[:, 2], 1600, 128, 384),
              (slab, 62, 4096, 4096), (odd, 37, 6, 6), (few, 3, 256, 256), (tall, 1000, 64, 64)]
     outs = [torch.full((c,), float("nan"), device=DEV) for _, _, c, _ in cases]
-    segs = (Seg * len(cases))()
+    segs = (N.ReduceSeg * len(cases))()
     for i, ((src, rows, cols, ld), dst) in enumerate(zip(cases, outs)):
-        segs[i] = Seg(src.data_ptr(), dst.data_ptr(), rows, cols, ld, 0)
+        segs[i] = N.ReduceSeg(src.data_ptr(), dst.data_ptr(), rows, cols, ld, 0)
     fn = N.load().xf_multi_rowsum
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    assert fn(C.cast(segs, C.c_void_p), len(cases), N.stream()) == 0
+    assert fn(segs, len(cases), N.stream()) == 0
     torch.cuda.synchronize()
     first = [o.clone() for o in outs]
     for (src, rows, cols, ld), o in zip(cases, outs):
         torch.testing.assert_close(o.double(), src.double().sum(0), rtol=1e-5, atol=2e-4)
-    assert fn(C.cast(segs, C.c_void_p), len(cases), N.stream()) == 0
+    assert fn(segs, len(cases), N.stream()) == 0
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(first, outs))
 
@@ -560,8 +552,6 @@ def test_linear_with_layernorm_in_the_epilogue(ops, K, M, p_drop, bf16_storage):
     bias + dropout + residual + LayerNorm in ONE kernel) against the two-kernel form it replaces: same pre-LayerNorm
     sum bit for bit (same GEMM arithmetic, same dropout mask), LayerNorm output / mean / rstd to fp32 rounding, and the
     bf16 copy = the rounded fp32 output. Partial last tile (M not a multiple of 64) included."""
-    import ctypes as C
-
     from xfmr_rec_amd import _native as N
 
     lib = N.load()
@@ -589,10 +579,6 @@ def test_linear_with_layernorm_in_the_epilogue(ops, K, M, p_drop, bf16_storage):
     mean = torch.empty(M, device=DEV)
     rstd = torch.empty(M, device=DEV)
     fn = lib.xf_linear_ln_fwd_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_float, N.Seed, C.c_uint32,
-                                      C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4 + [C.c_int32, C.c_uint32,
-                                                                                               C.c_void_p]
     rc = fn(N.ptr(xs), N.ptr(ws), N.ptr(b), N.ptr(pre), M, Nn, K, N.ptr(res), p_drop, 5, 9, N.ptr(gamma), N.ptr(beta),
             1e-12, N.ptr(y), N.ptr(y16), N.ptr(mean), N.ptr(rstd), N.precision_id("bf16"), s16, N.stream())
     assert rc == 0, rc
@@ -630,8 +616,6 @@ def test_ffn_forward_in_one_kernel_vs_the_two_gemm_form(ops, M, I, p_drop, chunk
     agrees with the saved gelu', and everything downstream agrees to bf16 rounding noise; against an fp64 restatement of
     the fused kernel's own rounding points the pre-LayerNorm sum agrees to fp32 accumulation error. Partial last tile,
     dropout, the benchmark's row count, and both chunk widths (XFMR_FFN_CHUNK, read per call)."""
-    import ctypes as C
-
     from xfmr_rec_amd import _native as N
 
     lib = N.load()
@@ -655,17 +639,10 @@ def test_ffn_forward_in_one_kernel_vs_the_two_gemm_form(ops, M, I, p_drop, chunk
     # the two-kernel form, with the encoder's storage masks (bf16 A, B, C; gelu' as the auxiliary output)
     ref = outs()
     f1 = lib.xf_linear_fwd_ex
-    f1.restype = C.c_int
-    f1.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float,
-                                      N.Seed, C.c_uint32, C.c_int32, C.c_uint32, C.c_void_p]
     rc = f1(N.ptr(x16), N.ptr(w1), N.ptr(b1), N.ptr(ref["g"]), M, I, H, N.EPI_BIAS_GELU, None, N.ptr(ref["d"]), 0.0, 0, 0,
             N.precision_id("bf16"), 1 | 2 | 4 | 0x100, N.stream())
     assert rc == 0, rc
     f2 = lib.xf_linear_ln_fwd_ex
-    f2.restype = C.c_int
-    f2.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_float, N.Seed, C.c_uint32,
-                                      C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 4 + [C.c_int32, C.c_uint32,
-                                                                                               C.c_void_p]
     rc = f2(N.ptr(ref["g"]), N.ptr(w2), N.ptr(b2), N.ptr(ref["pre"]), M, H, I, N.ptr(res), p_drop, 5, 9, N.ptr(gamma),
             N.ptr(beta), 1e-12, N.ptr(ref["y"]), N.ptr(ref["y16"]), N.ptr(ref["mean"]), N.ptr(ref["rstd"]),
             N.precision_id("bf16"), 3, N.stream())
@@ -673,9 +650,6 @@ def test_ffn_forward_in_one_kernel_vs_the_two_gemm_form(ops, M, I, p_drop, chunk
 
     monkeypatch.setenv("XFMR_FFN_CHUNK", chunk)  # read per call
     fn = lib.xf_ffn_fwd_fused_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_float, N.Seed, C.c_uint32,
-                                      C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5
 
     def run():
         o = outs()
@@ -741,13 +715,8 @@ def test_dx_gemm_with_layernorm_backward_epilogue_vs_separate_kernels_and_bit_re
     rstd = (lnx.var(-1, unbiased=False) + 1e-12).rsqrt().contiguous()
     gamma = (1 + 0.1 * torch.randn(K, generator=g)).to(DEV)
     fn = lib.xf_linear_bwd_dx_lnbwd_ex
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [
-        C.c_float, N.Seed, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int32,
-        C.c_uint32, C.c_void_p, C.c_float, C.c_uint32]
 
     # row tiles = LayerNorm partial records: (M + 63) / 64, or more when the last round is dealt as short tiles
-    lib.xf_ln_row_tiles.restype, lib.xf_ln_row_tiles.argtypes = C.c_int, [C.c_int64]
     n_tiles = lib.xf_ln_row_tiles(M)
     assert n_tiles >= (M + 63) // 64
 

@@ -21,7 +21,6 @@ Where the row counts come from (restated plans: row_cases.ln_form / ln_bwd_plan 
 * pos_grad_packed_kernel: 16 waves x 8 sequences per trip -> B = 16 | 17 and 128 | 129, 300 for a third trip; H = 1024 asks
   for exactly 64 KiB of dynamic LDS."""
 
-import ctypes as C
 import math
 
 import pytest
@@ -48,13 +47,7 @@ def ops():
 def N():
     from xfmr_rec_amd import _native
 
-    lib = _native.load()
-    P = C.c_void_p
-    for name, args in (("xf_layernorm_fwd_ex", [P, P, P, P, P, P, P, C.c_int64, C.c_int32, C.c_float, P]),
-                       ("xf_embed_param_grads_packed", [P, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P])):
-        if hasattr(lib, name):
-            getattr(lib, name).argtypes = args
-            getattr(lib, name).restype = C.c_int
+    _native.load()
     return _native
 
 

@@ -551,15 +551,12 @@ def test_row_tile_plan_of_the_whole_row_kernels(native):
     switch read once per process: measured, not kept -- DESIGN.md section 7) the rows left over after whole 64-row tiles
     per CU, when few (<= 32 per CU), become one short tile per CU: 102 400 rows on 256 CUs = 6 x 256 full tiles + 256 tiles
     of 16 rows instead of 1600 tiles with a seventh on 64 CUs."""
-    import subprocess
+    from abi_worker import run_worker
 
-    code = ("import ctypes as C, sys; lib = C.CDLL(sys.argv[1]); lib.xf_ln_row_tiles.restype = C.c_int; "
-            "lib.xf_ln_row_tiles.argtypes = [C.c_int64]; "
-            "print([lib.xf_ln_row_tiles(m) for m in (102400, 25600, 300, 64 * 256 * 3, 64 * 256 * 2 + 1)])")
+    code = "report(*(lib.xf_ln_row_tiles(m) for m in (102400, 25600, 300, 64 * 256 * 3, 64 * 256 * 2 + 1)))"
     env = {k: v for k, v in os.environ.items() if k != "XFMR_ROW_TILES_SHORT"}
-    plain = subprocess.run([sys.executable, "-c", code, str(native.LIB_PATH)], env=env, capture_output=True, text=True, check=True)
-    assert eval(plain.stdout) == [1600, 400, 5, 768, 513]
-    short = subprocess.run([sys.executable, "-c", code, str(native.LIB_PATH)], env=env | {"XFMR_ROW_TILES_SHORT": "1"},
-                           capture_output=True, text=True, check=True)
+    torch_imported, plain = run_worker(code, native.LIB_PATH, env)
+    assert torch_imported is False and plain == [1600, 400, 5, 768, 513]
+    torch_imported, short = run_worker(code, native.LIB_PATH, env | {"XFMR_ROW_TILES_SHORT": "1"})
     # 16 rows left per CU -> 256 short tiles; 36 per CU -> plain; < 1 tile per CU -> plain; nothing left -> plain; 1 row left
-    assert eval(short.stdout) == [6 * 256 + 256, 400, 5, 768, 512 + 1]
+    assert torch_imported is False and short == [6 * 256 + 256, 400, 5, 768, 512 + 1]

@@ -31,10 +31,7 @@ def native():
 
 @pytest.fixture(scope="module")
 def ask(native):
-    lib = C.CDLL(str(native.LIB_PATH))
-    sig = [C.c_int64, C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_uint32] + [C.c_int32] * 3 + [C.c_uint64, C.POINTER(C.c_int32)]
-    for fn in (lib.xf_loss_plan, lib.xf_loss_plan_ext):
-        fn.restype, fn.argtypes = C.c_int, sig
+    lib = native.load()
 
     def both(c):
         out, ext = (C.c_int32 * 40)(*([-1] * 40)), (C.c_int32 * 8)(*([-1] * 8))

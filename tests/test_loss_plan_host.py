@@ -12,10 +12,10 @@ import itertools
 import os
 import pathlib
 import re
-import subprocess
-import sys
 
 import pytest
+
+from abi_worker import run_worker
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 F32, BF16 = 0, 1
@@ -280,16 +280,7 @@ def native():
 
 @pytest.fixture(scope="module")
 def lib(native):
-    lib = C.CDLL(str(native.LIB_PATH))
-    lib.xf_loss_plan.restype = C.c_int
-    lib.xf_loss_plan.argtypes = ([C.c_int64, C.c_int32, C.c_int64] + [C.c_int32] * 6 + [C.c_uint32] + [C.c_int32] * 3 +
-                                 [C.c_uint64, C.POINTER(C.c_int32)])
-    lib.xfmr_sampled_loss_workspace_cfg.restype = C.c_size_t
-    lib.xfmr_sampled_loss_workspace_cfg.argtypes = [C.POINTER(native.LossCfg), C.c_int64, C.c_int32, C.c_int64]
-    lib.xfmr_sampled_loss_lists_workspace_cfg.restype = C.c_size_t
-    lib.xfmr_sampled_loss_lists_workspace_cfg.argtypes = [C.POINTER(native.LossCfg), C.c_int64, C.c_int64, C.c_int32,
-                                                          C.c_int64]
-    return lib
+    return native.load()
 
 
 @pytest.fixture(scope="module")
@@ -401,10 +392,7 @@ def test_pass_sequences_and_combine_wiring(plan):
 
 # ---------------------------------------------------------------------------------------------- environment reads
 SWITCH_WORKER = r"""
-import ctypes as C, sys
-lib = C.CDLL(sys.argv[1])
-lib.xf_loss_switches.restype, lib.xf_loss_switches.argtypes = C.c_uint64, []
-print(lib.xf_loss_switches(), lib.xf_loss_switches())
+report(lib.xf_loss_switches(), lib.xf_loss_switches())
 """
 
 
@@ -430,18 +418,16 @@ def _clean_env():
 ], ids=lambda v: "-".join(f"{k[10:]}={x}" for k, x in v.items()) or "unset" if isinstance(v, dict) else str(v))
 def test_switches_as_the_library_reads_them(native, env, want):
     """A fresh process each (three of the four are read once per process); no GPU."""
-    r = subprocess.run([sys.executable, "-c", SWITCH_WORKER, str(native.LIB_PATH)], env=_clean_env() | env,
-                       capture_output=True, text=True, check=True)
-    assert r.stdout.split() == [str(want)] * 2
+    torch_imported, got = run_worker(SWITCH_WORKER, native.LIB_PATH, _clean_env() | env)
+    assert torch_imported is False and got == [want] * 2
 
 
 def test_three_switches_are_read_once_and_q_fp32_per_call(native):
-    worker = SWITCH_WORKER.replace("print(", "import os\nfirst = lib.xf_loss_switches()\n"
+    worker = SWITCH_WORKER.replace("report(", "first = lib.xf_loss_switches()\n"
                                    "os.environ.update(XFMR_LOSS_NSPLIT='5', XFMR_LOSS_NSPLIT_GRAD='2', "
-                                   "XFMR_LOSS_LOGM256='0', XFMR_LOSS_Q_FP32='1')\nprint(first, ")
-    r = subprocess.run([sys.executable, "-c", worker, str(native.LIB_PATH)], env=_clean_env(), capture_output=True,
-                       text=True, check=True)
-    assert r.stdout.split() == [str(switches()), str(switches(q_fp32=True)), str(switches(q_fp32=True))]
+                                   "XFMR_LOSS_LOGM256='0', XFMR_LOSS_Q_FP32='1')\nreport(first, ")
+    torch_imported, got = run_worker(worker, native.LIB_PATH, _clean_env())
+    assert torch_imported is False and got == [switches(), switches(q_fp32=True), switches(q_fp32=True)]
 
 
 # ---------------------------------------------------------------------------------------------- the workspace carve

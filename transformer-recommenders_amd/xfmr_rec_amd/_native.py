@@ -1,4 +1,5 @@
-"""ctypes binding of ``libxfmr_hip.so`` (C ABI declared in ``include/xfmr_hip.h``).
+"""ctypes binding of ``libxfmr_hip.so`` (C ABI declared in ``include/xfmr_hip.h``; the Structures and the signature tables
+are in ``_abi.py`` and re-exported here).
 
 There is no CPU fallback: every op in this package goes through this library. If the shared object is
 missing, cannot be loaded, or a tensor is not on a HIP device, the call raises -- it never silently
@@ -12,6 +13,9 @@ import os
 import pathlib
 
 import torch
+
+from ._abi import (INTERNAL_SIGNATURES, NOT_BOUND, SIGNATURES, DwItem, EncoderCfg, LnResidual, LossCfg, OptCfg,  # noqa: F401
+                   ReduceSeg, Seed, bind)
 
 _HERE = pathlib.Path(__file__).resolve().parent
 # XFMR_HIP_LIB points at another build of the same library (kernel experiments); the default is the in-tree one
@@ -46,187 +50,20 @@ STAT = dict(
     n_valid=0, n_query=1, neg_density=2, pos_mean=3, pos_std=4, pos_min=5, pos_max=6,
     neg_mean=7, neg_std=8, neg_min=9, neg_max=10, neg_count=11, neg_distinct=12, pos_density=13, attn_density=14,
 )
-
-
-class EncoderCfg(C.Structure):
-    _fields_ = [
-        ("batch", C.c_int32), ("seq_len", C.c_int32), ("hidden", C.c_int32), ("heads", C.c_int32),
-        ("inter", C.c_int32), ("layers", C.c_int32), ("max_pos", C.c_int32), ("precision", C.c_int32),
-        ("ln_eps", C.c_float), ("hidden_dropout", C.c_float), ("attn_dropout", C.c_float),
-        ("flags", C.c_uint32), ("seed", C.c_uint64),
-        ("step_device", C.c_void_p), ("embed_event", C.c_void_p), ("context", C.c_void_p),
-        ("grads_half_event", C.c_void_p),
-        ("profile_kernel", C.c_int32), ("profile_layer", C.c_int32), ("profile_events", C.c_void_p * 2),
-        # ABI 3: packed rows (all NULL / 0 = the padded (B, L) layout)
-        ("seq_offsets", C.c_void_p), ("row_pos", C.c_void_p), ("packed_rows", C.c_int64),
-    ]
-
-
 PROF_FFN_FWD, PROF_FFN_BWD, PROF_ATTN_FWD, PROF_ATTN_BWD, PROF_DW, PROF_REDUCE = 1, 2, 3, 4, 5, 6
-
-
-class LossCfg(C.Structure):
-    _fields_ = [
-        ("train_head", C.c_int32), ("all_heads", C.c_int32), ("mask_false_negatives", C.c_int32),
-        ("mode", C.c_int32), ("precision", C.c_int32), ("scale", C.c_float), ("margin", C.c_float),
-        ("num_hard_negatives", C.c_int32), ("flags", C.c_uint32),
-        ("profile_grad", C.c_void_p * 2), ("profile_log", C.c_void_p * 2),
-        ("padded_positions", C.c_int64),  # ABI 3
-    ]
-
-
 CLIP_NONE, CLIP_NORM, CLIP_VALUE = 0, 1, 2  # xfmr_opt_cfg.clip_mode
 CLIP_MODES = {None: CLIP_NONE, "none": CLIP_NONE, "norm": CLIP_NORM, "value": CLIP_VALUE}
 # xfmr_opt_cfg.sched: a LambdaLR with the lr_lambda of transformers.optimization.get_*_schedule_with_warmup
 SCHEDULES = {"constant": 0, "warmup_constant": 1, "warmup_linear": 2, "warmup_cosine": 3}
 # the words of the xfmr_opt_ctl record (nonfinite is a uint32: read it through an int32 view)
 CTL = dict(grad_norm=0, grad_max_abs=1, clip_coef=2, lr=3, nonfinite=4)
-
-
-class OptCfg(C.Structure):
-    _fields_ = [
-        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
-        ("grad_scale", C.c_float), ("clip_mode", C.c_int32), ("clip_val", C.c_float), ("sched", C.c_int32),
-        ("step_offset", C.c_int32), ("warmup_steps", C.c_int64), ("total_steps", C.c_int64), ("step", C.c_int64),
-        ("step_device", C.c_void_p),
-    ]
-
-
-class Seed(C.Structure):
-    """csrc/common.h XfSeed, by value: the dropout seed argument of the library's INTERNAL entry points (xf_*_ex; tests and
-    probes call a few of them directly). A plain int converts to (seed, no device-side counter)."""
-
-    _fields_ = [("seed", C.c_uint64), ("dyn", C.c_void_p)]
-
-    @classmethod
-    def from_param(cls, v):
-        return v if isinstance(v, cls) else cls(int(v), None)
-
-
 TARGET_FIRST, TARGET_DIAGONAL, TARGET_EXPLICIT = 0, 1, 2
 TARGET_MODES = {"first": TARGET_FIRST, "diagonal": TARGET_DIAGONAL, None: TARGET_EXPLICIT}  # LossConfig.target_position
 POOL_MODES = {"mean": 0, "max": 1, "cls": 2, "lasttoken": 3}
-
-_P = C.c_void_p
-_SIGNATURES = {
-    "xfmr_strerror": (C.c_char_p, [C.c_int]),
-    "xfmr_abi_version": (C.c_int, []),
-    "xfmr_low_priority_stream_create": (C.c_int, [C.POINTER(C.c_void_p)]),
-    "xfmr_context_create": (C.c_int, [C.POINTER(C.c_void_p)]),
-    "xfmr_context_destroy": (C.c_int, [_P]),
-    "xfmr_stream_destroy": (C.c_int, [_P]),
-    "xfmr_stream_create": (C.c_int, [C.POINTER(C.c_void_p)]),
-    "xfmr_event_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32]),
-    "xfmr_event_destroy": (C.c_int, [_P]),
-    "xfmr_event_record": (C.c_int, [_P, _P]),
-    "xfmr_stream_wait_event": (C.c_int, [_P, _P]),
-    "xfmr_event_elapsed_ms": (C.c_int, [_P, _P, C.POINTER(C.c_float)]),
-    "xfmr_event_synchronize": (C.c_int, [_P]),
-    "xfmr_event_query": (C.c_int, [_P]),
-    "xfmr_batch_upload": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
-    "xfmr_param_count": (C.c_int64, [C.POINTER(EncoderCfg)]),
-    "xfmr_param_half_offset": (C.c_int64, [C.POINTER(EncoderCfg)]),
-    "xfmr_param_offsets": (C.c_int32, [C.POINTER(EncoderCfg), C.POINTER(C.c_int64), C.c_int32]),
-    "xfmr_embed_ln_fwd": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32,
-                                    C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint32, _P]),
-    "xfmr_pack_rows": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P]),
-    "xfmr_pack_rows_ordered": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P]),
-    "xfmr_embed_param_grads": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
-    "xfmr_layernorm_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
-    "xfmr_layernorm_bwd_workspace": (C.c_size_t, [C.c_int64, C.c_int32]),
-    "xfmr_layernorm_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float,
-                                     C.c_uint64, C.c_uint32, _P, _P]),
-    "xfmr_linear_fwd": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_float,
-                                  C.c_uint64, C.c_uint32, C.c_int32, _P]),
-    "xfmr_linear_bwd_dx": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P]),
-    "xfmr_linear_bwd_dw_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
-    "xfmr_linear_bwd_dw": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P]),
-    "xfmr_colsum_workspace": (C.c_size_t, [C.c_int64, C.c_int32]),
-    "xfmr_colsum": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P]),
-    "xfmr_attn_fwd": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64,
-                                C.c_uint32, C.c_int32, _P]),
-    "xfmr_attn_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                C.c_uint64, C.c_uint32, C.c_int32, _P]),
-    "xfmr_attn_fwd_mode": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64,
-                                     C.c_uint32, C.c_int32, C.c_int32, _P]),
-    "xfmr_attn_bwd_mode": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
-                                     C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, _P]),
-    "xfmr_encoder_workspace_bytes": (C.c_size_t, [C.POINTER(EncoderCfg)]),
-    "xfmr_encoder_fwd": (C.c_int, [C.POINTER(EncoderCfg), _P, _P, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_encoder_bwd": (C.c_int, [C.POINTER(EncoderCfg), _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_encoder_infer_workspace_bytes": (C.c_size_t, [C.POINTER(EncoderCfg)]),
-    "xfmr_encoder_infer": (C.c_int, [C.POINTER(EncoderCfg), _P, _P, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_mean_pool": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
-    "xfmr_pool": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
-    "xfmr_pool_rows": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
-    "xfmr_l2_normalize_fwd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
-    "xfmr_l2_normalize_bwd": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P]),
-    "xfmr_sampled_loss_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64]),
-    "xfmr_sampled_loss_workspace_cfg": (C.c_size_t, [C.POINTER(LossCfg), C.c_int64, C.c_int32, C.c_int64]),
-    "xfmr_sampled_loss": (C.c_int, [C.POINTER(LossCfg), _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32,
-                                    _P, _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_sampled_loss_prepare": (C.c_int, [C.POINTER(LossCfg), _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P,
-                                            C.c_size_t, _P]),
-    "xfmr_sampled_loss_prepared": (C.c_int, [C.POINTER(LossCfg), _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64,
-                                             C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_sampled_loss_lists_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int64]),
-    "xfmr_sampled_loss_lists_workspace_cfg": (C.c_size_t, [C.POINTER(LossCfg), C.c_int64, C.c_int64, C.c_int32,
-                                                           C.c_int64]),
-    "xfmr_sampled_loss_lists": (C.c_int, [C.POINTER(LossCfg), _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64,
-                                          C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_dense_loss_workspace": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
-    "xfmr_dense_loss": (C.c_int, [C.POINTER(LossCfg), _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P,
-                                  _P, _P, C.c_size_t, _P]),
-    "xfmr_dense_loss_grads": (C.c_int, [C.POINTER(LossCfg), _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P,
-                                        _P, _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_table_rnorm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
-    "xfmr_table_prepare": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P]),
-    "xfmr_seq_sample_workspace": (C.c_size_t, [C.c_int32, C.c_int64]),
-    "xfmr_seq_sample": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
-                                  C.c_uint64, _P, _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_seq_sample_rows_workspace": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "xfmr_seq_sample_rows": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P,
-                                       C.c_size_t, _P]),
-    "xfmr_topk_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
-    "xfmr_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P,
-                            C.c_size_t, _P]),
-    "xfmr_retrieval_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
-    "xfmr_retrieval_metrics_sum_workspace": (C.c_size_t, [C.c_int64]),
-    "xfmr_retrieval_metrics_sum": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_size_t,
-                                             _P]),
-    "xfmr_topk_tiled_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
-    "xfmr_topk_tiled": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P,
-                                  _P, C.c_size_t, _P]),
-    "xfmr_target_ranks_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
-    "xfmr_target_ranks": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32,
-                                    _P, _P, _P, C.c_size_t, _P]),
-    "xfmr_candidate_ranks": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32,
-                                       _P, _P, _P, _P]),
-    "xfmr_rank_metrics_sum_workspace": (C.c_size_t, [C.c_int64, C.c_int32]),
-    "xfmr_rank_metrics_sum": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _P, _P, _P, _P,
-                                        C.c_size_t, _P]),
-    "xfmr_table_sqnorm": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
-    "xfmr_adamw": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                             C.c_int64, C.c_float, _P]),
-    "xfmr_adamw_dev": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                 _P, C.c_int32, C.c_float, _P]),
-    "xfmr_step_advance": (C.c_int, [_P, _P]),
-    "xfmr_lr_lambda": (C.c_float, [C.c_int32, C.c_int64, C.c_int64, C.c_int64]),
-    "xfmr_opt_workspace": (C.c_size_t, [C.c_int64]),
-    "xfmr_opt_prepare": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P]),
-    "xfmr_adamw_ctl": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P]),
-    "xfmr_grad_accumulate": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),
-    "xfmr_scale_by_device_scalar": (C.c_int, [_P, C.c_int64, _P, _P]),
-    "xfmr_selftest_mfma": (C.c_int, [_P, _P]),
-    "xfmr_comm_unique_id": (C.c_int, [_P]),
-    "xfmr_comm_create": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
-    "xfmr_comm_destroy": (C.c_int, [_P]),
-    "xfmr_allreduce_flat": (C.c_int, [_P, _P, C.c_int64, _P]),
-    "xfmr_comm_last_error": (C.c_char_p, []),
-}
 COMM_ID_BYTES = 128
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+_SIGNATURES = SIGNATURES
+EXPORTED_SYMBOLS = tuple(SIGNATURES)  # the public C ABI
+INTERNAL_SYMBOLS = tuple(INTERNAL_SIGNATURES)  # csrc/internal.h: bound for tests and probes, no part of the public ABI
 
 _lib = None
 
@@ -254,14 +91,10 @@ def load() -> C.CDLL:
     if got != ABI_VERSION:  # checked before binding the symbols: an older build fails here with a version message
         raise NativeLibraryError(f"{LIB_PATH}: ABI version {got}, this package binds version {ABI_VERSION}: rebuild the "
                                  "library (python -c 'import __graft_entry__ as g; g.build()')")
-    for name, (res, args) in _SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
+    try:
+        _lib = bind(lib)
+    except AttributeError as e:
+        raise NativeLibraryError(str(e)) from e
     return lib
 
 
