@@ -244,3 +244,9 @@ int xf_layernorm_bwd_impl(const float* dy, const float* x, const float* mean, co
                           int64_t rows, int32_t H, XfDropout drop_out, XfDropout drop_lin, void* partials,
                           hipStream_t st, int* blocks_out = nullptr);
 }
+// norm.hip -> session.hip (C++ linkage, like gemm_plan: nothing outside the library calls it): xfmr_pool's rule over the
+// session store -- sequence i = rows [0, lens[i]) of slot slots[i] of tok [n_slots][max_len][H] with that slot's mask bytes,
+// and xfmr_l2_normalize_fwd in the same launch. An empty sequence or a slot out of range: a zero row.
+int pool_slots_launch(const float* tok, const uint8_t* mask, const int32_t* slots, const int32_t* lens, int32_t n,
+                      int32_t n_slots, int32_t max_len, int32_t H, int32_t mode, int32_t normalize, float eps, float* out,
+                      hipStream_t st);

@@ -1,8 +1,9 @@
 """The C ABI of ``libxfmr_hip.so`` as ctypes: the Structures and one signature table per header.
 
 ``SIGNATURES`` has one row per prototype of ``include/xfmr_hip.h`` (the public ``xfmr_*`` entries), ``INTERNAL_SIGNATURES`` one
-per ``extern "C"`` prototype of ``csrc/internal.h`` (the ``xf_*`` entries that tests and probes call directly); ``bind`` applies
-both to a ``CDLL``. No other file keeps a signature: ``tests/test_abi_tables_host.py`` holds every row and every Structure to its
+per ``extern "C"`` prototype of ``csrc/internal.h`` (the ``xf_*`` entries that tests and probes call directly),
+``SESSION_SIGNATURES`` one per prototype of ``include/xfmr_session.h`` (the session encoder); ``bind`` applies
+them to a ``CDLL``. No other file keeps a signature: ``tests/test_abi_tables_host.py`` holds every row and every Structure to its
 header. This module imports ``ctypes`` only, so that a child process without torch can load it by file path.
 """
 
@@ -254,6 +255,17 @@ INTERNAL_SIGNATURES = {
     "xf_loss_switches": (_U64, []),
 }
 
+# include/xfmr_session.h (the session encoder), in the header's order; tests/test_session_abi_host.py holds it to the header
+SESSION_SIGNATURES = {
+    "xfmr_session_state_bytes": (C.c_size_t, [C.POINTER(EncoderCfg), _I32]),
+    "xfmr_session_workspace_bytes": (C.c_size_t, [C.POINTER(EncoderCfg), _I64]),
+    "xfmr_session_plan": (C.c_int, [C.POINTER(EncoderCfg), _PI32]),
+    "xfmr_session_init": (C.c_int, [C.POINTER(EncoderCfg), _P, _P, C.c_size_t, _I32, _P]),
+    "xfmr_session_append": (C.c_int, [C.POINTER(EncoderCfg), _P, _P, C.c_size_t, _I32, _P, _P, _P, _I64, _P, _I64, _P, _P,
+                                      C.c_size_t, _P]),
+    "xfmr_session_pool": (C.c_int, [C.POINTER(EncoderCfg), _P, C.c_size_t, _I32, _P, _P, _I32, _I32, _I32, _F, _P, _P]),
+}
+
 # prototypes of csrc/internal.h that ctypes cannot call, each with its reason
 NOT_BOUND = (
     ("xf_layernorm_bwd_impl", "takes XfDropout by value, a C++ struct with no mirror here"),
@@ -262,8 +274,8 @@ NOT_BOUND = (
 
 
 def bind(cdll: C.CDLL) -> C.CDLL:
-    """Give every entry of both tables its restype and argtypes on ``cdll``; a symbol the library lacks is named."""
-    for table in (SIGNATURES, INTERNAL_SIGNATURES):
+    """Give every entry of the tables its restype and argtypes on ``cdll``; a symbol the library lacks is named."""
+    for table in (SIGNATURES, INTERNAL_SIGNATURES, SESSION_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(cdll, name)

@@ -14,8 +14,8 @@ import pathlib
 
 import torch
 
-from ._abi import (INTERNAL_SIGNATURES, NOT_BOUND, SIGNATURES, DwItem, EncoderCfg, LnResidual, LossCfg, OptCfg,  # noqa: F401
-                   ReduceSeg, Seed, bind)
+from ._abi import (INTERNAL_SIGNATURES, NOT_BOUND, SESSION_SIGNATURES, SIGNATURES, DwItem, EncoderCfg, LnResidual,  # noqa: F401
+                   LossCfg, OptCfg, ReduceSeg, Seed, bind)
 
 _HERE = pathlib.Path(__file__).resolve().parent
 # XFMR_HIP_LIB points at another build of the same library (kernel experiments); the default is the in-tree one
@@ -64,6 +64,7 @@ COMM_ID_BYTES = 128
 _SIGNATURES = SIGNATURES
 EXPORTED_SYMBOLS = tuple(SIGNATURES)  # the public C ABI
 INTERNAL_SYMBOLS = tuple(INTERNAL_SIGNATURES)  # csrc/internal.h: bound for tests and probes, no part of the public ABI
+SESSION_SYMBOLS = tuple(SESSION_SIGNATURES)  # include/xfmr_session.h: the session encoder's public entries
 
 _lib = None
 

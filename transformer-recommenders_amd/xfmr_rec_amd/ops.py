@@ -726,6 +726,65 @@ def encoder_infer_fwd(cfg: N.EncoderCfg, flat_params, item_idx, table, workspace
     return tok, key_mask, workspace
 
 
+# ------------------------------------------------------------------------------------------------ session encoder
+# include/xfmr_session.h. Eager only, no torch.library registration: there is no autograd and nothing to trace. The cfg is
+# :func:`make_encoder_cfg`'s (batch = n_slots, seq_len = max_pos by convention; neither is read beyond the cfg check).
+def session_plan(cfg: N.EncoderCfg) -> dict:
+    """xfmr_session_plan: what the attend kernel does for this cfg -- ``chunk`` (keys per online-softmax step of one wave),
+    ``lanes_per_key``, ``keys_per_load``, ``kv_bytes`` per element, ``bf16_storage``, ``max_len``. Touches no device; a cfg
+    the session entries refuse raises."""
+    out = (C.c_int32 * 8)()
+    N.check(N.load().xfmr_session_plan(C.byref(cfg), out), "xfmr_session_plan")
+    return dict(chunk=out[0], lanes_per_key=out[1], keys_per_load=out[2], kv_bytes=out[3], bf16_storage=bool(out[4]),
+                max_len=out[5])
+
+
+def session_state_bytes(cfg: N.EncoderCfg, n_slots: int) -> int:
+    """Bytes of the state buffer for ``n_slots`` sessions (0: the cfg is refused)."""
+    return int(N.load().xfmr_session_state_bytes(C.byref(cfg), int(n_slots)))
+
+
+def session_workspace_bytes(cfg: N.EncoderCfg, max_rows: int) -> int:
+    """Bytes of the scratch of one :func:`session_append` call of up to ``max_rows`` rows (0: refused)."""
+    return int(N.load().xfmr_session_workspace_bytes(C.byref(cfg), int(max_rows)))
+
+
+def session_init(cfg: N.EncoderCfg, flat_params, state, n_slots: int) -> None:
+    """xfmr_session_init: carve ``state`` (a uint8 device tensor), zero the mask bytes, convert the parameters (bf16
+    storage). Every slot is empty afterwards; call it again after the weights change."""
+    N.check(N.load().xfmr_session_init(C.byref(cfg), N.ptr(flat_params), N.ptr(state), state.numel(), int(n_slots),
+                                       N.stream()), "xfmr_session_init")
+
+
+def session_append(cfg: N.EncoderCfg, flat_params, state, n_slots: int, item_idx, row_slot, row_pos, table, workspace,
+                   *, want_tok: bool = True):
+    """xfmr_session_append: row r = item ``item_idx[r]`` (int64) at position ``row_pos[r]`` of slot ``row_slot[r]`` (int32
+    device tensors of one length). Returns the rows' last-layer outputs (n_rows, H), or None with ``want_tok=False``. A row
+    with a slot or position out of range stores nothing and comes back as a zero row; no (slot, position) pair twice."""
+    n = int(item_idx.numel())
+    assert item_idx.dtype == torch.int64 and row_slot.dtype == torch.int32 and row_pos.dtype == torch.int32
+    assert row_slot.numel() == n and row_pos.numel() == n
+    tok = _empty((n, cfg.hidden), flat_params) if want_tok else None
+    N.check(N.load().xfmr_session_append(C.byref(cfg), N.ptr(flat_params), N.ptr(state), state.numel(), int(n_slots),
+                                         N.ptr(item_idx), N.ptr(row_slot), N.ptr(row_pos), n, N.ptr(table), table.shape[0],
+                                         N.ptr(tok), N.ptr(workspace), workspace.numel(), N.stream()),
+            "xfmr_session_append")
+    return tok
+
+
+def session_pool(cfg: N.EncoderCfg, state, n_slots: int, slots, lens, mode: str = "mean", *, normalize: bool = False,
+                 eps: float = 1e-12):
+    """xfmr_session_pool: :func:`pool` (+ :func:`l2_normalize`) over the stored rows [0, lens[i]) of slot slots[i] (int32
+    device tensors). Returns (n, H); a length of 0 gives a zero row."""
+    n = int(slots.numel())
+    assert slots.dtype == torch.int32 and lens.dtype == torch.int32 and lens.numel() == n
+    out = torch.empty((n, cfg.hidden), dtype=f32, device=state.device)
+    N.check(N.load().xfmr_session_pool(C.byref(cfg), N.ptr(state), state.numel(), int(n_slots), N.ptr(slots), N.ptr(lens),
+                                       n, N.POOL_MODES[mode], int(bool(normalize)), float(eps), N.ptr(out), N.stream()),
+            "xfmr_session_pool")
+    return out
+
+
 last_encoder_grad_ptr = 0  # device address of the flat gradient buffer the last xfmr_encoder_bwd call wrote
 
 

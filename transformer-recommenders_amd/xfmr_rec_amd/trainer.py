@@ -417,6 +417,13 @@ class RecommenderLightningModule(_Base):
         hists = [list(r["history"]["item_id"]) for r in rows]
         return self.recommend_batch(hists, top_k=self.config.top_k, exclude_item_ids=hists)
 
+    def open_sessions(self, n_slots: int, **encoder_kw):
+        """A :class:`~xfmr_rec_amd.session.SessionRecommender` over this module's model and item index: sessions whose
+        histories grow by one event at a time are served from cached K / V instead of being re-encoded at every call."""
+        from .session import SessionRecommender
+
+        return SessionRecommender(self, n_slots, **encoder_kw)
+
     @torch.no_grad()
     def evaluate(self, rows, stage: str = "val", batch_size: int = 1024, cutoffs=None) -> dict[str, float]:
         """The epoch means of the seven retrieval metrics over ``rows`` (the reference's format: ``{"history":
