@@ -13,8 +13,10 @@ kernels to the same references through the same `check_*` helpers).
 * `check_*`: the assertions, with the project's tolerances (helpers.TOL["fp32"]: values 1e-4 scaled, gradients rel-L2
   1e-4) or torch.equal where the arithmetic is exact. They return the figures they measured.
 
-Row plans are restated from the launchers (`ln_bwd_plan` = ln_bwd_blocks, `colsum_plan`, `ln_form` = launch_ln_fwd): the
-case tables derive their row counts from them, and test_row_cases_host.py asserts what each count reaches."""
+`ln_form`, `ln_bwd_plan` and `colsum_plan` are the RULES of the row kernels' launch plan (csrc/row_plan.inc), written down
+from the launchers that plan replaced: test_row_plan_host.py holds the library's plan to them key by key, the GPU tests read
+the plan from the library and assert it equals them, the case tables derive their row counts from them, and
+test_row_cases_host.py asserts what each count reaches."""
 
 from __future__ import annotations
 
@@ -42,7 +44,7 @@ def _cdiv(a, b):
 
 # ------------------------------------------------------------------------------------------------ launch plans
 def ln_form(H: int, aligned: bool = True) -> str:
-    """The instantiation launch_ln_fwd / xf_layernorm_bwd_impl take: 'v4-16' / 'v4-32' / 'v4-64' at H = 64 / 128 / 256 with
+    """The instantiation row_plan takes for LayerNorm forward and backward: 'v4-16' / 'v4-32' / 'v4-64' at H = 64 / 128 / 256 with
     16-byte aligned pointers, else 'npl<N>' with N = the power of two >= ceil(H / 64); None above H = 1024 (refused)."""
     if aligned and H in (64, 128, 256):
         return f"v4-{H // 4}"
@@ -54,7 +56,7 @@ def ln_form(H: int, aligned: bool = True) -> str:
 
 
 def ln_bwd_plan(rows: int, H: int):
-    """(blocks, rows_per_block) of ln_bwd_blocks: one workgroup iteration (16 / 8 / 4 rows at H = 64 / 128 / other) per
+    """(records, rows_per_block) of row_plan for the LayerNorm backward: one workgroup iteration (16 / 8 / 4 rows at H = 64 / 128 / other) per
     block below 4 096 rows, 16 rows below 16 384, 32 from there; at most 1 024 blocks; whole iterations per block."""
     it = 16 if H == 64 else 8 if H == 128 else 4
     per = 32 if rows >= 16384 else 16 if rows >= 4096 else it
@@ -64,7 +66,7 @@ def ln_bwd_plan(rows: int, H: int):
 
 
 def colsum_plan(M: int):
-    """(blocks, rows_per) of gemm.hip's colsum_plan: 256 rows per block, at most 128 blocks, rows_per a multiple of 4."""
+    """(records, rows_per_block) of row_plan for the column sums: 256 rows per block, at most 128 blocks, rows_per a multiple of 4."""
     blocks = min(max(_cdiv(M, 256), 1), 128)
     rp = _cdiv(_cdiv(M, blocks), 4) * 4
     return _cdiv(M, rp), rp
@@ -211,7 +213,7 @@ def model_ln_bwd(dy, x, mean, rstd, gamma, form="npl", mutant=None, keep_scale=N
     return dx, red[0], red[1], red[2], (None if keep_scale is None else d_lin)
 
 
-# widths by instantiation (launch_ln_fwd / xf_layernorm_bwd_impl); 1025 and 2048 are refused
+# widths by instantiation (row_plan); 1025 and 2048 are refused
 LN_WIDTHS = (1, 48, 63, 65, 100, 129, 192, 255, 320, 384, 512, 768, 1000, 1024, 64, 128, 256)
 LN_REFUSED = (1025, 2048)
 LN_ROWS = (1, 3, 77)  # one wave of a workgroup, three of four, twenty workgroups with the last one partial
@@ -561,7 +563,7 @@ def check_scale(x, f, got):
     assert torch.equal(got[ok].view(torch.int32), want[ok].view(torch.int32)), f"scale n={x.numel()} f={f}: product differs"
 
 
-COLSUM_M = (1, 3, 255, 256, 257, 1000, 33000)  # 33 000 > 128 * 256: colsum_plan's block cap, 260 rows per block, last partial
+COLSUM_M = (1, 3, 255, 256, 257, 1000, 33000)  # 33 000 > 128 * 256: the column sums' block cap, 260 rows per block, last partial
 COLSUM_N = (1, 64, 96, 100)
 COLSUM_BIG_N = 96
 

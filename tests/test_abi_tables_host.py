@@ -172,7 +172,7 @@ def struct_problems(structure, c_name):
 
 # ---------------------------------------------------------------------------------------------- the tests
 def test_the_parser_reads_every_form_the_headers_use():
-    assert len(PUBLIC_PROTOS) == 90 and len(INTERNAL_PROTOS) == 39
+    assert len(PUBLIC_PROTOS) == 90 and len(INTERNAL_PROTOS) == 40
     assert PUBLIC_PROTOS["xfmr_abi_version"] == ("i32", [])  # (void)
     assert PUBLIC_PROTOS["xfmr_strerror"] == ("ptr", ["i32"]) and PUBLIC_PROTOS["xfmr_lr_lambda"][0] == "f32"
     assert INTERNAL_PROTOS["xf_gemm_switches"] == ("void", ["ptr"])  # int32_t sw[16]
@@ -181,6 +181,7 @@ def test_the_parser_reads_every_form_the_headers_use():
     assert INTERNAL_PROTOS["xf_linear_bwd_dx_lnbwd_ex"][1][-2:] == ["f32", "u32"]  # = 0.f, = 0
     assert INTERNAL_PROTOS["xf_layernorm_bwd_impl"][1].count("other:XfDropout") == 2
     assert "gemm_plan" not in INTERNAL_PROTOS and "gemm_switches" not in INTERNAL_PROTOS  # C++ linkage, no xf_ name
+    assert "row_plan" not in INTERNAL_PROTOS and INTERNAL_PROTOS["xf_row_plan"] == ("i32", ["i32", "i64", "i32", "i32", "i32", "ptr"])
     assert ("profile_events", "ptr", 2) in C_STRUCTS["xfmr_encoder_cfg"] and ("pad", "u32", 3) in C_STRUCTS["xfmr_opt_ctl"]
     assert C_STRUCTS["XfDwItem"][2:4] == [("N", "i32", 0), ("K", "i32", 0)]  # int32_t N, K; on a line of several
     assert C_STRUCTS["xfmr_opt_cfg"][:2] == [("lr", "f32", 0), ("beta1", "f32", 0)]
@@ -213,7 +214,7 @@ def test_what_python_calls_is_defined_with_c_linkage_and_declared():
     for src in sorted(CSRC.glob("*.hip")):
         defined |= set(re.findall(r"^[\w\*]+[\s\*]+(xf_\w+)\s*\([^;{}()]*\)\s*\{", extern_c(clean(src.read_text())), re.M))
     called = set(_abi.INTERNAL_SIGNATURES)
-    assert len(called) == 37 and called <= defined, sorted(called - defined)
+    assert len(called) == 38 and called <= defined, sorted(called - defined)
     assert defined <= set(INTERNAL_PROTOS), sorted(defined - set(INTERNAL_PROTOS))
 
 

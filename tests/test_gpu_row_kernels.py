@@ -8,16 +8,22 @@ Every case runs twice and must be bit-equal: once through the C entry with every
 over-allocated by GUARD rows (which must still be NaN afterwards), once through the xfmr_rec_amd.ops wrapper where there
 is one. Values are held to helpers.TOL["fp32"] (1e-4 scaled / rel-L2 1e-4), exact arithmetic to torch.equal.
 
-Where the row counts come from (restated plans: row_cases.ln_form / ln_bwd_plan / colsum_plan):
-* launch_ln_fwd: one wave per row, four per workgroup -> rows 1, 3, 77; the float4 kernels hold 256 / H rows per wave ->
+The instantiation a case runs, its partial records and its rows per block are read from the library (xf_row_plan: the plan
+the launchers themselves read) -- the test ids are built from them -- and every case asserts that they are what the rules of
+row_cases.ln_form / ln_bwd_plan / colsum_plan say, the rules tests/test_row_plan_host.py holds the whole plan to. The record
+tests tie the plan to the run: a NaN-filled workspace of the size query's bytes plus a guard holds exactly `records` finite
+records afterwards.
+
+Where the row counts come from:
+* LayerNorm forward: one wave per row, four per workgroup -> rows 1, 3, 77; the float4 kernels hold 256 / H rows per wave ->
   one row below, at and above a workgroup's 16 / 8 / 4 rows at H = 64 / 128 / 256. Widths: two or three per instantiation,
   its first and last width among them; 1025 and 2048 are refused.
-* ln_bwd_blocks: 4 095 | 4 096 rows (one iteration -> 16 rows per block), 16 383 | 16 384 (16 -> 32), 33 001 (1 032 blocks
+* LayerNorm backward row map: 4 095 | 4 096 rows (one iteration -> 16 rows per block), 16 383 | 16 384 (16 -> 32), 33 001 (1 032 blocks
   asked, capped at 1 024, rows per block rounded to whole iterations, the last block partial).
 * ln_bwd_reduce_kernel: its unrolled loop needs 49 records (b + 48 < blocks): 49, 50, 64, 65 and 113 records from 196, 200,
   256, 260 and 452 rows at four rows per record.
 * rowsum_kernel: its unrolled loop needs 13 rows (r + 12 < rows): B = 17, 33, 130 for d_pos, L = 13, 29 for d_type.
-* colsum_plan: 256 rows per block (255 | 256 | 257), at most 128 blocks (33 000 rows -> 127 blocks of 260, the last partial).
+* column sums: 256 rows per block (255 | 256 | 257), at most 128 blocks (33 000 rows -> 127 blocks of 260, the last partial).
 * pos_grad_packed_kernel: 16 waves x 8 sequences per trip -> B = 16 | 17 and 128 | 129, 300 for a third trip; H = 1024 asks
   for exactly 64 KiB of dynamic LDS."""
 
@@ -49,6 +55,41 @@ def N():
 
     _native.load()
     return _native
+
+
+LN_FWD, GATHER_LN_FWD, LN_BWD, COLSUM = range(4)  # internal.h RowOp
+
+
+def _plan(op, rows, H, keep=1, aligned=1):
+    """xf_row_plan's answer for a key: (form name as row_cases.ln_form writes it, grid, rows_per_block, records, room)."""
+    import ctypes
+
+    from xfmr_rec_amd import _native
+
+    out = (ctypes.c_int32 * 12)()
+    rc = _native.load().xf_row_plan(op, rows, H, keep, int(aligned), out)
+    form = None if rc else f"v4-{out[1]}" if out[0] == 2 else f"npl{out[1]}"
+    return form, out[2], out[5], out[6], out[7]
+
+
+def _form(H, aligned=True, op=LN_FWD):
+    """The instantiation the library takes at width H (the test ids), held to the rule."""
+    form = _plan(op, 77, H, 1, aligned)[0]
+    assert form == RC.ln_form(H, aligned) == _plan(LN_BWD, 77, H, 1, aligned)[0], (H, aligned, form)
+    return form
+
+
+def _nan_ws(nbytes):
+    """A float workspace of nbytes plus GUARD * 256 floats, all NaN."""
+    assert nbytes % 4 == 0
+    return torch.full((nbytes // 4 + GUARD * 256,), NAN, device=DEV)
+
+
+def _finite_prefix(ws, n, what):
+    """Exactly the first n floats of a NaN-filled workspace were written."""
+    torch.cuda.synchronize()
+    assert bool(ws[:n].isfinite().all()), f"{what}: fewer than {n} floats written"
+    assert bool(ws[n:].isnan().all()), f"{what}: wrote past its {n} floats"
 
 
 def _put(t, off=0):
@@ -89,7 +130,7 @@ def _worst(into, figs):
 
 
 # ---------------------------------------------------------------------------------------------------- LayerNorm
-def _ln_direct(N, case, off=0, p=0.0, seed=0, site=0):
+def _ln_direct(N, case, off=0, p=0.0, seed=0, site=0, ws=None):
     lib, st, rows, H = N.load(), N.stream(), case.rows, case.H
     x, gamma, beta, dy = (_put(t, off) for t in (case.x, case.gamma, case.beta, case.dy))
     y, mean, rstd = _out(rows, H, off), _out(rows), _out(rows)
@@ -97,7 +138,8 @@ def _ln_direct(N, case, off=0, p=0.0, seed=0, site=0):
                                    RC.LN_EPS, st), "xfmr_layernorm_fwd")
     dx, d_lin = _out(rows, H, off), (_out(rows, H, off) if p > 0 else None)
     dg, db, dbias = _out(1, H), _out(1, H), _out(1, H)
-    ws = torch.empty(max(lib.xfmr_layernorm_bwd_workspace(rows, H), 16), dtype=torch.uint8, device=DEV)
+    if ws is None:
+        ws = torch.empty(max(lib.xfmr_layernorm_bwd_workspace(rows, H), 16), dtype=torch.uint8, device=DEV)
     N.check(lib.xfmr_layernorm_bwd(N.ptr(dy), N.ptr(x), N.ptr(mean), N.ptr(rstd), N.ptr(gamma), N.ptr(dx), N.ptr(d_lin),
                                    N.ptr(dg), N.ptr(db), N.ptr(dbias), rows, H, p, seed, site, N.ptr(ws), st),
             "xfmr_layernorm_bwd")
@@ -120,44 +162,60 @@ def _ln_twice(N, ops, case, off=0):
     return RC.check_ln(case, got)
 
 
-@pytest.mark.parametrize("H", RC.LN_WIDTHS, ids=[f"{RC.ln_form(H)}-H{H}" for H in RC.LN_WIDTHS])
+@pytest.mark.parametrize("H", RC.LN_WIDTHS, ids=[f"{_form(H)}-H{H}" for H in RC.LN_WIDTHS])
 def test_layernorm_every_instantiation(N, ops, H):
     worst = {}
     for rows in RC.LN_ROWS + RC.LN_V4_EDGE_ROWS.get(H, ()):
         _worst(worst, _ln_twice(N, ops, RC.ln_case(H, rows)))
-    _fig(f"ln {RC.ln_form(H)} H={H}", worst)
+    _fig(f"ln {_form(H)} H={H}", worst)
 
 
-@pytest.mark.parametrize("H", RC.LN_OFFSET_WIDTHS, ids=[f"{RC.ln_form(H)}-H{H}" for H in RC.LN_OFFSET_WIDTHS])
+@pytest.mark.parametrize("H", RC.LN_OFFSET_WIDTHS, ids=[f"{_form(H)}-H{H}" for H in RC.LN_OFFSET_WIDTHS])
 def test_layernorm_offset_rows_need_a_two_pass_variance(N, ops, H):
     """x = 30 + 0.3 N(0,1): E[x^2] - mean^2 in fp32 errs by >= 9.7e-4 here, a two-pass variance by <= 1.9e-5."""
-    _fig(f"ln-offset {RC.ln_form(H)} H={H}", _ln_twice(N, ops, RC.ln_case(H, 77, "offset")))
+    _fig(f"ln-offset {_form(H)} H={H}", _ln_twice(N, ops, RC.ln_case(H, 77, "offset")))
 
 
-@pytest.mark.parametrize("H", [64, 128, 256], ids=lambda H: f"{RC.ln_form(H, aligned=False)}-H{H}-unaligned")
+@pytest.mark.parametrize("H", [64, 128, 256], ids=lambda H: f"{_form(H, aligned=False)}-H{H}-unaligned")
 def test_layernorm_unaligned_pointers_take_the_generic_kernel(N, ops, H):
     """Every fp32 tensor one float into its allocation: the float4 kernels would fault or read shifted rows; the launchers
     take ln_fwd_kernel / ln_bwd_kernel <1 | 2 | 4> instead (same row plan)."""
     worst = {}
     for rows in RC.LN_ROWS + RC.LN_V4_EDGE_ROWS[H]:
         _worst(worst, _ln_twice(N, ops, RC.ln_case(H, rows), off=1))
-    _fig(f"ln-unaligned {RC.ln_form(H, aligned=False)} H={H}", worst)
+    _fig(f"ln-unaligned {_form(H, aligned=False)} H={H}", worst)
 
 
 @pytest.mark.parametrize("rows", RC.LN_PLAN_ROWS)
-@pytest.mark.parametrize("H", RC.LN_PLAN_WIDTHS, ids=lambda H: f"{RC.ln_form(H)}-H{H}")
+@pytest.mark.parametrize("H", RC.LN_PLAN_WIDTHS, ids=lambda H: f"{_form(H)}-H{H}")
 def test_layernorm_backward_row_plans(N, ops, H, rows):
-    blocks, rpb = RC.ln_bwd_plan(rows, H)
-    _fig(f"ln-plan {RC.ln_form(H)} H={H} rows={rows} blocks={blocks} rows_per_block={rpb}", _ln_twice(N, ops, RC.ln_case(H, rows)))
+    _, grid, rpb, blocks, room = _plan(LN_BWD, rows, H)
+    assert (blocks, rpb) == RC.ln_bwd_plan(rows, H) and grid == blocks <= room
+    _fig(f"ln-plan {_form(H)} H={H} rows={rows} blocks={blocks} rows_per_block={rpb}", _ln_twice(N, ops, RC.ln_case(H, rows)))
 
 
-@pytest.mark.parametrize("H,rows,records", RC.LN_RECORD_CASES, ids=[f"records{r}-H{H}" for H, _, r in RC.LN_RECORD_CASES])
+LN_THRESHOLD_RECORD_CASES = tuple((H, rows, _plan(LN_BWD, rows, H)[3]) for H in RC.LN_PLAN_WIDTHS for rows in (4095, 4096))
+
+
+@pytest.mark.parametrize("H,rows,records", RC.LN_RECORD_CASES + LN_THRESHOLD_RECORD_CASES,
+                         ids=[f"records{r}-H{H}" for H, _, r in RC.LN_RECORD_CASES]
+                         + [f"records{r}-H{H}-rows{rows}" for H, rows, r in LN_THRESHOLD_RECORD_CASES])
 def test_layernorm_backward_partial_record_counts(N, ops, H, rows, records):
+    """The plan tied to the run: the partials workspace, sized by xfmr_layernorm_bwd_workspace plus a guard and filled with NaN,
+    holds exactly the plan's `records` records of 3 x H finite floats after the backward."""
     assert RC.ln_bwd_plan(rows, H)[0] == records
-    _fig(f"ln-records {records} H={H} rows={rows}", _ln_twice(N, ops, RC.ln_case(H, rows)))
+    _, _, rpb, plan_records, room = _plan(LN_BWD, rows, H)
+    assert (plan_records, rpb) == RC.ln_bwd_plan(rows, H) and plan_records == records <= room
+    nbytes = N.load().xfmr_layernorm_bwd_workspace(rows, H)
+    assert nbytes == room * 3 * H * 4
+    ws = _nan_ws(nbytes)
+    got = _ln_direct(N, RC.ln_case(H, rows), ws=ws)
+    _finite_prefix(ws, records * 3 * H, f"ln partials H={H} rows={rows}")
+    _same(got, _ln_ops(ops, RC.ln_case(H, rows)), f"ln H={H} rows={rows}")
+    _fig(f"ln-records {records} H={H} rows={rows}", RC.check_ln(RC.ln_case(H, rows), got))
 
 
-@pytest.mark.parametrize("H", [64, 96], ids=lambda H: f"{RC.ln_form(H)}-H{H}")
+@pytest.mark.parametrize("H", [64, 96], ids=lambda H: f"{_form(H)}-H{H}")
 def test_layernorm_backward_linear_output_dropout(N, ops, H):
     """d_lin = dx * keep / (1 - p) with the host model's mask of (seed, site); d_bias = the column sums of d_lin."""
     case, p, seed, site = RC.ln_case(H, 77), 0.25, 7, 3
@@ -169,7 +227,7 @@ def test_layernorm_backward_linear_output_dropout(N, ops, H):
     assert torch.equal(got["d_lin"].cpu() == 0, (ks == 0) | (dx64 == 0)), "d_lin: not the host model's mask"
     figs["d_lin"] = assert_close("ln.d_lin", got["d_lin"], case.ref["dx"] * ks, "fp32", "grad")
     figs["d_bias"] = assert_close("ln.d_bias", got["d_bias"], (case.ref["dx"] * ks).sum(0), "fp32", "grad")
-    _fig(f"ln-dropout {RC.ln_form(H)} H={H}", figs)
+    _fig(f"ln-dropout {_form(H)} H={H}", figs)
 
 
 @pytest.mark.parametrize("H", RC.LN_REFUSED)
@@ -190,7 +248,7 @@ def test_layernorm_refuses_widths_above_1024_and_writes_nothing(N, H):
         assert bool(t.isnan().all())
 
 
-@pytest.mark.parametrize("H", [64, 100], ids=lambda H: f"{RC.ln_form(H)}-H{H}")
+@pytest.mark.parametrize("H", [64, 100], ids=lambda H: f"{_form(H)}-H{H}")
 def test_layernorm_forward_only_and_bf16_copy_forms(N, H):
     """xf_layernorm_fwd_ex (extern "C", not in include/xfmr_hip.h; exported by the built library): with mean = rstd = NULL
     the forward-only instantiation, y bit-equal to the training form's; with y16 the bf16 copy = y.to(bfloat16) bit for bit."""
@@ -239,7 +297,7 @@ def _embed_ops(ops, case, **kw):
     return dict(out=out, pre=pre, mean=mean, rstd=rstd, mask=mask)
 
 
-@pytest.mark.parametrize("H", RC.EMBED_WIDTHS, ids=[f"{RC.ln_form(H)}-H{H}" for H in RC.EMBED_WIDTHS])
+@pytest.mark.parametrize("H", RC.EMBED_WIDTHS, ids=[f"{_form(H, op=GATHER_LN_FWD)}-H{H}" for H in RC.EMBED_WIDTHS])
 def test_embedding_gather_layernorm(N, ops, H):
     """pre and the key mask exact; an index outside [0, n_rows) -- n_rows, n_rows + 5, -1, -2^40 -- reads row 0 and is masked;
     a non-padding all-zero row is masked; L < max_pos. With dropout: the undropped fp64 output times the host model's mask."""
@@ -256,7 +314,7 @@ def test_embedding_gather_layernorm(N, ops, H):
         ks = RC.keep_scale(seed, 0, B * L, H, p).view(B, L, H)
         assert torch.equal(got["out"].cpu() == 0, ks == 0), "embed dropout: not the host model's mask"
         worst["out_dropout"] = max(worst.get("out_dropout", 0.0), RC.check_embed(case, got, keep_scale=ks)["out"])
-    _fig(f"embed {RC.ln_form(H)} H={H}", worst)
+    _fig(f"embed {_form(H, op=GATHER_LN_FWD)} H={H}", worst)
 
 
 # ---------------------------------------------------------------------------------------------------- d_pos / d_type
@@ -393,9 +451,16 @@ def test_scale_by_device_scalar(N, n, off):
 def test_colsum(N, ops, M, Nc):
     lib, st = N.load(), N.stream()
     case = RC.colsum_case(M, Nc)
+    """Against fp64, and the plan tied to the run: the workspace, sized by xfmr_colsum_workspace plus a guard and filled with
+    NaN, holds exactly the plan's `blocks` records of N finite floats afterwards."""
     a, out = _put(case.a), _out(1, Nc)
-    ws = torch.empty(max(lib.xfmr_colsum_workspace(M, Nc), 16), dtype=torch.uint8, device=DEV)
+    _, grid, rows_per, blocks, room = _plan(COLSUM, M, Nc)
+    assert (blocks, rows_per) == RC.colsum_plan(M) and blocks <= room and grid == blocks * -(-Nc // 64)
+    nbytes = lib.xfmr_colsum_workspace(M, Nc)
+    assert nbytes == room * Nc * 4
+    ws = _nan_ws(nbytes)
     N.check(lib.xfmr_colsum(N.ptr(a), N.ptr(out), M, Nc, N.ptr(ws), st), "xfmr_colsum")
+    _finite_prefix(ws, blocks * Nc, f"colsum partials M={M} N={Nc}")
     got = _used(out, 1, "colsum")[0]
     assert torch.equal(got, ops.colsum(a)), "colsum: two runs differ"
-    _fig(f"colsum M={M} N={Nc} blocks={RC.colsum_plan(M)[0]}", dict(sum=RC.check_colsum(case, got)))
+    _fig(f"colsum M={M} N={Nc} blocks={blocks}", dict(sum=RC.check_colsum(case, got)))

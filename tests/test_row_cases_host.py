@@ -3,7 +3,8 @@ test_gpu_row_kernels.py uses,
   (a) the fp32 model of every family passes every case of its table, and on the LayerNorm offset case with a margin:
       its error stays <= 1/4 of the tolerance (a width that breaks this gets a smaller offset, never a wider tolerance);
   (b) every mutant of row_cases.MUTANTS fails on a case this file names;
-  (c) the row counts reach the plans, record counts and loop trips they are chosen for (restated launch plans)."""
+  (c) the row counts reach the plans, record counts and loop trips they are chosen for (by row_cases' plan rules, which
+      test_row_plan_host.py holds the library to)."""
 
 import pytest
 import torch

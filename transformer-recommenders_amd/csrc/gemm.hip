@@ -1991,27 +1991,18 @@ int xfmr_linear_bwd_dw(const float* dy, const float* x, float* dw, int64_t M, in
   return xf_linear_bwd_dw_ex(dy, x, dw, M, N, K, precision, workspace, workspace_bytes, 0, (hipStream_t)stream);
 }
 
-static int colsum_plan(int64_t M, int* rows_per) {
-  int64_t blocks = (M + 255) / 256;
-  if (blocks > 128) blocks = 128;
-  if (blocks < 1) blocks = 1;
-  int64_t rp = (M + blocks - 1) / blocks;
-  rp = ((rp + 3) / 4) * 4;
-  *rows_per = (int)rp;
-  return (int)((M + rp - 1) / rp);
-}
-size_t xfmr_colsum_workspace(int64_t M, int32_t N) {
-  int rows_per;
-  return (size_t)colsum_plan(M, &rows_per) * (size_t)N * sizeof(float);
+// the column sums' plan is the row kernels' (norm.hip row_plan): records of rows_per_block rows each, then their sum
+size_t xfmr_colsum_workspace(int64_t M, int32_t N) {  // enough for every row count <= M
+  return (size_t)row_plan(RowKey{kRowColsum, M, N, 0, 0}).room * (size_t)N * sizeof(float);
 }
 int xf_colsum_ex(const void* a, bool a16, float* out, int64_t M, int32_t N, void* workspace, hipStream_t st) {
-  if (!a || !out || !workspace || M <= 0 || N <= 0) return XFMR_EINVAL;
-  int rows_per;
-  const int blocks = colsum_plan(M, &rows_per);
-  int rc = a16 ? launch_rowsum((float*)workspace, (const __bf16*)a, M, N, rows_per, st)
-               : launch_rowsum((float*)workspace, (const float*)a, M, N, rows_per, st);
+  if (!a || !out || !workspace) return XFMR_EINVAL;
+  const RowPlan p = row_plan(RowKey{kRowColsum, M, N, 0, 0});
+  if (p.rc) return p.rc;
+  int rc = a16 ? launch_rowsum((float*)workspace, (const __bf16*)a, M, N, p.rows_per_block, st)
+               : launch_rowsum((float*)workspace, (const float*)a, M, N, p.rows_per_block, st);
   if (rc) return rc;
-  return launch_rowsum(out, (const float*)workspace, blocks, N, blocks, st);
+  return launch_rowsum(out, (const float*)workspace, p.records, N, p.records, st);
 }
 int xfmr_colsum(const float* a, float* out, int64_t M, int32_t N, void* workspace, void* stream) {
   return xf_colsum_ex(a, false, out, M, N, workspace, (hipStream_t)stream);

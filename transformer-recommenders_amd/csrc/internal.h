@@ -81,7 +81,37 @@ constexpr int kDwRingTile = 128;                  // tile width in features, bot
 constexpr uint64_t kDwRingOffsetLimit = 1ull << 32;  // the gather's byte offsets into an operand are 32-bit
 constexpr int kDwRingLds = 2 * XF_DWR_NST * XF_DWR_RT * kDwRingTile * 2;  // dy and x images of every stage, bf16: 128 KB
 
+// ---- norm.hip (row_plan.inc): the plan of one call of the row kernels -- LayerNorm forward, gather + LayerNorm forward,
+// LayerNorm backward, the two-level column sum (xf_colsum_ex) -- as ONE pure function of the call's key (DESIGN.md section 4;
+// tests/test_row_plan_host.py walks the table without a GPU).
+enum RowOp : int32_t { kRowLnFwd = 0, kRowGatherLnFwd, kRowLnBwd, kRowColsum, kRowOps };
+enum RowForm : int32_t {
+  kRowNone = 0,  // nothing is launched: the call is refused (RowPlan::rc)
+  kRowGeneric,   // ln_fwd[_infer]_kernel / ln_bwd_kernel <NPL>: one wave per row, NPL columns per lane; colsum: rowsum_kernel
+  kRowFloat4,    // ln_fwd_v4[_infer]_kernel / ln_bwd_v4_kernel <LPR>: H = 4 * LPR, LPR lanes per row, 16 bytes per lane
+};
+struct RowKey {
+  RowOp op;
+  int64_t rows;
+  int32_t H;        // row width (colsum: the columns N)
+  int32_t keep;     // forward: pre / mean / rstd are stored for a backward
+  int32_t aligned;  // every pointer the float4 kernels touch is aligned for them: the entry looks at its pointers, the plan does not
+};
+struct RowPlan {
+  int32_t rc;                 // what the call returns for this key: XFMR_EINVAL, XFMR_EUNSUPPORTED (H > 1024) or XFMR_OK
+  int32_t form, width;        // RowForm; NPL | LPR (colsum: columns per workgroup)
+  int32_t grid, block, lds;   // workgroups (colsum: of the first level), threads, dynamic LDS bytes
+  int32_t rows_per_block;
+  int32_t records;            // partial records this launch writes (LayerNorm backward: *blocks_out; forward: none)
+  int32_t room;               // the most records ANY row count <= rows writes: what the two workspace queries size for
+  const void* kernel;         // the LayerNorm instantiation (colsum: rowsum_kernel by element type, gemm.hip)
+};
+RowPlan row_plan(const RowKey& k);
+
 extern "C" {
+// The row plan as integers. out: form, width, grid, block, lds, rows_per_block, records, room, then zeros (all zeros when
+// refused). Returns RowPlan::rc; touches no device.
+int xf_row_plan(int32_t op, int64_t rows, int32_t H, int32_t keep, int32_t aligned, int32_t out[12]);
 // The plan and the switches as integers. out: family, epi, precision, s16, bm, bn, bk, splits, k_chunk, nt_n, nt_m, nt_z,
 // nt_full, short_rows, grid, block, lds, ffn_chunk, ffn_ring, records, then zeros (all zeros when refused); sw: the fields
 // of GemmSwitches in their order. Returns GemmPlan::rc; touches no device.

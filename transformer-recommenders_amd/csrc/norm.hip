@@ -1,12 +1,15 @@
-// HBM-bound row kernels: item-embedding gather + BertEmbeddings LayerNorm, LayerNorm fwd/bwd,
-// embedding-parameter gradients, masked mean pooling, AdamW, per-item inverse norms.
-// One wavefront owns one row (H <= 1024): lanes stride the row in 4-byte steps, so every wave
-// instruction touches 256 contiguous bytes; row statistics are wave reductions, never LDS.
+// HBM-bound row kernels and their host path.
+//   kernels: LayerNorm forward (plain, or fused with the item-embedding gather of BertEmbeddings) and backward, each as a
+//     generic form (one wave per row, H <= 1024, lanes stride the row in 4-byte steps) and a float4 form (H = 64 / 128 / 256);
+//     the reduction of the backward's partial records; embedding-parameter gradients (padded and packed) and the row packer;
+//     pooling over padded rows, packed rows and the session store; L2 normalisation forward / backward; AdamW, the
+//     device-scalar scale and the per-item inverse norms. Row statistics are wave reductions, never LDS.
+//   row_plan.inc: the plan of a LayerNorm or column-sum call -- form, grid, partial records and record room -- which the
+//     LayerNorm entries below, the two workspace queries and gemm.hip's xf_colsum_ex read.
+//   entries: one per public or internal operator; those with one wave per row launch through launch_wave_per_row.
 #include <stdlib.h>
 
 #include "internal.h"
-
-// single-level deterministic column sum dst[c] = sum_r src[r*cols + c] (gemm.hip)
 
 namespace {
 
@@ -373,7 +376,9 @@ __global__ void embed_type_grad_kernel(const float* d_pos, float* d_type, int L,
 //   max:       max_t (m ? tok : -1e9)
 //   cls:       tok[0]
 //   lasttoken: tok[last t with m != 0] (t = 0 when the row has none), times its mask value
-// One column of one sequence: x = the column's first element (rows H apart), m = the sequence's L mask bytes.
+// One column of one sequence: x = the column's first element (rows H apart), m = the sequence's L mask bytes. MASKED = false
+// (the packed layout): m is not read, every row counts.
+template <bool MASKED = true>
 __device__ __forceinline__ float pool_column(const float* x, const uint8_t* m, int L, int H, int mode) {
   float r;
   if (mode == XFMR_POOL_MEAN) {
@@ -382,24 +387,38 @@ __device__ __forceinline__ float pool_column(const float* x, const uint8_t* m, i
     //  load measured 168 us for 1 024 sessions of 200 rows, each lane waiting out a memory latency per row.)
 #pragma unroll 16
     for (int t = 0; t < L; ++t) {
-      const float w = m[t] ? 1.f : 0.f;
+      const float w = (!MASKED || m[t]) ? 1.f : 0.f;
       s += x[(int64_t)t * H] * w;
       n += w;
     }
     r = s / fmaxf(n, 1e-9f);
   } else if (mode == XFMR_POOL_MAX) {
     r = -INFINITY;
-    for (int t = 0; t < L; ++t) r = fmaxf(r, m[t] ? x[(int64_t)t * H] : -1e9f);
+    for (int t = 0; t < L; ++t) r = fmaxf(r, (!MASKED || m[t]) ? x[(int64_t)t * H] : -1e9f);
   } else if (mode == XFMR_POOL_CLS) {
     r = x[0];
   } else {
-    int last = -1;
-    for (int t = 0; t < L; ++t)
-      if (m[t]) last = t;
+    int last = MASKED ? -1 : L - 1;
+    if constexpr (MASKED)
+      for (int t = 0; t < L; ++t)
+        if (m[t]) last = t;
     r = last >= 0 ? x[(int64_t)last * H] : 0.f;
   }
   return r;
 }
+// y = x / max(|x|, eps) for the row the wave owns (lane c: columns c, c + 64, ...; y may be x); returns 1 / max(|x|, eps)
+__device__ __forceinline__ float l2_scale_row(const float* x, float* y, int H, int lane, float eps) {
+  float s = 0.f;
+  for (int c = lane; c < H; c += 64) {
+    const float v = x[c];
+    s += v * v;
+  }
+  s = xf_wave_sum(s);
+  const float inv = 1.f / fmaxf(sqrtf(s), eps);
+  for (int c = lane; c < H; c += 64) y[c] = x[c] * inv;
+  return inv;
+}
+
 __global__ void pool_kernel(const float* tok, const uint8_t* mask, float* out, int L, int H, int mode) {
   const int b = blockIdx.y;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -423,15 +442,7 @@ __global__ __launch_bounds__(256) void pool_slots_kernel(const float* tok, const
   float* o = out + (int64_t)i * H;
   for (int c = lane; c < H; c += 64)
     o[c] = empty ? 0.f : pool_column(tok + (int64_t)slot * max_len * H + c, mask + (int64_t)slot * max_len, len, H, mode);
-  if (!normalize) return;
-  float s = 0.f;
-  for (int c = lane; c < H; c += 64) {
-    const float v = o[c];
-    s += v * v;
-  }
-  s = xf_wave_sum(s);
-  const float inv = 1.f / fmaxf(sqrtf(s), eps);
-  for (int c = lane; c < H; c += 64) o[c] = o[c] * inv;
+  if (normalize) l2_scale_row(o, o, H, lane, eps);
 }
 
 // pool_kernel over the packed layout (sequence b = rows [off[b], off[b+1]) of tok), with the row normalisation of
@@ -446,37 +457,8 @@ __global__ __launch_bounds__(256) void pool_rows_kernel(const float* tok, const 
   const int64_t r0 = off[b];
   const int n = off[b + 1] - off[b];
   float* o = out + (int64_t)b * H;
-  for (int c = lane; c < H; c += 64) {
-    const float* x = tok + r0 * H + c;
-    float r = 0.f;
-    if (n <= 0) {
-      r = 0.f;
-    } else if (mode == XFMR_POOL_MEAN) {
-      float s = 0.f, cnt = 0.f;
-      for (int t = 0; t < n; ++t) {
-        s += x[(int64_t)t * H];
-        cnt += 1.f;
-      }
-      r = s / fmaxf(cnt, 1e-9f);
-    } else if (mode == XFMR_POOL_MAX) {
-      r = -INFINITY;
-      for (int t = 0; t < n; ++t) r = fmaxf(r, x[(int64_t)t * H]);
-    } else if (mode == XFMR_POOL_CLS) {
-      r = x[0];
-    } else {
-      r = x[(int64_t)(n - 1) * H];
-    }
-    o[c] = r;
-  }
-  if (!normalize) return;
-  float s = 0.f;
-  for (int c = lane; c < H; c += 64) {
-    const float v = o[c];
-    s += v * v;
-  }
-  s = xf_wave_sum(s);
-  const float inv = 1.f / fmaxf(sqrtf(s), eps);
-  for (int c = lane; c < H; c += 64) o[c] = o[c] * inv;
+  for (int c = lane; c < H; c += 64) o[c] = n <= 0 ? 0.f : pool_column<false>(tok + r0 * H + c, nullptr, n, H, mode);
+  if (normalize) l2_scale_row(o, o, H, lane, eps);
 }
 
 // y = x / max(|x|, eps) per row (torch.nn.functional.normalize, models.py:393-394; sentence-transformers
@@ -486,14 +468,7 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* x, float* 
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  float s = 0.f;
-  for (int c = lane; c < H; c += 64) {
-    const float v = x[row * H + c];
-    s += v * v;
-  }
-  s = xf_wave_sum(s);
-  const float inv = 1.f / fmaxf(sqrtf(s), eps);
-  for (int c = lane; c < H; c += 64) y[row * H + c] = x[row * H + c] * inv;
+  const float inv = l2_scale_row(x + row * H, y + row * H, H, lane, eps);
   if (lane == 0 && inv_norm) inv_norm[row] = inv;
 }
 // dx = inv * (dy - y (y . dy)); with the norm clamped at eps the map is linear: dx = dy / eps
@@ -579,8 +554,6 @@ __global__ void table_rnorm_kernel(const float* table, float* out, int64_t rows,
   if (lane == 0) out[row] = 1.f / fmaxf(sqrtf(s), 1e-8f);
 }
 
-int npl_of(int H) { return (H + 63) / 64; }
-
 // The *_v4 kernels move 16 bytes per lane (8 into a bf16 copy): they are taken only when every pointer they touch that way
 // is aligned for it (a null one is never touched). Otherwise the generic kernel of the same width runs: NPL = 1 / 2 / 4.
 bool xf_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
@@ -593,66 +566,28 @@ bool ln_bwd_v4_aligned(const LnBwdArgs& a) {
          (a.lin16 ? xf_aligned8(a.d_lin) : xf_aligned16(a.d_lin));
 }
 
-template <bool GATHER>
-int launch_ln_fwd(const LnFwdArgs& a, hipStream_t st) {
-  // pre (GATHER) / mean / rstd all null: the forward-only instantiations; all given: the training ones (the entries check)
-  const bool keep = a.mean != nullptr;
-  using Kernel = void (*)(const LnFwdArgs);
-  dim3 block(256);
-  if ((a.H == 64 || a.H == 128 || a.H == 256) && ln_fwd_v4_aligned(a)) {
-    const int rpw = 256 / a.H;  // rows per wave
-    dim3 gridv((unsigned)((a.rows + 4 * rpw - 1) / (4 * rpw)));
-    const Kernel k = a.H == 64    ? (keep ? ln_fwd_v4_kernel<16, GATHER> : ln_fwd_v4_infer_kernel<16, GATHER>)
-                     : a.H == 128 ? (keep ? ln_fwd_v4_kernel<32, GATHER> : ln_fwd_v4_infer_kernel<32, GATHER>)
-                                  : (keep ? ln_fwd_v4_kernel<64, GATHER> : ln_fwd_v4_infer_kernel<64, GATHER>);
-    hipLaunchKernelGGL(k, gridv, block, 0, st, a);
-    XF_LAUNCH_CHECK();
-    return XFMR_OK;
-  }
-  dim3 grid((unsigned)((a.rows + 3) / 4));
-  const int npl = npl_of(a.H);
-  Kernel k;
-  if (npl <= 1) k = keep ? ln_fwd_kernel<1, GATHER> : ln_fwd_infer_kernel<1, GATHER>;
-  else if (npl <= 2) k = keep ? ln_fwd_kernel<2, GATHER> : ln_fwd_infer_kernel<2, GATHER>;
-  else if (npl <= 4) k = keep ? ln_fwd_kernel<4, GATHER> : ln_fwd_infer_kernel<4, GATHER>;
-  else if (npl <= 8) k = keep ? ln_fwd_kernel<8, GATHER> : ln_fwd_infer_kernel<8, GATHER>;
-  else if (npl <= kMaxPerLane) k = keep ? ln_fwd_kernel<16, GATHER> : ln_fwd_infer_kernel<16, GATHER>;
-  else return XFMR_EUNSUPPORTED;
-  hipLaunchKernelGGL(k, grid, block, 0, st, a);
+// launches a row plan's kernel on the plan's grid (Args = the kernel's one by-value argument)
+template <class Args>
+int launch_row_plan(const RowPlan& p, const Args& a, hipStream_t st) {
+  if (p.rc) return p.rc;
+  using Kernel = void (*)(const Args);
+  hipLaunchKernelGGL((Kernel)p.kernel, dim3((unsigned)p.grid), dim3((unsigned)p.block), (size_t)p.lds, st, a);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
 }
 
-// what a gather + LayerNorm keeps for its backward: all of pre / mean / rstd, or none of them (forward-only: `out` is then the
-// only fp32 copy of the output and has to be given)
-bool ln_keep_ok(const float* pre, const float* mean, const float* rstd, const float* out) {
-  const int n = (pre != nullptr) + (mean != nullptr) + (rstd != nullptr);
-  return n == 3 || (n == 0 && out != nullptr);
+// pre (gather) / mean / rstd all null: the forward-only instantiations; all given: the training ones (the entries check)
+int launch_ln_fwd(RowOp op, const LnFwdArgs& a, hipStream_t st) {
+  return launch_row_plan(row_plan(RowKey{op, a.rows, a.H, a.mean != nullptr, ln_fwd_v4_aligned(a)}), a, st);
 }
 
-int ln_bwd_blocks(int64_t rows, int H, int* rows_per_block) {
-  // 32 rows per workgroup, <= 1024 workgroups (measured at T = 25 600: 1.859 ms/step; 64 rows / 512: 1.877;
-  // 16 rows / 2048: 1.891 -- the partial records the final reduction reads grow with the workgroup count).
-  // Small steps (round 4): 32 rows per workgroup are 8 dependent row round trips per wave on rows / 32 CUs -- 1 024 tokens
-  // of H = 384 (the reference's default model) took 33 us per LayerNorm backward, a quarter of that step. Below 16 384 rows:
-  // 16 per workgroup; below 4 096: one wave-iteration (4 waves x 64 / lanes-per-row rows).
-  const int iter_rows = H == 64 ? 16 : H == 128 ? 8 : 4;  // rows of one workgroup iteration (ln_bwd_v4_kernel / ln_bwd_kernel)
-  const int64_t per = rows >= 16384 ? 32 : rows >= 4096 ? 16 : iter_rows;
-  int64_t blocks = (rows + per - 1) / per;
-  if (blocks > 1024) blocks = 1024;
-  if (blocks < 1) blocks = 1;
-  int64_t rpb = (rows + blocks - 1) / blocks;
-  rpb = ((rpb + iter_rows - 1) / iter_rows) * iter_rows;  // whole workgroup iterations
-  *rows_per_block = (int)rpb;
-  return (int)((rows + rpb - 1) / rpb);
+// The kernels with one wave per row (or per sequence), four waves per workgroup
+template <class Kernel, class... A>
+int launch_wave_per_row(Kernel kernel, int64_t rows, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, args...);
+  XF_LAUNCH_CHECK();
+  return XFMR_OK;
 }
-// The most partial records ln_bwd_blocks gives for ANY row count <= rows (the plan is not monotone in the row count; the
-// packed layout carves for batch x seq_len rows and launches with the real ones).
-int ln_bwd_blocks_bound(int64_t rows) {
-  const int64_t b = (rows + 3) / 4;
-  return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
-}
-
 
 // ---- packed rows (xfmr_encoder_cfg.seq_offsets) ----------------------------------------------------------------------
 // one block row per sequence: rows [0, len_b) of the three (B, L) index tensors -> their packed places
@@ -727,7 +662,38 @@ __global__ __launch_bounds__(1024) void pos_grad_packed_kernel(const float* d_pr
 }
 }  // namespace
 
+#include "row_plan.inc"
+
+namespace {
+// Gather + LayerNorm over `rows` rows, row r at position row_pos[r] (packed rows) or r % L (row_pos null). Keeps for its
+// backward all of pre / mean / rstd, or none of them (forward-only: `out` is then the only fp32 copy of the output and has to
+// be given); out may be null when out16 is given: the fp32 output is not stored -- its consumer re-derives it, xf_ln_out_drop4.
+int embed_ln_fwd(const int64_t* item_idx, const float* table, int64_t n_rows, const float* pos_emb, const float* type_emb,
+                 const float* gamma, const float* beta, float* out, void* out16, float* pre, float* mean, float* rstd,
+                 uint8_t* key_mask, int64_t rows, int32_t L, const int32_t* row_pos, int32_t H, float eps, float dropout_p,
+                 XfSeed seed, uint32_t site, hipStream_t stream) {
+  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !key_mask) return XFMR_EINVAL;
+  const int kept = (pre != nullptr) + (mean != nullptr) + (rstd != nullptr);
+  if (kept != 3 && (kept != 0 || !out)) return XFMR_EINVAL;
+  if (rows <= 0 || L <= 0 || H <= 0 || n_rows <= 0) return XFMR_EINVAL;
+  LnFwdArgs a{};
+  a.idx = item_idx; a.table = table; a.n_rows = n_rows; a.pos_emb = pos_emb; a.type_emb = type_emb;
+  a.L = L; a.row_pos = row_pos; a.gamma = gamma; a.beta = beta; a.y = out; a.pre = pre; a.mean = mean; a.rstd = rstd;
+  a.key_mask = key_mask; a.rows = rows; a.H = H; a.eps = eps;
+  a.drop = xf_make_dropout(dropout_p, seed, site);
+  a.y16 = reinterpret_cast<__bf16*>(out16);
+  return launch_ln_fwd(kRowGatherLnFwd, a, stream);
+}
+}  // namespace
+
 extern "C" {
+
+int xf_row_plan(int32_t op, int64_t rows, int32_t H, int32_t keep, int32_t aligned, int32_t out[12]) {
+  const RowPlan p = row_plan(RowKey{(RowOp)op, rows, H, keep, aligned});
+  const int32_t v[12] = {p.form, p.width, p.grid, p.block, p.lds, p.rows_per_block, p.records, p.room};
+  for (int i = 0; i < 12; ++i) out[i] = p.rc ? 0 : v[i];
+  return p.rc;
+}
 
 int xfmr_embed_ln_fwd(const int64_t* item_idx, const float* table, int64_t n_rows, const float* pos_emb,
                       const float* type_emb, const float* gamma, const float* beta, float* out, float* pre,
@@ -742,18 +708,9 @@ int xf_embed_ln_fwd_ex(const int64_t* item_idx, const float* table, int64_t n_ro
                        const float* type_emb, const float* gamma, const float* beta, float* out, void* out16,
                        float* pre, float* mean, float* rstd, uint8_t* key_mask, int32_t B, int32_t L, int32_t H,
                        float eps, float dropout_p, XfSeed seed, uint32_t site, hipStream_t stream) {
-  // (out may be null when out16 is given: the fp32 output is not stored -- its consumer re-derives it, xf_ln_out_drop4)
-  // (pre, mean and rstd all null: the forward-only form, nothing is kept for a backward -- the output is then stored)
-  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !key_mask) return XFMR_EINVAL;
-  if (!ln_keep_ok(pre, mean, rstd, out)) return XFMR_EINVAL;
-  if (B <= 0 || L <= 0 || H <= 0 || n_rows <= 0) return XFMR_EINVAL;
-  LnFwdArgs a{};
-  a.x = nullptr; a.idx = item_idx; a.table = table; a.n_rows = n_rows; a.pos_emb = pos_emb; a.type_emb = type_emb;
-  a.L = L; a.gamma = gamma; a.beta = beta; a.y = out; a.pre = pre; a.mean = mean; a.rstd = rstd;
-  a.key_mask = key_mask; a.rows = (int64_t)B * L; a.H = H; a.eps = eps;
-  a.drop = xf_make_dropout(dropout_p, seed, site);
-  a.y16 = reinterpret_cast<__bf16*>(out16);
-  return launch_ln_fwd<true>(a, stream);
+  if (B <= 0 || L <= 0) return XFMR_EINVAL;
+  return embed_ln_fwd(item_idx, table, n_rows, pos_emb, type_emb, gamma, beta, out, out16, pre, mean, rstd, key_mask,
+                      (int64_t)B * L, L, nullptr, H, eps, dropout_p, seed, site, stream);
 }
 
 // packed rows (xfmr_encoder_cfg.seq_offsets): `rows` packed rows, row r adds position row_pos[r]
@@ -761,16 +718,9 @@ int xf_embed_ln_fwd_packed_ex(const int64_t* item_idx, const float* table, int64
                               const float* type_emb, const float* gamma, const float* beta, float* out, void* out16,
                               float* pre, float* mean, float* rstd, uint8_t* key_mask, int64_t rows, const int32_t* row_pos,
                               int32_t H, float eps, float dropout_p, XfSeed seed, uint32_t site, hipStream_t stream) {
-  if (!item_idx || !table || !pos_emb || !type_emb || !gamma || !beta || (!out && !out16) || !key_mask || !row_pos) return XFMR_EINVAL;
-  if (!ln_keep_ok(pre, mean, rstd, out)) return XFMR_EINVAL;
-  if (rows <= 0 || H <= 0 || n_rows <= 0) return XFMR_EINVAL;
-  LnFwdArgs a{};
-  a.x = nullptr; a.idx = item_idx; a.table = table; a.n_rows = n_rows; a.pos_emb = pos_emb; a.type_emb = type_emb;
-  a.L = 1; a.row_pos = row_pos; a.gamma = gamma; a.beta = beta; a.y = out; a.pre = pre; a.mean = mean; a.rstd = rstd;
-  a.key_mask = key_mask; a.rows = rows; a.H = H; a.eps = eps;
-  a.drop = xf_make_dropout(dropout_p, seed, site);
-  a.y16 = reinterpret_cast<__bf16*>(out16);
-  return launch_ln_fwd<true>(a, stream);
+  if (!row_pos) return XFMR_EINVAL;
+  return embed_ln_fwd(item_idx, table, n_rows, pos_emb, type_emb, gamma, beta, out, out16, pre, mean, rstd, key_mask, rows, 1,
+                      row_pos, H, eps, dropout_p, seed, site, stream);
 }
 
 int xfmr_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
@@ -788,11 +738,11 @@ int xf_layernorm_fwd_ex(const float* x, const float* gamma, const float* beta, f
   a.eps = eps; a.L = 1;
   a.drop = xf_make_dropout(0.f, 0, 0);
   a.y16 = reinterpret_cast<__bf16*>(y16);
-  return launch_ln_fwd<false>(a, stream);
+  return launch_ln_fwd(kRowLnFwd, a, stream);
 }
 
 size_t xfmr_layernorm_bwd_workspace(int64_t rows, int32_t H) {
-  return (size_t)ln_bwd_blocks_bound(rows) * 3 * (size_t)H * sizeof(float);  // enough for every row count <= rows
+  return (size_t)row_plan(RowKey{kRowLnBwd, rows, H, 1, 0}).room * 3 * (size_t)H * sizeof(float);  // every row count <= rows
 }
 
 // Internal variant that also takes the dropout applied to the LayerNorm OUTPUT (embedding site).
@@ -805,26 +755,14 @@ int xf_layernorm_bwd_impl(const float* dy, const float* x, const float* mean, co
   LnBwdArgs a{};
   a.dy = dy; a.x = x; a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.dx = dx; a.d_lin = d_lin;
   a.partials = (float*)partials; a.rows = rows; a.H = H; a.lin16 = lin16 ? 1 : 0;
-  const int blocks = ln_bwd_blocks(rows, H, &a.rows_per_block);
   a.drop_out = drop_out; a.drop_lin = drop_lin;
-  const size_t shmem = (size_t)12 * H * sizeof(float);
-  const int npl = npl_of(H);
-  dim3 grid(blocks), block(256);
-  const bool v4 = ln_bwd_v4_aligned(a);  // (else the generic kernel of the same width; the row plan holds for both)
-  if (v4 && H == 64) hipLaunchKernelGGL((ln_bwd_v4_kernel<16>), grid, block, 0, st, a);
-  else if (v4 && H == 128) hipLaunchKernelGGL((ln_bwd_v4_kernel<32>), grid, block, 0, st, a);
-  else if (v4 && H == 256) hipLaunchKernelGGL((ln_bwd_v4_kernel<64>), grid, block, 0, st, a);
-  else if (npl <= 1) hipLaunchKernelGGL((ln_bwd_kernel<1>), grid, block, shmem, st, a);
-  else if (npl <= 2) hipLaunchKernelGGL((ln_bwd_kernel<2>), grid, block, shmem, st, a);
-  else if (npl <= 4) hipLaunchKernelGGL((ln_bwd_kernel<4>), grid, block, shmem, st, a);
-  else if (npl <= 8) hipLaunchKernelGGL((ln_bwd_kernel<8>), grid, block, shmem, st, a);
-  else if (npl <= kMaxPerLane) hipLaunchKernelGGL((ln_bwd_kernel<16>), grid, block, shmem, st, a);
-  else return XFMR_EUNSUPPORTED;
-  XF_LAUNCH_CHECK();
-  if (blocks_out) *blocks_out = blocks;
+  const RowPlan p = row_plan(RowKey{kRowLnBwd, rows, H, 1, ln_bwd_v4_aligned(a)});
+  a.rows_per_block = p.rows_per_block;
+  if (const int rc = launch_row_plan(p, a, st)) return rc;
+  if (blocks_out) *blocks_out = p.records;
   if (!d_gamma && !d_beta && !d_bias) return XFMR_OK;  // reduction deferred to the caller
   hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((3 * H + 63) / 64), dim3(1024), 0, st, (const float*)partials,
-                     blocks, H, d_gamma, d_beta, d_bias);
+                     (int)p.records, H, d_gamma, d_beta, d_bias);
   XF_LAUNCH_CHECK();
   return XFMR_OK;
 }
@@ -904,26 +842,17 @@ int xfmr_pool_rows(const float* tok, const int32_t* seq_offsets, float* out, int
   if (!tok || !seq_offsets || !out || B <= 0 || H <= 0) return XFMR_EINVAL;
   if (mode < XFMR_POOL_MEAN || mode > XFMR_POOL_LASTTOKEN) return XFMR_EINVAL;
   if (normalize && !(eps > 0.f)) return XFMR_EINVAL;
-  hipLaunchKernelGGL(pool_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tok, seq_offsets,
-                     out, B, H, mode, normalize, eps);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  return launch_wave_per_row(pool_rows_kernel, B, (hipStream_t)stream, tok, seq_offsets, out, B, H, mode, normalize, eps);
 }
 
 int xfmr_l2_normalize_fwd(const float* x, float* y, float* inv_norm, int64_t rows, int32_t H, float eps, void* stream) {
   if (!x || !y || rows <= 0 || H <= 0 || !(eps > 0.f)) return XFMR_EINVAL;
-  hipLaunchKernelGGL(l2norm_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, y,
-                     inv_norm, rows, H, eps);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  return launch_wave_per_row(l2norm_fwd_kernel, rows, (hipStream_t)stream, x, y, inv_norm, rows, H, eps);
 }
 int xfmr_l2_normalize_bwd(const float* dy, const float* y, const float* inv_norm, float* dx, int64_t rows, int32_t H,
                           float eps, void* stream) {
   if (!dy || !y || !inv_norm || !dx || rows <= 0 || H <= 0 || !(eps > 0.f)) return XFMR_EINVAL;
-  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dy, y,
-                     inv_norm, dx, rows, H, eps);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  return launch_wave_per_row(l2norm_bwd_kernel, rows, (hipStream_t)stream, dy, y, inv_norm, dx, rows, H, eps);
 }
 
 int xfmr_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -976,10 +905,7 @@ int xfmr_scale_by_device_scalar(float* x, int64_t n, const float* scalar, void* 
 
 int xfmr_table_rnorm(const float* table, float* table_rnorm, int64_t n_rows, int32_t H, void* stream) {
   if (!table || !table_rnorm || n_rows <= 0 || H <= 0) return XFMR_EINVAL;
-  hipLaunchKernelGGL(table_rnorm_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                     table, table_rnorm, n_rows, H);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  return launch_wave_per_row(table_rnorm_kernel, n_rows, (hipStream_t)stream, table, table_rnorm, n_rows, H);
 }
 
 }  // extern "C"
@@ -991,8 +917,5 @@ int pool_slots_launch(const float* tok, const uint8_t* mask, const int32_t* slot
   if (!tok || !mask || !slots || !lens || !out || n <= 0 || n_slots <= 0 || max_len <= 0 || H <= 0) return XFMR_EINVAL;
   if (mode < XFMR_POOL_MEAN || mode > XFMR_POOL_LASTTOKEN) return XFMR_EINVAL;
   if (normalize && !(eps > 0.f)) return XFMR_EINVAL;
-  hipLaunchKernelGGL(pool_slots_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, tok, mask, slots, lens, out, n,
-                     n_slots, max_len, H, mode, normalize, eps);
-  XF_LAUNCH_CHECK();
-  return XFMR_OK;
+  return launch_wave_per_row(pool_slots_kernel, n, st, tok, mask, slots, lens, out, n, n_slots, max_len, H, mode, normalize, eps);
 }

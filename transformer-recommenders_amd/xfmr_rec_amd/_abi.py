@@ -214,6 +214,7 @@ _LOSS_KEY = [_I64, _I32, _I64] + [_I32] * 6 + [_U32, _I32, _I32, _I32, _U64, _PI
 
 # csrc/internal.h, in the header's order; C++ default arguments are rows at full arity
 INTERNAL_SIGNATURES = {
+    "xf_row_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _PI32]),
     "xf_gemm_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _U32, _I32, _I32, _PI32, _PI32]),
     "xf_gemm_switches": (None, [_PI32]),
     "xf_linear_fwd_ex": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P] + _SEED_SITE + [_I32, _U32, _P]),
