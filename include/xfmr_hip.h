@@ -545,7 +545,9 @@ int xfmr_table_prepare(const float* table, float* table_rnorm, void* table_bf16,
  *   the catalogue minus the row's history, without replacement while possible (data.py:724-747); everything
  *   right-padded with 0 to `width` (pad_sequence, data.py:789-805; width = the batch's longest row, <= max_seq_length).
  * Outputs hist_out / pos_out / neg_out: (batch, width) int64 -- exactly the three index tensors of SeqBatch.
- * max_history >= the longest history among `rows` (<= 8192). Random stream: counter-based hash of
+ * max_history (<= 8192) sizes the kernel's LDS: a row whose history length is outside [1, max_history] is written as
+ * zeros and nothing of it is read. The row indices themselves are NOT checked (there is no row count to check them
+ * against): every rows[b] must be in [0, R). Random stream: counter-based hash of
  * (seed, row, purpose, counter) -- reproducible, but not numpy's generator: parity is distributional.
  * ---------------------------------------------------------------------------------------------- */
 size_t xfmr_seq_sample_workspace(int32_t batch, int64_t n_items);

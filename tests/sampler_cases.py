@@ -46,7 +46,7 @@ class Case:
     first: int = 0
     seed: int = 0
     epoch: int = 0
-    max_history: int | None = None   # rows only: None = the dataset's longest row
+    max_history: int | None = None   # None = the dataset's longest row
     valid: object = None             # valid(case, kernel, model output): asserts that the case is what it claims
 
     def __post_init__(self):
@@ -71,10 +71,10 @@ def _model(name, kernel):
         out = SM.rows_sample(c.hs, c.ls, c.order, c.batch, first=c.first, seed=c.seed, epoch=c.epoch,
                              max_history=c.max_history, **kw)
     else:
-        assert c.first == 0 and c.batch == len(c.order) and c.max_history is None
+        assert c.first == 0 and c.batch == len(c.order)
         assert all(0 <= r < len(c.hs) for r in c.order)
-        h, p, n, tr = SM.seq_sample(c.hs, c.ls, c.order, c.seed, **kw)
-        out = (h, p, n, np.array([t["cnt"] for t in tr], dtype=np.int32), tr)
+        h, p, n, tr = SM.seq_sample(c.hs, c.ls, c.order, c.seed, max_history=c.max_history, **kw)
+        out = (h, p, n, np.array([0 if t is None else t["cnt"] for t in tr], dtype=np.int32), tr)
     for a in out[:4]:
         a.setflags(write=False)
     return out
@@ -271,13 +271,13 @@ def _build():
         valid=_zero_rows([False, False, True, True]))
     add("zero-rows-outside-the-dataset", ("rows",), hs, ls, V, 32, 3, [3, -1, R, 5], 4, 32, seed=9,
         valid=_zero_rows([False, True, True, False]))
-    add("zero-rows-over-max_history", ("rows",), hs, ls, V, 32, 3, [4, 5, 9, 3], 4, 32, seed=9, max_history=64,
+    add("zero-rows-over-max_history", BOTH, hs, ls, V, 32, 3, [4, 5, 9, 3], 4, 32, seed=9, max_history=64,
         valid=_zero_rows([False, True, True, False]))
 
     # ---- catalogue size: the longest supported row against 100 003 items; 5e7 items (the closed form of rank -> item)
     Vb = 100_003
     hb = [rng.integers(1, Vb + 1, 8192), rng.integers(1, Vb + 1, 50)]
-    add("longest-row-big-catalogue", ("rows",), hb, [_labels(rng, len(h)) for h in hb], Vb, 32, 3, [0, 1], 2, 32, seed=3)
+    add("longest-row-big-catalogue", BOTH, hb, [_labels(rng, len(h)) for h in hb], Vb, 32, 3, [0, 1], 2, 32, seed=3)
     Vh = 50_000_000
     hh = [rng.integers(1, Vh + 1, n) for n in (2, 33, 64, 300)]
     hh[2][::2] = hh[2][1]  # repeated items

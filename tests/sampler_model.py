@@ -6,10 +6,10 @@ Taken from the library, as its contract (sampler.hip's header comments, csrc/com
 
     h(x)         = xf_hash32:  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16     (mod 2^32)
     below(r, n)  = (r * n) >> 32                                                     a uniform integer in [0, n)
-    xfmr_seq_sample       stream(purpose, ctr) = rnd(seed, row, purpose, ctr):
+    xfmr_seq_sample       stream(purpose, ctr) = SeqStream{seed, row}.draw(purpose, ctr):
                           x = h(lo32(seed) ^ hi32(seed) * 0x9e3779b9 ^ lo32(row) * 0x85ebca6b)
                           x = h(x ^ purpose * 0xc2b2ae35 ^ ctr);  h(x + 0x27d4eb2f * ctr)
-    xfmr_seq_sample_rows  stream(purpose, ctr) = rnd_row(row_key(seed, epoch, row), purpose, ctr):
+    xfmr_seq_sample_rows  stream(purpose, ctr) = RowsStream{row_key(seed, epoch, row)}.draw(purpose, ctr):
                           a = h(lo32(seed) ^ h(hi32(seed) + 0x9e3779b9));  a = h(a ^ lo32(epoch) * 0x85ebca6b)
                           a = h(a + hi32(epoch) * 0xc2b2ae35);  b = h(a ^ 0x27d4eb2f)
                           k0 = h(a ^ lo32(row));  k1 = h(b + hi32(row) * 0x165667b1 + lo32(row) * 0x9e3779b9)
@@ -37,8 +37,8 @@ network, no per-thread loops):
                                                    closes unless a filled slot, or an open slot of lower index, holds that
                                                    rank; a slot still open after 32 rounds -> the exact path for the row
                                    otherwise:      the cnt ranks with the smallest (stream(4, rank), rank), in that order
-    zero rows    `rows`: batch rows past n_order, row indices outside the dataset, lengths outside 1..max_history: zeros,
-                 length 0.
+    zero rows    both: lengths outside 1..max_history. `rows` also: batch rows past n_order, row indices outside the dataset
+                 (`xfmr_seq_sample` is given no row count and does not check the index). Zeros, length 0.
 
 The core functions work on ONE history and a batch of R streams ("lanes": the same row under R different (seed, row id)
 keys), so that a frequency table over 2e5 draws is a handful of array operations; ``seq_sample`` / ``rows_sample`` wrap them
@@ -102,7 +102,7 @@ class _Stream:
 
 
 class SeqStream(_Stream):
-    """rnd(seed, row, purpose, ctr) of xfmr_seq_sample for broadcast arrays of seeds and dataset rows."""
+    """SeqStream{seed, row}.draw(purpose, ctr) of xfmr_seq_sample for broadcast arrays of seeds and dataset rows."""
 
     def __init__(self, seed, row):
         slo, shi, rlo, _ = _lanes(seed, row)
@@ -115,7 +115,7 @@ class SeqStream(_Stream):
 
 
 class RowsStream(_Stream):
-    """rnd_row(row_key(seed, epoch, row), purpose, ctr) of xfmr_seq_sample_rows; ``epoch`` is one 64-bit number."""
+    """RowsStream{row_key(seed, epoch, row)}.draw(purpose, ctr) of xfmr_seq_sample_rows; ``epoch`` is one 64-bit number."""
 
     def __init__(self, seed, epoch, row):
         slo, shi, rlo, rhi = _lanes(seed, row)
@@ -328,15 +328,19 @@ def _lane0(tr):
 
 
 # --------------------------------------------------------------------------------------------------- one launch
-def seq_sample(hs, ls, rows, seed, *, max_seq_length, width, lookahead, n_items):
-    """xfmr_seq_sample over dataset rows ``rows``: hist, pos, neg [B, width] and one trace per batch row."""
+def seq_sample(hs, ls, rows, seed, *, max_seq_length, width, lookahead, n_items, max_history=None):
+    """xfmr_seq_sample over dataset rows ``rows`` (all inside the dataset: the entry does not check them): hist, pos, neg
+    [B, width] and one trace per batch row (None for a row written as zeros)."""
+    max_history = max(len(h) for h in hs) if max_history is None else max_history
     out = np.zeros((3, len(rows), width), dtype=np.int64)
-    traces = []
+    traces = [None] * len(rows)
     for b, r in enumerate(rows):
+        if not 1 <= len(hs[r]) <= max_history:
+            continue
         a = sample_row(SeqStream(seed, int(r)), "seq", hs[r], ls[r], max_seq_length=max_seq_length, width=width,
                        lookahead=lookahead, n_items=n_items)
         out[0, b], out[1, b], out[2, b] = a[0][0], a[1][0], a[2][0]
-        traces.append(_lane0(a[4]))
+        traces[b] = _lane0(a[4])
     return out[0], out[1], out[2], traces
 
 

@@ -9,8 +9,7 @@ that the model itself keeps the reference's guarantees and its uniformity. The l
 order, batch by batch.
 
 Not reachable, hence recorded (profiles/sampler_exact.md) and not tested: 32 rejection rounds that leave a slot open
-(probability below 4^-32 per slot), and dataset row indices at or beyond 2^32 (the high word of the row in ``row_key``).
-``xfmr_seq_sample`` is never given a row longer than the ``max_history`` of the call: it sizes its LDS from that argument."""
+(probability below 4^-32 per slot), and dataset row indices at or beyond 2^32 (the high word of the row in ``row_key``)."""
 
 import numpy as np
 import pytest
@@ -25,20 +24,21 @@ DEV = "cuda"
 NAMES = ("hist", "pos", "neg", "len")
 
 
-def _sample_seq(ds, rows, *, width, seed, n_items=None):
-    """One direct call of xfmr_seq_sample (the twin of test_gpu_epoch_loader._sample); numpy outputs ``hist, pos, neg``."""
+def _sample_seq(ds, rows, *, width, seed, n_items=None, max_history=None):
+    """One direct call of xfmr_seq_sample (the twin of test_gpu_epoch_loader._sample); numpy outputs ``hist, pos, neg``.
+    ``max_history``: None = the dataset's longest row."""
     from xfmr_rec_amd import _native as N
 
     lib = N.load()
     rows_t = torch.as_tensor(np.asarray(rows, dtype=np.int64)).to(DEV)
-    assert int(ds.lengths[np.asarray(rows)].max()) <= int(ds.lengths.max())  # no row over the max_history passed
+    max_history = int(ds.lengths.max()) if max_history is None else max_history
     n_items = ds.n_items if n_items is None else n_items
     out = [torch.full((len(rows), width), -7, dtype=torch.int64, device=DEV) for _ in range(3)]
     nbytes = lib.xfmr_seq_sample_workspace(len(rows), n_items)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
     N.check(lib.xfmr_seq_sample(
         N.ptr(ds.items), N.ptr(ds.labels), N.ptr(ds.offsets), N.ptr(rows_t), len(rows), width, ds.config.max_seq_length,
-        ds.config.pos_lookahead, n_items, int(ds.lengths.max()), seed, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.ptr(ws),
+        ds.config.pos_lookahead, n_items, max_history, seed, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.ptr(ws),
         nbytes, N.stream()), "xfmr_seq_sample")
     return [t.cpu().numpy() for t in out]
 
@@ -87,7 +87,7 @@ def test_launch_equals_the_model(name, kernel):
     want = SC.model(c, kernel)
     ds = _ds(c)
     if kernel == "seq":
-        got = _sample_seq(ds, c.order, width=c.width, seed=c.seed)
+        got = _sample_seq(ds, c.order, width=c.width, seed=c.seed, max_history=c.max_history)
         want_arrays = want[:3]
     elif c.max_history is not None:
         got = _sample_rows_max_history(ds, c.order, c.batch, width=c.width, max_history=c.max_history, first=c.first,

@@ -239,8 +239,8 @@ def test_case_is_what_it_claims(name, kernel):
     c = SC.BY_NAME[name]
     out = SC.model(c, kernel)
     assert out[0].shape == out[1].shape == out[2].shape == (c.batch, c.width) and out[3].shape == (c.batch,)
-    if kernel == "seq":  # never a row longer than the max_history the launch is given (the dataset's longest)
-        assert all(0 <= r < len(c.hs) for r in c.order) and c.max_history is None
+    if kernel == "seq":  # (the entry is given no row count and does not check the row index)
+        assert all(0 <= r < len(c.hs) for r in c.order)
     if c.valid is not None:
         c.valid(c, kernel, out)
 
@@ -252,7 +252,7 @@ def test_the_table_covers_what_it_has_to():
     assert {c.lookahead for c in SC.CASES if c.name.startswith("lengths-")} == {0, 1, 3, 10_000}
     assert {f"seed-{s}" for s in (0, 1, 2**32, 2**63 + 5)} | {f"epoch-{e}" for e in (0, 1, 2**32 + 1)} <= names
     big = SC.BY_NAME["longest-row-big-catalogue"]
-    assert len(big.hs[0]) == 8192 and big.n_items == 100_003 and big.kernels == ("rows",)
+    assert len(big.hs[0]) == 8192 and big.n_items == 100_003 and big.kernels == SC.BOTH
     for c in SC.CASES:
         if c.name not in ("longest-row-big-catalogue", "huge-catalogue", "tie-exact-path") and not c.name.startswith(
                 ("tie-positions", "regime-limits", "rounds-both")):
