@@ -2,8 +2,8 @@
 
 ``SIGNATURES`` has one row per prototype of ``include/xfmr_hip.h`` (the public ``xfmr_*`` entries), ``INTERNAL_SIGNATURES`` one
 per ``extern "C"`` prototype of ``csrc/internal.h`` (the ``xf_*`` entries that tests and probes call directly),
-``SESSION_SIGNATURES`` one per prototype of ``include/xfmr_session.h`` (the session encoder); ``bind`` applies
-them to a ``CDLL``. No other file keeps a signature: ``tests/test_abi_tables_host.py`` holds every row and every Structure to its
+``SESSION_SIGNATURES`` one per prototype of ``include/xfmr_session.h`` (the session encoder), ``SEARCH_SIGNATURES`` one per
+prototype of ``include/xfmr_search.h`` (the refined item search); ``bind`` applies them to a ``CDLL``. No other file keeps a signature: ``tests/test_abi_tables_host.py`` holds every row and every Structure to its
 header. This module imports ``ctypes`` only, so that a child process without torch can load it by file path.
 """
 
@@ -267,6 +267,14 @@ SESSION_SIGNATURES = {
     "xfmr_session_pool": (C.c_int, [C.POINTER(EncoderCfg), _P, C.c_size_t, _I32, _P, _P, _I32, _I32, _I32, _F, _P, _P]),
 }
 
+# include/xfmr_search.h (the refined item search), in the header's order; tests/test_search_refined_host.py holds it to the header
+SEARCH_SIGNATURES = {
+    "xfmr_search_refined_workspace": (C.c_size_t, [_I64, _I64, _I32]),
+    "xfmr_search_refined_plan": (C.c_int, [_I64, _I64, _I32, _I32, _I32, _PI32]),
+    "xfmr_search_refined": (C.c_int, [_P, _P, _P, _P, _P, _F, _F, _I64, _I64, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P,
+                                      C.c_size_t, _P]),
+}
+
 # prototypes of csrc/internal.h that ctypes cannot call, each with its reason
 NOT_BOUND = (
     ("xf_layernorm_bwd_impl", "takes XfDropout by value, a C++ struct with no mirror here"),
@@ -276,7 +284,7 @@ NOT_BOUND = (
 
 def bind(cdll: C.CDLL) -> C.CDLL:
     """Give every entry of the tables its restype and argtypes on ``cdll``; a symbol the library lacks is named."""
-    for table in (SIGNATURES, INTERNAL_SIGNATURES, SESSION_SIGNATURES):
+    for table in (SIGNATURES, INTERNAL_SIGNATURES, SESSION_SIGNATURES, SEARCH_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(cdll, name)

@@ -14,7 +14,7 @@ import pathlib
 
 import torch
 
-from ._abi import (INTERNAL_SIGNATURES, NOT_BOUND, SESSION_SIGNATURES, SIGNATURES, DwItem, EncoderCfg, LnResidual,  # noqa: F401
+from ._abi import (INTERNAL_SIGNATURES, NOT_BOUND, SEARCH_SIGNATURES, SESSION_SIGNATURES, SIGNATURES, DwItem, EncoderCfg, LnResidual,  # noqa: F401
                    LossCfg, OptCfg, ReduceSeg, Seed, bind)
 
 _HERE = pathlib.Path(__file__).resolve().parent
@@ -65,6 +65,7 @@ _SIGNATURES = SIGNATURES
 EXPORTED_SYMBOLS = tuple(SIGNATURES)  # the public C ABI
 INTERNAL_SYMBOLS = tuple(INTERNAL_SIGNATURES)  # csrc/internal.h: bound for tests and probes, no part of the public ABI
 SESSION_SYMBOLS = tuple(SESSION_SIGNATURES)  # include/xfmr_session.h: the session encoder's public entries
+SEARCH_SYMBOLS = tuple(SEARCH_SIGNATURES)  # include/xfmr_search.h: the refined item search's public entries
 
 _lib = None
 

@@ -10,6 +10,7 @@ same search for a whole user set (xfmr_topk_tiled: no per-(user, item) workspace
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -17,6 +18,13 @@ from . import _native as N
 from .eval_rows import METRIC_NAMES, flat_csr, normalize_cutoffs  # noqa: F401 - (names of this module too)
 
 METRICS = {"cosine": 0, "dot": 1, "l2": 2}
+SEARCH_MODES = ("exact", "refined")  # the ``search=`` option of recommend_batch / SessionRecommender.recommend
+
+
+def refined_search_enabled() -> bool:
+    """``XFMR_SEARCH=exact``, read per call, routes every refined search through the exact one again (A/B runs and a
+    way back without a code change, as ``XFMR_INFER=0`` is for the encoder)."""
+    return os.environ.get("XFMR_SEARCH", "") != "exact"
 
 
 def _csr(lists, device, sort_unique: bool = False):
@@ -58,13 +66,16 @@ def _use_mask(use, B):
 class ExactItemIndex:
     """``LanceIndex.search`` (``index.py:214-255``) as an exact scan of the item table (row 0 = padding)."""
 
-    def __init__(self, table: torch.Tensor, table_rnorm: torch.Tensor | None = None, index_metric: str = "cosine"):
+    def __init__(self, table: torch.Tensor, table_rnorm: torch.Tensor | None = None, index_metric: str = "cosine",
+                 table_bf16: torch.Tensor | None = None):
         from . import ops
 
         self.table = table.contiguous()
         self.rnorm = table_rnorm if table_rnorm is not None else ops.table_rnorm(self.table)
         self.metric = METRICS[index_metric]
         self._sqnorm = None
+        self._table_bf16 = table_bf16  # the model's bf16 copy of the table when it has one (ops.table_prepare)
+        self._norm_bounds = None
 
     @property
     def sqnorm(self) -> torch.Tensor:
@@ -136,6 +147,90 @@ class ExactItemIndex:
             )
 
         return run
+
+    @property
+    def table_bf16(self) -> torch.Tensor:
+        """The bf16 copy of the table that :meth:`search_refined`'s first pass reads (``xfmr_table_prepare``: round to
+        nearest even, bit for bit ``table.to(torch.bfloat16)``), made once when the index was not given the model's."""
+        if self._table_bf16 is None:
+            from . import ops
+
+            self._table_bf16 = ops.table_prepare(self.table)[1]
+        return self._table_bf16
+
+    @property
+    def norm_bounds(self) -> tuple[float, float]:
+        """(largest row norm, largest inverse row norm) over the items 1 .. n - 1, as host floats: the two table
+        constants of :meth:`search_refined`'s error bound. Computed once (one read-back), from the f32 squared norms and
+        rounded up by 2^-12 (the f32 sums are good to 2^-14 at H <= 1024); a non-finite table gives a non-finite bound,
+        which certifies nothing."""
+        if self._norm_bounds is None:
+            if self.table.shape[0] < 2:
+                self._norm_bounds = (0.0, 0.0)
+            else:
+                both = torch.stack([self.sqnorm[1:].max().sqrt(), self.rnorm[1:].max()]).double() * (1.0 + 2.0 ** -12)
+                self._norm_bounds = tuple(float(x) for x in both.tolist())
+        return self._norm_bounds
+
+    def search_refined(self, embedding: torch.Tensor, exclude_item_idx=None, top_k: int = 20, refine_factor: int = 4,
+                       exact: bool = True):
+        """The search in the reference's two-stage form (``LanceIndex.search(...).refine_factor(4)``,
+        ``index.py:214-255``) through xfmr_search_refined: a full scan on the bf16 matrix cores keeps the
+        ``k_short = max(top_k, min(top_k * refine_factor, 128))`` best items per query, the exact search's f32 arithmetic
+        re-ranks them, and ``certified[q]`` says that row q is provably :meth:`search_batch`'s row (DESIGN.md "Refined
+        search": may be pessimistic, never wrong). Returns ``(idx (B, top_k) int64, score (B, top_k), certified (B,)
+        bool)``; every score is the bits :meth:`search_batch` reports for the item.
+
+        ``exact=True``: the rows that are not certified are searched again by :meth:`search_batch` with their own
+        exclusions and patched in (one read-back of ``certified.all()``): idx and score are then :meth:`search_batch`'s
+        for every row, bit for bit; ``certified`` still reports which rows the first call proved. ``exact=False``: the
+        refined lists as they are, in the meaning of the reference's ``refine_factor``. ``XFMR_SEARCH=exact`` (read per
+        call) takes :meth:`search_batch` for everything. top_k <= 128, H a multiple of 8."""
+        if refine_factor < 1:
+            raise ValueError(f"refine_factor must be at least 1; got {refine_factor}")
+        q, B, H, dev = _queries(embedding)
+        if exclude_item_idx is not None and len(exclude_item_idx) != B:
+            raise ValueError(f"exclude_item_idx has {len(exclude_item_idx)} lists for {B} queries")
+        if not refined_search_enabled():
+            idx, score = self.search_batch(q, exclude_item_idx, top_k=top_k)
+            return idx, score, torch.ones((B,), dtype=torch.bool, device=dev)
+        idx = torch.empty((B, top_k), dtype=torch.int64, device=dev)
+        score = torch.empty((B, top_k), dtype=torch.float32, device=dev)
+        cert = torch.empty((B,), dtype=torch.uint8, device=dev)
+        if B == 0:
+            return idx, score, cert.bool()
+        ex, exo = (None, None) if exclude_item_idx is None else _csr(exclude_item_idx, dev, sort_unique=True)
+        k_short = max(top_k, min(top_k * refine_factor, 128))
+        n_rows = self.table.shape[0]
+        rnorm, sqnorm = self._norms()
+        max_norm, max_rnorm = self.norm_bounds
+        lib = N.load()
+        nbytes = lib.xfmr_search_refined_workspace(B, n_rows, k_short)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        N.check(
+            lib.xfmr_search_refined(N.ptr(q), N.ptr(self.table), N.ptr(self.table_bf16), N.ptr(rnorm), N.ptr(sqnorm),
+                                    max_norm, max_rnorm, n_rows, B, H, N.ptr(ex), N.ptr(exo), top_k, k_short,
+                                    self.metric, N.ptr(idx), N.ptr(score), N.ptr(cert), N.ptr(ws), nbytes, N.stream()),
+            "xfmr_search_refined",
+        )
+        cert = cert.bool()
+        if exact and not bool(cert.all()):
+            rows = (~cert).nonzero().flatten()
+            excl = None if exclude_item_idx is None else [exclude_item_idx[i] for i in rows.tolist()]
+            sub_idx, sub_score = self.search_batch(q[rows], excl, top_k=top_k)
+            idx[rows] = sub_idx
+            score[rows] = sub_score
+        return idx, score, cert
+
+    def search_rows(self, embedding: torch.Tensor, exclude_item_idx=None, top_k: int = 20, search: str = "exact"):
+        """``(idx, score)`` of :meth:`search_batch` (``search="exact"``) or of :meth:`search_refined` with
+        ``exact=True`` (``search="refined"``): the same bits either way. What ``recommend_batch`` and the session
+        recommender call with their ``search=`` option."""
+        if search not in SEARCH_MODES:
+            raise ValueError(f"search must be one of {SEARCH_MODES}; got {search!r}")
+        if search == "refined":
+            return self.search_refined(embedding, exclude_item_idx, top_k=top_k)[:2]
+        return self.search_batch(embedding, exclude_item_idx, top_k=top_k)
 
     def rank_targets(self, embedding: torch.Tensor, targets_csr, exclude_csr=None, *, n_targets: int | None = None,
                      out: torch.Tensor | None = None, return_scores: bool = False):

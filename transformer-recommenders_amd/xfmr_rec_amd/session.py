@@ -254,15 +254,16 @@ class SessionRecommender:
         self.encoder.reset([slot])
         self.free.append(slot)
 
-    def recommend(self, keys, top_k: int = 0, exclude_seen: bool = True) -> dict:
+    def recommend(self, keys, top_k: int = 0, exclude_seen: bool = True, search: str = "exact") -> dict:
         """``{"item_idx": (n, k), "score": (n, k)}`` for the sessions ``keys``: the pooled session embedding against the
-        item index, the session's own items left out; an empty session gets -1 / -inf (as ``recommend_batch``)."""
+        item index, the session's own items left out; an empty session gets -1 / -inf (as ``recommend_batch``).
+        ``search="refined"``: the bf16 shortlist + exact re-rank, the same bits (``ExactItemIndex.search_rows``)."""
         import torch
 
         keys = list(keys)
         emb = self.encoder.embeddings([self.slot_of[k] for k in keys])
         excl = [self.seen[k] for k in keys] if exclude_seen else None
-        idx, score = self.module.items_index.search_batch(emb, excl, top_k=top_k or self.module.config.top_k)
+        idx, score = self.module.items_index.search_rows(emb, excl, top_k=top_k or self.module.config.top_k, search=search)
         empty = [i for i, k in enumerate(keys) if not self.seen[k]]
         if empty:
             e = torch.as_tensor(empty, dtype=torch.int64, device=idx.device)

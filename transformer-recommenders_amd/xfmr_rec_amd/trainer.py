@@ -362,7 +362,7 @@ class RecommenderLightningModule(_Base):
         assert self.model is not None and self.model.embeddings is not None
         idx = getattr(self, "_items_index", None)
         if idx is None or idx.table.data_ptr() != self.model.embeddings.data_ptr():
-            idx = ExactItemIndex(self.model.embeddings, self.model.table_rnorm)
+            idx = ExactItemIndex(self.model.embeddings, self.model.table_rnorm, table_bf16=self.model.table_bf16)
             self._items_index = idx
         return idx
 
@@ -393,18 +393,19 @@ class RecommenderLightningModule(_Base):
         return self.recommend(hist, top_k=self.config.top_k, exclude_item_ids=hist)
 
     @torch.no_grad()
-    def recommend_batch(self, item_ids_lists, *, top_k: int = 0, exclude_item_ids=None):
+    def recommend_batch(self, item_ids_lists, *, top_k: int = 0, exclude_item_ids=None, search: str = "exact"):
         """:meth:`recommend` for many users in one pass: one batched encoder forward (``encode_batch``) and one
         xfmr_topk_tiled search. Returns ``{"item_idx": (B, k), "score": (B, k)}``; a history that is empty (also after
-        unknown ids are dropped) gets all -1 / -inf."""
+        unknown ids are dropped) gets all -1 / -inf. ``search="refined"`` takes the bf16 shortlist + exact re-rank
+        (``ExactItemIndex.search_refined`` with ``exact=True``): the same bits."""
         hists = [self._to_idx_or_empty(list(x)) for x in item_ids_lists]
         excl = None if exclude_item_ids is None else [self._to_idx_or_empty(list(x)) for x in exclude_item_ids]
-        return self._recommend_rows(hists, excl, top_k or self.config.top_k)
+        return self._recommend_rows(hists, excl, top_k or self.config.top_k, search)
 
-    def _recommend_rows(self, hists, excl, top_k: int):
+    def _recommend_rows(self, hists, excl, top_k: int, search: str = "exact"):
         """:meth:`recommend_batch` behind the id conversion: histories and exclusions are lists of table rows."""
         emb = self.model.encode_batch(hists)
-        idx, score = self.items_index.search_batch(emb, excl, top_k=top_k)
+        idx, score = self.items_index.search_rows(emb, excl, top_k=top_k, search=search)
         empty = [b for b, h in enumerate(hists) if not h]
         if empty:
             e = torch.as_tensor(empty, dtype=torch.int64, device=idx.device)
